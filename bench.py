@@ -2,6 +2,7 @@
 """Headline benchmark: graphs/sec + ms/batch of DAGNN.forward(G) on code2-like AST batches.
 
     python bench.py --gpus 1 --steps 50 --warmup 5
+    python bench.py --gpus 1 --steps 50 --warmup 5 --dump-outputs DIR   # + the last timed step's logits as DIR/head_<s>.npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -37,6 +38,7 @@ import torch.distributed as dist  # noqa: E402
 
 FP32_MATRIX_PEAK_TFLOPS = 157.3  # MI355X_MICROARCH.md: fp32 MFMA == fp32 vector peak
 HBM_PEAK_GBPS = 8000.0
+DUMP_MAX_BYTES = 64 * 1000 * 1000   # --dump-outputs: all files together, .npy headers included
 
 
 def build_model(H, L, V, S, device):
@@ -60,6 +62,26 @@ def fresh_inputs(master, n):
             _bi_layer_index0=master._bi_layer_index0, _bi_layer_idx1=master._bi_layer_idx1,
             _bi_layer_index1=master._bi_layer_index1, num_graphs=master.num_graphs))
     return out
+
+
+def dump_outputs(heads, path):
+    """What the last timed forward(G) returned - one [batch, vocab] float32 logit matrix per head - as <path>/head_<s>.npy,
+    so that two builds can be compared output for output on the same seeded inputs.  Above DUMP_MAX_BYTES every head keeps
+    the same fixed sample of rows (graphs), drawn with a fixed seed from the shapes alone."""
+    import numpy as np
+    arrs = [h.numpy() for h in heads]
+    budget = DUMP_MAX_BYTES - 256 * len(arrs)   # room for the .npy headers
+    total = sum(a.nbytes for a in arrs)
+    if total > budget:
+        rows = arrs[0].shape[0]
+        keep = rows * budget // total
+        if keep < 1:
+            raise SystemExit("--dump-outputs: one row of every head is already more than %d bytes" % DUMP_MAX_BYTES)
+        idx = np.sort(np.random.default_rng(0).choice(rows, keep, replace=False))
+        arrs = [a[idx] for a in arrs]
+    os.makedirs(path, exist_ok=True)
+    for s, a in enumerate(arrs):
+        np.save(os.path.join(path, "head_%d.npy" % s), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def _cpu_model() -> str:
@@ -442,7 +464,12 @@ def main():
     ap.add_argument("--cpu-threads", type=int, default=8,
                     help="torch threads for the CPU baseline leg (8 = the thread count BASELINE.md was measured with; "
                          "the op-by-op path is slower with every core of a big host)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the logits the last timed step returned (rank 0) as DIR/head_<s>.npy, "
+                         "float32, at most 64 MB in all (beyond that, a fixed seeded sample of the graphs' rows)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -518,6 +545,8 @@ def main():
         elapsed = time.perf_counter() - t0
         gc.enable()
         engine.TIMER = None
+        # the last timed step's results, taken off the device before anything else runs (outside the timed region)
+        dumped = [o.detach().cpu() for o in out] if args.dump_outputs and rank == 0 else None
         # second pass (not the headline): every launch bracketed + one event per step boundary
         detail, marks = None, None
         if not args.no_kernel_timer and rank == 0 and streams is None:
@@ -538,6 +567,8 @@ def main():
     assert all(torch.isfinite(o).all() for o in out)
     for a in model._arenas.values():
         a.poll(block=True)   # a device-side failure (expired wait, plan contract) invalidates the run
+    if dumped is not None:
+        dump_outputs(dumped, args.dump_outputs)
     per_step = sorted(a.elapsed_time(b) for a, b in zip(marks[:-1], marks[1:])) if marks else None
 
     t = torch.tensor([elapsed], dtype=torch.float64, device=device)

@@ -86,10 +86,44 @@ def _run_bench(args, env_extra=None, launcher=()):
     return json.loads(lines[0])
 
 
+def test_dump_outputs_keeps_the_cap_and_a_fixed_sample(tmp_path):
+    import numpy as np
+    import torch
+    import bench
+    small = [torch.full((4, 3), float(s)) for s in range(2)]
+    bench.dump_outputs(small, str(tmp_path / "small"))
+    for s in range(2):
+        a = np.load(tmp_path / "small" / ("head_%d.npy" % s))
+        assert a.dtype == np.float32 and np.array_equal(a, small[s].numpy())
+    # 5 heads x 1024 graphs x 5002 vocabulary = 102 MB: a sample of rows, the same rows in every head and on every call
+    g = torch.Generator().manual_seed(0)
+    big = [torch.randn(1024, 5002, generator=g) for _ in range(5)]
+    for t in big:
+        t[:, 0] = torch.arange(1024)   # column 0 names the row
+    for d in ("a", "b"):
+        bench.dump_outputs(big, str(tmp_path / d))
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["head_%d.npy" % s for s in range(5)]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= bench.DUMP_MAX_BYTES
+    rows = None
+    for s, f in enumerate(files):
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype == np.float32 and a.shape[1] == 5002 and 0 < a.shape[0] < 1024 and np.array_equal(a, b)
+        idx = a[:, 0].astype(np.int64)   # which graphs were kept
+        assert np.array_equal(a, big[s].numpy()[idx]) and (np.diff(idx) > 0).all() and (rows is None or np.array_equal(idx, rows))
+        rows = idx
+
+
 @pytest.mark.gpu
-def test_bench_single_gpu_line():
-    j = _run_bench(["--gpus", "1", "--steps", "3", "--warmup", "1", "--cpu-passes", "0", "--train-steps", "0", "--other-configs", "0"])
+def test_bench_single_gpu_line(tmp_path):
+    import numpy as np
+    j = _run_bench(["--gpus", "1", "--steps", "3", "--warmup", "1", "--cpu-passes", "0", "--train-steps", "0", "--other-configs", "0",
+                    "--dump-outputs", str(tmp_path)])
     _check_line(j, 1, 3, 1, with_cpu=False)
+    # the headline forward's five [128, 5002] logit matrices
+    for s in range(5):
+        a = np.load(tmp_path / ("head_%d.npy" % s))
+        assert a.dtype == np.float32 and a.shape == (128, 5002) and np.isfinite(a).all()
 
 
 @pytest.mark.gpu
