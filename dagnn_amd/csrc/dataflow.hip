@@ -1686,6 +1686,8 @@ extern "C" int dagnn_dataflow_run(const dagnn_plan* pl, const dagnn_dataflow_arg
     if (pl->N >= (1 << 24) || (int64_t)pl->N * a->ld_h >= (1ll << 31) || (int64_t)pl->N * 3 * H >= (1ll << 31) || a->ld_h >= (1 << 24) ||
         a->gld >= (1 << 24) || a->pld >= (1 << 24))
         return DAGNN_EINVAL;
+    // ... and the AUX == 2 epilogue addresses a node's static record with a 32-bit byte offset
+    if (a->stat_rows && (int64_t)pl->N * df_stat_floats(H) * 4 >= (1ll << 32)) return DAGNN_EINVAL;
     DfArgs S;
     int nc = 0;
     for (int d = 0; d < 2; ++d) {

@@ -371,7 +371,7 @@ class _DvaeDagnn(_DvaeBase):
             from .core import guard_params
             p0 = next(self.parameters())
             if p0.is_cuda:
-                guard_params(self, self._arena_for(p0).err)
+                guard_params(self, self._arena_for(p0).error_word(p0.device))
         return out
 
     def invalidate_caches(self) -> None:

@@ -872,6 +872,13 @@ class GranuleArena(object):
         self.epoch += 1
         return self.bufs, self.epoch, self.err
 
+    def error_word(self, device) -> torch.Tensor:
+        """`err`, made here when no persistent launch has made it yet: the parameter guard of passes that run no persistent
+        kernel (the constructor-string variants, the D-VAE `add` / `max` encoders) reports through it too."""
+        if self.err is None or self.err.device != device:
+            self.err = torch.zeros(1, dtype=torch.int32, device=device)
+        return self.err
+
     def xcc_table(self, device):
         """Tagged table the workgroups of a dataflow launch publish their XCD in (zero-initialised once, tagged with the
         arena's epochs like the granule buffers; re-created with them)."""

@@ -561,7 +561,9 @@ class DAGNN(nn.Module):
                     variants.warn_torch_path(self, G)
                 return self._finish(G, None, G.x, variants.run(self, G, G.x), B)   # training: differentiable torch ops
             plan = self._plan_of(G, B)
-            return self._finish(G, plan, G.x, variants.run_hip(self, G, G.x, plan), B)
+            h = variants.run_hip(self, G, G.x, plan)
+            self._guard_params(G.x)
+            return self._finish(G, plan, G.x, h, B)
         train = self._training_pass()
 
         B = num_graphs_of(G)
@@ -612,7 +614,7 @@ class DAGNN(nn.Module):
         if self.training or not engine.PARAM_GUARD:
             return
         from .core import guard_params
-        guard_params(self, self._arena_for(x).err)
+        guard_params(self, self._arena_for(x).error_word(x.device))
 
     def invalidate_caches(self) -> None:
         """Drop every tensor derived from the parameters (what `train()` / `eval()` do): call it after updating parameters in

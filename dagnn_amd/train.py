@@ -222,8 +222,10 @@ class _SeqCE(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        dl, ctx.dl = ctx.dl, None
-        return dl.mul_(g), None, None, None
+        # out of place (`backward(retain_graph=True)` may run this again on the same `ctx.dl`), into rows of the same pitch
+        dl = ctx.dl
+        out = torch.empty(dl.shape[0], dl.stride(0), dtype=dl.dtype, device=dl.device)[:, :dl.shape[1]]
+        return torch.mul(dl, g, out=out), None, None, None
 
 
 def seq_cross_entropy(pred_list, y_arr: torch.Tensor) -> torch.Tensor:
@@ -264,6 +266,7 @@ class ClipAdam(torch.optim.Optimizer):
     layout (`step`, `exp_avg`, `exp_avg_sq` per parameter), so checkpoints move between the two.  `max_norm=None` (or <= 0)
     leaves the gradients unclipped.  Gradients themselves are NOT scaled in place (unlike `clip_grad_norm_`): the coefficient
     only enters the update.  `last_norm` is the device float of the last step's total norm (what `clip_grad_norm_` returns).
+    The updated parameters' version counters move as under torch's Adam, so caches keyed on them see every step.
     fp32 parameters on one ROCm device."""
 
     def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
@@ -347,4 +350,7 @@ class ClipAdam(torch.optim.Optimizer):
                     engine.check(lib.dagnn_clip_adam(arr, len(part), float(group["lr"]), float(b1), float(b2), float(group["eps"]),
                                                      float(group["weight_decay"]), stepno, float(self.max_norm) if clip else 0.0,
                                                      self._scratch[1].data_ptr() + 4 if clip else None, st), "dagnn_clip_adam")
+        # the kernel wrote the parameters through raw pointers: bump their version counters as an in-place torch op would, so
+        # that the derived-weight caches (keyed on data_ptr, _version) rebuild and autograd sees the modification
+        torch.autograd.graph.increment_version(allp)
         return loss

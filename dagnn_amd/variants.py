@@ -617,6 +617,12 @@ class VariantRecurrence(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, mod, G, plan, x, *params):
+        # a training pass never reads derived weights cached from earlier parameters: the module may stay in eval() mode while
+        # it trains (dropout 0), and an optimizer step that does not bump version counters leaves the cache key where it was
+        # (the backward below reuses what this call derives)
+        cache = mod.__dict__.get("_variant_cache")
+        if cache is not None:
+            cache.invalidate()
         h = run_hip(mod, G, x, plan, dataflow=False)
         ctx.mod, ctx.plan, ctx.h = mod, plan, h
         ctx.save_for_backward(x, *params)

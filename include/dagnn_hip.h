@@ -381,7 +381,9 @@ typedef struct dagnn_dataflow_args {
                             * cell's static-record buffer `stat` (dagnn_bwd_dataflow_static_bytes_h; zero-filled by the caller when
                             * H is neither 256 nor 320) and the kernel writes the state and the six gate-coefficient rows of each
                             * node's record instead of the pre-activations; `gi_out` must be NULL.  The reverse pass then only
-                            * adds the external-gradient row (dagnn_bwd_dataflow_args.stat_rows_written) */
+                            * adds the external-gradient row (dagnn_bwd_dataflow_args.stat_rows_written).  The records are
+                            * addressed with 32-bit byte offsets: N x 4 x (8 x 256) bytes (H <= 256) or N x 4 x (8 x 320) bytes
+                            * (H = 320) must stay below 2^32, otherwise the call returns DAGNN_EINVAL */
     int slices64;           /* nonzero and H = 256 / 320: the workgroup shape of csrc/dataflow_x.hip - 64 hidden units, 8 compute
                             * waves and one stream per workgroup, `groups` workgroup sets of (kernel cells x H / 64) workgroups
                             * (the caller guarantees they fit the device: groups <= 2 * floor(CUs / (cells x H / 32)), what

@@ -165,3 +165,80 @@ def check_ipropagate(name, step, device, tol):
             Hg = step(model, iprop_graphs(meta, arr, device), v, H=torch.from_numpy(arr["H_given"].copy()).to(device))
             assert maxdiff(Hg, arr["v%d_Hv_given" % v]) < tol
         assert step(model, iprop_graphs(meta, arr, device), n + 3) is None   # no graph has that vertex
+
+
+# ------------------------------------------------------------------ float64 references (the oracle's autograd at any size)
+_REF64 = {}
+
+
+def _cpu_state(model):
+    """`state_dict` on the CPU with its aliases kept (the D-VAE encoders register their GRUs under two names; the oracle
+    reports a gradient under every name of one storage)."""
+    seen, out = {}, {}
+    for k, v in model.state_dict().items():
+        key = (v.data_ptr(), tuple(v.shape), tuple(v.stride()))
+        if key not in seen:
+            seen[key] = v.detach().cpu()
+        out[k] = seen[key]
+    return out
+
+
+def code2_grads64(key, model, b, y, **kw):
+    """`(loss, {name: gradient})` of `O.code2_grads` in float64 for (model, batch, y): computed once per session and `key` (the
+    full-size cases cost ~30-60 s of CPU each; several GPU paths compare against the SAME reference).  `key=None`: not cached.
+    The oracle mutates its batch: it gets a deep copy."""
+    import copy
+    from oracle import dagnn_oracle as O
+    if key is None or key not in _REF64:
+        sd = _cpu_state(model)
+        loss, grads = O.code2_grads(sd, copy.deepcopy(b), y.cpu(), dtype=torch.float64, **kw)
+        # one module under several names (`agg` = add / max: ONE AggConv for every cell, dagnn.py:74-75) takes the sum of
+        # the gradients the oracle's separate leaves received, under each of its names
+        groups = {}
+        for k, v in sd.items():
+            if k in grads:
+                groups.setdefault((v.data_ptr(), tuple(v.shape), tuple(v.stride())), []).append(k)
+        for ks in groups.values():
+            if len(ks) > 1:
+                tot = sum(grads[k] for k in ks)
+                grads.update({k: tot for k in ks})
+        val = (loss, grads)
+        if key is None:
+            return val
+        _REF64[key] = val
+    return _REF64[key]
+
+
+def dvae_grads64(key, model, G, r1, r2, **kw):
+    """`(loss, {name: gradient})` of `O.dvae_grads` in float64 (loss <mu, r1> + <logvar, r2>), cached like `code2_grads64`."""
+    import copy
+    from oracle import dagnn_oracle as O
+    if key is None or key not in _REF64:
+        val = O.dvae_grads(_cpu_state(model), copy.deepcopy(G), r1.cpu(), r2.cpu(), dtype=torch.float64, **kw)
+        if key is None:
+            return val
+        _REF64[key] = val
+    return _REF64[key]
+
+
+def check_grads_full(model, ref, rtol=1e-4, atol=2e-7):
+    """Every named parameter's `.grad` (zeros where there is none) against the full reference gradient: max abs error
+    <= rtol x its largest entry + atol (`atol`: the mathematically zero gradients of the attention and edge-encoder biases
+    come out as rounding noise).  Returns (worst error relative to the largest entry, its parameter) over the gradients
+    larger than 100 x atol - the baseline a later change can be compared with."""
+    worst = (0.0, None)
+    for k, p in model.named_parameters():
+        r = ref[k] if k in ref else torch.zeros(p.shape, dtype=torch.float64)   # (the oracle omits what takes no part)
+        g = torch.zeros_like(p) if p.grad is None else p.grad
+        assert g.shape == r.shape, (k, g.shape, r.shape)
+        scale = float(r.abs().max())
+        err = maxdiff(g, r)
+        assert err <= rtol * scale + atol, "%s: max abs err %.3g at scale %.3g" % (k, err, scale)
+        if scale > 100 * atol:
+            worst = max(worst, (err / scale, k))
+    return worst
+
+
+def grad_norm64(model, ref):
+    """The float64 global 2-norm of the reference gradients of `model`'s parameters (what clip_grad_norm_ sees)."""
+    return float(torch.sqrt(sum((ref[k].double() ** 2).sum() for k, _ in model.named_parameters() if k in ref)))

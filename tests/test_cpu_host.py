@@ -120,6 +120,30 @@ def test_dataflow_argument_structs_carry_the_round6_fields():
     assert _lib.BwdDataflowArgs.stat_rows_written.offset >= _lib.BwdDataflowArgs.xcd_first.offset + 4
 
 
+@pytest.mark.parametrize("H,N", [(256, 600000), (256, 524288), (320, 420000)])
+def test_dataflow_refuses_static_rows_beyond_32_bit_record_offsets(H, N):
+    """With `stat_rows` the forward launch addresses every node's static record (8 rows of 256 floats, 320 for H = 320) with
+    a 32-bit byte offset: all three entry points refuse a batch whose records reach 2^32 bytes before any HIP call.  The same
+    struct is otherwise valid (N x granule pitch < 2^31, N < 2^24)."""
+    lib = _lib.load()
+    plan = _lib.Plan(64, 0, N, 2 * N, 1000, 2, 0)
+    a = _lib.DataflowArgs()
+    gld = H + H // 16
+    a.num_stacked, a.dir_mask, a.H, a.ld_h, a.gld, a.pld, a.groups, a.epoch = 1, 3, H, gld, gld, gld, 1, 1
+    a.schedule, a.err = 64, 64
+    for d in range(2):
+        c = a.cell[d][0]
+        c.w_hh = c.b_hh = c.w_key = c.h_out = c.granules = c.edge_gain = c.gi0 = c.gh_out = 64
+    a.stat_rows = 1
+    assert N * 8 * (320 if H > 256 else 256) * 4 >= 1 << 32 and N * gld < 1 << 31
+    assert lib.dagnn_dataflow_run(ctypes.byref(plan), ctypes.byref(a), None) == -22
+    entry = lib.dagnn_dataflow_run_wide if H > 256 else lib.dagnn_dataflow_run_x
+    assert entry(ctypes.byref(plan), ctypes.byref(a), None) == -22
+    a.slices64 = 1
+    assert lib.dagnn_dataflow_run(ctypes.byref(plan), ctypes.byref(a), None) == -22
+    assert lib.dagnn_dataflow_run_x(ctypes.byref(plan), ctypes.byref(a), None) == -22
+
+
 def test_engine_refuses_cpu_tensors():
     from dagnn_amd import engine
     with pytest.raises(_lib.DagnnHipError):

@@ -2352,3 +2352,231 @@ def test_tile_kernel_split_feeds_the_backward_pass(device, monkeypatch):
     for k, g in res[0][1].items():
         scale = max(float(g.abs().max()), 1e-6)
         assert float((res[1][1][k] - g).abs().max()) <= 2e-5 * scale + 2e-7, k
+
+
+# ----------------------------------------------------------------------------- training at the bench's own shapes, against float64
+def _spy_entries(monkeypatch, fields):
+    """{C entry point: [the named fields of its argument struct (second argument), one tuple per call]} - which paths a
+    pass really took (a flag that silently falls back to the default path must not pass for the path it names)."""
+    lib = engine._lib.load()
+    seen = {}
+    for name, fl in fields.items():
+        seen[name] = []
+        orig = getattr(lib, name)
+
+        def spy(*a, _name=name, _fl=fl, _orig=orig):
+            seen[_name].append(tuple(int(getattr(a[1]._obj, f)) for f in _fl))
+            return _orig(*a)
+        monkeypatch.setattr(lib, name, spy, raising=False)
+    return seen
+
+
+_TRAIN_ENTRIES = {"dagnn_dataflow_run": ("H", "stat_rows", "slices64"), "dagnn_bwd_dataflow_prepare": ("H", "stat_rows_written"),
+                  "dagnn_bwd_dataflow_run": ("H",), "dagnn_backward_run": ("H",)}
+
+
+def _full_size_training_step(device, model, b, y, key):
+    """One bench-shaped training step (fused loss, `ClipAdam(max_norm=0.25)`) against float64 autograd through the oracle:
+    the loss, every parameter's gradient (the `encoder.*` tables, the heads and the attention weights included) and the
+    global gradient norm `ClipAdam` clips with.  Returns (worst relative gradient error, its parameter)."""
+    from dagnn_amd.train import ClipAdam
+    L = model.num_layers
+    loss_ref, ref = Hh.code2_grads64(key, model, b, y, num_layers=L, bidirectional=True, max_seq_len=5)
+    model = model.to(device)
+    opt = ClipAdam(model.parameters(), lr=1e-3, max_norm=0.25)
+    loss, _ = _train_step(model, b.clone().to(device), y.to(device), fused_loss=True)
+    model.check()
+    assert abs(float(loss) - float(loss_ref)) < 1e-5, (float(loss), float(loss_ref))
+    worst = Hh.check_grads_full(model, ref)
+    opt.step()
+    norm_ref = Hh.grad_norm64(model, ref)
+    assert abs(float(opt.last_norm) - norm_ref) <= 1e-5 * norm_ref, (float(opt.last_norm), norm_ref)
+    print("%s: loss %.8f (float64 %.8f), worst relative gradient error %.3e on %s, norm %.6f (float64 %.6f)"
+          % (key, float(loss), float(loss_ref), worst[0], worst[1], float(opt.last_norm), norm_ref))
+    return worst
+
+
+@pytest.mark.parametrize("path", ["default", "stat_fwd0", "bwd_per_layer", "slices64"])
+def test_headline_training_step_matches_float64_autograd(device, monkeypatch, path):
+    """The bench's training leg at its own shape (B = 128, N = 16 561, T = 374 layers; h = 256, L = 2, 5 heads of 5002) against
+    float64 autograd: the reverse sweep (csrc/bwd_dataflow.hip) fed by the forward launch's static rows (the default), by
+    `bd_stat_kernel`'s records (`STAT_FWD=0`), the per-layer and persistent-tail launches of csrc/backward.hip
+    (`BWD_DATAFLOW=0`), and the 64-unit forward shape (csrc/dataflow_x.hip) - each against the same reference, and each
+    really on the path it names."""
+    flags = dict(BWD_DATAFLOW=1, STAT_FWD=1, DF_SLICES64=0)
+    flags.update({"stat_fwd0": dict(STAT_FWD=0), "bwd_per_layer": dict(BWD_DATAFLOW=0), "slices64": dict(DF_SLICES64=1)}.get(path, {}))
+    for k, v in flags.items():
+        monkeypatch.setattr(engine, k, v)
+    model = _headline_model(H=256, L=2, V=5002)
+    b = synth.code2_batch(0, 128)
+    y = torch.randint(0, 5002, (128, 5), generator=torch.Generator().manual_seed(128))
+    seen = _spy_entries(monkeypatch, _TRAIN_ENTRIES)
+    _full_size_training_step(device, model, b, y, "cfg2_train_f64")
+    fwd = seen["dagnn_dataflow_run"]
+    assert fwd and all(h == 256 and s64 == flags["DF_SLICES64"] for h, _, s64 in fwd), fwd
+    if path == "bwd_per_layer":
+        assert seen["dagnn_backward_run"] and not seen["dagnn_bwd_dataflow_run"], seen
+        assert [s for _, s, _ in fwd] == [0], fwd
+    else:
+        assert seen["dagnn_bwd_dataflow_run"] == [(256,)] and not seen["dagnn_backward_run"], seen
+        assert seen["dagnn_bwd_dataflow_prepare"] == [(256, flags["STAT_FWD"])], seen
+        assert [s for _, s, _ in fwd] == [flags["STAT_FWD"]], fwd
+
+
+def test_reference_training_shape_step_matches_float64_autograd(device, monkeypatch):
+    """The reference's training shape (emb_dim = hidden = 300, B = 160: N = 20 168; L = 2, 5 heads of 5002): the 320-wide forward
+    (csrc/dataflow_w.hip) writing the padded 320-float static records, the 320-wide reverse sweep (csrc/bwd_dataflow_w.hip),
+    against float64 autograd."""
+    model = _headline_model(H=300, L=2, V=5002, seed=6)
+    b = synth.code2_batch(0, 160)
+    y = torch.randint(0, 5002, (160, 5), generator=torch.Generator().manual_seed(160))
+    seen = _spy_entries(monkeypatch, _TRAIN_ENTRIES)
+    _full_size_training_step(device, model, b, y, "ogb_tok_h300_B160_train_f64")
+    assert seen["dagnn_dataflow_run"] == [(320, 1, 0)], seen
+    assert seen["dagnn_bwd_dataflow_prepare"] == [(320, 1)] and seen["dagnn_bwd_dataflow_run"] == [(320,)], seen
+    assert not seen["dagnn_backward_run"], seen
+
+
+@pytest.mark.parametrize("cfg", ["cfg1_na_B64_h128", "cfg4_bn_B128_h256"])
+def test_dvae_encoder_training_at_full_batch_matches_float64_autograd(device, cfg):
+    """The D-VAE encoders at the bench's batch sizes (cfg 1: NA, 64 ENAS graphs, hs 128, unidirectional; cfg 4: BN, 128 graphs,
+    hs 256, bidirectional; L = 2): gradients of <mu, r1> + <logvar, r2> against float64 autograd through the oracle (the
+    reference fixtures hold 12-32 graphs), and the norm `ClipAdam` clips with."""
+    from dagnn_amd import DAGNN_NA, DAGNN_BN
+    from dagnn_amd.train import ClipAdam
+    na = cfg.startswith("cfg1")
+    cls, nn_, hs, B, bidir = (DAGNN_NA, 8, 128, 64, False) if na else (DAGNN_BN, 10, 256, 128, True)
+    model = cls(nn_, hs, hs, nn_, nn_, 0, 1, hs=hs, nz=56, num_nodes=nn_, num_layers=2, bidirectional=bidir).eval()
+    seeded_fill(model, 4000 + B)
+    rows = synth.enas_rows(0, B) if na else synth.bn_rows(0, B)
+    G = synth.dvae_batch([(synth.decode_enas_row if na else synth.decode_bn_row)(r) for r in rows])
+    gen = torch.Generator().manual_seed(B)
+    r1, r2 = torch.randn(B, 56, generator=gen), torch.randn(B, 56, generator=gen)
+    loss_ref, ref = Hh.dvae_grads64(cfg, model, G, r1, r2, num_layers=2, bidirectional=bidir, num_nodes=nn_, vids=na)
+    model = model.to(device).train()
+    opt = ClipAdam(model.parameters(), lr=1e-3, max_norm=0.25)
+    model.zero_grad(set_to_none=True)
+    Hg = model(G.clone().to(device))
+    loss = (model.fc1(Hg) * r1.to(device)).sum() + (model.fc2(Hg) * r2.to(device)).sum()
+    loss.backward()
+    model.check()
+    assert abs(float(loss) - float(loss_ref)) < 1e-4 * max(1.0, abs(float(loss_ref))), (float(loss), float(loss_ref))
+    worst = Hh.check_grads_full(model, ref)
+    opt.step()
+    norm_ref = Hh.grad_norm64(model, ref)
+    assert abs(float(opt.last_norm) - norm_ref) <= 1e-5 * norm_ref, (float(opt.last_norm), norm_ref)
+    print("%s: loss %.6f (float64 %.6f), worst relative gradient error %.3e on %s" % (cfg, float(loss), float(loss_ref), *worst))
+
+
+# ----------------------------------------------------------------------------- optimizer steps reach every later pass
+_EVAL_MODE_PATHS = ["code2_default", "code2_h512_L3", "code2_gated_sum", "code2_mattn_h", "code2_add_dataflow",
+                    "code2_max_dataflow", "na_attn_h", "bn_attn_h", "na_add", "na_max", "bn_add", "bn_max"]
+
+
+def _eval_mode_case(path, device):
+    """(model on `device` in eval(), batch on the CPU, outputs of a pass, loss of the outputs, float64 oracle outputs of a state
+    dict, float64 oracle gradients of the model as it stands) for one path of `test_optimizer_steps_reach_every_later_pass`."""
+    if path.startswith("code2"):
+        from dagnn_amd import DAGNN, ASTNodeEncoder
+        H, L = (512, 3) if path == "code2_h512_L3" else (64, 2)
+        agg = {"gated_sum": "gated_sum", "mattn_h": "mattn_h", "add_dataflow": "add", "max_dataflow": "max"}.get(path[6:], "attn_h")
+        kw = dict(num_layers=L, bidirectional=True, out_wx=False, out_pool_all=False, out_pool="max")
+        model = DAGNN(num_vocab=24, max_seq_len=5, emb_dim=H, hidden_dim=H, out_dim=None, encoder=ASTNodeEncoder(H, 98, 10030, 20),
+                      w_edge_attr=True, agg=agg, dropout=0.0, **kw).eval()
+        seeded_fill(model, 500 + H + L)
+        b = synth.code2_batch(41, 10, 40)
+        y = torch.randint(0, 24, (10, 5), generator=torch.Generator().manual_seed(41))
+        model = model.to(device)
+        yd = y.to(device)
+        run = lambda: list(model(b.clone().to(device)))   # noqa: E731
+        loss_of = lambda out: sum(torch.nn.functional.cross_entropy(p, yd[:, s]) for s, p in enumerate(out)) / len(out)  # noqa: E731
+        ref_out = lambda sd: O.code2_forward(sd, copy.deepcopy(b), max_seq_len=5, agg=agg, dtype=torch.float64, **kw)  # noqa: E731
+        ref_grads = lambda: Hh.code2_grads64(None, model, b, y, max_seq_len=5, agg=agg, **kw)   # noqa: E731
+        return model, run, loss_of, ref_out, ref_grads
+    kind, agg = path.split("_", 1)
+    bidir = kind == "bn"
+    model, nn_ = Hh.dvae_model(dict(kind=kind, hs=64, L=2, bidir=bidir, agg=agg, w_seed=600 + len(path)))
+    rows = synth.enas_rows(5, 12) if kind == "na" else synth.bn_rows(6, 10)
+    G = synth.dvae_batch([(synth.decode_enas_row if kind == "na" else synth.decode_bn_row)(r) for r in rows])
+    gen = torch.Generator().manual_seed(7)
+    r1, r2 = torch.randn(len(rows), 56, generator=gen), torch.randn(len(rows), 56, generator=gen)
+    kw = dict(num_layers=2, bidirectional=bidir, num_nodes=nn_, vids=kind == "na", agg=agg)
+    model = model.to(device)
+    r1d, r2d = r1.to(device), r2.to(device)
+
+    def run():
+        Hg = model(G.clone().to(device))
+        return [model.fc1(Hg), model.fc2(Hg)]
+    loss_of = lambda out: (out[0] * r1d).sum() + (out[1] * r2d).sum()   # noqa: E731
+    ref_out = lambda sd: list(O.dvae_encode(sd, copy.deepcopy(G), dtype=torch.float64, **kw))   # noqa: E731
+    ref_grads = lambda: Hh.dvae_grads64(None, model, G, r1, r2, **kw)   # noqa: E731
+    return model, run, loss_of, ref_out, ref_grads
+
+
+@pytest.mark.parametrize("optim", ["clip_adam", "fused_adam"])
+@pytest.mark.parametrize("path", _EVAL_MODE_PATHS)
+def test_optimizer_steps_reach_every_later_pass(device, monkeypatch, path, optim):
+    """A training loop that leaves the module in eval() (dropout 0: both modes compute the same) and runs an evaluation pass
+    between `backward()` and the optimizer step - which builds the derived-weight caches from the OLD parameters.  With
+    `train.ClipAdam` (its kernel writes through raw pointers and bumps the version counters itself) the evaluation pass after
+    the step and the next training pass must see the new parameters: outputs and gradients against the float64 oracle on the
+    updated state.  `torch.optim.Adam(fused=True)` moves no version counter; there the stale evaluation pass must at least be
+    reported at `check()`.  Paths: code2 on the dataflow kernel and the tile kernel (H = 512), the variants on
+    csrc/variants.hip and `add` / `max` on the dataflow kernel, the D-VAE encoders with `attn_h`, `add` and `max`."""
+    from dagnn_amd.train import ClipAdam
+    monkeypatch.setattr(engine, "VARIANT_DATAFLOW", 1)
+    model, run, loss_of, ref_out, ref_grads = _eval_mode_case(path, device)
+    params = [p for p in model.parameters() if p.requires_grad]
+    opt = ClipAdam(params, lr=1e-2, max_norm=0.25) if optim == "clip_adam" else torch.optim.Adam(params, lr=1e-2, fused=True)
+    model.zero_grad(set_to_none=True)
+    loss_of(run()).backward()                                    # 1. a training pass (the module stays in eval())
+    with torch.no_grad():
+        before = [o.clone() for o in run()]                      # 2. evaluation: caches built from the old parameters
+    opt.step()                                                   # 3.
+    with torch.no_grad():
+        after = [o.clone() for o in run()]                       # 4.
+    assert not model.training
+    if optim == "fused_adam":
+        with pytest.raises(DagnnHipError, match="version counter"):
+            model.check()                                        # (stale or not: the pass after the silent write is reported)
+        return
+    model.zero_grad(set_to_none=True)
+    loss = loss_of(run())                                        # 5. the next training pass
+    loss.backward()
+    model.check()
+    assert max(Hh.maxdiff(a, c) for a, c in zip(after, before)) > 1e-4   # (the step really happened)
+    sd = Hh._cpu_state(model)
+    for o, r in zip(after, ref_out(sd)):
+        assert Hh.maxdiff(o, r) <= TOL * max(1.0, float(r.abs().max()))
+    loss_ref, ref = ref_grads()
+    # (the neighbouring tests' loss tolerances: 1e-5 for the mean cross-entropy, 1e-4 relative for the D-VAE sums)
+    assert abs(float(loss) - float(loss_ref)) < (1e-5 if path.startswith("code2") else 1e-4 * max(1.0, abs(float(loss_ref))))
+    Hh.check_grads_full(model, ref)
+
+
+def test_fused_loss_backward_can_run_twice(device):
+    """`backward(retain_graph=True)` twice through the fused sequence loss (csrc/loss.hip) accumulates exactly twice the
+    gradients of one pass, as the loss loop does - and the same gradients as the loop."""
+    from dagnn_amd.train import seq_cross_entropy
+    model = _headline_model(H=64, L=2, V=40, seed=3).to(device).train()
+    b = synth.code2_batch(17, 16, 40)
+    y = torch.randint(0, 40, (16, 5), generator=torch.Generator().manual_seed(6)).to(device)
+    got = {}
+    for fused in (True, False):
+        for times in (1, 2):
+            model.zero_grad(set_to_none=True)
+            pred = model(b.clone().to(device))
+            loss = seq_cross_entropy(pred, y) if fused else \
+                sum(torch.nn.functional.cross_entropy(p, y[:, s]) for s, p in enumerate(pred)) / len(pred)
+            for _ in range(times):
+                loss.backward(retain_graph=True)
+            got[(fused, times)] = {k: p.grad.clone() for k, p in model.named_parameters() if p.grad is not None}
+    one, two = got[(True, 1)], got[(True, 2)]
+    assert one.keys() == two.keys() and "graph_pred_linear_list.4.weight" in one
+    for k in one:
+        if "encoder." not in k:   # (torch's embedding backward accumulates with atomics)
+            assert torch.equal(two[k], 2 * one[k]), k
+        else:
+            assert Hh.maxdiff(two[k], 2 * one[k]) <= 1e-6 * max(1.0, float(one[k].abs().max())), k
+        ref = got[(False, 2)][k]
+        assert Hh.maxdiff(two[k], ref) <= 2e-6 * max(1.0, float(ref.abs().max())) + 1e-9, k
