@@ -199,6 +199,30 @@ class IpropLayer(C.Structure):
     _fields_ = [("w_ih", C.c_void_p), ("w_hh", C.c_void_p), ("b_ih", C.c_void_p), ("b_hh", C.c_void_p), ("in_dim", C.c_int)]
 
 
+MAX_STACKED = 8   # DAGNN_MAX_STACKED
+DVAE_MAX_N = 32   # DAGNN_DVAE_MAX_N
+
+
+class DvaeDecodeArgs(C.Structure):
+    _fields_ = [("B", C.c_int64), ("n", C.c_int), ("hs", C.c_int), ("L", C.c_int), ("nvt", C.c_int), ("start_type", C.c_int),
+                ("bn", C.c_int), ("edge_hidden", C.c_int), ("vertex_hidden", C.c_int),
+                ("types", C.c_void_p), ("preds", C.c_void_p), ("h0", C.c_void_p),
+                ("w_ih", C.c_void_p * MAX_STACKED), ("w_hh", C.c_void_p * MAX_STACKED), ("b_ih", C.c_void_p * MAX_STACKED),
+                ("b_hh", C.c_void_p * MAX_STACKED), ("w_key", C.c_void_p), ("vid_bias", C.c_void_p),
+                ("av_w1", C.c_void_p), ("av_b1", C.c_void_p), ("av_w2", C.c_void_p), ("av_b2", C.c_void_p),
+                ("ae_w1", C.c_void_p), ("ae_b1", C.c_void_p), ("ae_w2", C.c_void_p), ("ae_b2", C.c_void_p),
+                ("ll", C.c_void_p), ("saved", C.c_void_p), ("saved_bytes", C.c_size_t)]
+
+
+class DvaeDecodeGrads(C.Structure):
+    _fields_ = [("g_res", C.c_void_p), ("work", C.c_void_p), ("work_bytes", C.c_size_t), ("d_h0", C.c_void_p),
+                ("d_w_ih", C.c_void_p * MAX_STACKED), ("d_w_hh", C.c_void_p * MAX_STACKED),
+                ("d_b_ih", C.c_void_p * MAX_STACKED), ("d_b_hh", C.c_void_p * MAX_STACKED),
+                ("d_w_key", C.c_void_p), ("d_vid_bias", C.c_void_p),
+                ("d_av_w1", C.c_void_p), ("d_av_b1", C.c_void_p), ("d_av_w2", C.c_void_p), ("d_av_b2", C.c_void_p),
+                ("d_ae_w1", C.c_void_p), ("d_ae_b1", C.c_void_p), ("d_ae_w2", C.c_void_p), ("d_ae_b2", C.c_void_p)]
+
+
 class VariantBwdCell(C.Structure):
     _fields_ = [("mode", C.c_int32), ("lands", C.c_int32), ("in_dim", C.c_int32), ("proj_dim", C.c_int32),
                 ("recurrent", C.c_int32), ("reserved", C.c_int32)] + \
@@ -305,6 +329,10 @@ SYMBOLS = {
     "dagnn_iprop_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.c_void_p, C.c_int, C.POINTER(IpropLayer), C.c_int, C.c_void_p, C.c_void_p]),
     "dagnn_encode_forward": (C.c_int, [C.POINTER(EncodeArgs), C.c_void_p]),
+    "dagnn_dvae_decode_saved_bytes": (C.c_size_t, [C.POINTER(DvaeDecodeArgs)]),
+    "dagnn_dvae_decode_work_bytes": (C.c_size_t, [C.POINTER(DvaeDecodeArgs)]),
+    "dagnn_dvae_decode_forward": (C.c_int, [C.POINTER(DvaeDecodeArgs), C.c_void_p]),
+    "dagnn_dvae_decode_backward": (C.c_int, [C.POINTER(DvaeDecodeArgs), C.POINTER(DvaeDecodeGrads), C.c_void_p]),
     "dagnn_debug_occupy": (C.c_int, [C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p]),
     "dagnn_tn_product": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                    C.c_void_p]),

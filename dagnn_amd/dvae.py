@@ -3,15 +3,18 @@ there) for ENAS neural-architecture DAGs and `DAGNN_BN` (`dvae/dagnn_bn.py:19-17
 Bayesian-network DAGs.
 
 Constructor arguments, parameter names and shapes follow the reference (including the decoder-side
-parameters of `DVAE_PYG` / `DVAE_BN_PYG`, `dvae/models_pyg.py:18-85,539-560`, which this build
-does not use but keeps so that `state_dict`s are interchangeable).  `forward(G)` / `encode(list)`
-run the layer-by-layer message passing in HIP; the igraph teacher-forced decoder and loss are out
-of scope.
+parameters of `DVAE_PYG` / `DVAE_BN_PYG`, `dvae/models_pyg.py:18-85,539-560`: `loss()` trains
+fc3 / grud / add_vertex / add_edge; the rest is kept so that `state_dict`s are interchangeable).  `forward(G)` / `encode(list)`
+run the layer-by-layer message passing in HIP; `loss(mu, logvar, G_true)` runs the teacher-forced decoder of
+`DVAE_PYG.loss()` (`dvae/models_pyg.py:398-456`) and its reverse pass in HIP (csrc/dvae_decode.hip); `decode()`
+(sampling) is out of scope.
 """
 from __future__ import annotations
 
 import copy
 from typing import List
+
+import numpy as np
 
 import torch
 import torch.nn as nn
@@ -148,6 +151,77 @@ class _IpropStep(torch.autograd.Function):
             for slot, g in zip(slots, torch.autograd.grad(out, leaves, g_states.contiguous(), allow_unused=True)):
                 grads[slot] = g
         return tuple(grads)
+
+
+def decode_schedule(G_true, max_n: int, nvt: int):
+    """What the teacher-forced decoder reads of the true graphs: types [B, max_n] (`g.vs[v]['type']`, as
+    `models_pyg.py:405-406` reads them) and predecessor bitmasks [B, max_n] (bit u of preds[b, v]: the edge u -> v,
+    from `g.edge_index` as `:417-420`), both int32.  Every graph must have exactly max_n vertices."""
+    B = len(G_true)
+    if max_n > 32:
+        raise ValueError("loss(): at most 32 vertices per graph (got max_n=%d)" % max_n)
+    types = np.empty((B, max_n), dtype=np.int64)
+    preds = np.zeros((B, max_n), dtype=np.uint32)
+    for b, g in enumerate(G_true):
+        if int(g.x.shape[0]) != max_n:
+            raise ValueError("loss(): every graph must have exactly max_n=%d vertices (graph %d has %d)"
+                             % (max_n, b, int(g.x.shape[0])))
+        types[b] = [int(g.vs[v]["type"]) for v in range(max_n)]
+        ei = g.edge_index
+        ei = ei.cpu().numpy() if isinstance(ei, torch.Tensor) else np.asarray(ei)
+        src, dst = ei[0].astype(np.int64), ei[1].astype(np.int64)
+        keep = (src < dst) & (dst < max_n) & (src >= 0)
+        np.bitwise_or.at(preds[b], dst[keep], (np.uint32(1) << src[keep].astype(np.uint32)))
+    if B and (types[:, 1:].min() < 0 or types.max() >= nvt):
+        raise ValueError("loss(): vertex types must lie in [0, nvt=%d)" % nvt)
+    return types.astype(np.int32), preds.view(np.int32)
+
+
+def update_widths(preds: np.ndarray, max_n: int) -> List[int]:
+    """The padding width P of every `_update_iv` call of the teacher-forced decoder, in the reference's call order
+    (vertex 0 with H0 given: 0; then per vertex v: the fresh update, then one per earlier vertex vi = v-1 .. 0): the
+    largest number of true predecessors >= vi over the batch - the same numbers the device derives from the masks."""
+    m = preds.view(np.uint32)
+    out = [0]
+    for v in range(1, max_n):
+        for k in range(v, -1, -1):
+            sel = m[:, v] & np.uint32(((1 << v) - 1) & ~((1 << k) - 1))
+            out.append(int(max(bin(int(x)).count("1") for x in sel)) if len(sel) else 0)
+    return out
+
+
+class _DecodeLoss(torch.autograd.Function):
+    """`res` of `DVAE_PYG.loss()` (the negative log-likelihood of the true graphs under teacher forcing) as ONE call of
+    `dagnn_dvae_decode_forward`; its gradients as ONE call of `dagnn_dvae_decode_backward`.  Inputs after the fixed
+    ones: attn_lin.weight, then 4 tensors per grud cell, add_vertex.{0,2}.{weight,bias}, add_edge.{0,2}.{weight,bias}."""
+
+    @staticmethod
+    def forward(ctx, spec, types, preds, h0, attn_w, *params):
+        dec = _make_decode(spec, types, preds, h0, attn_w, params)
+        ll = dec.forward()
+        ctx.dec, ctx.spec = dec, spec
+        ctx.save_for_backward(h0, attn_w, *params)   # (version checks: backward reads these through the saved pointers)
+        return ll[2 * h0.shape[0]].clone()
+
+    @staticmethod
+    def backward(ctx, g_res):
+        ctx.saved_tensors   # raises if a parameter was modified in place since the forward call
+        spec, dec = ctx.spec, ctx.dec
+        d_attn = torch.zeros_like(ctx.saved_tensors[1])
+        d_h0, d_cells, d_av, d_ae = dec.backward(g_res, d_attn, spec["dq"], spec["dq"] + spec["hs"] if spec["vid"] else None)
+        ctx.dec = None
+        flat = [t for c in d_cells for t in c] + d_av + d_ae
+        return (None, None, None, d_h0, d_attn) + tuple(flat)
+
+
+def _make_decode(spec, types, preds, h0, attn_w, params):
+    L, hs, dq = spec["L"], spec["hs"], spec["dq"]
+    w = attn_w.detach()[0]
+    cells = [tuple(params[4 * l:4 * l + 4]) for l in range(L)]
+    av, ae = list(params[4 * L:4 * L + 4]), list(params[4 * L + 4:4 * L + 8])
+    return engine.DvaeDecode(spec["n"], spec["nvt"], spec["start_type"], spec["bn"], dict(
+        h0=h0.detach(), types=types, preds=preds, cells=cells, w_key=w[dq:dq + hs],
+        vid_bias=w[dq + hs:dq + hs + spec["n"]] if spec["vid"] else None, av=av, ae=ae))
 
 
 class _DvaeBase(nn.Module):
@@ -640,6 +714,51 @@ class _DvaeDagnn(_DvaeBase):
         Hg = self(b)
         return self.fc1(Hg), self.fc2(Hg)
 
+
+    # ------------------------------------------------------------------ teacher-forced decoder loss (dvae/models_pyg.py:324-456)
+    def reparameterize(self, mu, logvar, eps_scale=0.01):
+        """z ~ N(mu, std) in training mode, mu in evaluation mode (`models_pyg.py:324-331`)."""
+        if self.training:
+            std = logvar.mul(0.5).exp_()
+            eps = torch.randn_like(std) * eps_scale
+            return eps.mul(std).add_(mu)
+        return mu
+
+    def loss(self, mu, logvar, G_true, beta=0.005):
+        """`(res + beta * kld, res, kld)` of `DVAE_PYG.loss()` (`models_pyg.py:398-456`): the negative log-likelihood of
+        the true graphs under the teacher-forced decoder plus the KL term.  The decoder and its reverse pass are HIP
+        (csrc/dvae_decode.hip: one library call each); the schedule (types, predecessor masks) is built once on the host
+        and copied once.  Gradients reach mu / logvar, fc3, grud, attn_lin (key / vertex-id part), add_vertex and
+        add_edge.  Graphs must have exactly max_n vertices; agg must be attn_h."""
+        if self.agg != K.NA_ATTN_H:
+            raise NotImplementedError("loss(): the teacher-forced decoder is built for agg='attn_h' (the reference's D-VAE "
+                                      "default, dvae/train.py:86), not %r" % (self.agg,))
+        if type(G_true) != list:
+            G_true = [G_true]
+        types, preds = decode_schedule(G_true, self.max_n, self.nvt)
+        if len(G_true) != mu.shape[0]:
+            raise ValueError("loss(): %d graphs for %d latent rows" % (len(G_true), mu.shape[0]))
+        z = self.reparameterize(mu, logvar)
+        H0 = self.tanh(self.fc3(z))
+        if not H0.is_cuda:
+            raise engine.DagnnHipError("loss(): the model must live on a ROCm GPU - the teacher-forced decoder is HIP "
+                                       "(csrc/dvae_decode.hip) and has no CPU path")
+        dev = H0.device
+        t_types = torch.from_numpy(types).pin_memory().to(dev, non_blocking=True)
+        t_preds = torch.from_numpy(preds).pin_memory().to(dev, non_blocking=True)
+        cells = list(self.grud)[:self.num_layers]
+        attn_w = self.node_aggr_0[0].attn_lin.weight
+        params = [t for c in cells for t in (c.weight_ih, c.weight_hh, c.bias_ih, c.bias_hh)]
+        params += [self.add_vertex[0].weight, self.add_vertex[0].bias, self.add_vertex[2].weight, self.add_vertex[2].bias,
+                   self.add_edge[0].weight, self.add_edge[0].bias, self.add_edge[2].weight, self.add_edge[2].bias]
+        spec = dict(n=self.max_n, nvt=self.nvt, start_type=int(self.START_TYPE), bn=not self._use_vids, vid=self._use_vids,
+                    L=len(cells), hs=self.hs, dq=self._key_offset(0))
+        if torch.is_grad_enabled() and any(t.requires_grad for t in [H0, attn_w] + params):
+            res = _DecodeLoss.apply(spec, t_types, t_preds, H0, attn_w, *params)
+        else:   # (no autograd record: the saved activations die with this call)
+            res = _make_decode(spec, t_types, t_preds, H0, attn_w, params).forward()[2 * H0.shape[0]].clone()
+        kld = -0.5 * torch.sum(1 + logvar - mu.pow(2) - logvar.exp())
+        return res + beta * kld, res, kld
 
     # ------------------------------------------------------------------ decoder-side single-vertex step (SURVEY §8 f4)
     def _get_zeros(self, n, length):

@@ -1585,3 +1585,94 @@ def topo_layers(edge_index: torch.Tensor, batch: torch.Tensor, num_graphs: int):
     check(_lib.load().dagnn_topo_layers(edge_index.data_ptr(), batch.data_ptr(), N, E, int(num_graphs), lf.data_ptr(),
                                         lb.data_ptr(), status.data_ptr(), _stream(batch)), "dagnn_topo_layers")
     return lf, lb, status
+
+
+# ------------------------------------------------------------------ teacher-forced D-VAE decoder (csrc/dvae_decode.hip)
+class DvaeDecode(object):
+    """One teacher-forced decode (`dagnn_dvae_decode_forward` / `_backward`): the argument struct, the tensors its pointers
+    borrow, and the saved activations of the forward call.  `tensors`: dict with h0 [B,hs], types / preds [B,n] int32,
+    w_key [hs], vid_bias [n] or None, cells (list of (w_ih, w_hh, b_ih, b_hh)), av / ae (lists of (w1, b1, w2, b2))."""
+
+    def __init__(self, n: int, nvt: int, start_type: int, bn: bool, tensors: dict):
+        h0 = _dev(tensors["h0"], "H0", torch.float32)
+        dev = h0.device
+        self.keep = {"h0": h0}
+        f = lambda t, what: _dev(t.detach(), what, torch.float32)  # noqa: E731
+        a = _lib.DvaeDecodeArgs()
+        B, hs = h0.shape
+        cells = tensors["cells"]
+        a.B, a.n, a.hs, a.L, a.nvt, a.start_type, a.bn = B, n, hs, len(cells), nvt, start_type, int(bool(bn))
+        types = _dev(tensors["types"], "types", torch.int32)
+        preds = _dev(tensors["preds"], "predecessor masks", torch.int32)
+        a.types, a.preds, a.h0 = types.data_ptr(), preds.data_ptr(), h0.data_ptr()
+        keep = [types, preds]
+        if len(cells) > _lib.MAX_STACKED:
+            raise DagnnHipError("dagnn_dvae_decode: at most %d stacked cells" % _lib.MAX_STACKED)
+        for l, c in enumerate(cells):
+            ts = [f(t, "grud parameter") for t in c]
+            keep += ts
+            a.w_ih[l], a.w_hh[l], a.b_ih[l], a.b_hh[l] = (t.data_ptr() for t in ts)
+        wk = f(tensors["w_key"], "w_key")
+        vb = None if tensors.get("vid_bias") is None else f(tensors["vid_bias"], "vid_bias")
+        a.w_key, a.vid_bias = wk.data_ptr(), _ptr(vb)
+        av = [f(t, "add_vertex parameter") for t in tensors["av"]]
+        ae = [f(t, "add_edge parameter") for t in tensors["ae"]]
+        a.av_w1, a.av_b1, a.av_w2, a.av_b2 = (t.data_ptr() for t in av)
+        a.ae_w1, a.ae_b1, a.ae_w2, a.ae_b2 = (t.data_ptr() for t in ae)
+        a.vertex_hidden, a.edge_hidden = av[0].shape[0], ae[0].shape[0]
+        # the library reads these through bare pointers: every shape is checked here
+        V1, E1, ein = av[0].shape[0], ae[0].shape[0], (3 if bn else 2) * hs
+        want = [(types, (B, n)), (preds, (B, n)), (wk, (hs,)), (av[0], (V1, hs)), (av[1], (V1,)), (av[2], (nvt, V1)), (av[3], (nvt,)),
+                (ae[0], (E1, ein)), (ae[1], (E1,)), (ae[2], (1, E1)), (ae[3], (1,))]
+        if vb is not None:
+            want.append((vb, (n,)))
+        for l in range(len(cells)):
+            w_ih, w_hh, b_ih, b_hh = keep[2 + 4 * l:6 + 4 * l]
+            want += [(w_ih, (3 * hs, nvt if l == 0 else hs)), (w_hh, (3 * hs, hs)), (b_ih, (3 * hs,)), (b_hh, (3 * hs,))]
+        for t, shape in want:
+            if tuple(t.shape) != shape:
+                raise ValueError("dagnn_dvae_decode: a tensor of shape %s where %s is needed" % (tuple(t.shape), shape))
+        keep += [wk, vb] + av + ae
+        self.ll = torch.empty(2 * B + 1, dtype=torch.float32, device=dev)
+        a.ll = self.ll.data_ptr()
+        lib = _lib.load()
+        nbytes = lib.dagnn_dvae_decode_saved_bytes(C.byref(a))
+        if nbytes == 0:
+            raise DagnnHipError("dagnn_dvae_decode: unsupported shape (B=%d, n=%d, hs=%d, L=%d, nvt=%d)" % (B, n, hs, len(cells), nvt))
+        self.saved = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=dev)
+        a.saved, a.saved_bytes = self.saved.data_ptr(), nbytes
+        self.args, self.tensors, self.B, self.hs, self.L = a, keep, B, hs, len(cells)
+        self.av, self.ae, self.cells, self.h0 = av, ae, keep[2:2 + 4 * len(cells)], h0
+
+    def forward(self) -> torch.Tensor:
+        """Runs the decode; returns ll [2B+1]: per-graph vertex and edge log-likelihoods, then res."""
+        check(_lib.load().dagnn_dvae_decode_forward(C.byref(self.args), _stream(self.h0)), "dagnn_dvae_decode_forward")
+        return self.ll
+
+    def backward(self, g_res: torch.Tensor, d_attn: torch.Tensor, key_off: int, vid_off: Optional[int]):
+        """Gradients of res (scaled by the device scalar g_res) for h0, the cells, the add_vertex / add_edge tensors;
+        the key / vertex-id parts are written into the zeroed `d_attn` (a [1, D] attn_lin.weight gradient) at the given
+        column offsets.  Returns (d_h0, [per cell (d_w_ih, d_w_hh, d_b_ih, d_b_hh)], d_av, d_ae)."""
+        lib = _lib.load()
+        g_res = _dev(g_res.reshape(1), "grad", torch.float32)
+        nbytes = lib.dagnn_dvae_decode_work_bytes(C.byref(self.args))
+        work = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=self.h0.device)
+        g = _lib.DvaeDecodeGrads()
+        g.g_res, g.work, g.work_bytes = g_res.data_ptr(), work.data_ptr(), nbytes
+        d_h0 = torch.empty_like(self.h0)
+        g.d_h0 = d_h0.data_ptr()
+        d_cells = []
+        for l in range(self.L):
+            ts = [torch.empty_like(t) for t in self.cells[4 * l:4 * l + 4]]
+            d_cells.append(ts)
+            g.d_w_ih[l], g.d_w_hh[l], g.d_b_ih[l], g.d_b_hh[l] = (t.data_ptr() for t in ts)
+        d_av = [torch.empty_like(t) for t in self.av]
+        d_ae = [torch.empty_like(t) for t in self.ae]
+        g.d_av_w1, g.d_av_b1, g.d_av_w2, g.d_av_b2 = (t.data_ptr() for t in d_av)
+        g.d_ae_w1, g.d_ae_b1, g.d_ae_w2, g.d_ae_b2 = (t.data_ptr() for t in d_ae)
+        if not d_attn.is_contiguous():
+            raise DagnnHipError("dagnn_dvae_decode_backward: the attn_lin gradient must be contiguous")
+        g.d_w_key = d_attn.data_ptr() + 4 * key_off
+        g.d_vid_bias = None if vid_off is None else d_attn.data_ptr() + 4 * vid_off
+        check(lib.dagnn_dvae_decode_backward(C.byref(self.args), C.byref(g), _stream(self.h0)), "dagnn_dvae_decode_backward")
+        return d_h0, d_cells, d_av, d_ae

@@ -862,6 +862,75 @@ int dagnn_iprop_step(const float* values, const int32_t* pred_vid, int64_t B, in
                      const dagnn_iprop_layer* layers /* host [L] */, int L, float* states, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Teacher-forced D-VAE decoder: `DVAE_PYG.loss()` (dvae/models_pyg.py:398-456) without the latent part - H0 =
+ * tanh(fc3(z)) and the KL term stay with the caller - for graphs of exactly n vertices.  One call issues every launch
+ * of the decode: the n-1 vertex steps with all v+1 updates of vertex v (`_update_iv`, dvae/dagnn.py:187-239 /
+ * dvae/dagnn_bn.py:179-238, the padded soft-max quirk included) at once per stacked layer, then the vertex head
+ * (log-softmax at the true type, models_pyg.py:410-414) and the edge head (sigmoid score and torch's
+ * binary_cross_entropy with its log clamp at -100, :423-448) over all rows.  `bn` = 1: the graph state is the sum of
+ * the top states of vertices 0..v-1 and the edge head reads [H_vi, H_v, H0] (models_pyg.py:591-614, 733-736); bn = 0:
+ * the top state of v-1 and [H_vi, H_v].
+ *   types [B,n] int32: true vertex types (vertex 0 is decoded as start_type whatever it holds);
+ *   preds [B,n] uint32: bit u of preds[b,v] = the true edge u -> v (u < v);
+ *   h0 [B,hs]; w_key [hs] and vid_bias [n] (NULL for BN): the key half of node_aggr_0[0].attn_lin.weight;
+ *   grud cell l: torch GRUCell tensors (layer 0 reads nvt-wide one-hot inputs, the others hs);
+ *   av_* / ae_*: add_vertex.{0,2} / add_edge.{0,2} weight and bias (edge_hidden = add_edge.0 rows,
+ *   vertex_hidden = add_vertex.0 rows);
+ *   ll [2B+1]: vertex log-likelihood per graph, edge log-likelihood per graph, then res = -(sum of both), all reduced
+ *   in a fixed order;
+ *   saved: the activations the reverse pass reads, >= dagnn_dvae_decode_saved_bytes(args) bytes.
+ * dagnn_dvae_decode_backward reads the same args (and the saved activations of the forward call) and writes - not
+ * accumulates - d res scaled by the device scalar *g_res for every input above; d_w_key / d_vid_bias may point into one
+ * zeroed attn_lin.weight gradient.  `work` >= dagnn_dvae_decode_work_bytes(args) bytes.  Both are bitwise deterministic
+ * (no float atomics).  The size queries return 0 for arguments the entry points refuse with DAGNN_EINVAL.
+ * ---------------------------------------------------------------------------------------- */
+#define DAGNN_DVAE_MAX_N 32
+#define DAGNN_DVAE_MAX_TYPES 64
+typedef struct dagnn_dvae_decode_args {
+    int64_t B;               /* graphs */
+    int n;                   /* vertices per graph (max_n), 2..DAGNN_DVAE_MAX_N */
+    int hs;                  /* state width */
+    int L;                   /* stacked grud cells, 1..DAGNN_MAX_STACKED */
+    int nvt;                 /* vertex types, 1..DAGNN_DVAE_MAX_TYPES */
+    int start_type;
+    int bn;                  /* 0: D-VAE (NA), 1: D-VAE for Bayesian networks */
+    int edge_hidden, vertex_hidden;
+    const int32_t* types;
+    const uint32_t* preds;
+    const float* h0;
+    const float* w_ih[DAGNN_MAX_STACKED];
+    const float* w_hh[DAGNN_MAX_STACKED];
+    const float* b_ih[DAGNN_MAX_STACKED];
+    const float* b_hh[DAGNN_MAX_STACKED];
+    const float* w_key;
+    const float* vid_bias;
+    const float *av_w1, *av_b1, *av_w2, *av_b2;
+    const float *ae_w1, *ae_b1, *ae_w2, *ae_b2;
+    float* ll;
+    float* saved;
+    size_t saved_bytes;
+} dagnn_dvae_decode_args;
+typedef struct dagnn_dvae_decode_grads {
+    const float* g_res;      /* device scalar: d loss / d res */
+    float* work;
+    size_t work_bytes;
+    float* d_h0;
+    float* d_w_ih[DAGNN_MAX_STACKED];
+    float* d_w_hh[DAGNN_MAX_STACKED];
+    float* d_b_ih[DAGNN_MAX_STACKED];
+    float* d_b_hh[DAGNN_MAX_STACKED];
+    float* d_w_key;
+    float* d_vid_bias;
+    float *d_av_w1, *d_av_b1, *d_av_w2, *d_av_b2;
+    float *d_ae_w1, *d_ae_b1, *d_ae_w2, *d_ae_b2;
+} dagnn_dvae_decode_grads;
+size_t dagnn_dvae_decode_saved_bytes(const dagnn_dvae_decode_args* args /* host */);
+size_t dagnn_dvae_decode_work_bytes(const dagnn_dvae_decode_args* args /* host */);
+int dagnn_dvae_decode_forward(const dagnn_dvae_decode_args* args /* host */, void* stream);
+int dagnn_dvae_decode_backward(const dagnn_dvae_decode_args* args /* host */, const dagnn_dvae_decode_grads* grads /* host */,
+                               void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Topological layering on the device: replaces `top_sort` / `add_order_info_01` (src/utils_dag.py:8-52) for a
  * whole collated batch.  layer_fwd[v] = longest-path distance of v from any source, layer_bwd[v] = the same on
  * the flipped edges; both int64 [N], i.e. `_bi_layer_idx0/1` (`_bi_layer_index0/1` is arange(N)).  `batch`
