@@ -223,6 +223,18 @@ class DvaeDecodeGrads(C.Structure):
                 ("d_ae_w1", C.c_void_p), ("d_ae_b1", C.c_void_p), ("d_ae_w2", C.c_void_p), ("d_ae_b2", C.c_void_p)]
 
 
+class DvaeSampleArgs(C.Structure):
+    _fields_ = [("G", C.c_int64), ("B", C.c_int64), ("n", C.c_int), ("hs", C.c_int), ("L", C.c_int), ("nvt", C.c_int),
+                ("start_type", C.c_int), ("end_type", C.c_int), ("bn", C.c_int), ("stochastic", C.c_int),
+                ("edge_hidden", C.c_int), ("vertex_hidden", C.c_int), ("h0", C.c_void_p),
+                ("w_ih", C.c_void_p * MAX_STACKED), ("w_hh", C.c_void_p * MAX_STACKED), ("b_ih", C.c_void_p * MAX_STACKED),
+                ("b_hh", C.c_void_p * MAX_STACKED), ("w_key", C.c_void_p), ("vid_bias", C.c_void_p),
+                ("av_w1", C.c_void_p), ("av_b1", C.c_void_p), ("av_w2", C.c_void_p), ("av_b2", C.c_void_p),
+                ("ae_w1", C.c_void_p), ("ae_b1", C.c_void_p), ("ae_w2", C.c_void_p), ("ae_b2", C.c_void_p),
+                ("u_type", C.c_void_p), ("u_edge", C.c_void_p), ("types", C.c_void_p), ("preds", C.c_void_p),
+                ("nv", C.c_void_p), ("states", C.c_void_p), ("work", C.c_void_p), ("work_bytes", C.c_size_t)]
+
+
 class VariantBwdCell(C.Structure):
     _fields_ = [("mode", C.c_int32), ("lands", C.c_int32), ("in_dim", C.c_int32), ("proj_dim", C.c_int32),
                 ("recurrent", C.c_int32), ("reserved", C.c_int32)] + \
@@ -333,6 +345,8 @@ SYMBOLS = {
     "dagnn_dvae_decode_work_bytes": (C.c_size_t, [C.POINTER(DvaeDecodeArgs)]),
     "dagnn_dvae_decode_forward": (C.c_int, [C.POINTER(DvaeDecodeArgs), C.c_void_p]),
     "dagnn_dvae_decode_backward": (C.c_int, [C.POINTER(DvaeDecodeArgs), C.POINTER(DvaeDecodeGrads), C.c_void_p]),
+    "dagnn_dvae_sample_work_bytes": (C.c_size_t, [C.POINTER(DvaeSampleArgs)]),
+    "dagnn_dvae_sample": (C.c_int, [C.POINTER(DvaeSampleArgs), C.c_void_p]),
     "dagnn_debug_occupy": (C.c_int, [C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p]),
     "dagnn_tn_product": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                    C.c_void_p]),

@@ -6,12 +6,14 @@ Constructor arguments, parameter names and shapes follow the reference (includin
 parameters of `DVAE_PYG` / `DVAE_BN_PYG`, `dvae/models_pyg.py:18-85,539-560`: `loss()` trains
 fc3 / grud / add_vertex / add_edge; the rest is kept so that `state_dict`s are interchangeable).  `forward(G)` / `encode(list)`
 run the layer-by-layer message passing in HIP; `loss(mu, logvar, G_true)` runs the teacher-forced decoder of
-`DVAE_PYG.loss()` (`dvae/models_pyg.py:398-456`) and its reverse pass in HIP (csrc/dvae_decode.hip); `decode()`
-(sampling) is out of scope.
+`DVAE_PYG.loss()` (`dvae/models_pyg.py:398-456`) and its reverse pass in HIP (csrc/dvae_decode.hip); `decode(z)`
+samples graphs from latent vectors as `DVAE_PYG.decode()` (`dvae/models_pyg.py:338-396`) does, the whole decode in one
+HIP call (csrc/dvae_sample.hip).
 """
 from __future__ import annotations
 
 import copy
+from collections import namedtuple
 from typing import List
 
 import numpy as np
@@ -188,6 +190,129 @@ def update_widths(preds: np.ndarray, max_n: int) -> List[int]:
             sel = m[:, v] & np.uint32(((1 << v) - 1) & ~((1 << k) - 1))
             out.append(int(max(bin(int(x)).count("1") for x in sel)) if len(sel) else 0)
     return out
+
+
+# ------------------------------------------------------------------ sampling decoder: draws and decoded graphs
+def edge_draw_index(idx: int, vi: int) -> int:
+    """Row of `u_edge` that serves the edge step (idx, vi): the reference's call order, idx ascending, vi = idx-1 .. 0."""
+    if not 0 <= vi < idx:
+        raise ValueError("edge_draw_index: need 0 <= vi < idx (got idx=%d, vi=%d)" % (idx, vi))
+    return idx * (idx - 1) // 2 + (idx - 1 - vi)
+
+
+def draw_shapes(max_n: int, B: int, attempts: int = 1):
+    """Shapes of (u_type, u_edge) for `decode_dense(..., draws=...)`: [attempts, max_n, B] (row idx serves the type draw
+    of vertex idx = 1 .. max_n-2, the other rows are unused) and [attempts, max_n(max_n-1)/2, B]."""
+    return (attempts, max_n, B), (attempts, max_n * (max_n - 1) // 2, B)
+
+
+class _VertexSeq(object):
+    def __init__(self, types):
+        self._types = types
+
+    def __len__(self):
+        return len(self._types)
+
+    def attributes(self):
+        return ["type"]
+
+    def __getitem__(self, key):
+        if isinstance(key, str):
+            if key != "type":
+                raise KeyError(key)
+            return list(self._types)
+        return {"type": self._types[key]}
+
+
+class DecodedGraph(object):
+    """A decoded DAG when python-igraph is not installed: the parts of `igraph.Graph` that D-VAE code reads of a decoded
+    graph (`vcount`, `ecount`, `vs[v]['type']`, `vs['type']`, `vs.attributes()`, `predecessors`, `successors`, `get_edgelist`, `indegree`,
+    `outdegree`, `is_dag`).  Edges are listed in the order the reference's `decode()` adds them."""
+
+    def __init__(self, types, edges):
+        self._types = [int(t) for t in types]
+        self._edges = [(int(u), int(v)) for u, v in edges]
+        self.vs = _VertexSeq(self._types)
+
+    def vcount(self):
+        return len(self._types)
+
+    def ecount(self):
+        return len(self._edges)
+
+    def get_edgelist(self):
+        return list(self._edges)
+
+    def predecessors(self, v):
+        return sorted(u for u, w in self._edges if w == v)
+
+    def successors(self, v):
+        return sorted(w for u, w in self._edges if u == v)
+
+    def indegree(self, vertices=None):
+        deg = [len(self.predecessors(v)) for v in range(self.vcount())]
+        return deg if vertices is None else (deg[vertices] if isinstance(vertices, int) else [deg[v] for v in vertices])
+
+    def outdegree(self, vertices=None):
+        deg = [len(self.successors(v)) for v in range(self.vcount())]
+        return deg if vertices is None else (deg[vertices] if isinstance(vertices, int) else [deg[v] for v in vertices])
+
+    def is_dag(self):
+        indeg = self.indegree()
+        ready = [v for v in range(self.vcount()) if indeg[v] == 0]
+        seen = 0
+        while ready:
+            u = ready.pop()
+            seen += 1
+            for w in self.successors(u):
+                indeg[w] -= 1
+                if indeg[w] == 0:
+                    ready.append(w)
+        return seen == self.vcount()
+
+
+def decoded_edges(types, preds, nv, end_type):
+    """The edge list of one decoded graph in the reference's insertion order: per vertex v ascending, its predecessors
+    descending (one per edge step vi = v-1 .. 0), except the END vertex, whose loose ends are added at once in the
+    iteration order of a python set of them.  types / preds: the graph's rows of decode_dense (preds as bitmasks), nv its vertex count."""
+    out = []
+    for v in range(1, int(nv)):
+        m = int(preds[v]) & 0xFFFFFFFF
+        us = [u for u in range(v) if m >> u & 1]
+        # (the END vertex: the reference iterates a python set of the loose ends, built in ascending order)
+        out += [(u, v) for u in (list(set(us)) if int(types[v]) == end_type else us[::-1])]
+    return out
+
+
+def graphs_from_dense(types, preds, nv, end_type, use_igraph=None):
+    """Host graphs from the dense rows of decode_dense (numpy arrays [B, n], [B, n], [B]): `igraph.Graph` objects built
+    as the reference builds them (a 'type' vertex attribute, nothing else) when igraph imports, else DecodedGraph."""
+    ig = None
+    if use_igraph is None or use_igraph:
+        try:
+            import igraph as ig
+        except ImportError:
+            if use_igraph:
+                raise
+            ig = None
+    out = []
+    for b in range(len(nv)):
+        k = int(nv[b])
+        ts = [int(t) for t in types[b][:k]]
+        edges = decoded_edges(types[b], preds[b], k, end_type)
+        if ig is None:
+            out.append(DecodedGraph(ts, edges))
+        else:
+            g = ig.Graph(directed=True)
+            for t in ts:
+                g.add_vertex(type=t)
+            for u, v in edges:
+                g.add_edge(u, v)
+            out.append(g)
+    return out
+
+
+DecodedDense = namedtuple("DecodedDense", ["types", "preds", "nv", "states"])
 
 
 class _DecodeLoss(torch.autograd.Function):
@@ -759,6 +884,66 @@ class _DvaeDagnn(_DvaeBase):
             res = _make_decode(spec, t_types, t_preds, H0, attn_w, params).forward()[2 * H0.shape[0]].clone()
         kld = -0.5 * torch.sum(1 + logvar - mu.pow(2) - logvar.exp())
         return res + beta * kld, res, kld
+
+    # ------------------------------------------------------------------ sampling decoder (dvae/models_pyg.py:338-396)
+    def _decode_tensors(self):
+        cells = list(self.grud)[:self.num_layers]
+        w = self.node_aggr_0[0].attn_lin.weight.detach()[0]
+        dq = self._key_offset(0)
+        return dict(cells=[(c.weight_ih, c.weight_hh, c.bias_ih, c.bias_hh) for c in cells], w_key=w[dq:dq + self.hs],
+                    vid_bias=w[dq + self.hs:dq + self.hs + self.max_n] if self._use_vids else None,
+                    av=[self.add_vertex[0].weight, self.add_vertex[0].bias, self.add_vertex[2].weight, self.add_vertex[2].bias],
+                    ae=[self.add_edge[0].weight, self.add_edge[0].bias, self.add_edge[2].weight, self.add_edge[2].bias])
+
+    def decode_dense(self, z, stochastic=True, attempts=1, draws=None, states=False):
+        """`decode(z, stochastic)` for `attempts` independent attempts on the same B latent rows, as dense device tensors,
+        without synchronising: DecodedDense(types [attempts, B, max_n] int32 (-1 past the end), preds [attempts, B, max_n]
+        int32 predecessor bitmasks (bit u: the edge u -> v), nv [attempts, B] int32 vertex counts, states
+        [attempts, B, max_n, hs] final top-layer states or None).  Each attempt is decoded exactly as one reference call on
+        its B rows.  Sampled draws come from ONE torch.rand call on z's device (so torch.manual_seed makes decoding
+        reproducible) unless `draws = (u_type, u_edge)` is given, shaped as `draw_shapes(max_n, B, attempts)`."""
+        if self.agg != K.NA_ATTN_H:
+            raise NotImplementedError("decode(): the decoder step is built for agg='attn_h' (the reference's D-VAE default, "
+                                      "dvae/train.py:86), not %r" % (self.agg,))
+        if self.max_n > 32:
+            raise ValueError("decode(): at most 32 vertices per graph (got max_n=%d)" % self.max_n)
+        if not isinstance(z, torch.Tensor) or z.dim() != 2 or z.shape[1] != self.nz or z.shape[0] == 0:
+            raise ValueError("decode(): z must be [B, nz=%d] with B >= 1 (got %s)"
+                             % (self.nz, tuple(z.shape) if isinstance(z, torch.Tensor) else type(z)))
+        attempts = int(attempts)
+        if attempts < 1:
+            raise ValueError("decode(): attempts must be >= 1 (got %d)" % attempts)
+        with torch.no_grad():
+            H0 = self.tanh(self.fc3(z))
+            if not H0.is_cuda:
+                raise engine.DagnnHipError("decode(): the model must live on a ROCm GPU - the decoder is HIP "
+                                           "(csrc/dvae_sample.hip) and has no CPU path")
+            B, n = z.shape[0], self.max_n
+            h0 = H0.float().repeat(attempts, 1)
+            u_type = u_edge = None
+            if stochastic:
+                st, se = draw_shapes(n, B, attempts)
+                if draws is None:
+                    u = torch.rand(int(np.prod(st)) + int(np.prod(se)), device=H0.device)
+                    u_type, u_edge = u[:int(np.prod(st))].view(st), u[int(np.prod(st)):].view(se)
+                else:
+                    u_type, u_edge = draws
+                    if tuple(u_type.shape) != st or tuple(u_edge.shape) != se:
+                        raise ValueError("decode(): draws must be shaped %s and %s" % (st, se))
+            types, preds, nv, hs = engine.dvae_sample(h0, attempts, n, self.nvt, self.START_TYPE, self.END_TYPE,
+                                                      not self._use_vids, self._decode_tensors(), u_type, u_edge, states)
+        return DecodedDense(types.view(attempts, B, n), preds.view(attempts, B, n), nv.view(attempts, B),
+                            None if hs is None else hs.view(attempts, B, n, self.hs))
+
+    def decode(self, z, stochastic=True):
+        """Graphs decoded from latent vectors z [B, nz] (`DVAE_PYG.decode`, `dvae/models_pyg.py:338-396`): a list of B
+        `igraph.Graph`s with a 'type' vertex attribute, or `DecodedGraph`s when igraph is not installed.
+        stochastic=True samples every type and edge, False takes the argmax / score > 0.5.  The decode is one HIP call;
+        the result reaches the host with one synchronisation."""
+        d = self.decode_dense(z, stochastic)
+        B, n = d.nv.shape[1], self.max_n
+        host = torch.cat([d.types.view(B, n), d.preds.view(B, n), d.nv.view(B, 1)], 1).cpu().numpy()
+        return graphs_from_dense(host[:, :n], host[:, n:2 * n], host[:, 2 * n], self.END_TYPE)
 
     # ------------------------------------------------------------------ decoder-side single-vertex step (SURVEY §8 f4)
     def _get_zeros(self, n, length):

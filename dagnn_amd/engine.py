@@ -1676,3 +1676,69 @@ class DvaeDecode(object):
         g.d_vid_bias = None if vid_off is None else d_attn.data_ptr() + 4 * vid_off
         check(lib.dagnn_dvae_decode_backward(C.byref(self.args), C.byref(g), _stream(self.h0)), "dagnn_dvae_decode_backward")
         return d_h0, d_cells, d_av, d_ae
+
+
+# ------------------------------------------------------------------ sampling D-VAE decoder (csrc/dvae_sample.hip)
+def dvae_sample(h0: torch.Tensor, groups: int, n: int, nvt: int, start_type: int, end_type: int, bn: bool, tensors: dict,
+                u_type: Optional[torch.Tensor] = None, u_edge: Optional[torch.Tensor] = None, states: bool = False):
+    """One call of `dagnn_dvae_sample` over `groups` groups of h0.shape[0] // groups rows.  `tensors`: cells (list of
+    (w_ih, w_hh, b_ih, b_hh)), w_key [hs], vid_bias [n] or None, av / ae (lists of (w1, b1, w2, b2)).  u_type [G,n,B] and
+    u_edge [G,n(n-1)/2,B] (both or neither): the draws of a sampled decode; None: argmax.  Returns (types [R,n] int32,
+    preds [R,n] int32 bitmasks, nv [R] int32, states [R,n,hs] or None) on h0's device, without synchronising."""
+    h0 = _dev(h0, "H0", torch.float32)
+    dev = h0.device
+    R, hs = h0.shape
+    if groups <= 0 or R % groups:
+        raise ValueError("dagnn_dvae_sample: %d rows do not split into %d groups" % (R, groups))
+    B = R // groups
+    f = lambda t, what: _dev(t.detach(), what, torch.float32)  # noqa: E731
+    cells = [[f(t, "grud parameter") for t in c] for c in tensors["cells"]]
+    if not 1 <= len(cells) <= _lib.MAX_STACKED:
+        raise DagnnHipError("dagnn_dvae_sample: 1 to %d stacked cells" % _lib.MAX_STACKED)
+    wk = f(tensors["w_key"], "w_key")
+    vb = None if tensors.get("vid_bias") is None else f(tensors["vid_bias"], "vid_bias")
+    av = [f(t, "add_vertex parameter") for t in tensors["av"]]
+    ae = [f(t, "add_edge parameter") for t in tensors["ae"]]
+    V1, E1, ein = av[0].shape[0], ae[0].shape[0], (3 if bn else 2) * hs
+    # the library reads these through bare pointers: every shape is checked here
+    want = [(wk, (hs,)), (av[0], (V1, hs)), (av[1], (V1,)), (av[2], (nvt, V1)), (av[3], (nvt,)),
+            (ae[0], (E1, ein)), (ae[1], (E1,)), (ae[2], (1, E1)), (ae[3], (1,))]
+    if vb is not None:
+        want.append((vb, (n,)))
+    for l, (w_ih, w_hh, b_ih, b_hh) in enumerate(cells):
+        want += [(w_ih, (3 * hs, nvt if l == 0 else hs)), (w_hh, (3 * hs, hs)), (b_ih, (3 * hs,)), (b_hh, (3 * hs,))]
+    stochastic = u_type is not None or u_edge is not None
+    if stochastic:
+        if u_type is None or u_edge is None:
+            raise ValueError("dagnn_dvae_sample: give both u_type and u_edge, or neither")
+        u_type = _dev(u_type, "u_type", torch.float32)
+        u_edge = _dev(u_edge, "u_edge", torch.float32)
+        want += [(u_type, (groups, n, B)), (u_edge, (groups, n * (n - 1) // 2, B))]
+    for t, shape in want:
+        if tuple(t.shape) != shape:
+            raise ValueError("dagnn_dvae_sample: a tensor of shape %s where %s is needed" % (tuple(t.shape), shape))
+    a = _lib.DvaeSampleArgs()
+    a.G, a.B, a.n, a.hs, a.L, a.nvt = groups, B, n, hs, len(cells), nvt
+    a.start_type, a.end_type, a.bn, a.stochastic = int(start_type), int(end_type), int(bool(bn)), int(stochastic)
+    a.edge_hidden, a.vertex_hidden = E1, V1
+    a.h0 = h0.data_ptr()
+    for l, c in enumerate(cells):
+        a.w_ih[l], a.w_hh[l], a.b_ih[l], a.b_hh[l] = (t.data_ptr() for t in c)
+    a.w_key, a.vid_bias = wk.data_ptr(), _ptr(vb)
+    a.av_w1, a.av_b1, a.av_w2, a.av_b2 = (t.data_ptr() for t in av)
+    a.ae_w1, a.ae_b1, a.ae_w2, a.ae_b2 = (t.data_ptr() for t in ae)
+    a.u_type, a.u_edge = _ptr(u_type), _ptr(u_edge)
+    types = torch.empty(R, n, dtype=torch.int32, device=dev)
+    preds = torch.empty(R, n, dtype=torch.int32, device=dev)
+    nv = torch.empty(R, dtype=torch.int32, device=dev)
+    st = torch.empty(R, n, hs, dtype=torch.float32, device=dev) if states else None
+    a.types, a.preds, a.nv, a.states = types.data_ptr(), preds.data_ptr(), nv.data_ptr(), _ptr(st)
+    lib = _lib.load()
+    nbytes = lib.dagnn_dvae_sample_work_bytes(C.byref(a))
+    if nbytes == 0:
+        raise DagnnHipError("dagnn_dvae_sample: unsupported shape (G=%d, B=%d, n=%d, hs=%d, L=%d, nvt=%d)"
+                            % (groups, B, n, hs, len(cells), nvt))
+    work = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=dev)
+    a.work, a.work_bytes = work.data_ptr(), nbytes
+    check(lib.dagnn_dvae_sample(C.byref(a), _stream(h0)), "dagnn_dvae_sample")
+    return types, preds, nv, st

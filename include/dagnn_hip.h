@@ -931,6 +931,54 @@ int dagnn_dvae_decode_backward(const dagnn_dvae_decode_args* args /* host */, co
                                void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Sampling D-VAE decoder: `DVAE_PYG.decode(z, stochastic)` (dvae/models_pyg.py:338-396; BN through DVAE_BN_PYG, graph
+ * state = sum of the vertex states, edge head on [H_vi, H_v, H0]) for G independent groups of B rows, R = G*B, in ONE
+ * call with no host round trip.  Each group is decoded exactly as one reference call on its B rows: the padding width P
+ * of every update and the set of rows still being updated are reduced per group, never across groups.
+ *   h0 [R,hs] = tanh(fc3(z)); grud cells, w_key / vid_bias, add_vertex (av_*) and add_edge (ae_*) as in
+ *   dagnn_dvae_decode_args; stochastic = 0: argmax types and score > 0.5 edges (the draws are not read);
+ *   stochastic = 1: u_type [G,n,B] (row idx serves the type draw of vertex idx = 1..n-2, as np.random.choice maps
+ *   its uniform: searchsorted(cumsum(p)/sum(p), u, 'right') in float64), u_edge [G,n(n-1)/2,B] (pair
+ *   idx(idx-1)/2 + (idx-1-vi) serves the edge step (idx, vi) in the reference's call order; edge kept on u < score).
+ *   Outputs: types [R,n] int32 (-1 past the graph's end), preds [R,n] uint32 (bit u of preds[r,v]: edge u -> v, the
+ *   encoding of dagnn_dvae_decode_args), nv [R] int32 vertex counts, states [R,n,hs] (or NULL): the final top-layer
+ *   state of every vertex, zero past the end.
+ *   work >= dagnn_dvae_sample_work_bytes(args) bytes.  No allocation, no synchronisation, bitwise repeatable (no float
+ *   atomics).  The size query returns 0 for arguments the entry point refuses with DAGNN_EINVAL.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct dagnn_dvae_sample_args {
+    int64_t G;               /* groups (independent decode calls) */
+    int64_t B;               /* rows per group */
+    int n;                   /* max_n, 2..DAGNN_DVAE_MAX_N */
+    int hs;
+    int L;                   /* stacked grud cells, 1..DAGNN_MAX_STACKED */
+    int nvt;                 /* vertex types, 1..DAGNN_DVAE_MAX_TYPES */
+    int start_type, end_type;
+    int bn;                  /* 0: D-VAE (NA), 1: D-VAE for Bayesian networks */
+    int stochastic;          /* 0: argmax, 1: sample with the given draws */
+    int edge_hidden, vertex_hidden;
+    const float* h0;
+    const float* w_ih[DAGNN_MAX_STACKED];
+    const float* w_hh[DAGNN_MAX_STACKED];
+    const float* b_ih[DAGNN_MAX_STACKED];
+    const float* b_hh[DAGNN_MAX_STACKED];
+    const float* w_key;
+    const float* vid_bias;   /* [n] or NULL */
+    const float *av_w1, *av_b1, *av_w2, *av_b2;
+    const float *ae_w1, *ae_b1, *ae_w2, *ae_b2;
+    const float* u_type;
+    const float* u_edge;
+    int32_t* types;
+    uint32_t* preds;
+    int32_t* nv;
+    float* states;           /* or NULL */
+    float* work;
+    size_t work_bytes;
+} dagnn_dvae_sample_args;
+size_t dagnn_dvae_sample_work_bytes(const dagnn_dvae_sample_args* args /* host */);
+int dagnn_dvae_sample(const dagnn_dvae_sample_args* args /* host */, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Topological layering on the device: replaces `top_sort` / `add_order_info_01` (src/utils_dag.py:8-52) for a
  * whole collated batch.  layer_fwd[v] = longest-path distance of v from any source, layer_bwd[v] = the same on
  * the flipped edges; both int64 [N], i.e. `_bi_layer_idx0/1` (`_bi_layer_index0/1` is arange(N)).  `batch`
