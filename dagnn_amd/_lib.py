@@ -211,7 +211,8 @@ class DvaeDecodeArgs(C.Structure):
                 ("b_hh", C.c_void_p * MAX_STACKED), ("w_key", C.c_void_p), ("vid_bias", C.c_void_p),
                 ("av_w1", C.c_void_p), ("av_b1", C.c_void_p), ("av_w2", C.c_void_p), ("av_b2", C.c_void_p),
                 ("ae_w1", C.c_void_p), ("ae_b1", C.c_void_p), ("ae_w2", C.c_void_p), ("ae_b2", C.c_void_p),
-                ("ll", C.c_void_p), ("saved", C.c_void_p), ("saved_bytes", C.c_size_t)]
+                ("ll", C.c_void_p), ("saved", C.c_void_p), ("saved_bytes", C.c_size_t),
+                ("agg", C.c_int), ("gate_w", C.c_void_p), ("gate_b", C.c_void_p), ("mapper_w", C.c_void_p)]
 
 
 class DvaeDecodeGrads(C.Structure):
@@ -220,7 +221,8 @@ class DvaeDecodeGrads(C.Structure):
                 ("d_b_ih", C.c_void_p * MAX_STACKED), ("d_b_hh", C.c_void_p * MAX_STACKED),
                 ("d_w_key", C.c_void_p), ("d_vid_bias", C.c_void_p),
                 ("d_av_w1", C.c_void_p), ("d_av_b1", C.c_void_p), ("d_av_w2", C.c_void_p), ("d_av_b2", C.c_void_p),
-                ("d_ae_w1", C.c_void_p), ("d_ae_b1", C.c_void_p), ("d_ae_w2", C.c_void_p), ("d_ae_b2", C.c_void_p)]
+                ("d_ae_w1", C.c_void_p), ("d_ae_b1", C.c_void_p), ("d_ae_w2", C.c_void_p), ("d_ae_b2", C.c_void_p),
+                ("d_gate_w", C.c_void_p), ("d_gate_b", C.c_void_p), ("d_mapper_w", C.c_void_p)]
 
 
 class DvaeSampleArgs(C.Structure):
@@ -232,7 +234,8 @@ class DvaeSampleArgs(C.Structure):
                 ("av_w1", C.c_void_p), ("av_b1", C.c_void_p), ("av_w2", C.c_void_p), ("av_b2", C.c_void_p),
                 ("ae_w1", C.c_void_p), ("ae_b1", C.c_void_p), ("ae_w2", C.c_void_p), ("ae_b2", C.c_void_p),
                 ("u_type", C.c_void_p), ("u_edge", C.c_void_p), ("types", C.c_void_p), ("preds", C.c_void_p),
-                ("nv", C.c_void_p), ("states", C.c_void_p), ("work", C.c_void_p), ("work_bytes", C.c_size_t)]
+                ("nv", C.c_void_p), ("states", C.c_void_p), ("work", C.c_void_p), ("work_bytes", C.c_size_t),
+                ("agg", C.c_int), ("gate_w", C.c_void_p), ("gate_b", C.c_void_p), ("mapper_w", C.c_void_p)]
 
 
 class VariantBwdCell(C.Structure):

@@ -15,6 +15,14 @@
 //
 // Gradients are pulled (each output element is written by one thread in a fixed order), so results are bitwise
 // run-to-run deterministic.  No kernel waits on another workgroup.
+//
+// agg = gated_sum (NA): the message of vertex u, m_u = sigmoid(Wg [h_u ; e_u] + bg) * (Wm [h_u ; e_u]), depends on u's
+// final layer-0 state only, so it is formed once, right after u's launches: one product [B, hs] x [hs, 2hs] (gate and
+// mapper stacked), then an epilogue that adds the vertex-id columns and bg.  The aggregate of update (v, k) is the sum
+// of the messages of v's predecessors >= k in ascending order (padding rows contribute exactly 0: the mapper has no
+// bias).  In reverse, dm_u pulls d hagg from every update that read it, and one product turns it into u's layer-0
+// state gradient before u's own cells run backwards.
+//   message rows  q = u * B + b                 for u = 0..n-2 (vertex n-1 has no successors)
 #include "common.h"
 
 namespace {
@@ -128,6 +136,10 @@ struct DDLayout {
     // backward workspace
     int64_t dlog_e, dpre, dxe, dlog_v, dhid_v, dhg, dH[DAGNN_MAX_STACKED], dhagg, dGi[DAGNN_MAX_STACKED],
         dGh[DAGNN_MAX_STACKED], ds, work_end;
+    // gated_sum (behind the attn_h layout): stacked weights [2H, H], message inputs / pre-activations / gate / mapper /
+    // message per message row, and (backward) the pre-activation gradients
+    int gated;
+    int64_t RM, wgm, xmsg, mpre, mgate, mmap, msg, dmpre;
 };
 
 inline int64_t dd_take(int64_t& at, int64_t count) {
@@ -139,9 +151,11 @@ inline int64_t dd_take(int64_t& at, int64_t count) {
 bool dd_layout(const dagnn_dvae_decode_args* a, DDLayout& o) {
     if (!a || a->B <= 0 || a->n < 2 || a->n > DAGNN_DVAE_MAX_N || a->hs <= 0 || a->L < 1 || a->L > DAGNN_MAX_STACKED ||
         a->nvt <= 0 || a->nvt > DAGNN_DVAE_MAX_TYPES || a->start_type < 0 || a->start_type >= a->nvt || a->edge_hidden <= 0 ||
-        a->vertex_hidden <= 0 || (a->bn != 0 && a->bn != 1))
+        a->vertex_hidden <= 0 || (a->bn != 0 && a->bn != 1) || (a->agg != 0 && a->agg != 1))
         return false;
+    if (a->agg == 1 && (a->bn || !a->gate_w || !a->gate_b || !a->mapper_w)) return false;
     o.B = a->B; o.n = a->n; o.H = a->hs; o.L = a->L; o.nvt = a->nvt;
+    o.gated = a->agg;
     o.ein = (a->bn ? 3 : 2) * a->hs; o.E1 = a->edge_hidden; o.V1 = a->vertex_hidden;
     o.NU = dd_U(o.n);
     o.RU = o.NU * o.B; o.RE = dd_E(o.n) * o.B; o.RV = (int64_t)(o.n - 1) * o.B;
@@ -164,6 +178,15 @@ bool dd_layout(const dagnn_dvae_decode_args* a, DDLayout& o) {
     o.hid_v = dd_take(at, o.RV * o.V1);
     o.logit_v = dd_take(at, o.RV * o.nvt);
     o.ll_v = dd_take(at, o.RV);
+    o.RM = (int64_t)(o.n - 1) * o.B;
+    if (o.gated) {
+        o.wgm = dd_take(at, 2 * H * H);
+        o.xmsg = dd_take(at, o.RM * H);
+        o.mpre = dd_take(at, o.RM * 2 * H);
+        o.mgate = dd_take(at, o.RM * H);
+        o.mmap = dd_take(at, o.RM * H);
+        o.msg = dd_take(at, o.RM * H);
+    }
     o.saved_end = at;
     at = 0;
     o.dlog_e = dd_take(at, o.RE);
@@ -176,6 +199,7 @@ bool dd_layout(const dagnn_dvae_decode_args* a, DDLayout& o) {
     o.dhagg = dd_take(at, o.RU * H);
     for (int l = 0; l < o.L; ++l) { o.dGi[l] = dd_take(at, o.RU * 3 * H); o.dGh[l] = dd_take(at, o.RU * 3 * H); }
     o.ds = dd_take(at, o.RU * o.n);
+    if (o.gated) o.dmpre = dd_take(at, o.RM * 2 * H);
     o.work_end = at;
     return true;
 }
@@ -536,6 +560,85 @@ __global__ void __launch_bounds__(DD_T) dd_type_grad_kernel(int64_t B, int n, in
     dw[(int64_t)m * nvt + t] = s;
 }
 
+// ---- gated_sum
+// wgm [2H, H]: rows 0..H-1 the state columns of Wg, rows H..2H-1 those of Wm (both [H, H+n] row-major)
+__global__ void __launch_bounds__(DD_T) dd_gated_stack_kernel(int H, int n, const float* __restrict__ gate_w,
+                                                              const float* __restrict__ mapper_w, float* __restrict__ wgm) {
+    const int64_t total = 2 * (int64_t)H * H;
+    for (int64_t e = (int64_t)blockIdx.x * DD_T + threadIdx.x; e < total; e += (int64_t)gridDim.x * DD_T) {
+        const int64_t j = e / H, k = e - j * H;
+        wgm[e] = j < H ? gate_w[j * (H + n) + k] : mapper_w[(j - H) * (H + n) + k];
+    }
+}
+
+// epilogue of vertex u's message product (grid [hb, B]): vertex-id column and bias, sigmoid-times; keeps the input row,
+// the gate and the mapper output for the reverse pass
+__global__ void __launch_bounds__(DD_T) dd_gated_msg_kernel(int u, int n, int64_t B, int H, const float* __restrict__ h0state,
+                                                            const float* __restrict__ pre, const float* __restrict__ gate_w,
+                                                            const float* __restrict__ gate_b, const float* __restrict__ mapper_w,
+                                                            float* __restrict__ xmsg, float* __restrict__ mgate,
+                                                            float* __restrict__ mmap, float* __restrict__ msg) {
+    const int c = blockIdx.x * DD_T + threadIdx.x;
+    if (c >= H) return;
+    const int64_t b = blockIdx.y, q = (int64_t)u * B + b;
+    const float g = dd_sigmoid(pre[q * 2 * H + c] + gate_w[(int64_t)c * (H + n) + H + u] + gate_b[c]);
+    const float m = pre[q * 2 * H + H + c] + mapper_w[(int64_t)c * (H + n) + H + u];
+    xmsg[q * H + c] = h0state[(dd_U(u) * B + b) * H + c];
+    mgate[q * H + c] = g;
+    mmap[q * H + c] = m;
+    msg[q * H + c] = g * m;
+}
+
+// the aggregate of every update of vertex v (grid [hb, (v+1) B]): the messages of v's predecessors >= k, ascending; v = 0: H0
+__global__ void __launch_bounds__(DD_T) dd_gated_agg_kernel(int v, int n, int64_t B, int H, const uint32_t* __restrict__ preds,
+                                                            const float* __restrict__ msg, const float* __restrict__ H0,
+                                                            float* __restrict__ hagg) {
+    const int c = blockIdx.x * DD_T + threadIdx.x;
+    if (c >= H) return;
+    const int64_t i = blockIdx.y, k = i / B, b = i - k * B, row = dd_U(v) * B + i;
+    if (v == 0) {
+        hagg[row * H + c] = H0[b * H + c];
+        return;
+    }
+    const uint32_t m = preds[b * n + v] & (~0u << k) & ((1u << v) - 1u);
+    float a = 0.f;
+    for (int u = 0; u < v; ++u)
+        if (m >> u & 1u) a += msg[((int64_t)u * B + b) * H + c];
+    hagg[row * H + c] = a;
+}
+
+// reverse of vertex u's message (grid [hb, B]): dm_u pulls d hagg from every update (v > u, k <= u) that read it, v then
+// k ascending; then the gate / mapper pre-activation gradients [B, 2H]
+__global__ void __launch_bounds__(DD_T) dd_gated_msg_bwd_kernel(int u, int n, int64_t B, int H, const uint32_t* __restrict__ preds,
+                                                                const float* __restrict__ dhagg, const float* __restrict__ mgate,
+                                                                const float* __restrict__ mmap, float* __restrict__ dmpre) {
+    const int c = blockIdx.x * DD_T + threadIdx.x;
+    if (c >= H) return;
+    const int64_t b = blockIdx.y, q = (int64_t)u * B + b;
+    float s = 0.f;
+    for (int v = u + 1; v < n; ++v) {
+        if (!(preds[b * n + v] >> u & 1u)) continue;
+        for (int k = 0; k <= u; ++k) s += dhagg[((dd_U(v) + k) * B + b) * H + c];
+    }
+    const float g = mgate[q * H + c], m = mmap[q * H + c];
+    dmpre[q * 2 * H + c] = s * m * g * (1.0f - g);
+    dmpre[q * 2 * H + H + c] = s * g;
+}
+
+// vertex-id columns of d Wg / d Wm (grid [ceil(2H / DD_T), n]): column H+u sums the pre-activation gradients of u's
+// message rows (zero for u = n-1, which sends none)
+__global__ void __launch_bounds__(DD_T) dd_gated_vid_grad_kernel(int64_t B, int n, int H, const float* __restrict__ dmpre,
+                                                                 float* __restrict__ d_gate_w, float* __restrict__ d_mapper_w) {
+    const int j = blockIdx.x * DD_T + threadIdx.x;
+    const int u = blockIdx.y;
+    if (j >= 2 * H) return;
+    float s = 0.f;
+    if (u < n - 1)
+        for (int64_t b = 0; b < B; ++b) s += dmpre[((int64_t)u * B + b) * 2 * H + j];
+    if (j < H) d_gate_w[(int64_t)j * (H + n) + H + u] = s;
+    else d_mapper_w[(int64_t)(j - H) * (H + n) + H + u] = s;
+}
+
 // ---- host helpers
 int dd_gemm(hipStream_t st, int64_t M, int64_t N, int64_t K, const float* A, int64_t sam, int64_t sak, const float* Bm,
             int64_t sbk, int64_t sbn, const float* bias, float* C, int64_t ldc, int accumulate, int relu,
@@ -561,7 +664,7 @@ int dd_colsum(hipStream_t st, const float* A, int64_t lda, int64_t R, int N, con
     } while (0)
 
 bool dd_weights_ok(const dagnn_dvae_decode_args* a) {
-    if (!a->types || !a->preds || !a->h0 || !a->w_key || !a->ll || !a->saved || !a->av_w1 || !a->av_b1 || !a->av_w2 ||
+    if (!a->types || !a->preds || !a->h0 || (a->agg == 0 && !a->w_key) || !a->ll || !a->saved || !a->av_w1 || !a->av_b1 || !a->av_w2 ||
         !a->av_b2 || !a->ae_w1 || !a->ae_b1 || !a->ae_w2 || !a->ae_b2)
         return false;
     for (int l = 0; l < a->L; ++l)
@@ -592,11 +695,21 @@ extern "C" int dagnn_dvae_decode_forward(const dagnn_dvae_decode_args* a, void* 
     int32_t* pid = reinterpret_cast<int32_t*>(S + o.pid);
     int32_t* pcount = reinterpret_cast<int32_t*>(S + o.pcount);
     const unsigned hb = (unsigned)((H + DD_T - 1) / DD_T);
+    if (o.gated) {
+        hipLaunchKernelGGL(dd_gated_stack_kernel, dim3((unsigned)((2 * H * H + DD_T - 1) / DD_T)), dim3(DD_T), 0, st, (int)H, n,
+                           a->gate_w, a->mapper_w, S + o.wgm);
+        DAGNN_CHECK_LAUNCH();
+    }
     // the chain: vertex by vertex, every update of the vertex at once, one launch per stacked layer
     for (int v = 0; v < n; ++v) {
         const int64_t r0 = dd_U(v) * B, M = (int64_t)(v == 0 ? 1 : v + 1) * B;
-        hipLaunchKernelGGL(dd_agg_kernel, dim3((unsigned)(v == 0 ? 1 : v + 1), (unsigned)B), dim3(DD_T), 0, st, v, n, B, (int)H,
-                           a->preds, S + o.h[0], a->w_key, a->vid_bias, a->h0, S + o.hagg, S + o.alpha, pid, pcount);
+        if (o.gated) {
+            hipLaunchKernelGGL(dd_gated_agg_kernel, dim3(hb, (unsigned)M), dim3(DD_T), 0, st, v, n, B, (int)H, a->preds, S + o.msg,
+                               a->h0, S + o.hagg);
+        } else {
+            hipLaunchKernelGGL(dd_agg_kernel, dim3((unsigned)(v == 0 ? 1 : v + 1), (unsigned)B), dim3(DD_T), 0, st, v, n, B, (int)H,
+                               a->preds, S + o.h[0], a->w_key, a->vid_bias, a->h0, S + o.hagg, S + o.alpha, pid, pcount);
+        }
         DAGNN_CHECK_LAUNCH();
         for (int l = 0; l < L; ++l) {
             // gh = Hagg W_hh^T + b_hh; layers above 0: gi = h_{l-1} W_ih^T + b_ih
@@ -606,6 +719,12 @@ extern "C" int dagnn_dvae_decode_forward(const dagnn_dvae_decode_args* a, void* 
             hipLaunchKernelGGL(dd_gru_kernel, dim3(hb, (unsigned)M), dim3(DD_T), 0, st, r0, v, B, n, (int)H, o.nvt, a->start_type,
                                a->types, l == 0 ? a->w_ih[0] : nullptr, a->b_ih[0], S + o.gi, S + o.gh, S + o.hagg, S + o.h[l],
                                S + o.gates[l]);
+            DAGNN_CHECK_LAUNCH();
+        }
+        if (o.gated && v + 1 < n) {   // v's layer-0 state is final: its message to every later vertex
+            DD_TRY(dd_gemm(st, B, 2 * H, H, S + o.h[0] + r0 * H, H, 1, S + o.wgm, 1, H, nullptr, S + o.mpre + v * B * 2 * H, 2 * H, 0, 0));
+            hipLaunchKernelGGL(dd_gated_msg_kernel, dim3(hb, (unsigned)B), dim3(DD_T), 0, st, v, n, B, (int)H, S + o.h[0],
+                               S + o.mpre, a->gate_w, a->gate_b, a->mapper_w, S + o.xmsg, S + o.mgate, S + o.mmap, S + o.msg);
             DAGNN_CHECK_LAUNCH();
         }
     }
@@ -632,9 +751,9 @@ extern "C" int dagnn_dvae_decode_forward(const dagnn_dvae_decode_args* a, void* 
 
 extern "C" int dagnn_dvae_decode_backward(const dagnn_dvae_decode_args* a, const dagnn_dvae_decode_grads* g, void* stream) {
     DDLayout o;
-    if (!dd_layout(a, o) || !dd_weights_ok(a) || !g || !g->g_res || !g->work || !g->d_h0 || !g->d_w_key || !g->d_av_w1 ||
+    if (!dd_layout(a, o) || !dd_weights_ok(a) || !g || !g->g_res || !g->work || !g->d_h0 || (a->agg == 0 && !g->d_w_key) || !g->d_av_w1 ||
         !g->d_av_b1 || !g->d_av_w2 || !g->d_av_b2 || !g->d_ae_w1 || !g->d_ae_b1 || !g->d_ae_w2 || !g->d_ae_b2 ||
-        (a->vid_bias && !g->d_vid_bias))
+        (a->agg == 0 && a->vid_bias && !g->d_vid_bias) || (a->agg == 1 && (!g->d_gate_w || !g->d_gate_b || !g->d_mapper_w)))
         return DAGNN_EINVAL;
     for (int l = 0; l < a->L; ++l)
         if (!g->d_w_ih[l] || !g->d_w_hh[l] || !g->d_b_ih[l] || !g->d_b_hh[l]) return DAGNN_EINVAL;
@@ -665,6 +784,12 @@ extern "C" int dagnn_dvae_decode_backward(const dagnn_dvae_decode_args* a, const
     DAGNN_CHECK_LAUNCH();
     for (int v = n - 1; v >= 0; --v) {
         const int64_t r0 = dd_U(v) * B, M = (int64_t)(v == 0 ? 1 : v + 1) * B;
+        if (o.gated && v + 1 < n) {   // every reader of v's message is done: its gradient joins v's final layer-0 state
+            hipLaunchKernelGGL(dd_gated_msg_bwd_kernel, dim3(hb, (unsigned)B), dim3(DD_T), 0, st, v, n, B, (int)H, a->preds,
+                               W + o.dhagg, S + o.mgate, S + o.mmap, W + o.dmpre);
+            DAGNN_CHECK_LAUNCH();
+            DD_TRY(dd_gemm(st, B, H, 2 * H, W + o.dmpre + v * B * 2 * H, 2 * H, 1, S + o.wgm, H, 1, nullptr, W + o.dH[0] + r0 * H, H, 1, 0));
+        }
         for (int l = L - 1; l >= 0; --l) {
             hipLaunchKernelGGL(dd_gru_bwd_kernel, dim3(hb, (unsigned)M), dim3(DD_T), 0, st, r0, (int)H, W + o.dH[l], S + o.gates[l],
                                S + o.hagg, W + o.dGi[l], W + o.dGh[l], W + o.dhagg);
@@ -674,7 +799,7 @@ extern "C" int dagnn_dvae_decode_backward(const dagnn_dvae_decode_args* a, const
                 DD_TRY(dd_gemm(st, M, H, 3 * H, W + o.dGi[l] + r0 * 3 * H, 3 * H, 1, a->w_ih[l], H, 1, nullptr,
                                W + o.dH[l - 1] + r0 * H, H, 1, 0));
         }
-        if (v > 0) {
+        if (v > 0 && !o.gated) {
             hipLaunchKernelGGL(dd_agg_bwd_kernel, dim3((unsigned)B), dim3(DD_T), 0, st, v, n, B, (int)H, S + o.h[0], a->w_key,
                                S + o.alpha, pid, pcount, W + o.dhagg, W + o.ds, W + o.dH[0]);
             DAGNN_CHECK_LAUNCH();
@@ -693,9 +818,19 @@ extern "C" int dagnn_dvae_decode_backward(const dagnn_dvae_decode_args* a, const
             DAGNN_CHECK_LAUNCH();
         }
     }
-    hipLaunchKernelGGL(dd_key_grad_kernel, dim3(hb + 1), dim3(DD_T), 0, st, B, n, (int)H, o.NU, S + o.h[0], pid, W + o.ds, g->d_w_key,
-                       a->vid_bias ? g->d_vid_bias : nullptr);
-    DAGNN_CHECK_LAUNCH();
+    if (o.gated) {
+        const int64_t ld = H + n;
+        DD_TRY(dd_gemm(st, H, H, o.RM, W + o.dmpre, 1, 2 * H, S + o.xmsg, H, 1, nullptr, g->d_gate_w, ld, 0, 0));
+        DD_TRY(dd_gemm(st, H, H, o.RM, W + o.dmpre + H, 1, 2 * H, S + o.xmsg, H, 1, nullptr, g->d_mapper_w, ld, 0, 0));
+        hipLaunchKernelGGL(dd_gated_vid_grad_kernel, dim3((unsigned)((2 * H + DD_T - 1) / DD_T), (unsigned)n), dim3(DD_T), 0, st, B, n,
+                           (int)H, W + o.dmpre, g->d_gate_w, g->d_mapper_w);
+        DAGNN_CHECK_LAUNCH();
+        DD_TRY(dd_colsum(st, W + o.dmpre, 2 * H, o.RM, (int)H, nullptr, g->d_gate_b));
+    } else {
+        hipLaunchKernelGGL(dd_key_grad_kernel, dim3(hb + 1), dim3(DD_T), 0, st, B, n, (int)H, o.NU, S + o.h[0], pid, W + o.ds,
+                           g->d_w_key, a->vid_bias ? g->d_vid_bias : nullptr);
+        DAGNN_CHECK_LAUNCH();
+    }
     hipLaunchKernelGGL(dd_h0_grad_kernel, dim3(hb, (unsigned)B), dim3(DD_T), 0, st, B, n, (int)H, a->bn, W + o.dhagg, W + o.dxe,
                        g->d_h0);
     DAGNN_CHECK_LAUNCH();

@@ -18,6 +18,11 @@
 // States live in [R, n, HP] buffers, HP = hs rounded up to 4 with zero columns, so that every product runs the
 // 16-byte-row MFMA path of dagnn_gemm_nt_bias; the weights are copied into the same padded layout inside `work`.
 // No float atomics: every value is written by one thread in a fixed order, so results are bitwise repeatable.
+//
+// agg = gated_sum (NA): in place of its key, a vertex gets its message row once its layer-0 state is final (one
+// product against the stacked state columns of the gate and the mapper, then the vertex-id columns, bg and the
+// sigmoid-times), and the aggregate launch becomes a masked sum of message rows in ascending order, with no soft-max.
+// The padding width P is still reduced but not read: the reference's zero padding rows contribute exactly 0.
 #include "common.h"
 
 namespace {
@@ -33,6 +38,9 @@ struct DSLayout {
     int64_t w_hh_all, b_hh_all, w_ih[DAGNN_MAX_STACKED], w_left, w_mid, w_h0, w_v1, h0p;
     // chain state
     int64_t h[DAGNN_MAX_STACKED], hagg, gh, gi, etmp, aedge, c0, key, hg, hidv, fin, succ, pbuf, end;
+    // gated_sum: stacked padded state columns of Wg / Wm [2 hs, HP], the message pre-activations [R, 2 hs], messages [R, n, hs]
+    int gated;
+    int64_t wgm, mpre, msg;
 };
 
 inline int64_t ds_take(int64_t& at, int64_t count) {
@@ -45,8 +53,9 @@ bool ds_layout(const dagnn_dvae_sample_args* a, DSLayout& o) {
     if (!a || a->G <= 0 || a->B <= 0 || a->n < 2 || a->n > DAGNN_DVAE_MAX_N || a->hs <= 0 || a->L < 1 ||
         a->L > DAGNN_MAX_STACKED || a->nvt <= 0 || a->nvt > DAGNN_DVAE_MAX_TYPES || a->start_type < 0 ||
         a->start_type >= a->nvt || a->end_type < 0 || a->end_type >= a->nvt || (a->bn != 0 && a->bn != 1) ||
-        (a->stochastic != 0 && a->stochastic != 1) || a->edge_hidden <= 0 || a->vertex_hidden <= 0)
+        (a->stochastic != 0 && a->stochastic != 1) || a->edge_hidden <= 0 || a->vertex_hidden <= 0 || (a->agg != 0 && a->agg != 1))
         return false;
+    if (a->agg == 1 && (a->bn || !a->gate_w || !a->gate_b || !a->mapper_w)) return false;
     if (a->G > ((int64_t)1 << 31) || a->B > ((int64_t)1 << 31) || a->G * a->B > ((int64_t)1 << 30) || a->hs > (1 << 20) ||
         a->edge_hidden > (1 << 22) || a->vertex_hidden > (1 << 22))
         return false;
@@ -79,6 +88,12 @@ bool ds_layout(const dagnn_dvae_sample_args* a, DSLayout& o) {
     o.fin = ds_take(at, R);
     o.succ = ds_take(at, R);
     o.pbuf = ds_take(at, o.NE * o.G);
+    o.gated = a->agg;
+    if (o.gated) {
+        o.wgm = ds_take(at, 2 * (int64_t)o.hs * HP);
+        o.mpre = ds_take(at, R * 2 * o.hs);
+        o.msg = ds_take(at, R * n * o.hs);
+    }
     o.end = at;
     return true;
 }
@@ -316,6 +331,39 @@ __global__ void __launch_bounds__(DS_T) ds_agg_kernel(int64_t B, int n, int hs, 
     }
 }
 
+// message of vertex v for every row, from its product row [gate | mapper]: vertex-id columns, bg, sigmoid-times
+__global__ void __launch_bounds__(DS_T) ds_gated_msg_kernel(int64_t R, int n, int hs, int v, const float* __restrict__ mpre,
+                                                            const float* __restrict__ gate_w, const float* __restrict__ gate_b,
+                                                            const float* __restrict__ mapper_w, float* __restrict__ msg) {
+    const int64_t total = R * hs;
+    for (int64_t e = (int64_t)blockIdx.x * DS_T + threadIdx.x; e < total; e += (int64_t)gridDim.x * DS_T) {
+        const int64_t r = e / hs;
+        const int c = (int)(e - r * hs);
+        const float* p = mpre + r * 2 * hs;
+        const float g = 1.0f / (1.0f + expf(-(p[c] + gate_w[(int64_t)c * (hs + n) + hs + v] + gate_b[c])));
+        msg[(r * n + v) * hs + c] = g * (p[hs + c] + mapper_w[(int64_t)c * (hs + n) + hs + v]);
+    }
+}
+
+// gated_sum aggregate of vertex idx: the messages of its predecessors so far, ascending (stride HP, zero pad)
+__global__ void __launch_bounds__(DS_T) ds_gated_agg_kernel(int64_t R, int n, int hs, int HP, int idx, const int32_t* __restrict__ nv,
+                                                            const uint32_t* __restrict__ preds, const float* __restrict__ msg,
+                                                            float* __restrict__ hagg) {
+    const int64_t total = R * HP;
+    for (int64_t e = (int64_t)blockIdx.x * DS_T + threadIdx.x; e < total; e += (int64_t)gridDim.x * DS_T) {
+        const int64_t r = e / HP;
+        const int c = (int)(e - r * HP);
+        if (nv[r] <= idx) continue;
+        float a = 0.f;
+        if (c < hs) {
+            const uint32_t m = preds[r * n + idx];
+            for (int u = 0; u < idx; ++u)
+                if (m >> u & 1u) a += msg[(r * n + u) * hs + c];
+        }
+        hagg[e] = a;
+    }
+}
+
 __global__ void __launch_bounds__(DS_T) ds_states_kernel(int64_t R, int n, int hs, int HP, const int32_t* __restrict__ nv,
                                                          const float* __restrict__ htop, float* __restrict__ out) {
     const int64_t total = R * n * hs;
@@ -345,7 +393,7 @@ int ds_pad(hipStream_t st, int64_t rows, int cols, const float* src, int64_t lds
 }
 
 bool ds_pointers_ok(const dagnn_dvae_sample_args* a) {
-    if (!a->h0 || !a->w_key || !a->av_w1 || !a->av_b1 || !a->av_w2 || !a->av_b2 || !a->ae_w1 || !a->ae_b1 || !a->ae_w2 ||
+    if (!a->h0 || (a->agg == 0 && !a->w_key) || !a->av_w1 || !a->av_b1 || !a->av_w2 || !a->av_b2 || !a->ae_w1 || !a->ae_b1 || !a->ae_w2 ||
         !a->ae_b2 || !a->types || !a->preds || !a->nv || !a->work || (a->stochastic && (!a->u_type || !a->u_edge)))
         return false;
     for (int l = 0; l < a->L; ++l)
@@ -386,6 +434,10 @@ extern "C" int dagnn_dvae_sample(const dagnn_dvae_sample_args* a, void* stream) 
     if (a->bn) DS_TRY(ds_pad(st, E1, hs, a->ae_w1 + 2 * hs, o.ein, W + o.w_h0, HP));
     DS_TRY(ds_pad(st, o.V1, hs, a->av_w1, hs, W + o.w_v1, HP));
     DS_TRY(ds_pad(st, R, hs, a->h0, hs, W + o.h0p, HP));
+    if (o.gated) {
+        DS_TRY(ds_pad(st, hs, hs, a->gate_w, hs + n, W + o.wgm, HP));
+        DS_TRY(ds_pad(st, hs, hs, a->mapper_w, hs + n, W + o.wgm + (int64_t)hs * HP, HP));
+    }
     for (int l = 0; l < L; ++l)
         if (hipMemsetAsync(W + o.h[l], 0, (size_t)R * n * HP * sizeof(float), st) != hipSuccess) return DAGNN_EHIP(hipGetLastError());
     if (hipMemsetAsync(pslot, 0, (size_t)o.NE * G * sizeof(int32_t), st) != hipSuccess) return DAGNN_EHIP(hipGetLastError());
@@ -408,10 +460,16 @@ extern "C" int dagnn_dvae_sample(const dagnn_dvae_sample_args* a, void* stream) 
         }
         return DAGNN_OK;
     };
-    // vertex idx is final: its key and add_edge.0's H_vi part (+ bias) for every later edge step
+    // vertex idx is final: its key (gated_sum: its message) and add_edge.0's H_vi part (+ bias) for every later edge step
     auto finalize = [&](int idx) -> int {
-        hipLaunchKernelGGL(ds_key_kernel, dim3(row_waves), dim3(DS_T), 0, st, R, n, hs, HP, idx, W + o.h[0], a->w_key, a->vid_bias,
-                           W + o.key);
+        if (o.gated) {
+            DS_TRY(ds_gemm(st, R, 2 * hs, HP, W + o.h[0] + (int64_t)idx * HP, ldh, W + o.wgm, nullptr, W + o.mpre, 2 * hs));
+            hipLaunchKernelGGL(ds_gated_msg_kernel, dim3(ds_blocks(R * hs)), dim3(DS_T), 0, st, R, n, hs, idx, W + o.mpre, a->gate_w,
+                               a->gate_b, a->mapper_w, W + o.msg);
+        } else {
+            hipLaunchKernelGGL(ds_key_kernel, dim3(row_waves), dim3(DS_T), 0, st, R, n, hs, HP, idx, W + o.h[0], a->w_key, a->vid_bias,
+                               W + o.key);
+        }
         DAGNN_CHECK_LAUNCH();
         return ds_gemm(st, R, E1, HP, htop + (int64_t)idx * HP, ldh, W + o.w_left, a->ae_b1, W + o.aedge + (int64_t)idx * E1,
                        (n - 1) * E1);
@@ -439,8 +497,12 @@ extern "C" int dagnn_dvae_sample(const dagnn_dvae_sample_args* a, void* stream) 
                                a->stochastic, W + o.etmp, W + o.aedge, a->bn ? W + o.c0 : nullptr, a->ae_w2, a->ae_b2, a->u_edge,
                                o.NE, a->types, a->nv, fin, succ, a->preds, pslot);
             DAGNN_CHECK_LAUNCH();
-            hipLaunchKernelGGL(ds_agg_kernel, dim3((unsigned)R), dim3(DS_T), 0, st, B, n, hs, HP, idx, ds_pair(idx, vi), G, a->nv,
-                               a->preds, pslot, W + o.key, W + o.h[0], W + o.hagg);
+            if (o.gated)
+                hipLaunchKernelGGL(ds_gated_agg_kernel, dim3(ds_blocks(R * HP)), dim3(DS_T), 0, st, R, n, hs, HP, idx, a->nv, a->preds,
+                                   W + o.msg, W + o.hagg);
+            else
+                hipLaunchKernelGGL(ds_agg_kernel, dim3((unsigned)R), dim3(DS_T), 0, st, B, n, hs, HP, idx, ds_pair(idx, vi), G, a->nv,
+                                   a->preds, pslot, W + o.key, W + o.h[0], W + o.hagg);
             DAGNN_CHECK_LAUNCH();
             DS_TRY(cells(idx, W + o.hagg, true));
         }

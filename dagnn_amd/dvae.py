@@ -318,35 +318,45 @@ DecodedDense = namedtuple("DecodedDense", ["types", "preds", "nv", "states"])
 class _DecodeLoss(torch.autograd.Function):
     """`res` of `DVAE_PYG.loss()` (the negative log-likelihood of the true graphs under teacher forcing) as ONE call of
     `dagnn_dvae_decode_forward`; its gradients as ONE call of `dagnn_dvae_decode_backward`.  Inputs after the fixed
-    ones: attn_lin.weight, then 4 tensors per grud cell, add_vertex.{0,2}.{weight,bias}, add_edge.{0,2}.{weight,bias}."""
+    ones: the aggregator's tensors (attn_h: attn_lin.weight; gated_sum: gate_forward.0.0.{weight,bias},
+    mapper_forward.0.0.weight), then 4 tensors per grud cell, add_vertex.{0,2}.{weight,bias}, add_edge.{0,2}.{weight,bias}."""
 
     @staticmethod
-    def forward(ctx, spec, types, preds, h0, attn_w, *params):
-        dec = _make_decode(spec, types, preds, h0, attn_w, params)
+    def forward(ctx, spec, types, preds, h0, *params):
+        dec = _make_decode(spec, types, preds, h0, params)
         ll = dec.forward()
         ctx.dec, ctx.spec = dec, spec
-        ctx.save_for_backward(h0, attn_w, *params)   # (version checks: backward reads these through the saved pointers)
+        ctx.save_for_backward(h0, *params)   # (version checks: backward reads these through the saved pointers)
         return ll[2 * h0.shape[0]].clone()
 
     @staticmethod
     def backward(ctx, g_res):
-        ctx.saved_tensors   # raises if a parameter was modified in place since the forward call
+        saved = ctx.saved_tensors   # raises if a parameter was modified in place since the forward call
         spec, dec = ctx.spec, ctx.dec
-        d_attn = torch.zeros_like(ctx.saved_tensors[1])
-        d_h0, d_cells, d_av, d_ae = dec.backward(g_res, d_attn, spec["dq"], spec["dq"] + spec["hs"] if spec["vid"] else None)
+        if spec["agg"] == K.NA_GATED_SUM:
+            d_h0, d_cells, d_av, d_ae, d_agg = dec.backward(g_res, None, 0, None)
+        else:
+            d_attn = torch.zeros_like(saved[1])
+            d_h0, d_cells, d_av, d_ae = dec.backward(g_res, d_attn, spec["dq"], spec["dq"] + spec["hs"] if spec["vid"] else None)
+            d_agg = [d_attn]
         ctx.dec = None
         flat = [t for c in d_cells for t in c] + d_av + d_ae
-        return (None, None, None, d_h0, d_attn) + tuple(flat)
+        return (None, None, None, d_h0) + tuple(d_agg) + tuple(flat)
 
 
-def _make_decode(spec, types, preds, h0, attn_w, params):
+def _make_decode(spec, types, preds, h0, params):
     L, hs, dq = spec["L"], spec["hs"], spec["dq"]
-    w = attn_w.detach()[0]
+    na = 3 if spec["agg"] == K.NA_GATED_SUM else 1
+    agg, params = params[:na], params[na:]
     cells = [tuple(params[4 * l:4 * l + 4]) for l in range(L)]
     av, ae = list(params[4 * L:4 * L + 4]), list(params[4 * L + 4:4 * L + 8])
-    return engine.DvaeDecode(spec["n"], spec["nvt"], spec["start_type"], spec["bn"], dict(
-        h0=h0.detach(), types=types, preds=preds, cells=cells, w_key=w[dq:dq + hs],
-        vid_bias=w[dq + hs:dq + hs + spec["n"]] if spec["vid"] else None, av=av, ae=ae))
+    t = dict(h0=h0.detach(), types=types, preds=preds, cells=cells, av=av, ae=ae)
+    if na == 3:
+        t["gate"] = [x.detach() for x in agg]
+    else:
+        w = agg[0].detach()[0]
+        t.update(w_key=w[dq:dq + hs], vid_bias=w[dq + hs:dq + hs + spec["n"]] if spec["vid"] else None)
+    return engine.DvaeDecode(spec["n"], spec["nvt"], spec["start_type"], spec["bn"], t)
 
 
 class _DvaeBase(nn.Module):
@@ -854,10 +864,9 @@ class _DvaeDagnn(_DvaeBase):
         the true graphs under the teacher-forced decoder plus the KL term.  The decoder and its reverse pass are HIP
         (csrc/dvae_decode.hip: one library call each); the schedule (types, predecessor masks) is built once on the host
         and copied once.  Gradients reach mu / logvar, fc3, grud, attn_lin (key / vertex-id part), add_vertex and
-        add_edge.  Graphs must have exactly max_n vertices; agg must be attn_h."""
-        if self.agg != K.NA_ATTN_H:
-            raise NotImplementedError("loss(): the teacher-forced decoder is built for agg='attn_h' (the reference's D-VAE "
-                                      "default, dvae/train.py:86), not %r" % (self.agg,))
+        add_edge.  Graphs must have exactly max_n vertices; agg must be attn_h or (DAGNN_NA) gated_sum, whose gradients
+        reach gate_forward.0.0 / mapper_forward.0.0 (the encoder's layer-0 gate and mapper: both add up in .grad)."""
+        self._check_decoder_agg("loss(): the teacher-forced decoder")
         if type(G_true) != list:
             G_true = [G_true]
         types, preds = decode_schedule(G_true, self.max_n, self.nvt)
@@ -872,28 +881,50 @@ class _DvaeDagnn(_DvaeBase):
         t_types = torch.from_numpy(types).pin_memory().to(dev, non_blocking=True)
         t_preds = torch.from_numpy(preds).pin_memory().to(dev, non_blocking=True)
         cells = list(self.grud)[:self.num_layers]
-        attn_w = self.node_aggr_0[0].attn_lin.weight
-        params = [t for c in cells for t in (c.weight_ih, c.weight_hh, c.bias_ih, c.bias_hh)]
+        params = self._decoder_agg_tensors()
+        params += [t for c in cells for t in (c.weight_ih, c.weight_hh, c.bias_ih, c.bias_hh)]
         params += [self.add_vertex[0].weight, self.add_vertex[0].bias, self.add_vertex[2].weight, self.add_vertex[2].bias,
                    self.add_edge[0].weight, self.add_edge[0].bias, self.add_edge[2].weight, self.add_edge[2].bias]
         spec = dict(n=self.max_n, nvt=self.nvt, start_type=int(self.START_TYPE), bn=not self._use_vids, vid=self._use_vids,
-                    L=len(cells), hs=self.hs, dq=self._key_offset(0))
-        if torch.is_grad_enabled() and any(t.requires_grad for t in [H0, attn_w] + params):
-            res = _DecodeLoss.apply(spec, t_types, t_preds, H0, attn_w, *params)
+                    L=len(cells), hs=self.hs, dq=self._key_offset(0), agg=self.agg)
+        if torch.is_grad_enabled() and any(t.requires_grad for t in [H0] + params):
+            res = _DecodeLoss.apply(spec, t_types, t_preds, H0, *params)
         else:   # (no autograd record: the saved activations die with this call)
-            res = _make_decode(spec, t_types, t_preds, H0, attn_w, params).forward()[2 * H0.shape[0]].clone()
+            res = _make_decode(spec, t_types, t_preds, H0, params).forward()[2 * H0.shape[0]].clone()
         kld = -0.5 * torch.sum(1 + logvar - mu.pow(2) - logvar.exp())
         return res + beta * kld, res, kld
+
+    def _check_decoder_agg(self, what):
+        """The decoders serve attn_h and (NA) gated_sum; gated_sum's messages read [hs-wide state ; one-hot(u, max_n)]
+        through the encoder's layer-0 gate / mapper, so the reference itself needs hidden_dim == hs and
+        num_nodes == max_n (a shape error otherwise)."""
+        if self.agg not in (K.NA_ATTN_H, K.NA_GATED_SUM):
+            raise NotImplementedError("%s is built for agg='attn_h' (the reference's D-VAE default, dvae/train.py:86) and "
+                                      "agg='gated_sum', not %r" % (what, self.agg))
+        if self.agg == K.NA_GATED_SUM and (self.hidden_dim != self.hs or self.num_nodes != self.max_n):
+            raise ValueError("%s with agg='gated_sum' needs hidden_dim == hs and num_nodes == max_n (got hidden_dim=%d, "
+                             "hs=%d, num_nodes=%d, max_n=%d)" % (what, self.hidden_dim, self.hs, self.num_nodes, self.max_n))
+
+    def _decoder_agg_tensors(self):
+        """The decoder's aggregator tensors: attn_h the attn_lin weight, gated_sum the layer-0 gate (weight, bias) and
+        mapper weight that node_aggr_0[0] shares with the encoder."""
+        if self.agg == K.NA_GATED_SUM:
+            return [self.gate_forward[0][0].weight, self.gate_forward[0][0].bias, self.mapper_forward[0][0].weight]
+        return [self.node_aggr_0[0].attn_lin.weight]
 
     # ------------------------------------------------------------------ sampling decoder (dvae/models_pyg.py:338-396)
     def _decode_tensors(self):
         cells = list(self.grud)[:self.num_layers]
+        t = dict(cells=[(c.weight_ih, c.weight_hh, c.bias_ih, c.bias_hh) for c in cells],
+                 av=[self.add_vertex[0].weight, self.add_vertex[0].bias, self.add_vertex[2].weight, self.add_vertex[2].bias],
+                 ae=[self.add_edge[0].weight, self.add_edge[0].bias, self.add_edge[2].weight, self.add_edge[2].bias])
+        if self.agg == K.NA_GATED_SUM:
+            t["gate"] = [x.detach() for x in self._decoder_agg_tensors()]
+            return t
         w = self.node_aggr_0[0].attn_lin.weight.detach()[0]
         dq = self._key_offset(0)
-        return dict(cells=[(c.weight_ih, c.weight_hh, c.bias_ih, c.bias_hh) for c in cells], w_key=w[dq:dq + self.hs],
-                    vid_bias=w[dq + self.hs:dq + self.hs + self.max_n] if self._use_vids else None,
-                    av=[self.add_vertex[0].weight, self.add_vertex[0].bias, self.add_vertex[2].weight, self.add_vertex[2].bias],
-                    ae=[self.add_edge[0].weight, self.add_edge[0].bias, self.add_edge[2].weight, self.add_edge[2].bias])
+        t.update(w_key=w[dq:dq + self.hs], vid_bias=w[dq + self.hs:dq + self.hs + self.max_n] if self._use_vids else None)
+        return t
 
     def decode_dense(self, z, stochastic=True, attempts=1, draws=None, states=False):
         """`decode(z, stochastic)` for `attempts` independent attempts on the same B latent rows, as dense device tensors,
@@ -902,9 +933,7 @@ class _DvaeDagnn(_DvaeBase):
         [attempts, B, max_n, hs] final top-layer states or None).  Each attempt is decoded exactly as one reference call on
         its B rows.  Sampled draws come from ONE torch.rand call on z's device (so torch.manual_seed makes decoding
         reproducible) unless `draws = (u_type, u_edge)` is given, shaped as `draw_shapes(max_n, B, attempts)`."""
-        if self.agg != K.NA_ATTN_H:
-            raise NotImplementedError("decode(): the decoder step is built for agg='attn_h' (the reference's D-VAE default, "
-                                      "dvae/train.py:86), not %r" % (self.agg,))
+        self._check_decoder_agg("decode(): the decoder step")
         if self.max_n > 32:
             raise ValueError("decode(): at most 32 vertices per graph (got max_n=%d)" % self.max_n)
         if not isinstance(z, torch.Tensor) or z.dim() != 2 or z.shape[1] != self.nz or z.shape[0] == 0:

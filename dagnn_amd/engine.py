@@ -1591,7 +1591,8 @@ def topo_layers(edge_index: torch.Tensor, batch: torch.Tensor, num_graphs: int):
 class DvaeDecode(object):
     """One teacher-forced decode (`dagnn_dvae_decode_forward` / `_backward`): the argument struct, the tensors its pointers
     borrow, and the saved activations of the forward call.  `tensors`: dict with h0 [B,hs], types / preds [B,n] int32,
-    w_key [hs], vid_bias [n] or None, cells (list of (w_ih, w_hh, b_ih, b_hh)), av / ae (lists of (w1, b1, w2, b2))."""
+    w_key [hs], vid_bias [n] or None, cells (list of (w_ih, w_hh, b_ih, b_hh)), av / ae (lists of (w1, b1, w2, b2));
+    agg = gated_sum: gate = (gate_w [hs,hs+n], gate_b [hs], mapper_w [hs,hs+n]) in place of w_key / vid_bias."""
 
     def __init__(self, n: int, nvt: int, start_type: int, bn: bool, tensors: dict):
         h0 = _dev(tensors["h0"], "H0", torch.float32)
@@ -1612,9 +1613,14 @@ class DvaeDecode(object):
             ts = [f(t, "grud parameter") for t in c]
             keep += ts
             a.w_ih[l], a.w_hh[l], a.b_ih[l], a.b_hh[l] = (t.data_ptr() for t in ts)
-        wk = f(tensors["w_key"], "w_key")
-        vb = None if tensors.get("vid_bias") is None else f(tensors["vid_bias"], "vid_bias")
-        a.w_key, a.vid_bias = wk.data_ptr(), _ptr(vb)
+        gate = tensors.get("gate")
+        gate = None if gate is None else [f(t, "gate / mapper parameter") for t in gate]
+        wk = None if gate is not None else f(tensors["w_key"], "w_key")
+        vb = None if gate is not None or tensors.get("vid_bias") is None else f(tensors["vid_bias"], "vid_bias")
+        a.w_key, a.vid_bias = _ptr(wk), _ptr(vb)
+        if gate is not None:
+            a.agg = 1
+            a.gate_w, a.gate_b, a.mapper_w = (t.data_ptr() for t in gate)
         av = [f(t, "add_vertex parameter") for t in tensors["av"]]
         ae = [f(t, "add_edge parameter") for t in tensors["ae"]]
         a.av_w1, a.av_b1, a.av_w2, a.av_b2 = (t.data_ptr() for t in av)
@@ -1622,8 +1628,12 @@ class DvaeDecode(object):
         a.vertex_hidden, a.edge_hidden = av[0].shape[0], ae[0].shape[0]
         # the library reads these through bare pointers: every shape is checked here
         V1, E1, ein = av[0].shape[0], ae[0].shape[0], (3 if bn else 2) * hs
-        want = [(types, (B, n)), (preds, (B, n)), (wk, (hs,)), (av[0], (V1, hs)), (av[1], (V1,)), (av[2], (nvt, V1)), (av[3], (nvt,)),
+        want = [(types, (B, n)), (preds, (B, n)), (av[0], (V1, hs)), (av[1], (V1,)), (av[2], (nvt, V1)), (av[3], (nvt,)),
                 (ae[0], (E1, ein)), (ae[1], (E1,)), (ae[2], (1, E1)), (ae[3], (1,))]
+        if gate is not None:
+            want += [(gate[0], (hs, hs + n)), (gate[1], (hs,)), (gate[2], (hs, hs + n))]
+        else:
+            want.append((wk, (hs,)))
         if vb is not None:
             want.append((vb, (n,)))
         for l in range(len(cells)):
@@ -1632,7 +1642,7 @@ class DvaeDecode(object):
         for t, shape in want:
             if tuple(t.shape) != shape:
                 raise ValueError("dagnn_dvae_decode: a tensor of shape %s where %s is needed" % (tuple(t.shape), shape))
-        keep += [wk, vb] + av + ae
+        keep += [wk, vb] + av + ae + (gate or [])
         self.ll = torch.empty(2 * B + 1, dtype=torch.float32, device=dev)
         a.ll = self.ll.data_ptr()
         lib = _lib.load()
@@ -1642,17 +1652,18 @@ class DvaeDecode(object):
         self.saved = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=dev)
         a.saved, a.saved_bytes = self.saved.data_ptr(), nbytes
         self.args, self.tensors, self.B, self.hs, self.L = a, keep, B, hs, len(cells)
-        self.av, self.ae, self.cells, self.h0 = av, ae, keep[2:2 + 4 * len(cells)], h0
+        self.av, self.ae, self.cells, self.h0, self.gate = av, ae, keep[2:2 + 4 * len(cells)], h0, gate
 
     def forward(self) -> torch.Tensor:
         """Runs the decode; returns ll [2B+1]: per-graph vertex and edge log-likelihoods, then res."""
         check(_lib.load().dagnn_dvae_decode_forward(C.byref(self.args), _stream(self.h0)), "dagnn_dvae_decode_forward")
         return self.ll
 
-    def backward(self, g_res: torch.Tensor, d_attn: torch.Tensor, key_off: int, vid_off: Optional[int]):
+    def backward(self, g_res: torch.Tensor, d_attn: Optional[torch.Tensor], key_off: int, vid_off: Optional[int]):
         """Gradients of res (scaled by the device scalar g_res) for h0, the cells, the add_vertex / add_edge tensors;
         the key / vertex-id parts are written into the zeroed `d_attn` (a [1, D] attn_lin.weight gradient) at the given
-        column offsets.  Returns (d_h0, [per cell (d_w_ih, d_w_hh, d_b_ih, d_b_hh)], d_av, d_ae)."""
+        column offsets.  Returns (d_h0, [per cell (d_w_ih, d_w_hh, d_b_ih, d_b_hh)], d_av, d_ae); gated_sum (d_attn =
+        None): (d_h0, d_cells, d_av, d_ae, [d_gate_w, d_gate_b, d_mapper_w])."""
         lib = _lib.load()
         g_res = _dev(g_res.reshape(1), "grad", torch.float32)
         nbytes = lib.dagnn_dvae_decode_work_bytes(C.byref(self.args))
@@ -1670,6 +1681,11 @@ class DvaeDecode(object):
         d_ae = [torch.empty_like(t) for t in self.ae]
         g.d_av_w1, g.d_av_b1, g.d_av_w2, g.d_av_b2 = (t.data_ptr() for t in d_av)
         g.d_ae_w1, g.d_ae_b1, g.d_ae_w2, g.d_ae_b2 = (t.data_ptr() for t in d_ae)
+        if self.gate is not None:
+            d_gate = [torch.empty_like(t) for t in self.gate]
+            g.d_gate_w, g.d_gate_b, g.d_mapper_w = (t.data_ptr() for t in d_gate)
+            check(lib.dagnn_dvae_decode_backward(C.byref(self.args), C.byref(g), _stream(self.h0)), "dagnn_dvae_decode_backward")
+            return d_h0, d_cells, d_av, d_ae, d_gate
         if not d_attn.is_contiguous():
             raise DagnnHipError("dagnn_dvae_decode_backward: the attn_lin gradient must be contiguous")
         g.d_w_key = d_attn.data_ptr() + 4 * key_off
@@ -1682,7 +1698,8 @@ class DvaeDecode(object):
 def dvae_sample(h0: torch.Tensor, groups: int, n: int, nvt: int, start_type: int, end_type: int, bn: bool, tensors: dict,
                 u_type: Optional[torch.Tensor] = None, u_edge: Optional[torch.Tensor] = None, states: bool = False):
     """One call of `dagnn_dvae_sample` over `groups` groups of h0.shape[0] // groups rows.  `tensors`: cells (list of
-    (w_ih, w_hh, b_ih, b_hh)), w_key [hs], vid_bias [n] or None, av / ae (lists of (w1, b1, w2, b2)).  u_type [G,n,B] and
+    (w_ih, w_hh, b_ih, b_hh)), w_key [hs], vid_bias [n] or None, av / ae (lists of (w1, b1, w2, b2)); agg = gated_sum:
+    gate = (gate_w [hs,hs+n], gate_b [hs], mapper_w [hs,hs+n]) in place of w_key / vid_bias.  u_type [G,n,B] and
     u_edge [G,n(n-1)/2,B] (both or neither): the draws of a sampled decode; None: argmax.  Returns (types [R,n] int32,
     preds [R,n] int32 bitmasks, nv [R] int32, states [R,n,hs] or None) on h0's device, without synchronising."""
     h0 = _dev(h0, "H0", torch.float32)
@@ -1695,14 +1712,20 @@ def dvae_sample(h0: torch.Tensor, groups: int, n: int, nvt: int, start_type: int
     cells = [[f(t, "grud parameter") for t in c] for c in tensors["cells"]]
     if not 1 <= len(cells) <= _lib.MAX_STACKED:
         raise DagnnHipError("dagnn_dvae_sample: 1 to %d stacked cells" % _lib.MAX_STACKED)
-    wk = f(tensors["w_key"], "w_key")
-    vb = None if tensors.get("vid_bias") is None else f(tensors["vid_bias"], "vid_bias")
+    gate = tensors.get("gate")
+    gate = None if gate is None else [f(t, "gate / mapper parameter") for t in gate]
+    wk = None if gate is not None else f(tensors["w_key"], "w_key")
+    vb = None if gate is not None or tensors.get("vid_bias") is None else f(tensors["vid_bias"], "vid_bias")
     av = [f(t, "add_vertex parameter") for t in tensors["av"]]
     ae = [f(t, "add_edge parameter") for t in tensors["ae"]]
     V1, E1, ein = av[0].shape[0], ae[0].shape[0], (3 if bn else 2) * hs
     # the library reads these through bare pointers: every shape is checked here
-    want = [(wk, (hs,)), (av[0], (V1, hs)), (av[1], (V1,)), (av[2], (nvt, V1)), (av[3], (nvt,)),
+    want = [(av[0], (V1, hs)), (av[1], (V1,)), (av[2], (nvt, V1)), (av[3], (nvt,)),
             (ae[0], (E1, ein)), (ae[1], (E1,)), (ae[2], (1, E1)), (ae[3], (1,))]
+    if gate is not None:
+        want += [(gate[0], (hs, hs + n)), (gate[1], (hs,)), (gate[2], (hs, hs + n))]
+    else:
+        want.append((wk, (hs,)))
     if vb is not None:
         want.append((vb, (n,)))
     for l, (w_ih, w_hh, b_ih, b_hh) in enumerate(cells):
@@ -1724,7 +1747,10 @@ def dvae_sample(h0: torch.Tensor, groups: int, n: int, nvt: int, start_type: int
     a.h0 = h0.data_ptr()
     for l, c in enumerate(cells):
         a.w_ih[l], a.w_hh[l], a.b_ih[l], a.b_hh[l] = (t.data_ptr() for t in c)
-    a.w_key, a.vid_bias = wk.data_ptr(), _ptr(vb)
+    a.w_key, a.vid_bias = _ptr(wk), _ptr(vb)
+    if gate is not None:
+        a.agg = 1
+        a.gate_w, a.gate_b, a.mapper_w = (t.data_ptr() for t in gate)
     a.av_w1, a.av_b1, a.av_w2, a.av_b2 = (t.data_ptr() for t in av)
     a.ae_w1, a.ae_b1, a.ae_w2, a.ae_b2 = (t.data_ptr() for t in ae)
     a.u_type, a.u_edge = _ptr(u_type), _ptr(u_edge)

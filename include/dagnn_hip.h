@@ -883,6 +883,11 @@ int dagnn_iprop_step(const float* values, const int32_t* pred_vid, int64_t B, in
  * accumulates - d res scaled by the device scalar *g_res for every input above; d_w_key / d_vid_bias may point into one
  * zeroed attn_lin.weight gradient.  `work` >= dagnn_dvae_decode_work_bytes(args) bytes.  Both are bitwise deterministic
  * (no float atomics).  The size queries return 0 for arguments the entry points refuse with DAGNN_EINVAL.
+ * agg = 1 (`gated_sum`, NA only): the aggregate of vertex v is sum over its predecessors u of sigmoid(Wg x_u + bg) *
+ * (Wm x_u), x_u = [layer-0 state of u ; one-hot(u, n)], from gate_w / gate_b / mapper_w (gate_forward.0.0 and
+ * mapper_forward.0.0, [hs, hs+n] row-major); w_key / vid_bias are not read.  Their gradients go to d_gate_w / d_gate_b
+ * / d_mapper_w, and d_w_key / d_vid_bias are not written.  agg = 1 with bn = 1 or a missing gate / mapper pointer is
+ * refused (the size queries return 0).  The fields are appended: a zero-filled struct is agg = 0 (attn_h).
  * ---------------------------------------------------------------------------------------- */
 #define DAGNN_DVAE_MAX_N 32
 #define DAGNN_DVAE_MAX_TYPES 64
@@ -909,6 +914,10 @@ typedef struct dagnn_dvae_decode_args {
     float* ll;
     float* saved;
     size_t saved_bytes;
+    int agg;                 /* 0: attn_h (w_key / vid_bias), 1: gated_sum (gate_w / gate_b / mapper_w) */
+    const float* gate_w;     /* [hs, hs+n] */
+    const float* gate_b;     /* [hs] */
+    const float* mapper_w;   /* [hs, hs+n] */
 } dagnn_dvae_decode_args;
 typedef struct dagnn_dvae_decode_grads {
     const float* g_res;      /* device scalar: d loss / d res */
@@ -923,6 +932,7 @@ typedef struct dagnn_dvae_decode_grads {
     float* d_vid_bias;
     float *d_av_w1, *d_av_b1, *d_av_w2, *d_av_b2;
     float *d_ae_w1, *d_ae_b1, *d_ae_w2, *d_ae_b2;
+    float *d_gate_w, *d_gate_b, *d_mapper_w;   /* agg = 1 */
 } dagnn_dvae_decode_grads;
 size_t dagnn_dvae_decode_saved_bytes(const dagnn_dvae_decode_args* args /* host */);
 size_t dagnn_dvae_decode_work_bytes(const dagnn_dvae_decode_args* args /* host */);
@@ -945,6 +955,7 @@ int dagnn_dvae_decode_backward(const dagnn_dvae_decode_args* args /* host */, co
  *   state of every vertex, zero past the end.
  *   work >= dagnn_dvae_sample_work_bytes(args) bytes.  No allocation, no synchronisation, bitwise repeatable (no float
  *   atomics).  The size query returns 0 for arguments the entry point refuses with DAGNN_EINVAL.
+ *   agg = 1: the gated_sum aggregate, with the gate / mapper tensors and rules of dagnn_dvae_decode_args.
  * ---------------------------------------------------------------------------------------- */
 typedef struct dagnn_dvae_sample_args {
     int64_t G;               /* groups (independent decode calls) */
@@ -974,6 +985,10 @@ typedef struct dagnn_dvae_sample_args {
     float* states;           /* or NULL */
     float* work;
     size_t work_bytes;
+    int agg;                 /* as in dagnn_dvae_decode_args: 0 attn_h, 1 gated_sum */
+    const float* gate_w;
+    const float* gate_b;
+    const float* mapper_w;
 } dagnn_dvae_sample_args;
 size_t dagnn_dvae_sample_work_bytes(const dagnn_dvae_sample_args* args /* host */);
 int dagnn_dvae_sample(const dagnn_dvae_sample_args* args /* host */, void* stream);

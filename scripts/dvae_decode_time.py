@@ -5,7 +5,10 @@ B = 32 argmax and sampled, and --attempts attempts x 32 points sampled.  For the
 MFMA products the call issues and their share of the fp32 matrix peak (157.3 TFLOP/s) over the whole call; then one
 JSON line.
 
-    python scripts/dvae_decode_time.py [--steps 20] [--warmup 3] [--attempts 500] [--hs 501]
+    python scripts/dvae_decode_time.py [--steps 20] [--warmup 3] [--attempts 500] [--hs 501] [--agg attn_h]
+
+--agg gated_sum times the ENAS model with the gated_sum aggregator ('enas_gated') beside its attn_h numbers from the same
+run (DAGNN_BN has no gated_sum).
     rocprofv3 --kernel-trace --stats -d OUT -- python scripts/dvae_decode_time.py --steps 3 --warmup 1
 """
 from __future__ import annotations
@@ -25,7 +28,7 @@ from oracle.seeding import seeded_fill  # noqa: E402
 PEAK_F32_MATRIX = 157.3e12
 
 
-def product_flops(R, n, hs, L, edge_hidden, vertex_hidden, bn):
+def product_flops(R, n, hs, L, edge_hidden, vertex_hidden, bn, gated=False):
     """FLOPs (2 per multiply-add) of the MFMA products of one call, on the padded width HP = hs rounded up to 4."""
     HP = (hs + 3) // 4 * 4
     updates = 1 + sum(idx + 1 for idx in range(1, n - 1)) + 2   # idx = n-1: the fresh update and the END step only
@@ -35,7 +38,8 @@ def product_flops(R, n, hs, L, edge_hidden, vertex_hidden, bn):
     edge_steps = sum(range(1, n - 1))
     edge = 2 * R * HP * edge_hidden * (edge_steps + (n - 1) + (1 if bn else 0))   # H_v part per step, H_vi part per vertex, H0
     vert = 2 * R * HP * vertex_hidden * (n - 2)
-    return gh + gi + edge + vert
+    msg = 2 * R * HP * 2 * hs * (n - 1) if gated else 0   # gated_sum: one message product per final vertex
+    return gh + gi + edge + vert + msg
 
 
 def time_call(fn, steps, warmup):
@@ -61,13 +65,15 @@ def main():
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--hs", type=int, default=501)
     ap.add_argument("--layers", type=int, default=2)
+    ap.add_argument("--agg", choices=("attn_h", "gated_sum"), default="attn_h")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     hs, L, B = args.hs, args.layers, args.batch
     res = {}
-    for kind in ("enas", "bn"):
-        if kind == "enas":
-            model = DAGNN_NA(8, hs, hs, 8, 8, 0, 1, hs=hs, nz=56, num_nodes=8, num_layers=L, bidirectional=False)
+    for kind in ("enas", "bn") if args.agg == "attn_h" else ("enas", "enas_gated"):
+        if kind in ("enas", "enas_gated"):
+            model = DAGNN_NA(8, hs, hs, 8, 8, 0, 1, hs=hs, nz=56, num_nodes=8, num_layers=L, bidirectional=False,
+                             agg="gated_sum" if kind == "enas_gated" else "attn_h")
         else:
             model = DAGNN_BN(10, hs, hs, 10, 10, 0, 1, hs=hs, nz=56, num_nodes=10, num_layers=L, bidirectional=True)
         seeded_fill(model, 7)
@@ -77,15 +83,15 @@ def main():
             tag = "%s_B%d_%s" % (kind, B, "sample" if stochastic else "argmax")
             med, p90 = time_call(lambda: model.decode_dense(z, stochastic), args.steps, args.warmup)
             res[tag] = dict(median_ms=med, p90_ms=p90)
-            print("%-22s median %8.3f ms   p90 %8.3f ms" % (tag, med, p90))
+            print("%-28s median %8.3f ms   p90 %8.3f ms" % (tag, med, p90))
         A = args.attempts
         tag = "%s_%dx%d_sample" % (kind, A, B)
         med, p90 = time_call(lambda: model.decode_dense(z, True, attempts=A), max(3, args.steps // 4), 1)
         fl = product_flops(A * B, model.max_n, hs, L, model.add_edge[0].weight.shape[0], model.add_vertex[0].weight.shape[0],
-                           kind == "bn")
+                           kind == "bn", kind == "enas_gated")
         frac = fl / (med * 1e-3) / PEAK_F32_MATRIX
         res[tag] = dict(median_ms=med, p90_ms=p90, product_tflop=fl / 1e12, product_peak_fraction=frac)
-        print("%-22s median %8.3f ms   p90 %8.3f ms   products %.2f TFLOP = %.1f %% of the fp32 matrix peak over the call"
+        print("%-28s median %8.3f ms   p90 %8.3f ms   products %.2f TFLOP = %.1f %% of the fp32 matrix peak over the call"
               % (tag, med, p90, fl / 1e12, 100 * frac))
         del model
         torch.cuda.empty_cache()
