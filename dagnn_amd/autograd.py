@@ -55,13 +55,10 @@ def _wgrad(dg: torch.Tensor, u: torch.Tensor, splits: int = 32) -> torch.Tensor:
 class Recurrence(torch.autograd.Function):
     """Plan + node inputs -> graph read-out, differentiable (dagnn.py:144-193; dvae/dagnn.py:99-175).
 
-    `mod` is the calling module; it supplies `num_layers`, `hidden_dim`, `dirs`, `_cells()`, `_arena_for(x, role)`,
-    `_vid_nodes` (node count per graph when the keys carry a vertex-id one-hot, else 0), `_key_offset(i)` (position of
-    the key weights inside attn_lin.weight of stacked layer i) and the two read-out hooks
-    `_readout(plan, B, x, h) -> out`, `_readout_backward(plan, x, h, grad_out, g_ext, dx)`.
-    Inputs after `x` are the cells' parameters, 8 per (direction, stacked layer): weight_ih, weight_hh, bias_ih,
-    bias_hh, attn_lin.weight, attn_lin.bias, edge_encoder.weight, edge_encoder.bias (the last two None without edge
-    features)."""
+    `mod` is the calling module, a `core.HipModule` (its docstring lists the hooks this reads).
+    Inputs after `x` are the cells' parameters (`mod._train_params()`), 8 per (direction, stacked layer): weight_ih,
+    weight_hh, bias_ih, bias_hh, attn_lin.weight, attn_lin.bias, edge_encoder.weight, edge_encoder.bias (the last two
+    None without edge features)."""
 
     PER_CELL = 8
 

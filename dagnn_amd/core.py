@@ -16,6 +16,7 @@ from __future__ import annotations
 from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 import torch
+import torch.nn as nn
 
 from . import engine
 from ._lib import DagnnHipError
@@ -108,20 +109,99 @@ class ParamGuard(object):
                                                      err.data_ptr(), engine.ERR_PARAMS_MOVED, st), "dagnn_param_fingerprint")
 
 
-def guard_params(mod, err: Optional[torch.Tensor]) -> None:
-    """`ParamGuard.check` of module `mod`'s fp32 GPU parameters (evaluation passes of all three modules call this)."""
-    if mod.training or not engine.PARAM_GUARD or err is None:
-        return
-    g = mod.__dict__.get("_param_guard")
-    if g is None:
-        g = mod.__dict__["_param_guard"] = ParamGuard()
-        mod.__dict__["_param_list"] = [p for p in mod.parameters() if p.is_cuda and p.dtype == torch.float32]
-    g.check(mod.__dict__["_param_list"], err)
+class HipModule(nn.Module):
+    """Host plumbing of the modules whose passes run on the HIP kernels (`DAGNN`, the D-VAE encoders): the derived-weight
+    caches, the granule arenas, the parameter guard and the blocking error check, kept in one place so that every pass
+    and every cache a module grows obeys the same invalidation rules.
 
+    `_derived` holds EVERY `DerivedCache` of the module and of the helpers that derive weights for it, by name (`_cache`):
+    the recurrence cells under the schedule's name ("lockstep" / "pergraph"), the constructor-string variants' weights
+    under "variant" (`variants._derive`) and "plain_df" (`variants.run_plain_dataflow`).  `invalidate_caches()` (what
+    `train()` / `eval()` call) drops all of them and the parameter guard's record.
 
-def drop_guard(mod) -> None:
-    mod.__dict__.pop("_param_list", None)
-    mod.__dict__.pop("_param_guard", None)
+    Hooks a subclass supplies for `autograd.Recurrence` and `variants`, besides `num_layers`, `hidden_dim` and `dirs`:
+    `_cells(fresh)` (the kernel-ready cells, `derive_cell`), `_vid_nodes` (node count per graph when the keys carry a
+    vertex-id one-hot, else 0), `_key_offset(i)` (position of the key weights inside attn_lin.weight of stacked layer i),
+    `_static_scores(x, cells)` (per-node key scores of the `*_x` aggregators, else None) and the two read-out hooks
+    `_readout(plan, B, x, h) -> out`, `_readout_backward(plan, x, h, grad_out, g_ext, dx)`.  `_train_params()` below
+    reads `cells_<d>[i]` (GRU cells) and `node_aggr_<d>[i]` (an `attn_lin`, an `edge_encoder` where `wea`)."""
+
+    def __init__(self):
+        super().__init__()
+        self._derived = {}   # name -> DerivedCache (`_cache`)
+        self._arenas = {}    # (role, device, stream) -> engine.GranuleArena (`_arena_for`)
+
+    def _cache(self, name: str) -> DerivedCache:
+        c = self._derived.get(name)
+        if c is None:
+            c = self._derived[name] = DerivedCache()
+        return c
+
+    def invalidate_caches(self) -> None:
+        """Drop every tensor derived from the parameters (what `train()` / `eval()` do): call it after updating parameters in
+        evaluation mode through a path the version counters do not see (`.data`, a fused optimizer)."""
+        for c in self._derived.values():
+            c.invalidate()
+        self.__dict__.pop("_param_guard", None)
+
+    def train(self, mode: bool = True):
+        """Mode switches drop the derived-weight caches (`DerivedCache`: an optimizer may have updated the parameters
+        without bumping their version counters)."""
+        self.invalidate_caches()
+        return super().train(mode)
+
+    def _guard_params(self, ref: torch.Tensor) -> None:
+        """Evaluation passes: the parameters behind the derived-weight caches still are what the caches were built from
+        (`ParamGuard` over the module's fp32 GPU parameters, reported through the error word of `ref`'s arena; a
+        training-mode pass rebuilds everything anyway)."""
+        if self.training or not engine.PARAM_GUARD or not ref.is_cuda:
+            return
+        g = self.__dict__.get("_param_guard")
+        if g is None:
+            params = [p for p in self.parameters() if p.is_cuda and p.dtype == torch.float32]
+            g = self.__dict__["_param_guard"] = (ParamGuard(), params)
+        g[0].check(g[1], self._arena_for(ref).error_word(ref.device))
+
+    def check(self) -> None:
+        """Blocking device-side error check of every pass the module has launched (all devices / streams it ran on): raises
+        `DagnnHipError` if a bounded wait of a persistent kernel expired or a batch violated the plan contract.  The
+        healthy path never synchronises - `forward` only looks at finished read-backs of EARLIER passes - so a caller that
+        consumes outputs without another forward behind them (the last batch of an evaluation loop,
+        `ogbg-code/main_pyg.py:91-124`) calls this once where it synchronises anyway."""
+        for a in list(self._arenas.values()):
+            a.check()
+
+    def _arena_for(self, x, role="forward"):
+        # one arena per stream: passes issued on different streams keep their own granule buffers, epochs and error words
+        # (their plan / encoder / GEMM / head kernels may overlap; the all-resident persistent launches themselves are
+        # ordered device-wide by engine.persistent_launch - two of them in flight would deadlock on each other's CUs)
+        key = (role, x.device, engine._stream(x))
+        arena = self._arenas.get(key)
+        if arena is None:
+            arena = engine.GranuleArena()
+            # passes of further streams (micro-batches in flight) start their workgroup packing two XCDs further on
+            arena.xcd_first = 2 * sum(1 for k in self._arenas if k[0] == role and k[1] == x.device) % 8
+            self._arenas[key] = arena
+        return arena
+
+    def _train_params(self):
+        """The inputs of `autograd.Recurrence` after `x`: 8 per (direction, stacked layer)."""
+        flat = []
+        for d in self.dirs:
+            for i in range(self.num_layers):
+                c = getattr(self, "cells_%d" % d)[i]
+                a = getattr(self, "node_aggr_%d" % d)[i]
+                flat += [c.weight_ih, c.weight_hh, c.bias_ih, c.bias_hh, a.attn_lin.weight, a.attn_lin.bias,
+                         a.edge_encoder.weight if a.wea else None, a.edge_encoder.bias if a.wea else None]
+        return flat
+
+    def _unflatten(self, flat) -> List[List[Optional[torch.Tensor]]]:
+        """h[d][i] from the flat per-(direction, stacked layer) states `Recurrence` / `VariantRecurrence` return."""
+        L = self.num_layers
+        h: List[List[Optional[torch.Tensor]]] = [[None] * L for _ in range(2)]
+        for q, d in enumerate(self.dirs):
+            h[d] = list(flat[q * L:(q + 1) * L])
+        return h
 
 
 def built_marker(t):
@@ -417,16 +497,6 @@ def run_stack(plan: engine.PlanHandle, x: torch.Tensor, cells: Dict[Tuple[int, i
     if Hp != H:
         return [[h[d][i][:, :H] if h[d][i] is not None else None for i in range(L)] for d in range(2)]
     return h  # type: ignore[return-value]
-
-
-def check_arenas(mod) -> None:
-    """Blocking device-side error check of every pass `mod` has launched (all devices / streams it ran on): raises
-    `DagnnHipError` if a bounded wait of a persistent kernel expired or a batch violated the plan contract.  The
-    healthy path never synchronises - `forward` only looks at finished read-backs of EARLIER passes - so a caller that
-    consumes outputs without another forward behind them (the last batch of an evaluation loop,
-    `ogbg-code/main_pyg.py:91-124`) calls this once where it synchronises anyway."""
-    for a in list(mod._arenas.values()):
-        a.check()
 
 
 def default_schedule() -> str:

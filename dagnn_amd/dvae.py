@@ -24,7 +24,7 @@ import torch.nn.functional as F
 
 from . import constants as K
 from . import engine
-from .core import DerivedCache, default_schedule, derive_cell, pack_lockstep, run_stack
+from .core import HipModule, default_schedule, derive_cell, pack_lockstep, run_stack
 from .data import GraphBatch
 
 ENCODE_FUSED = int(__import__("os").environ.get("DAGNN_AMD_ENCODE_FUSED", "1"))   # 1: evaluation passes of the encoders as ONE library call (csrc/encode.hip)
@@ -69,7 +69,7 @@ class _AggView(object):
         self.node_aggr_0 = [_NoParams() for _ in range(m.num_layers)]
         self.node_aggr_1 = [_NoParams() for _ in range(m.num_layers)]
 
-    def __getattr__(self, name):   # cells_0 / cells_1, training, ...
+    def __getattr__(self, name):   # cells_0 / cells_1, training, _cache (the caches land in the module's `_derived`), ...
         return getattr(self.__dict__["_m"], name)
 
     def parameters(self):
@@ -359,7 +359,7 @@ def _make_decode(spec, types, preds, h0, params):
     return engine.DvaeDecode(spec["n"], spec["nvt"], spec["start_type"], spec["bn"], t)
 
 
-class _DvaeBase(nn.Module):
+class _DvaeBase(HipModule):
     """Parameters of `DVAE_PYG.__init__` (`dvae/models_pyg.py:18-85`), same names and order."""
 
     def __init__(self, max_n, nvt, START_TYPE, END_TYPE, hs=501, nz=56, bidirectional=False, vid=True,
@@ -458,8 +458,6 @@ class _DvaeDagnn(_DvaeBase):
             self.cells_1 = self.grue_backward
         self.dropout = nn.Dropout(dropout)
         self.out_linear = nn.Linear(self.out_hidden_dim, out_dim) if num_layers > 1 else None
-        self._derived = {}
-        self._arenas = {}  # per device: granule buffers of the persistent tail kernel
         self.schedule = default_schedule()  # 'lockstep' (frontier launches) or 'pergraph' (persistent workgroups)
 
     def _cells(self, fresh: bool = False):
@@ -493,15 +491,7 @@ class _DvaeDagnn(_DvaeBase):
                 pack_lockstep(out.values())
             return out
 
-        return self._derived.setdefault(self.schedule, DerivedCache()).get(srcs, make, fresh=fresh or self.training)
-
-    def train(self, mode: bool = True):
-        """Mode switches drop the derived-weight caches (see core.DerivedCache)."""
-        # (the `add` / `max` aggregators derive their weights on the cached view object - variants._derive keeps its DerivedCache
-        # on the module it is handed: fused optimizers and `.data` writes do not bump `_version`, so a train() / eval() switch
-        # must drop that cache too, exactly as DAGNN.train() does for its own)
-        self.invalidate_caches()
-        return super().train(mode)
+        return self._cache(self.schedule).get(srcs, make, fresh=fresh or self.training)
 
     # ---- hooks of autograd.Recurrence
     @property
@@ -516,23 +506,6 @@ class _DvaeDagnn(_DvaeBase):
 
     def _static_scores(self, x, cells):
         return None
-
-    def check(self) -> None:
-        """Blocking check for device-side failures of every pass launched so far (`core.check_arenas`): call it where
-        the outputs of the LAST forward of a loop are consumed - the non-blocking poll inside `forward` only reports
-        earlier passes."""
-        from .core import check_arenas
-        check_arenas(self)
-
-    def _arena_for(self, x, role="forward"):
-        key = (role, x.device, engine._stream(x))   # one arena per stream: passes on different streams may overlap
-        arena = self._arenas.get(key)
-        if arena is None:
-            arena = engine.GranuleArena()
-            # passes of further streams (micro-batches in flight) start their workgroup packing two XCDs further on
-            arena.xcd_first = 2 * sum(1 for k in self._arenas if k[0] == role and k[1] == x.device) % 8
-            self._arenas[key] = arena
-        return arena
 
     def _readout(self, plan, B, x, h):
         """End vertex of every graph for d = 0, start vertex for d = 1 (dvae/dagnn.py:147-161, dagnn_bn.py:138-152)."""
@@ -555,15 +528,6 @@ class _DvaeDagnn(_DvaeBase):
             if self.bidirectional:
                 g_ext[1][i][0::nn_, :H] = gout[:, (L + i) * H:(L + i + 1) * H]
 
-    def _train_params(self):
-        flat = []
-        for d in self.dirs:
-            for i in range(self.num_layers):
-                c = getattr(self, "cells_%d" % d)[i]
-                a = getattr(self, "node_aggr_%d" % d)[i]
-                flat += [c.weight_ih, c.weight_hh, c.bias_ih, c.bias_hh, a.attn_lin.weight, a.attn_lin.bias, None, None]
-        return flat
-
     def _training_pass(self) -> bool:
         if not (torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())):
             return False
@@ -574,27 +538,8 @@ class _DvaeDagnn(_DvaeBase):
     def forward(self, G):
         """`dvae/dagnn.py:99-175` / `dvae/dagnn_bn.py:98-168`."""
         out = self._forward(G)
-        if not self.training and engine.PARAM_GUARD:
-            # evaluation passes: the parameters behind the derived-weight caches still are what the caches were built from
-            # (core.ParamGuard; one small launch, reported like a device-side failure)
-            from .core import guard_params
-            p0 = next(self.parameters())
-            if p0.is_cuda:
-                guard_params(self, self._arena_for(p0).error_word(p0.device))
+        self._guard_params(next(self.parameters()))
         return out
-
-    def invalidate_caches(self) -> None:
-        """Drop every tensor derived from the parameters (what `train()` / `eval()` do): call it after updating parameters in
-        evaluation mode through a path the version counters do not see (`.data`, a fused optimizer)."""
-        for c in self.__dict__.get("_derived", {}).values():
-            c.invalidate()
-        view = self.__dict__.get("_agg_view_obj")
-        if view is not None:
-            vc = view.__dict__.get("_variant_cache")
-            if vc is not None:
-                vc.invalidate()
-        from .core import drop_guard
-        drop_guard(self)
 
     def _forward(self, G):
         if self.output_all and self.out_pool not in (K.P_MAX, K.P_MEAN, K.P_ADD):
@@ -618,7 +563,7 @@ class _DvaeDagnn(_DvaeBase):
         plan = engine.build_plan(G.edge_index, bl[0][0], bl[1][0], G.batch, B, None)
         if self._agg_plain:
             return self._forward_plain_agg(G, plan, x, B, train)
-        if self.output_all:   # pool over ALL nodes (dvae/dagnn.py:163-172): states, per-node projection, torch pooling
+        if self.output_all:
             if train:
                 from .autograd import Recurrence
                 flat = Recurrence.apply(self, plan, B, False, x, *self._train_params())
@@ -626,21 +571,7 @@ class _DvaeDagnn(_DvaeBase):
                 hh = run_stack(plan, x, self._cells(), self.dirs, L, H, vid_nodes=self._vid_nodes,
                                schedule=self.schedule, arena=self._arena_for(x))
                 flat = [hh[d][i] for d in self.dirs for i in range(L)]
-            G.h = torch.cat(([x] if self.out_wx else []) + list(flat), dim=-1)
-            if self.bidirectional:
-                G.h = self.hg_unify(G.h)
-            elif L > 1:
-                G.h = self.out_linear(G.h)
-            if not (torch.is_grad_enabled() and G.h.requires_grad):   # HIP pooling over the nodes of every graph
-                out = torch.empty(B, G.h.shape[1], dtype=torch.float32, device=G.h.device)
-                engine.readout_pool(plan, G.h, 2, self.out_pool, out, 0)
-                return out
-            idx = G.batch.view(-1, 1).expand_as(G.h)
-            out = G.h.new_zeros(B, G.h.shape[1])
-            if self.out_pool == K.P_MAX:
-                return out.scatter_reduce(0, idx, G.h, "amax", include_self=False)
-            out = out.scatter_add(0, idx, G.h)
-            return out / nn_ if self.out_pool == K.P_MEAN else out
+            return self._pool_all(G, plan, x, flat, B)
         if train:
             from .autograd import Recurrence
             hcat = Recurrence.apply(self, plan, B, True, x, *self._train_params())[0]
@@ -661,6 +592,25 @@ class _DvaeDagnn(_DvaeBase):
         # library dispatch and cfg 1 is host-bound (scripts/small_host_profile.py: 155 -> 134 us per forward); cfg 4's
         # 128 x 1024 x 256 stays with the library (its split-K kernel is the faster one there: 196 vs 285 us)
         return engine.gemm_nt_bias([G.h], [lin.weight.detach()], [None if lin.bias is None else lin.bias.detach()])[0]
+
+    def _pool_all(self, G, plan, x, flat, B):
+        """Pool over ALL nodes (dvae/dagnn.py:163-172) of the flat states: per-node projection, then HIP pooling over the
+        nodes of every graph (`plan` given, no gradient wanted) or torch pooling."""
+        G.h = torch.cat(([x] if self.out_wx else []) + list(flat), dim=-1)
+        if self.bidirectional:
+            G.h = self.hg_unify(G.h)
+        elif self.num_layers > 1:
+            G.h = self.out_linear(G.h)
+        if plan is not None and not (torch.is_grad_enabled() and G.h.requires_grad):
+            out = torch.empty(B, G.h.shape[1], dtype=torch.float32, device=G.h.device)
+            engine.readout_pool(plan, G.h, 2, self.out_pool, out, 0)
+            return out
+        idx = G.batch.view(-1, 1).expand_as(G.h)
+        out = G.h.new_zeros(B, G.h.shape[1])
+        if self.out_pool == K.P_MAX:
+            return out.scatter_reduce(0, idx, G.h, "amax", include_self=False)
+        out = out.scatter_add(0, idx, G.h)
+        return out / self.num_nodes if self.out_pool == K.P_MEAN else out
 
     # ------------------------------------------------------------------ agg in {gated_sum, add, max} (dvae/dagnn.py:60-70)
     def _agg_view(self):
@@ -733,11 +683,7 @@ class _DvaeDagnn(_DvaeBase):
             if train:
                 if variants.hip_backward_supported(view, G):
                     flat_params = [p for d in self.dirs for i in range(L) for _, p in variants._cell_params(view, d, i)]
-                    flat = variants.VariantRecurrence.apply(view, G, plan, x, *flat_params)
-                    h = [[None] * L for _ in range(2)]
-                    for q, d in enumerate(self.dirs):
-                        for i in range(L):
-                            h[d][i] = flat[q * L + i]
+                    h = self._unflatten(variants.VariantRecurrence.apply(view, G, plan, x, *flat_params))
                 else:
                     variants.warn_torch_path(view, G)
                     h = variants.run(view, G, x)
@@ -745,17 +691,7 @@ class _DvaeDagnn(_DvaeBase):
                 h = variants.run_hip(view, G, x, plan)
         N = x.shape[0]
         if self.output_all:
-            G.h = torch.cat(([x] if self.out_wx else []) + [h[d][i] for d in self.dirs for i in range(L)], dim=-1)
-            if self.bidirectional:
-                G.h = self.hg_unify(G.h)
-            elif L > 1:
-                G.h = self.out_linear(G.h)
-            idx = G.batch.view(-1, 1).expand_as(G.h)
-            out = G.h.new_zeros(B, G.h.shape[1])
-            if self.out_pool == K.P_MAX:
-                return out.scatter_reduce(0, idx, G.h, "amax", include_self=False)
-            out = out.scatter_add(0, idx, G.h)
-            return out / nn_ if self.out_pool == K.P_MEAN else out
+            return self._pool_all(G, None, x, [h[d][i] for d in self.dirs for i in range(L)], B)
         first = torch.arange(0, N, nn_, device=x.device)
         last = first + (nn_ - 1)
         parts = [h[0][i][last] for i in range(L)]

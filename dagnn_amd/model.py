@@ -24,7 +24,7 @@ import torch.nn.functional as F
 
 from . import constants as K
 from . import engine
-from .core import DerivedCache, built_marker, default_schedule, derive_cell, meet_built, num_graphs_of, pack_lockstep, run_stack
+from .core import HipModule, built_marker, default_schedule, derive_cell, meet_built, num_graphs_of, pack_lockstep, run_stack
 
 
 class ASTNodeEncoder(nn.Module):
@@ -147,7 +147,7 @@ class _HeadsLinear(torch.autograd.Function):
         return (d_out, None, None, None, *gw, *gb)
 
 
-class DAGNN(nn.Module):
+class DAGNN(HipModule):
     """See module docstring.  Constructor mirrors `dagnn.py:18-112` argument for argument."""
 
     _plain_dataflow_ok = True   # (variants.run_plain_dataflow: `add` / `max` of THIS class - one shared AggConv - on the dataflow kernel)
@@ -232,9 +232,6 @@ class DAGNN(nn.Module):
                 for _ in range(max_seq_len):
                     self.graph_pred_linear_list.append(nn.Linear(self.out_hidden_dim, self.num_vocab))
 
-        self._derived = {}
-        self._head_cache = DerivedCache()
-        self._arenas = {}  # per device: granule buffers of the persistent tail kernel
         self.schedule = default_schedule()  # 'lockstep' (frontier launches) or 'pergraph' (persistent workgroups)
         self.variant_backend = "hip"       # constructor-string variants (a12): 'hip' = csrc/variants.hip forward and
                                             # csrc/variants_bwd.hip reverse sweep; 'torch' = always the differentiable
@@ -280,7 +277,7 @@ class DAGNN(nn.Module):
                 pack_lockstep(out.values())
             return out
 
-        return self._derived.setdefault(self.schedule, DerivedCache()).get(srcs, make, fresh=fresh or self.training)
+        return self._cache(self.schedule).get(srcs, make, fresh=fresh or self.training)
 
     def _folded_tables(self, cells):
         """Input side of stacked layer 0 by constant folding (evaluation only).  The node embedding is a sum of three table
@@ -362,26 +359,6 @@ class DAGNN(nn.Module):
         G.x = tables[0][3]                       # side effects 2 + 3 (dagnn.py:139, utils.py:27)
         return plan, gi0
 
-    def check(self) -> None:
-        """Blocking check for device-side failures of every pass launched so far (`core.check_arenas`): call it where
-        the outputs of the LAST forward of a loop are consumed - the non-blocking poll inside `forward` only reports
-        earlier passes."""
-        from .core import check_arenas
-        check_arenas(self)
-
-    def _arena_for(self, x, role="forward"):
-        # one arena per stream: passes issued on different streams keep their own granule buffers, epochs and error words
-        # (their plan / encoder / GEMM / head kernels may overlap; the all-resident persistent launches themselves are
-        # ordered device-wide by engine.persistent_launch - two of them in flight would deadlock on each other's CUs)
-        key = (role, x.device, engine._stream(x))
-        arena = self._arenas.get(key)
-        if arena is None:
-            arena = engine.GranuleArena()
-            # passes of further streams (micro-batches in flight) start their workgroup packing two XCDs further on
-            arena.xcd_first = 2 * sum(1 for k in self._arenas if k[0] == role and k[1] == x.device) % 8
-            self._arenas[key] = arena
-        return arena
-
     def _training_pass(self) -> bool:
         """True when this call must be differentiable.  The HIP backward (csrc/backward.hip) covers what the
         reference's training scripts run (scripts/ogb_tok.sh: attn_h, bidirectional, max-pool over the output
@@ -433,16 +410,6 @@ class DAGNN(nn.Module):
                 col += self.hidden_dim
         engine.readout_max_backward_batch(plan, jobs, gout)   # one launch for all (direction, stacked layer) state buffers
 
-    def _train_params(self):
-        flat = []
-        for d in self.dirs:
-            for i in range(self.num_layers):
-                c = getattr(self, "cells_%d" % d)[i]
-                a = getattr(self, "node_aggr_%d" % d)[i]
-                flat += [c.weight_ih, c.weight_hh, c.bias_ih, c.bias_hh, a.attn_lin.weight, a.attn_lin.bias,
-                         a.edge_encoder.weight if a.wea else None, a.edge_encoder.bias if a.wea else None]
-        return flat
-
     def _pool(self, h, batch, B):
         """`global_{max,mean,add}_pool` / P_ATTN read-outs on torch (variants outside BASELINE)."""
         how = self.out_pool
@@ -458,12 +425,6 @@ class DAGNN(nn.Module):
             cnt = torch.bincount(batch, minlength=B).clamp(min=1).to(h.dtype).view(-1, 1)
             out = out / cnt
         return out
-
-    def train(self, mode: bool = True):
-        """Mode switches drop the derived-weight caches (core.DerivedCache: an optimizer may have updated the
-        parameters without bumping their version counters)."""
-        self.invalidate_caches()
-        return super().train(mode)
 
     def _plan_of(self, G, B, overlap: bool = False):
         """The batch's plan.  With `overlap` the plan kernels (and the dataflow schedule's) run on a side stream next
@@ -544,19 +505,13 @@ class DAGNN(nn.Module):
             G.x = self.encoder(G.x, G.node_depth.view(-1, ))
             if self.variant_backend == "torch" or (torch.is_grad_enabled()
                                                     and any(p.requires_grad for p in self.parameters())):
-                for c in (self._head_cache, self.__dict__.get("_variant_cache"), self.__dict__.get("_plain_df_cache")):
-                    if c is not None:
-                        c.invalidate()
+                variants.drop_caches(self)
                 if self.variant_backend != "torch" and variants.hip_backward_supported(self, G):
                     # gated_sum / mattn_h / add with GRU cells: forward AND reverse sweep in HIP (csrc/variants_bwd.hip)
                     plan = self._plan_of(G, B)
                     flat_params = [p for d in self.dirs for i in range(L) for _, p in variants._cell_params(self, d, i)]
                     flat = variants.VariantRecurrence.apply(self, G, plan, G.x, *flat_params)
-                    h = [[None] * L for _ in range(2)]
-                    for q, d in enumerate(dirs):
-                        for i in range(L):
-                            h[d][i] = flat[q * L + i]
-                    return self._finish(G, None, G.x, h, B)
+                    return self._finish(G, None, G.x, self._unflatten(flat), B)
                 if self.variant_backend != "torch":   # (an explicit 'torch' backend is a choice, not a cliff)
                     variants.warn_torch_path(self, G)
                 return self._finish(G, None, G.x, variants.run(self, G, G.x), B)   # training: differentiable torch ops
@@ -587,16 +542,11 @@ class DAGNN(nn.Module):
         x = G.x
         fused_readout = self.bidirectional and not self.output_all and self.out_pool == K.P_MAX
         if train:
-            self._head_cache.invalidate()   # the optimizer step that follows may not bump version counters
             # differentiable call: HIP read-out + its backward for the configuration the reference trains
             # (scripts/ogb_tok.sh), otherwise differentiable states and the torch read-outs below
             from .autograd import Recurrence
             res = Recurrence.apply(self, plan, B, fused_readout, x, *self._train_params())
-            flat = res[1:] if fused_readout else res
-            h = [[None] * L for _ in range(2)]
-            for q, d in enumerate(dirs):
-                for i in range(L):
-                    h[d][i] = flat[q * L + i]
+            h = self._unflatten(res[1:] if fused_readout else res)
             if fused_readout:
                 G.h = [[h[d][i] for i in range(L)] for d in dirs]
                 return self._heads(self.dropout(res[0]))
@@ -607,25 +557,6 @@ class DAGNN(nn.Module):
                       arena=self._arena_for(x), gi0=self._folded_gi0(x_idx, depth, cells))
         self._guard_params(x)
         return self._finish(G, plan, x, h, B)
-
-    def _guard_params(self, x) -> None:
-        """Evaluation passes: the parameters behind the derived-weight caches still are what the caches were built from
-        (`core.ParamGuard`; a training-mode pass rebuilds everything anyway)."""
-        if self.training or not engine.PARAM_GUARD:
-            return
-        from .core import guard_params
-        guard_params(self, self._arena_for(x).error_word(x.device))
-
-    def invalidate_caches(self) -> None:
-        """Drop every tensor derived from the parameters (what `train()` / `eval()` do): call it after updating parameters in
-        evaluation mode through a path the version counters do not see (`.data`, a fused optimizer)."""
-        for c in list(self.__dict__.get("_derived", {}).values()) + [self.__dict__.get("_head_cache"),
-                                                                      self.__dict__.get("_variant_cache"),
-                                                                      self.__dict__.get("_plain_df_cache")]:
-            if c is not None:
-                c.invalidate()
-        from .core import drop_guard
-        drop_guard(self)
 
     def _head_storage(self):
         """The S vocabulary heads' weights and biases as ONE [S V, D] / [S V] pair: each head's parameter is (made) a VIEW of

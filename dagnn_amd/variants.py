@@ -33,7 +33,6 @@ from typing import List, Optional
 import torch
 
 from . import _lib, engine
-from .core import DerivedCache
 
 
 def _segment_softmax(logit: torch.Tensor, seg: torch.Tensor, num_seg: int) -> torch.Tensor:
@@ -216,8 +215,13 @@ def _derive(mod):
         return out
 
     srcs = [q for q in mod.parameters()]
-    cache = mod.__dict__.setdefault("_variant_cache", DerivedCache())
-    return cache.get(srcs, make, fresh=mod.training)
+    return mod._cache("variant").get(srcs, make, fresh=mod.training)
+
+
+def drop_caches(mod) -> None:
+    """Drop the weights `_derive` and `run_plain_dataflow` derived for `mod` (its cells and its parameter guard stay)."""
+    mod._cache("variant").invalidate()
+    mod._cache("plain_df").invalidate()
 
 
 _MODES = {"add": _lib.AGG_ADD, "max": _lib.AGG_MAX, "gated_sum": _lib.AGG_GATED}
@@ -272,8 +276,7 @@ def run_plain_dataflow(mod, x: torch.Tensor, plan) -> Optional[List[List[Optiona
         pack_dataflow(out.values())
         return out
 
-    cache = mod.__dict__.setdefault("_plain_df_cache", DerivedCache())
-    cells = cache.get(srcs, make, fresh=mod.training)
+    cells = mod._cache("plain_df").get(srcs, make, fresh=mod.training)
     if cells is None:
         return None
     Hp = cells[(dirs[0], 0)].Hp
@@ -620,9 +623,7 @@ class VariantRecurrence(torch.autograd.Function):
         # a training pass never reads derived weights cached from earlier parameters: the module may stay in eval() mode while
         # it trains (dropout 0), and an optimizer step that does not bump version counters leaves the cache key where it was
         # (the backward below reuses what this call derives)
-        cache = mod.__dict__.get("_variant_cache")
-        if cache is not None:
-            cache.invalidate()
+        mod._cache("variant").invalidate()
         h = run_hip(mod, G, x, plan, dataflow=False)
         ctx.mod, ctx.plan, ctx.h = mod, plan, h
         ctx.save_for_backward(x, *params)

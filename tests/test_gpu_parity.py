@@ -287,7 +287,7 @@ def test_dvae_encode_matches_reference_golden(device, name, schedule):
 
 @pytest.mark.parametrize("name", ["na_h64_add", "bn_h64_max", "na_h64_gated_sum"])
 def test_dvae_aggregator_weights_follow_silent_parameter_updates(device, name):
-    """`add` / `max` on the D-VAE encoders derive their weights on a cached view object (variants._derive).  A fused
+    """`add` / `max` on the D-VAE encoders derive their weights through a cached view object (variants._derive).  A fused
     optimizer (or a write through `.data`) changes parameters without bumping `_version`: a train() / eval() switch has
     to drop that cache too (round-4 advisor finding: eval -> silent update -> eval returned the OLD weights)."""
     meta, arr = Hh.load(name)
