@@ -155,10 +155,12 @@ class _IpropStep(torch.autograd.Function):
         return tuple(grads)
 
 
-def decode_schedule(G_true, max_n: int, nvt: int):
+def decode_schedule(G_true, max_n: int, nvt: int, start_type: int = 0):
     """What the teacher-forced decoder reads of the true graphs: types [B, max_n] (`g.vs[v]['type']`, as
     `models_pyg.py:405-406` reads them) and predecessor bitmasks [B, max_n] (bit u of preds[b, v]: the edge u -> v,
-    from `g.edge_index` as `:417-420`), both int32.  Every graph must have exactly max_n vertices."""
+    from `g.edge_index` as `:417-420`), both int32.  Every graph must have exactly max_n vertices, and no vertex but
+    vertex 0 may have type `start_type`: the reference reads START_TYPE there as padding and does not add the vertex
+    (`:413-414`), which shifts every later index - a different computation from the one the kernel runs."""
     B = len(G_true)
     if max_n > 32:
         raise ValueError("loss(): at most 32 vertices per graph (got max_n=%d)" % max_n)
@@ -176,6 +178,10 @@ def decode_schedule(G_true, max_n: int, nvt: int):
         np.bitwise_or.at(preds[b], dst[keep], (np.uint32(1) << src[keep].astype(np.uint32)))
     if B and (types[:, 1:].min() < 0 or types.max() >= nvt):
         raise ValueError("loss(): vertex types must lie in [0, nvt=%d)" % nvt)
+    if B and (types[:, 1:] == start_type).any():
+        b, v = (int(x[0]) for x in np.nonzero(types[:, 1:] == start_type))
+        raise ValueError("loss(): vertex %d of graph %d has START_TYPE=%d, which only vertex 0 may have (the reference "
+                         "treats it as padding and skips the vertex)" % (v + 1, b, start_type))
     return types.astype(np.int32), preds.view(np.int32)
 
 
@@ -805,7 +811,7 @@ class _DvaeDagnn(_DvaeBase):
         self._check_decoder_agg("loss(): the teacher-forced decoder")
         if type(G_true) != list:
             G_true = [G_true]
-        types, preds = decode_schedule(G_true, self.max_n, self.nvt)
+        types, preds = decode_schedule(G_true, self.max_n, self.nvt, int(self.START_TYPE))
         if len(G_true) != mu.shape[0]:
             raise ValueError("loss(): %d graphs for %d latent rows" % (len(G_true), mu.shape[0]))
         z = self.reparameterize(mu, logvar)
@@ -816,13 +822,7 @@ class _DvaeDagnn(_DvaeBase):
         dev = H0.device
         t_types = torch.from_numpy(types).pin_memory().to(dev, non_blocking=True)
         t_preds = torch.from_numpy(preds).pin_memory().to(dev, non_blocking=True)
-        cells = list(self.grud)[:self.num_layers]
-        params = self._decoder_agg_tensors()
-        params += [t for c in cells for t in (c.weight_ih, c.weight_hh, c.bias_ih, c.bias_hh)]
-        params += [self.add_vertex[0].weight, self.add_vertex[0].bias, self.add_vertex[2].weight, self.add_vertex[2].bias,
-                   self.add_edge[0].weight, self.add_edge[0].bias, self.add_edge[2].weight, self.add_edge[2].bias]
-        spec = dict(n=self.max_n, nvt=self.nvt, start_type=int(self.START_TYPE), bn=not self._use_vids, vid=self._use_vids,
-                    L=len(cells), hs=self.hs, dq=self._key_offset(0), agg=self.agg)
+        spec, params = self._decode_loss_inputs()
         if torch.is_grad_enabled() and any(t.requires_grad for t in [H0] + params):
             res = _DecodeLoss.apply(spec, t_types, t_preds, H0, *params)
         else:   # (no autograd record: the saved activations die with this call)
@@ -830,16 +830,30 @@ class _DvaeDagnn(_DvaeBase):
         kld = -0.5 * torch.sum(1 + logvar - mu.pow(2) - logvar.exp())
         return res + beta * kld, res, kld
 
+    def _decode_loss_inputs(self):
+        """(spec, tensors) of `_DecodeLoss` / `_make_decode`: the aggregator's tensors, 4 per grud cell, then add_vertex
+        and add_edge."""
+        cells = list(self.grud)[:self.num_layers]
+        params = self._decoder_agg_tensors()
+        params += [t for c in cells for t in (c.weight_ih, c.weight_hh, c.bias_ih, c.bias_hh)]
+        params += [self.add_vertex[0].weight, self.add_vertex[0].bias, self.add_vertex[2].weight, self.add_vertex[2].bias,
+                   self.add_edge[0].weight, self.add_edge[0].bias, self.add_edge[2].weight, self.add_edge[2].bias]
+        spec = dict(n=self.max_n, nvt=self.nvt, start_type=int(self.START_TYPE), bn=not self._use_vids, vid=self._use_vids,
+                    L=len(cells), hs=self.hs, dq=self._key_offset(0), agg=self.agg)
+        return spec, params
+
     def _check_decoder_agg(self, what):
-        """The decoders serve attn_h and (NA) gated_sum; gated_sum's messages read [hs-wide state ; one-hot(u, max_n)]
-        through the encoder's layer-0 gate / mapper, so the reference itself needs hidden_dim == hs and
-        num_nodes == max_n (a shape error otherwise)."""
+        """The decoders serve attn_h and (NA) gated_sum.  Both read the predecessors' hs-wide states (NA: with a
+        one-hot(u, max_n) vertex id) through the encoder's layer-0 module: gated_sum's gate / mapper, attn_h's key half of
+        attn_lin, which is hidden_dim (+ num_nodes) wide.  So the reference itself needs hidden_dim == hs and (NA)
+        num_nodes == max_n - a shape error otherwise - and the kernels would read the wrong columns."""
         if self.agg not in (K.NA_ATTN_H, K.NA_GATED_SUM):
             raise NotImplementedError("%s is built for agg='attn_h' (the reference's D-VAE default, dvae/train.py:86) and "
                                       "agg='gated_sum', not %r" % (what, self.agg))
-        if self.agg == K.NA_GATED_SUM and (self.hidden_dim != self.hs or self.num_nodes != self.max_n):
-            raise ValueError("%s with agg='gated_sum' needs hidden_dim == hs and num_nodes == max_n (got hidden_dim=%d, "
-                             "hs=%d, num_nodes=%d, max_n=%d)" % (what, self.hidden_dim, self.hs, self.num_nodes, self.max_n))
+        if self.hidden_dim != self.hs or (self._use_vids and self.num_nodes != self.max_n):
+            raise ValueError("%s with agg=%r needs hidden_dim == hs%s (got hidden_dim=%d, hs=%d, num_nodes=%d, max_n=%d)"
+                             % (what, self.agg, " and num_nodes == max_n" if self._use_vids else "", self.hidden_dim,
+                                self.hs, self.num_nodes, self.max_n))
 
     def _decoder_agg_tensors(self):
         """The decoder's aggregator tensors: attn_h the attn_lin weight, gated_sum the layer-0 gate (weight, bias) and
@@ -869,9 +883,9 @@ class _DvaeDagnn(_DvaeBase):
         [attempts, B, max_n, hs] final top-layer states or None).  Each attempt is decoded exactly as one reference call on
         its B rows.  Sampled draws come from ONE torch.rand call on z's device (so torch.manual_seed makes decoding
         reproducible) unless `draws = (u_type, u_edge)` is given, shaped as `draw_shapes(max_n, B, attempts)`."""
-        self._check_decoder_agg("decode(): the decoder step")
         if self.max_n > 32:
             raise ValueError("decode(): at most 32 vertices per graph (got max_n=%d)" % self.max_n)
+        self._check_decoder_agg("decode(): the decoder step")
         if not isinstance(z, torch.Tensor) or z.dim() != 2 or z.shape[1] != self.nz or z.shape[0] == 0:
             raise ValueError("decode(): z must be [B, nz=%d] with B >= 1 (got %s)"
                              % (self.nz, tuple(z.shape) if isinstance(z, torch.Tensor) else type(z)))

@@ -242,3 +242,98 @@ def check_grads_full(model, ref, rtol=1e-4, atol=2e-7):
 def grad_norm64(model, ref):
     """The float64 global 2-norm of the reference gradients of `model`'s parameters (what clip_grad_norm_ sees)."""
     return float(torch.sqrt(sum((ref[k].double() ** 2).sum() for k, _ in model.named_parameters() if k in ref)))
+
+
+# ------------------------------------------------------------------ D-VAE decoders at free shapes (test_dvae_decoder_f64_gpu)
+def dvae_decoder_model(kind, *, max_n, nvt, hs, L, nz=8, start_type=0, end_type=1, agg="attn_h", seed=0):
+    """DAGNN_NA (kind 'na') or DAGNN_BN ('bn') with free max_n / nvt / hs / L / nz / START_TYPE / END_TYPE: emb_dim = nvt,
+    hidden_dim = hs, num_nodes = max_n (the widths the reference's decoder needs), weights from `seeded_fill`."""
+    cls = DAGNN_NA if kind == "na" else DAGNN_BN
+    model = cls(nvt, hs, hs, max_n, nvt, start_type, end_type, hs=hs, nz=nz, num_nodes=max_n, agg=agg, num_layers=L,
+                bidirectional=kind == "bn", out_wx=False, out_pool_all=False, out_pool="max", dropout=0.0).eval()
+    seeded_fill(model, seed)
+    return model
+
+
+GRAPH_FAMILIES = ("none", "chain", "star", "complete", "random0.2", "random0.5", "random0.8", "one_complete")
+
+
+def dvae_dense_graphs(family, B, n, nvt, start_type, seed):
+    """(types [B, n], preds [B, n]) int32 of B graphs of one family: no edges, a chain, a star out of vertex 0, the
+    complete DAG (P = v at every vertex), random at density 0.2 / 0.5 / 0.8, or one complete graph among edgeless ones
+    (that row alone sets every padding width).  Types at vertices >= 1 avoid start_type; vertex 0 has start_type."""
+    rng = np.random.default_rng(seed)
+    others = [t for t in range(nvt) if t != start_type]
+    types = np.asarray(others, np.int64)[rng.integers(0, len(others), size=(B, n))]
+    types[:, 0] = start_type
+    adj = np.zeros((B, n, n), bool)   # [b, v, u]: edge u -> v
+    lower = np.tril(np.ones((n, n), bool), -1)
+    if family == "chain":
+        adj[:, np.arange(1, n), np.arange(n - 1)] = True
+    elif family == "star":
+        adj[:, 1:, 0] = True
+    elif family == "complete":
+        adj[:] = lower
+    elif family.startswith("random"):
+        adj = (rng.random((B, n, n)) < float(family[6:])) & lower
+    elif family == "one_complete":
+        adj[int(rng.integers(0, B))] = lower
+    elif family != "none":
+        raise ValueError(family)
+    preds = (adj.astype(np.int64) << np.arange(n)).sum(2)
+    return types.astype(np.int32), preds.astype(np.uint32).view(np.int32)
+
+
+def dvae_graphs_from_dense(types, preds, nvt):
+    """Graph objects `loss()` / `encode()` take, from dense types and predecessor masks."""
+    from dagnn_amd import synth
+    out = []
+    for t, p in zip(np.asarray(types), np.asarray(preds).view(np.uint32)):
+        n = len(t)
+        adj = np.zeros((n, n))
+        for v in range(n):
+            for u in range(v):
+                if int(p[v]) >> u & 1:
+                    adj[u, v] = 1
+        out.append(synth._adj_to_graph(adj, [int(x) for x in t], nvt))
+    return out
+
+
+def dvae_decoder64(key, model, types, preds, mu, logvar, graphs=None, diag=None):
+    """The float64 teacher-forced `loss()` of `oracle.dvae_decoder_oracle` for (model, types, preds, mu, logvar):
+    (loss, res, kld, vertex_ll, edge_ll, {name: gradient}, diag), cached per `key` like `code2_grads64`.  With `graphs`,
+    mu / logvar come from the float64 encoder oracle on those graphs (one leaf per shared storage, so the layer-0
+    gate / mapper get the encoder's and the decoder's gradients added)."""
+    from oracle import dagnn_oracle as O
+    from oracle import dvae_decoder_oracle as DO
+    if key is not None and key in _REF64:
+        return _REF64[key]
+    sd = _cpu_state(model)
+    kind = "bn" if isinstance(model, DAGNN_BN) else "na"
+    kw = dict(kind=kind, agg=model.agg, L=model.num_layers, start_type=int(model.START_TYPE))
+    d = {}
+    if graphs is None:
+        loss, res, kld, vll, ell, grads = DO.decoder_loss_grads(sd, types, preds, mu.cpu(), logvar.cpu(), diag=d, **kw)
+    else:
+        by_ptr, leaves = {}, {}
+        for k, v in sd.items():
+            if v.is_floating_point():
+                pk = (v.data_ptr(), tuple(v.shape), tuple(v.stride()))
+                by_ptr.setdefault(pk, v.detach().double().clone().requires_grad_(True))
+                leaves[k] = by_ptr[pk]
+        b = dagnn_amd.GraphBatch.from_data_list([g.clone() for g in graphs])
+        mu64, lv64 = O.dvae_encode(leaves, b, num_layers=model.num_layers, bidirectional=model.bidirectional,
+                                   num_nodes=model.num_nodes, vids=kind == "na", agg=model.agg, dtype=torch.float64,
+                                   keep_graph=True)
+        H0 = torch.tanh(mu64 @ leaves["fc3.weight"].t() + leaves["fc3.bias"])
+        res, vll, ell = DO.decoder_loss(leaves, types, preds, H0, diag=d, **kw)
+        kld = -0.5 * torch.sum(1 + lv64 - mu64.pow(2) - lv64.exp())
+        loss = res + 0.005 * kld
+        names = list(leaves)
+        gs = torch.autograd.grad(loss, [leaves[k] for k in names], allow_unused=True)
+        grads = {k: g for k, g in zip(names, gs) if g is not None}
+        loss, res, kld, vll, ell = (t.detach() for t in (loss, res, kld, vll, ell))
+    val = (loss, res, kld, vll, ell, grads, d)
+    if key is not None:
+        _REF64[key] = val
+    return val

@@ -91,3 +91,45 @@ def test_reparameterize_follows_the_mode():
     torch.manual_seed(3)
     eps = torch.randn_like(mu) * 0.01
     assert torch.equal(z, eps.mul(lv.mul(0.5).exp()).add(mu))
+
+
+def test_schedule_refuses_start_type_after_vertex_0():
+    """The reference reads START_TYPE at a vertex >= 1 as padding and does not add that vertex (models_pyg.py:413-414),
+    which shifts every later index; the kernel would compute something else, so the schedule refuses it."""
+    model, graphs, mu, lv = _model_and_graphs()
+    n = model.max_n
+    types, _ = dvae.decode_schedule(graphs, n, n, 0)
+    assert (types[:, 1:] != 0).all()
+    for st in (2, 5):   # another START_TYPE that the graphs do use at a later vertex
+        b, v = (int(x[0]) for x in np.nonzero(types[:, 1:] == st))
+        with pytest.raises(ValueError, match="vertex %d of graph %d has START_TYPE=%d" % (v + 1, b, st)):
+            dvae.decode_schedule(graphs, n, n, st)
+    types0 = types[:, 0].copy()   # vertex 0 may carry any type: the decoder sets it to START_TYPE itself
+    g = graphs[0]
+    g.vs[0]["type"] = 3
+    t2, _ = dvae.decode_schedule(graphs, n, n, 0)
+    assert t2[0, 0] == 3 and np.array_equal(t2[1:, 0], types0[1:])
+    model.START_TYPE = int(types[0, 2])
+    with pytest.raises(ValueError, match="START_TYPE"):
+        model.loss(mu, lv, graphs)
+
+
+@pytest.mark.parametrize("kind", ["na", "bn"])
+def test_decoders_refuse_attention_keys_of_another_width(kind):
+    """attn_h's key half of attn_lin is hidden_dim (+ num_nodes for NA) wide; the decoders read hs (+ max_n) columns of
+    it, so a model whose widths differ is refused (the reference fails with a shape error)."""
+    from dagnn_amd import DAGNN_BN, DAGNN_NA
+    cls, n = (DAGNN_NA, 8) if kind == "na" else (DAGNN_BN, 10)
+    bad = [dict(hidden_dim=24)] + ([dict(num_nodes=9)] if kind == "na" else [])
+    for kw in bad:
+        args = dict(hidden_dim=16, num_nodes=n)
+        args.update(kw)
+        model = cls(n, args["hidden_dim"], 16, n, n, 0, 1, hs=16, nz=4, num_nodes=args["num_nodes"], num_layers=2)
+        z = torch.zeros(2, 4)
+        with pytest.raises(ValueError, match="hidden_dim == hs"):
+            model.decode(z)
+        with pytest.raises(ValueError, match="hidden_dim == hs"):
+            model.loss(z, z, [])
+    ok = cls(n, 16, 16, n, n, 0, 1, hs=16, nz=4, num_nodes=20 if kind == "bn" else n, num_layers=2)
+    with pytest.raises(_lib.DagnnHipError, match="GPU"):   # past the check: only the missing GPU stops it
+        ok.decode(torch.zeros(2, 4))
