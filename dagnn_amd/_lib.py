@@ -238,6 +238,18 @@ class DvaeSampleArgs(C.Structure):
                 ("agg", C.c_int), ("gate_w", C.c_void_p), ("gate_b", C.c_void_p), ("mapper_w", C.c_void_p)]
 
 
+DVAE_ENAS, DVAE_BN = 0, 1                        # DAGNN_DVAE_ENAS / DAGNN_DVAE_BN
+DVAE_FIRST_VALID, DVAE_MOST_FREQUENT = 0, 1      # DAGNN_DVAE_FIRST_VALID / DAGNN_DVAE_MOST_FREQUENT
+
+
+class DvaeSelectArgs(C.Structure):
+    _fields_ = [("A", C.c_int64), ("B", C.c_int64), ("n", C.c_int), ("nvt", C.c_int), ("start_type", C.c_int),
+                ("end_type", C.c_int), ("kind", C.c_int), ("n_nodes", C.c_int), ("select", C.c_int),
+                ("types", C.c_void_p), ("preds", C.c_void_p), ("nv", C.c_void_p), ("valid", C.c_void_p),
+                ("pick", C.c_void_p), ("n_valid", C.c_void_p), ("n_same", C.c_void_p), ("work", C.c_void_p),
+                ("work_bytes", C.c_size_t)]
+
+
 class VariantBwdCell(C.Structure):
     _fields_ = [("mode", C.c_int32), ("lands", C.c_int32), ("in_dim", C.c_int32), ("proj_dim", C.c_int32),
                 ("recurrent", C.c_int32), ("reserved", C.c_int32)] + \
@@ -350,6 +362,9 @@ SYMBOLS = {
     "dagnn_dvae_decode_backward": (C.c_int, [C.POINTER(DvaeDecodeArgs), C.POINTER(DvaeDecodeGrads), C.c_void_p]),
     "dagnn_dvae_sample_work_bytes": (C.c_size_t, [C.POINTER(DvaeSampleArgs)]),
     "dagnn_dvae_sample": (C.c_int, [C.POINTER(DvaeSampleArgs), C.c_void_p]),
+    "dagnn_dvae_select_key_words": (C.c_int, [C.c_int, C.c_int, C.c_int]),
+    "dagnn_dvae_select_work_bytes": (C.c_size_t, [C.POINTER(DvaeSelectArgs)]),
+    "dagnn_dvae_select": (C.c_int, [C.POINTER(DvaeSelectArgs), C.c_void_p]),
     "dagnn_debug_occupy": (C.c_int, [C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p]),
     "dagnn_tn_product": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                    C.c_void_p]),

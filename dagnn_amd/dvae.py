@@ -12,6 +12,7 @@ HIP call (csrc/dvae_sample.hip).
 """
 from __future__ import annotations
 
+import collections
 import copy
 from collections import namedtuple
 from typing import List
@@ -212,12 +213,43 @@ def draw_shapes(max_n: int, B: int, attempts: int = 1):
     return (attempts, max_n, B), (attempts, max_n * (max_n - 1) // 2, B)
 
 
+IGRAPH_OUT, IGRAPH_IN, IGRAPH_ALL = 1, 2, 3   # igraph.OUT / IN / ALL
+
+
+def _neighbor_mode(mode):
+    if isinstance(mode, str):
+        m = {"out": IGRAPH_OUT, "in": IGRAPH_IN, "all": IGRAPH_ALL}.get(mode.lower())
+    else:
+        m = int(mode) if int(mode) in (IGRAPH_OUT, IGRAPH_IN, IGRAPH_ALL) else None
+    if m is None:
+        raise ValueError("neighbour mode must be 'out', 'in', 'all' or igraph's OUT / IN / ALL (got %r)" % (mode,))
+    return m
+
+
+class _Vertex(dict):
+    """`g.vs[v]`: a dict of the vertex's attributes ('type') with igraph's `index`, `indegree()` and `outdegree()`."""
+
+    def __init__(self, graph, index, t):
+        dict.__init__(self, type=t)
+        self._graph, self.index = graph, index
+
+    def indegree(self):
+        return len(self._graph._pred[self.index])
+
+    def outdegree(self):
+        return len(self._graph._succ[self.index])
+
+
 class _VertexSeq(object):
-    def __init__(self, types):
-        self._types = types
+    def __init__(self, graph):
+        self._graph = graph
+        self._types = graph._types
 
     def __len__(self):
         return len(self._types)
+
+    def __iter__(self):
+        return (_Vertex(self._graph, v, t) for v, t in enumerate(self._types))
 
     def attributes(self):
         return ["type"]
@@ -227,18 +259,36 @@ class _VertexSeq(object):
             if key != "type":
                 raise KeyError(key)
             return list(self._types)
-        return {"type": self._types[key]}
+        v = range(len(self._types))[key]
+        return _Vertex(self._graph, v, self._types[v])
+
+
+class _Matrix(object):
+    """What `get_adjacency()` returns: igraph's Matrix, read through `.data` (a list of rows)."""
+
+    def __init__(self, data):
+        self.data = data
+
+    def __getitem__(self, key):
+        return self.data[key]
 
 
 class DecodedGraph(object):
     """A decoded DAG when python-igraph is not installed: the parts of `igraph.Graph` that D-VAE code reads of a decoded
     graph (`vcount`, `ecount`, `vs[v]['type']`, `vs['type']`, `vs.attributes()`, `predecessors`, `successors`, `get_edgelist`, `indegree`,
-    `outdegree`, `is_dag`).  Edges are listed in the order the reference's `decode()` adds them."""
+    `outdegree`, `is_dag`), and what dvae/util.py's checks and string forms call: iteration over `vs` (vertices with
+    `.index`, `['type']`, `.indegree()`, `.outdegree()`), `are_connected`, `get_adjlist(mode)`, `get_adjacency().data`
+    and `neighbors(v, mode)`.  Edges are listed in the order the reference's `decode()` adds them."""
 
     def __init__(self, types, edges):
         self._types = [int(t) for t in types]
         self._edges = [(int(u), int(v)) for u, v in edges]
-        self.vs = _VertexSeq(self._types)
+        n = len(self._types)
+        self._pred, self._succ = [[] for _ in range(n)], [[] for _ in range(n)]
+        for u, v in self._edges:
+            self._pred[v].append(u)
+            self._succ[u].append(v)
+        self.vs = _VertexSeq(self)
 
     def vcount(self):
         return len(self._types)
@@ -250,18 +300,36 @@ class DecodedGraph(object):
         return list(self._edges)
 
     def predecessors(self, v):
-        return sorted(u for u, w in self._edges if w == v)
+        return sorted(self._pred[v])
 
     def successors(self, v):
-        return sorted(w for u, w in self._edges if u == v)
+        return sorted(self._succ[v])
 
     def indegree(self, vertices=None):
-        deg = [len(self.predecessors(v)) for v in range(self.vcount())]
+        deg = [len(p) for p in self._pred]
         return deg if vertices is None else (deg[vertices] if isinstance(vertices, int) else [deg[v] for v in vertices])
 
     def outdegree(self, vertices=None):
-        deg = [len(self.successors(v)) for v in range(self.vcount())]
+        deg = [len(s) for s in self._succ]
         return deg if vertices is None else (deg[vertices] if isinstance(vertices, int) else [deg[v] for v in vertices])
+
+    def are_connected(self, u, v):
+        return int(v) in self._succ[int(u)]
+
+    def neighbors(self, vertex, mode="all"):
+        m = _neighbor_mode(mode)
+        v = int(vertex)
+        return sorted((self._pred[v] if m != IGRAPH_OUT else []) + (self._succ[v] if m != IGRAPH_IN else []))
+
+    def get_adjlist(self, mode="out"):
+        return [self.neighbors(v, mode) for v in range(self.vcount())]
+
+    def get_adjacency(self):
+        n = self.vcount()
+        data = [[0] * n for _ in range(n)]
+        for u, v in self._edges:
+            data[u][v] += 1
+        return _Matrix(data)
 
     def is_dag(self):
         indeg = self.indegree()
@@ -319,6 +387,169 @@ def graphs_from_dense(types, preds, nv, end_type, use_igraph=None):
 
 
 DecodedDense = namedtuple("DecodedDense", ["types", "preds", "nv", "states"])
+
+
+# ------------------------------------------------------------------ validity, strings and selection (dvae/util.py)
+SelectedDense = namedtuple("SelectedDense", ["valid", "pick", "n_valid", "n_same", "keys"])
+_KINDS = {"ENAS": 0, "BN": 1}            # DAGNN_DVAE_ENAS / DAGNN_DVAE_BN
+_SELECTS = {"first": 0, "most_common": 1}  # DAGNN_DVAE_FIRST_VALID / DAGNN_DVAE_MOST_FREQUENT
+SELECT_ROWS = 1 << 15   # rows (attempts x points) per decode_dense call of decode_from_latent_space by default
+
+
+def _kind(data_type):
+    if data_type not in _KINDS:
+        raise ValueError("data_type must be 'ENAS' or 'BN' (got %r)" % (data_type,))
+    return _KINDS[data_type]
+
+
+def _select_mode(select):
+    if select not in _SELECTS:
+        raise ValueError("select must be 'first' (the reference's pick) or 'most_common' (got %r)" % (select,))
+    return _SELECTS[select]
+
+
+def _n_nodes(n_nodes):
+    """0 for any vertex count ('variable' as the reference spells it, or None), else the required count."""
+    if n_nodes is None or (isinstance(n_nodes, str) and n_nodes == "variable"):
+        return 0
+    if isinstance(n_nodes, str) or int(n_nodes) < 1 or int(n_nodes) > 32:
+        raise ValueError("n_nodes must be 'variable' or a vertex count in 1..32 (got %r)" % (n_nodes,))
+    return int(n_nodes)
+
+
+def _row_edges(preds, k):
+    return [(u, v) for v in range(k) for u in range(v) if int(preds[v]) >> u & 1]
+
+
+def enas_string(types, preds, nv):
+    """`decode_igraph_to_ENAS` (dvae/util.py:168-180) of one dense row: per middle vertex i, type-2 then the i-1 bits
+    j -> i for j < i-1."""
+    res = []
+    for i in range(1, int(nv) - 1):
+        m = int(preds[i]) & 0xFFFFFFFF
+        res.append(int(types[i]) - 2)
+        res += [m >> j & 1 for j in range(i - 1)]
+    return " ".join(str(x) for x in res)
+
+
+def bn_adj_string(types, preds, nv):
+    """`decode_igraph_to_BN_adj` (dvae/util.py:388-394) of one dense row: the middle vertices' adjacency, rows and
+    columns permuted by the argsort of their types."""
+    k = int(nv)
+    order = np.argsort([int(t) for t in types[:k]][1:-1]).tolist()
+    adj = np.zeros((k, k), dtype=np.int64)
+    for u, v in _row_edges(preds, k):
+        adj[u, v] += 1
+    adj = adj[1:-1, 1:-1][order][:, order]
+    return " ".join(str(x) for x in adj.reshape(-1))
+
+
+def row_valid(types, preds, nv, data_type, nvt, start_type, end_type, n_nodes=None):
+    """The reference's rules on one dense row, restated over its edge list: `is_valid_ENAS` (dvae/util.py:599-631;
+    with n_nodes, also exactly n_nodes vertices) or `is_valid_BN` (:634-649).  A vertex count outside [1, len(types)] or
+    a type outside [0, nvt) is invalid (the decoder writes neither), as in dagnn_dvae_select."""
+    k, kind, nn_ = int(nv), _kind(data_type), _n_nodes(n_nodes)
+    if not 1 <= k <= len(types):
+        return False
+    ts = [int(t) for t in types[:k]]
+    if any(t < 0 or t >= nvt for t in ts):
+        return False
+    edges = _row_edges(preds, k)
+    indeg, outdeg = [0] * k, [0] * k
+    for u, v in edges:
+        outdeg[u] += 1
+        indeg[v] += 1
+    n_start = sum(t == start_type for t in ts)
+    n_end = sum(t == end_type and t != start_type for t in ts)
+    if kind == 1:
+        return n_start == 1 and n_end == 1 and len(set(ts)) == nvt and k == nvt
+    res = n_start == 1 and n_end == 1
+    for v in range(k):
+        if (indeg[v] == 0 and ts[v] != start_type) or (outdeg[v] == 0 and ts[v] != end_type):
+            return False
+    res = res and all((i, i + 1) in edges for i in range(k - 2)) and indeg[k - 1] == 1
+    return res and (nn_ == 0 or k == nn_)
+
+
+def select_key_words(data_type, n, nvt):
+    """W: 64-bit words of a canonical key (dagnn_dvae_select_key_words)."""
+    if _kind(data_type) == 0:
+        bits = 6 + (n - 2) * max(1, int(nvt - 1).bit_length()) + (n - 2) * (n - 3) // 2
+    else:
+        bits = max(min(nvt, n) - 2, 0) ** 2
+    return max(1, (bits + 63) // 64)
+
+
+def select_key(types, preds, nv, data_type, n, nvt):
+    """The canonical key dagnn_dvae_select writes for a valid row (W signed 64-bit words, bit fields appended low bit
+    first): ENAS the vertex count (6 bits), the middle types, then the row bits j < i-1 of vertices i = 2 .. nv-2; BN the
+    type-ordered adjacency of the middle vertices, row by row."""
+    k, acc, pos = int(nv), 0, 0
+    fields = []
+    if _kind(data_type) == 0:
+        tb = max(1, int(nvt - 1).bit_length())
+        fields = [(k, 6)] + [(int(types[v]), tb) for v in range(1, k - 1)]
+        fields += [(int(preds[v]) & ((1 << (v - 1)) - 1), v - 1) for v in range(2, k - 1)]
+    else:
+        mid = [int(t) for t in types[1:k - 1]]
+        rank = {t: r for r, t in enumerate(sorted(mid))}
+        by_rank = sorted(range(1, k - 1), key=lambda v: rank[int(types[v])])
+        for u in by_rank:
+            fields.append((sum(1 << rank[int(types[v])] for v in range(u + 1, k - 1) if int(preds[v]) >> u & 1), k - 2))
+    for val, width in fields:
+        acc |= val << pos
+        pos += width
+    W = select_key_words(data_type, n, nvt)
+    return [int(np.int64(np.uint64((acc >> (64 * w)) & 0xFFFFFFFFFFFFFFFF))) for w in range(W)]
+
+
+def select_host(types, preds, nv, data_type, nvt, start_type, end_type, n_nodes=None, select="first"):
+    """Host mirror of dagnn_dvae_select on numpy rows types / preds [A,B,n], nv [A,B], written as the reference's loop
+    (dvae/util.py:430-461): validity per attempt, the string of every valid one, then per point the first valid string
+    (select='first') or Counter.most_common(1) ('most_common').  Returns (valid [A,B] bool, pick [B], n_valid [B],
+    n_same [B], strings: per point the list of (attempt, string) of its valid attempts)."""
+    types, preds, nv = np.asarray(types), np.asarray(preds), np.asarray(nv)
+    A, B = nv.shape
+    form = enas_string if _kind(data_type) == 0 else bn_adj_string
+    mode = _select_mode(select)
+    valid = np.zeros((A, B), dtype=bool)
+    pick, n_valid, n_same = (np.zeros(B, dtype=np.int32) for _ in range(3))
+    strings = []
+    for b in range(B):
+        cur = []
+        for a in range(A):
+            if row_valid(types[a, b], preds[a, b], nv[a, b], data_type, nvt, start_type, end_type, n_nodes):
+                valid[a, b] = True
+                cur.append((a, form(types[a, b], preds[a, b], nv[a, b])))
+        strings.append(cur)
+        n_valid[b] = len(cur)
+        if not cur:
+            pick[b] = -1
+            continue
+        counts = collections.Counter(s for _, s in cur)
+        best = cur[0][1] if mode == 0 else counts.most_common(1)[0][0]
+        pick[b] = next(a for a, s in cur if s == best)
+        n_same[b] = counts[best]
+    return valid, pick, n_valid, n_same, strings
+
+
+def select_decoded(decoded, data_type, nvt, start_type, end_type, n_nodes=None, select="first"):
+    """Validity of every attempt of a DecodedDense [A,B,...] and the pick per point: SelectedDense(valid [A,B], pick [B]
+    (-1: no valid attempt), n_valid [B], n_same [B], keys [B,A,W]), int32 but the int64 keys.  On the GPU one call of
+    dagnn_dvae_select, without synchronising; rows already on the host go through the host mirror."""
+    kind, mode = _kind(data_type), _select_mode(select)
+    nn_ = _n_nodes(n_nodes) if kind == 0 else 0
+    if decoded.types.is_cuda:
+        return SelectedDense(*engine.dvae_select(decoded.types, decoded.preds, decoded.nv, nvt, start_type, end_type, kind, nn_,
+                                                 mode))
+    types, preds, nv = (t.cpu().numpy() for t in (decoded.types, decoded.preds, decoded.nv))
+    A, B, n = types.shape
+    valid, pick, n_valid, n_same, _ = select_host(types, preds, nv, data_type, nvt, start_type, end_type, nn_ or None, select)
+    keys = np.zeros((B, A, select_key_words(data_type, n, nvt)), dtype=np.int64)
+    for a, b in zip(*np.nonzero(valid)):
+        keys[b, a] = select_key(types[a, b], preds[a, b], nv[a, b], data_type, n, nvt)
+    t = lambda x: torch.from_numpy(np.ascontiguousarray(x, dtype=np.int32))  # noqa: E731
+    return SelectedDense(t(valid), t(pick), t(n_valid), t(n_same), torch.from_numpy(keys))
 
 
 class _DecodeLoss(torch.autograd.Function):
@@ -407,6 +638,12 @@ class _DvaeBase(HipModule):
 
     def _collate_fn(self, G):
         return [copy.deepcopy(g) for g in G]
+
+    def select_dense(self, decoded, data_type="ENAS", n_nodes=None, select="first"):
+        """Validity and the pick per latent point of a `decode_dense(z, attempts=A)` result, as the reference's
+        `decode_from_latent_space` (dvae/util.py:430-461) applies them: SelectedDense(valid [A,B], pick [B], n_valid [B],
+        n_same [B], keys [B,A,W]) - see `select_decoded`.  ONE HIP call (csrc/dvae_select.hip), no synchronisation."""
+        return select_decoded(decoded, data_type, self.nvt, self.START_TYPE, self.END_TYPE, n_nodes, select)
 
 
 class _DvaeDagnn(_DvaeBase):
@@ -1028,3 +1265,85 @@ class DAGNN_BN(_DvaeDagnn):
         self.add_edge = nn.Sequential(nn.Linear(hs * 3, hs), nn.ReLU(), nn.Linear(hs, 1))
         self._setup(emb_dim, hidden_dim, out_dim, num_layers, bidirectional, agg, out_wx, out_pool_all, out_pool,
                     dropout, num_nodes)
+
+
+def _gather_rows(d, a, b):
+    """types / preds / nv of the rows (a[i], b[i]) of a DecodedDense, as one int32 matrix [len(a), 2n+1]."""
+    return torch.cat([d.types[a, b], d.preds[a, b], d.nv[a, b].view(-1, 1)], 1)
+
+
+def _last_occurrence(sel, pick, B, A):
+    """Per point: the flat index b' * A + a' of the LAST valid attempt of the whole call whose key equals the picked one
+    (point-major, attempt-minor - the order in which the reference overwrites `str2igraph`)."""
+    W = sel.keys.shape[2]
+    keys = sel.keys.reshape(B * A, W)
+    ok = sel.valid.t().reshape(B * A) != 0
+    idx = torch.arange(B * A, device=keys.device)
+    want = sel.keys[torch.arange(B, device=keys.device), pick]
+    out = []
+    step = max(1, (1 << 24) // (B * A * W))
+    for b0 in range(0, B, step):
+        eq = (keys.unsqueeze(0) == want[b0:b0 + step].unsqueeze(1)).all(2) & ok
+        out.append(torch.where(eq, idx, torch.full_like(idx, -1)).max(1).values)
+    return torch.cat(out).clamp(min=0)
+
+
+def decode_from_latent_space(latent_points, model, decode_attempts=500, n_nodes="variable", return_igraph=False,
+                             data_type="ENAS", select="first", chunk=None, draws=None):
+    """`decode_from_latent_space` of dvae/util.py:408-466 on the HIP decoder: `decode_attempts` stochastic decodes of
+    every latent point, the reference's validity rules, and one string per point - the first valid one in attempt order
+    (what the reference returns), or None when no attempt is valid.  Returns the strings, or (graphs, strings) with
+    return_igraph: per point the graph of the last attempt of the whole call with the same string (the reference's
+    shared `str2igraph` dict), an igraph.Graph or DecodedGraph.  select='most_common' takes the most frequent valid
+    string instead (Counter.most_common(1)).
+
+    All attempts' uniforms are drawn at once, laid out as one `decode_dense(attempts=decode_attempts)` call (so
+    torch.manual_seed reproduces the result), or given as `draws` shaped as `draw_shapes(max_n, B, decode_attempts)`;
+    the decode runs in chunks of `chunk` attempts (default: about SELECT_ROWS rows per call), which does not change the
+    result.  Validity, keys and selection are one HIP call; the result reaches the host with one synchronisation."""
+    kind = _kind(data_type)
+    if n_nodes != "variable" and kind == 0:
+        _n_nodes(n_nodes)
+    _select_mode(select)
+    z = latent_points
+    if not isinstance(z, torch.Tensor) or z.dim() != 2 or z.shape[0] == 0:
+        raise ValueError("decode_from_latent_space(): latent_points must be a [B, nz] tensor with B >= 1")
+    A, B, n = int(decode_attempts), int(z.shape[0]), model.max_n
+    if A < 1:
+        raise ValueError("decode_from_latent_space(): decode_attempts must be >= 1 (got %d)" % A)
+    st, se = draw_shapes(n, B, A)
+    if draws is None:
+        u = torch.rand(int(np.prod(st)) + int(np.prod(se)), device=z.device)
+        u_type, u_edge = u[:int(np.prod(st))].view(st), u[int(np.prod(st)):].view(se)
+    else:
+        u_type, u_edge = draws
+        if tuple(u_type.shape) != st or tuple(u_edge.shape) != se:
+            raise ValueError("decode_from_latent_space(): draws must be shaped %s and %s" % (st, se))
+    step = max(1, SELECT_ROWS // B) if chunk is None else int(chunk)
+    if step < 1:
+        raise ValueError("decode_from_latent_space(): chunk must be >= 1 (got %d)" % step)
+    parts = [model.decode_dense(z, True, min(A, a0 + step) - a0, (u_type[a0:a0 + step], u_edge[a0:a0 + step]))
+             for a0 in range(0, A, step)]
+    d = DecodedDense(*(torch.cat([getattr(p, f) for p in parts]) if len(parts) > 1 else getattr(parts[0], f)
+                       for f in ("types", "preds", "nv")), None)
+    sel = model.select_dense(d, data_type, None if n_nodes == "variable" else n_nodes, select)
+    ar = torch.arange(B, device=d.types.device)
+    pick = sel.pick.long().clamp(min=0)
+    cols = [sel.pick.view(B, 1), _gather_rows(d, pick, ar)]
+    if return_igraph:
+        last = _last_occurrence(sel, pick, B, A)
+        cols.append(_gather_rows(d, last % A, last // A))
+    host = torch.cat(cols, 1).cpu().numpy()   # the one synchronisation
+    form = enas_string if kind == 0 else bn_adj_string
+    w = 2 * n + 1
+    strings = [None if host[b, 0] < 0 else form(host[b, 1:1 + n], host[b, 1 + n:1 + 2 * n], host[b, 2 * n + 1])
+               for b in range(B)]
+    if not return_igraph:
+        return strings
+    rows = host[:, 1 + w:]
+    keep = [b for b in range(B) if host[b, 0] >= 0]
+    built = graphs_from_dense(rows[keep, :n], rows[keep, n:2 * n], rows[keep, 2 * n], model.END_TYPE) if keep else []
+    graphs = [None] * B
+    for b, g in zip(keep, built):
+        graphs[b] = g
+    return graphs, strings

@@ -1768,3 +1768,36 @@ def dvae_sample(h0: torch.Tensor, groups: int, n: int, nvt: int, start_type: int
     a.work, a.work_bytes = work.data_ptr(), nbytes
     check(lib.dagnn_dvae_sample(C.byref(a), _stream(h0)), "dagnn_dvae_sample")
     return types, preds, nv, st
+
+
+def dvae_select(types: torch.Tensor, preds: torch.Tensor, nv: torch.Tensor, nvt: int, start_type: int, end_type: int,
+                kind: int, n_nodes: int = 0, select: int = 0):
+    """One call of `dagnn_dvae_select` on the dense decode of A attempts of B points: types / preds [A,B,n] int32 (preds
+    as bitmasks), nv [A,B] int32.  kind: _lib.DVAE_ENAS / DVAE_BN; n_nodes: 0 or the ENAS vertex count required;
+    select: _lib.DVAE_FIRST_VALID / DVAE_MOST_FREQUENT.  Returns (valid [A,B], pick [B], n_valid [B], n_same [B], all
+    int32, and keys [B,A,W] int64, the canonical keys) on types' device, without synchronising."""
+    types = _dev(types, "types", torch.int32)
+    preds = _dev(preds, "preds", torch.int32)
+    nv = _dev(nv, "nv", torch.int32)
+    if types.dim() != 3 or tuple(preds.shape) != tuple(types.shape) or tuple(nv.shape) != tuple(types.shape[:2]):
+        raise ValueError("dagnn_dvae_select: types / preds [A,B,n] and nv [A,B] (got %s, %s, %s)"
+                         % (tuple(types.shape), tuple(preds.shape), tuple(nv.shape)))
+    A, B, n = types.shape
+    dev = types.device
+    a = _lib.DvaeSelectArgs()
+    a.A, a.B, a.n, a.nvt, a.start_type, a.end_type = A, B, n, int(nvt), int(start_type), int(end_type)
+    a.kind, a.n_nodes, a.select = int(kind), int(n_nodes), int(select)
+    valid = torch.empty(A, B, dtype=torch.int32, device=dev)
+    out = torch.empty(3, B, dtype=torch.int32, device=dev)
+    a.types, a.preds, a.nv, a.valid = types.data_ptr(), preds.data_ptr(), nv.data_ptr(), valid.data_ptr()
+    a.pick, a.n_valid, a.n_same = out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr()
+    lib = _lib.load()
+    nbytes = lib.dagnn_dvae_select_work_bytes(C.byref(a))
+    if nbytes == 0:
+        raise ValueError("dagnn_dvae_select: unsupported arguments (A=%d, B=%d, n=%d, nvt=%d, kind=%d, n_nodes=%d, select=%d)"
+                         % (A, B, n, nvt, kind, n_nodes, select))
+    W = lib.dagnn_dvae_select_key_words(int(kind), n, int(nvt))
+    keys = torch.empty(B, A, W, dtype=torch.int64, device=dev)
+    a.work, a.work_bytes = keys.data_ptr(), nbytes
+    check(lib.dagnn_dvae_select(C.byref(a), _stream(types)), "dagnn_dvae_select")
+    return valid, out[0], out[1], out[2], keys

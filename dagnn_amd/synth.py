@@ -145,3 +145,117 @@ def bn_rows(seed: int, num_graphs: int) -> list:
 def dvae_batch(graphs: Sequence[GraphData]) -> GraphBatch:
     """Collate D-VAE graphs the way `dvae/batch.py:26-146` does (`bi_layer_index` row 1 shifted)."""
     return GraphBatch.from_data_list([g for g in graphs])
+
+
+# --------------------------------------------------------------------------- decoded graphs (decode_from_latent_space)
+def _loose_ends(preds: np.ndarray, k: int) -> int:
+    """END's predecessor mask as the decoder sets it: every vertex 0..k-2 without a successor."""
+    has_succ = 0
+    for v in range(k - 1):
+        has_succ |= int(preds[v])
+    return sum(1 << u for u in range(k - 1) if not has_succ >> u & 1)
+
+
+def _template(rng, kind: str, n: int, nvt: int, start: int, end: int):
+    if kind == "ENAS":
+        k = n if rng.random() < 0.5 else int(rng.integers(3, n + 1))
+        types = [start] + [int(t) for t in rng.integers(2, nvt, size=k - 2)] + [end]
+    else:
+        k = min(nvt, n)
+        mid = [t for t in range(nvt) if t not in (start, end)][:k - 2]
+        types = [start] + [int(t) for t in rng.permutation(mid)] + [end]
+    preds = np.zeros(n, dtype=np.int64)
+    for v in range(1, k - 1):
+        if kind == "ENAS":
+            preds[v] = 1 << (v - 1)
+        for u in range(v):
+            if rng.random() < 0.3:
+                preds[v] |= 1 << u
+        if preds[v] == 0:
+            preds[v] = 1 << int(rng.integers(0, v))
+    preds[k - 1] = _loose_ends(preds, k)
+    return k, types, preds
+
+
+def _reorder(rng, k: int, types, preds):
+    """The same graph in another topological order of its middle vertices: equal BN string, different rows."""
+    succ = {v: [w for w in range(1, k - 1) if preds[w] >> v & 1] for v in range(1, k - 1)}
+    indeg = {v: sum(1 for u in range(1, k - 1) if preds[v] >> u & 1) for v in range(1, k - 1)}
+    ready, order = [v for v in range(1, k - 1) if indeg[v] == 0], []
+    while ready:
+        v = ready.pop(int(rng.integers(0, len(ready))))
+        order.append(v)
+        for w in succ[v]:
+            indeg[w] -= 1
+            if indeg[w] == 0:
+                ready.append(w)
+    pos = {0: 0, k - 1: k - 1}
+    pos.update({v: i + 1 for i, v in enumerate(order)})
+    t2, p2 = list(types), np.zeros_like(preds)
+    for v in range(k):
+        t2[pos[v]] = types[v]
+        for u in range(v):
+            if preds[v] >> u & 1:
+                p2[pos[v]] |= 1 << pos[u]
+    return t2, p2
+
+
+def decoded_rows(seed: int, kind: str, A: int, B: int, n: int, nvt: int, start: int = 0, end: int = 1):
+    """Decoder-shaped dense rows (types [A,B,n] int32, -1 past the end; preds [A,B,n] int32 bitmasks; nv [A,B] int32) for
+    the validity and selection checks of `decode_from_latent_space`.  Each point draws its attempts from three graphs
+    with uneven odds (so the first valid string is often not the most frequent one; for BN each graph also comes in a
+    second vertex order with the same string), and spoils some: a middle vertex of START type, a middle vertex without
+    predecessors, a missing chain edge (END then joins two loose ends), an early END, duplicate BN types.  A few points
+    spoil every attempt, and some rows carry stray bits at or above the vertex and past the end, which the rules ignore."""
+    rng = np.random.default_rng(seed)
+    types = np.full((A, B, n), -1, dtype=np.int32)
+    preds = np.zeros((A, B, n), dtype=np.int64)
+    nv = np.zeros((A, B), dtype=np.int32)
+    for b in range(B):
+        pool = []
+        for _ in range(3):
+            k, t, p = _template(rng, kind, n, nvt, start, end)
+            pool.append([(k, t, p), (k,) + _reorder(rng, k, t, p)] if kind == "BN" else [(k, t, p)])
+        odds = rng.permutation([0.15, 0.5, 0.35])
+        hopeless = rng.random() < 0.1
+        for a in range(A):
+            forms = pool[int(rng.choice(3, p=odds))]
+            k, t, p = forms[int(rng.integers(0, len(forms)))]
+            t, p = list(t), p.copy()
+            if hopeless or rng.random() < 0.4:
+                how = int(rng.integers(0, 5))
+                v = int(rng.integers(1, max(2, k - 1)))
+                if how == 0 and k > 2:
+                    t[v] = start
+                elif how == 1 and k > 2:
+                    p[v] = 0
+                    p[k - 1] = _loose_ends(p, k)
+                elif how == 2 and k > 3 and kind == "ENAS":
+                    v = int(rng.integers(2, k - 1))
+                    p[v] &= ~(1 << (v - 1))
+                    if p[v] == 0:
+                        p[v] = 1
+                    p[k - 1] = _loose_ends(p, k)
+                elif how == 3 and k > 3:
+                    k2 = int(rng.integers(2, k))
+                    t = t[:k2 - 1] + [end]
+                    p = p.copy()
+                    p[k2:] = 0
+                    p[k2 - 1] = _loose_ends(p, k2)
+                    k = k2
+                elif k > 3:
+                    w = int(rng.integers(1, k - 1))
+                    t[v] = t[w] if w != v else t[v % (k - 2) + 1]
+                    if kind == "ENAS":
+                        t[v] = nvt - 1 - (t[v] - 2) % (nvt - 2)
+                if hopeless:
+                    t[1 if k >= 3 else 0] = start if k >= 3 else end
+            types[a, b, :k] = t
+            preds[a, b] = p
+            nv[a, b] = k
+            if rng.random() < 0.1:   # stray bits the rules must ignore
+                for v in range(n):
+                    preds[a, b, v] |= int(rng.integers(0, 1 << 31)) & ~((1 << v) - 1 if v < k else 0)
+                if k < n:
+                    types[a, b, k] = int(rng.integers(0, nvt))
+    return types, (preds & 0xFFFFFFFF).astype(np.uint32).view(np.int32), nv

@@ -994,6 +994,50 @@ size_t dagnn_dvae_sample_work_bytes(const dagnn_dvae_sample_args* args /* host *
 int dagnn_dvae_sample(const dagnn_dvae_sample_args* args /* host */, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Validity and selection of decoded D-VAE graphs: the loop of `decode_from_latent_space` (dvae/util.py:408-466) over
+ * A attempts of B latent points, on the dense output of dagnn_dvae_sample (G = A groups of B rows).
+ *   types [A,B,n] int32 (-1 past the end), preds [A,B,n] uint32 (bit u of preds[a,b,v]: edge u -> v, u < v; other
+ *   bits are ignored), nv [A,B] int32 vertex counts.
+ *   kind = DAGNN_DVAE_ENAS: is_valid_ENAS (util.py:621-631), and with n_nodes > 0 exactly n_nodes vertices; kind =
+ *   DAGNN_DVAE_BN: is_valid_BN (util.py:634-649) with nvt types, n_nodes not read.  A type outside [0, nvt) or a vertex
+ *   count outside [1, n] makes a row invalid.
+ *   Outputs: valid [A,B] int32 (0 / 1); per point b: pick [B] the chosen attempt or -1 when none is valid, n_valid [B],
+ *   n_same [B] the valid attempts whose string equals the picked one.  select = DAGNN_DVAE_FIRST_VALID: the first valid
+ *   attempt (what the reference returns: np.argmax over a dict_values object is always 0); DAGNN_DVAE_MOST_FREQUENT:
+ *   the most frequent string, ties to the earliest first occurrence (Counter.most_common(1)), picked at that occurrence.
+ *   work >= dagnn_dvae_select_work_bytes(args) bytes receives the canonical keys, uint64 [B,A,W] with
+ *   W = dagnn_dvae_select_key_words(kind, n, nvt): the string's content bit-packed (equal keys <=> equal strings; zero
+ *   for invalid rows).  No allocation, no synchronisation, integer work only: bitwise repeatable.  The size query
+ *   returns 0 (the key query 0) for arguments the entry point refuses with DAGNN_EINVAL.
+ * ---------------------------------------------------------------------------------------- */
+#define DAGNN_DVAE_ENAS 0
+#define DAGNN_DVAE_BN 1
+#define DAGNN_DVAE_FIRST_VALID 0
+#define DAGNN_DVAE_MOST_FREQUENT 1
+typedef struct dagnn_dvae_select_args {
+    int64_t A;               /* attempts */
+    int64_t B;               /* latent points; A * B <= 2^30 */
+    int n;                   /* max_n, 2..DAGNN_DVAE_MAX_N */
+    int nvt;                 /* vertex types, 1..DAGNN_DVAE_MAX_TYPES */
+    int start_type, end_type;
+    int kind;                /* DAGNN_DVAE_ENAS or DAGNN_DVAE_BN */
+    int n_nodes;             /* ENAS: 0 any vertex count, else exactly this many (0..DAGNN_DVAE_MAX_N) */
+    int select;              /* DAGNN_DVAE_FIRST_VALID or DAGNN_DVAE_MOST_FREQUENT */
+    const int32_t* types;
+    const uint32_t* preds;
+    const int32_t* nv;
+    int32_t* valid;
+    int32_t* pick;
+    int32_t* n_valid;
+    int32_t* n_same;
+    void* work;
+    size_t work_bytes;
+} dagnn_dvae_select_args;
+int dagnn_dvae_select_key_words(int kind, int n, int nvt);
+size_t dagnn_dvae_select_work_bytes(const dagnn_dvae_select_args* args /* host */);
+int dagnn_dvae_select(const dagnn_dvae_select_args* args /* host */, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Topological layering on the device: replaces `top_sort` / `add_order_info_01` (src/utils_dag.py:8-52) for a
  * whole collated batch.  layer_fwd[v] = longest-path distance of v from any source, layer_bwd[v] = the same on
  * the flipped edges; both int64 [N], i.e. `_bi_layer_idx0/1` (`_bi_layer_index0/1` is arange(N)).  `batch`
