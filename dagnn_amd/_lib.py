@@ -250,6 +250,28 @@ class DvaeSelectArgs(C.Structure):
                 ("work_bytes", C.c_size_t)]
 
 
+DVAE_SET_GRAPHS, DVAE_SET_KEYS = 0, 1             # DAGNN_DVAE_SET_GRAPHS / DAGNN_DVAE_SET_KEYS
+DVAE_SET_MAX_ROWS = 1 << 20                      # DAGNN_DVAE_SET_MAX_ROWS
+DVAE_SET_HEADER_WORDS, DVAE_SET_COUNT, DVAE_SET_ERR = 16, 4, 5   # header words of a set's storage
+DVAE_SET_ERR_FULL, DVAE_SET_ERR_HEADER = 1, 2
+
+
+class DvaeSameDagArgs(C.Structure):
+    _fields_ = [("A", C.c_int64), ("B", C.c_int64), ("n", C.c_int), ("types", C.c_void_p), ("preds", C.c_void_p),
+                ("nv", C.c_void_p), ("types_true", C.c_void_p), ("preds_true", C.c_void_p), ("nv_true", C.c_void_p),
+                ("same", C.c_void_p), ("per_graph", C.c_void_p), ("total", C.c_void_p)]
+
+
+class DvaeSet(C.Structure):
+    _fields_ = [("form", C.c_int), ("width", C.c_int), ("max_rows", C.c_int64), ("data", C.c_void_p), ("bytes", C.c_size_t)]
+
+
+class DvaeSetRowsArgs(C.Structure):
+    _fields_ = [("set", DvaeSet), ("base", C.c_int64), ("A", C.c_int64), ("B", C.c_int64), ("types", C.c_void_p),
+                ("preds", C.c_void_p), ("nv", C.c_void_p), ("keys", C.c_void_p), ("mask", C.c_void_p),
+                ("member", C.c_void_p), ("count", C.c_void_p)]
+
+
 class VariantBwdCell(C.Structure):
     _fields_ = [("mode", C.c_int32), ("lands", C.c_int32), ("in_dim", C.c_int32), ("proj_dim", C.c_int32),
                 ("recurrent", C.c_int32), ("reserved", C.c_int32)] + \
@@ -365,6 +387,11 @@ SYMBOLS = {
     "dagnn_dvae_select_key_words": (C.c_int, [C.c_int, C.c_int, C.c_int]),
     "dagnn_dvae_select_work_bytes": (C.c_size_t, [C.POINTER(DvaeSelectArgs)]),
     "dagnn_dvae_select": (C.c_int, [C.POINTER(DvaeSelectArgs), C.c_void_p]),
+    "dagnn_dvae_same_dag": (C.c_int, [C.POINTER(DvaeSameDagArgs), C.c_void_p]),
+    "dagnn_dvae_set_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int64]),
+    "dagnn_dvae_set_init": (C.c_int, [C.POINTER(DvaeSet), C.c_void_p]),
+    "dagnn_dvae_set_add": (C.c_int, [C.POINTER(DvaeSetRowsArgs), C.c_void_p]),
+    "dagnn_dvae_set_query": (C.c_int, [C.POINTER(DvaeSetRowsArgs), C.c_void_p]),
     "dagnn_debug_occupy": (C.c_int, [C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p]),
     "dagnn_tn_product": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                    C.c_void_p]),

@@ -23,6 +23,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from . import _lib
 from . import constants as K
 from . import engine
 from .core import HipModule, default_schedule, derive_cell, pack_lockstep, run_stack
@@ -1347,3 +1348,341 @@ def decode_from_latent_space(latent_points, model, decode_attempts=500, n_nodes=
     for b, g in zip(keep, built):
         graphs[b] = g
     return graphs, strings
+
+
+# ------------------------------------------------------------------ evaluation metrics (dvae/train.py:276-311, prior_validity)
+SameDag = namedtuple("SameDag", ["same", "per_graph", "total"])
+PriorValidity = namedtuple("PriorValidity", ["r_valid", "r_unique", "r_novel", "n_valid", "n_total", "n_unique", "n_in_train"])
+
+
+def dense_rows(G, max_n: int, nvt: int):
+    """Graphs as dense rows (types [N, max_n] int32, -1 past the end; preds [N, max_n] int32 predecessor bitmasks; nv [N]
+    int32 vertex counts): what `decode_schedule` reads of a graph, for graphs of up to max_n vertices - `is_same_DAG`
+    compares graphs of any size."""
+    if max_n > 32:
+        raise ValueError("dense_rows(): at most 32 vertices per graph (got max_n=%d)" % max_n)
+    N = len(G)
+    types = np.full((N, max_n), -1, dtype=np.int32)
+    preds = np.zeros((N, max_n), dtype=np.uint32)
+    nv = np.zeros(N, dtype=np.int32)
+    for b, g in enumerate(G):
+        k = int(g.x.shape[0])
+        if not 1 <= k <= max_n:
+            raise ValueError("dense_rows(): graph %d has %d vertices, 1..max_n=%d are possible" % (b, k, max_n))
+        nv[b] = k
+        types[b, :k] = [int(g.vs[v]["type"]) for v in range(k)]
+        ei = g.edge_index
+        ei = ei.cpu().numpy() if isinstance(ei, torch.Tensor) else np.asarray(ei)
+        src, dst = ei[0].astype(np.int64), ei[1].astype(np.int64)
+        keep = (src < dst) & (dst < k) & (src >= 0)
+        np.bitwise_or.at(preds[b], dst[keep], (np.uint32(1) << src[keep].astype(np.uint32)))
+        if types[b, :k].min() < 0 or types[b, :k].max() >= nvt:
+            raise ValueError("dense_rows(): vertex types must lie in [0, nvt=%d) (graph %d)" % (nvt, b))
+    return types, preds.view(np.int32), nv
+
+
+def _record(types, preds, nv):
+    """What identifies a dense row under `is_same_DAG`: the vertex count, then type and predecessors below v of every
+    vertex v < nv (the record csrc/dvae_match.hip compares)."""
+    k = max(int(nv), 0)
+    return (int(nv),) + tuple(int(t) for t in types[:k]) + tuple(int(p) & ((1 << v) - 1) for v, p in enumerate(preds[:k]))
+
+
+def is_same_dag_rows(t0, p0, k0, t1, p1, k1):
+    """`is_same_DAG` (dvae/util.py:576-585) of two dense rows: it does not check isomorphism."""
+    if int(k0) != int(k1):
+        return False
+    for vi in range(int(k0)):
+        if int(t0[vi]) != int(t1[vi]):
+            return False
+        if int(p0[vi]) & ((1 << vi) - 1) != int(p1[vi]) & ((1 << vi) - 1):
+            return False
+    return True
+
+
+def same_dag_host(types, preds, nv, types_true, preds_true, nv_true=None):
+    """Host mirror of dagnn_dvae_same_dag on numpy rows, written as the reference's loop: (same [A,B] bool, per_graph
+    [B] int32, total)."""
+    types, preds, nv = np.asarray(types), np.asarray(preds), np.asarray(nv)
+    A, B = nv.shape
+    n = types.shape[-1]
+    same = np.zeros((A, B), dtype=bool)
+    for b in range(B):
+        kt = n if nv_true is None else nv_true[b]
+        for a in range(A):
+            same[a, b] = is_same_dag_rows(types[a, b], preds[a, b], nv[a, b], types_true[b], preds_true[b], kt)
+    return same, same.sum(0).astype(np.int32), int(same.sum())
+
+
+def same_dag_dense(decoded, types_true, preds_true, nv_true=None):
+    """`is_same_DAG` of every attempt of a DecodedDense [A,B,...] against true graph b (types_true / preds_true [B,n],
+    nv_true [B] or None: max_n vertices each): SameDag(same [A,B], per_graph [B], total [1]), int32.  On the GPU one call
+    of dagnn_dvae_same_dag, without synchronising; rows on the host go through the host mirror."""
+    if decoded.types.is_cuda:
+        return SameDag(*engine.dvae_same_dag(decoded.types, decoded.preds, decoded.nv, types_true, preds_true, nv_true))
+    h = lambda x: None if x is None else (x.cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x))  # noqa: E731
+    same, per, total = same_dag_host(h(decoded.types), h(decoded.preds), h(decoded.nv), h(types_true), h(preds_true), h(nv_true))
+    return SameDag(torch.from_numpy(same.astype(np.int32)), torch.from_numpy(per), torch.tensor([total], dtype=torch.int32))
+
+
+def _raise_set_error(err: int, what: str):
+    if err & _lib.DVAE_SET_ERR_HEADER:
+        raise engine.DagnnHipError("%s: the set's storage does not hold the set it was queried as (results are invalid)" % what)
+    if err:
+        raise engine.DagnnHipError("%s: a bounded probe of the set ran out - the table is full or damaged (results are "
+                                   "invalid, device-side error word %d)" % (what, err))
+
+
+class _DeviceSet(object):
+    """Storage and bookkeeping of one set of csrc/dvae_match.hip: the caller-owned buffer, the rows added so far (known
+    on the host, so adding needs no read-back) and the device words {distinct count, error}."""
+
+    def __init__(self, form, width, max_rows, device):
+        self.form, self.width, self.max_rows, self.rows = form, int(width), int(max_rows), 0
+        self.storage = torch.empty(engine.dvae_set_words(form, width, max_rows), dtype=torch.int32, device=device)
+        engine.dvae_set_init(self.storage, form, width, max_rows)
+
+    def add(self, rows, mask, count):
+        engine.dvae_set_add(self.storage, self.form, self.width, self.max_rows, self.rows, rows, mask)
+        self.rows += count
+
+    def status(self):
+        """Device view [2] int32: the distinct rows added so far and the error word (no synchronisation)."""
+        return self.storage[_lib.DVAE_SET_COUNT:_lib.DVAE_SET_ERR + 1]
+
+
+def _rows_of(decoded):
+    return (decoded.types, decoded.preds, decoded.nv) if hasattr(decoded, "types") else tuple(decoded)
+
+
+class GraphSet(object):
+    """A set of graphs for `ratio_same_DAG(G_train, .)` (dvae/util.py:588-596): built once from the training set,
+    queried with decoded rows.  Membership is `is_same_DAG` against any stored graph, exactly (csrc/dvae_match.hip: the
+    hash only picks the bucket).  Rows on a GPU make a device set; rows on the host a Python set of the same records,
+    the host mirror.  len() is the number of graphs given, duplicates included, as len(G_train)."""
+
+    def __init__(self, n, rows, device_set=None, records=None):
+        self.n, self.rows, self._dev, self._records = int(n), int(rows), device_set, records
+
+    @classmethod
+    def from_dense(cls, types, preds, nv=None):
+        """types / preds [N, n] int32 and nv [N] (None: n vertices each), torch tensors on the GPU (device set) or on
+        the host / numpy arrays (host mirror)."""
+        if isinstance(types, torch.Tensor) and types.is_cuda:
+            N, n = types.shape
+            ds = _DeviceSet(_lib.DVAE_SET_GRAPHS, n, N, types.device)
+            ds.add((types, preds, nv), None, N)
+            return cls(n, N, device_set=ds)
+        h = lambda x: None if x is None else (x.numpy() if isinstance(x, torch.Tensor) else np.asarray(x))  # noqa: E731
+        types, preds, nv = h(types), h(preds), h(nv)
+        N, n = types.shape
+        return cls(n, N, records={_record(types[i], preds[i], n if nv is None else nv[i]) for i in range(N)})
+
+    @classmethod
+    def from_graphs(cls, G, max_n, nvt, device=None):
+        """From graph objects (what `encode` / `loss` take), of up to max_n vertices each; device None: the host mirror."""
+        rows = tuple(torch.from_numpy(x) for x in dense_rows(G, max_n, nvt))
+        return cls.from_dense(*(rows if device is None else (t.to(device) for t in rows)))
+
+    def __len__(self):
+        return self.rows
+
+    def contains(self, decoded, mask=None):
+        """(member, count [1]) int32 for a DecodedDense [A,B,...] or a (types, preds, nv) triple: member = 1 where the
+        row is in the set and mask (int32, None: all rows) is not 0; count = the number of such rows.  A device set does
+        not synchronise."""
+        types, preds, nv = _rows_of(decoded)
+        if self._dev is not None:
+            return engine.dvae_set_query(self._dev.storage, self.n, self._dev.max_rows, types, preds, nv, mask)
+        t, p, k = (x.cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x) for x in (types, preds, nv))
+        if t.shape[-1] != self.n:
+            raise ValueError("GraphSet.contains(): rows of %d vertices needed (got %s)" % (self.n, t.shape))
+        m = np.ones(k.shape, dtype=bool) if mask is None else \
+            (mask.cpu().numpy() if isinstance(mask, torch.Tensor) else np.asarray(mask)).reshape(k.shape) != 0
+        member = np.zeros(k.shape, dtype=np.int32)
+        for i in zip(*np.nonzero(m)):
+            member[i] = _record(t[i], p[i], k[i]) in self._records
+        return torch.from_numpy(member), torch.tensor([int(member.sum())], dtype=torch.int32)
+
+    def status(self):
+        """Device set: the device words [distinct graphs, error word] (no synchronisation); host mirror: the same on the host."""
+        if self._dev is not None:
+            return self._dev.status()
+        return torch.tensor([len(self._records), 0], dtype=torch.int32)
+
+    def distinct(self):
+        """The number of different graphs in the set (one synchronisation on a device set; raises DagnnHipError if the
+        build reported a device-side error)."""
+        count, err = self.status().tolist()
+        _raise_set_error(err, "GraphSet")
+        return count
+
+
+class DistinctKeys(object):
+    """`len(set(G_valid_str))` over several `select_dense` results: the distinct canonical keys among the valid rows of
+    every call added (equal keys <=> equal strings).  A device set of csrc/dvae_match.hip sized for max_rows rows in all,
+    or, with device None or a CPU device, a Python set (the host mirror)."""
+
+    def __init__(self, W, max_rows, device=None):
+        self.W = int(W)
+        host = device is None or torch.device(device).type == "cpu"
+        self._dev = None if host else _DeviceSet(_lib.DVAE_SET_KEYS, W, max_rows, device)
+        self._keys = set() if host else None
+
+    def add(self, keys, valid):
+        """keys [B,A,W] int64 and valid [A,B] of one SelectedDense."""
+        if self._dev is not None:
+            self._dev.add(keys, valid, valid.numel())
+            return
+        k, v = keys.cpu().numpy(), valid.cpu().numpy() != 0
+        for a, b in zip(*np.nonzero(v)):
+            self._keys.add(tuple(int(x) for x in k[b, a]))
+
+    def status(self):
+        """[distinct keys, error word] int32, on the device for a device set (no synchronisation)."""
+        if self._dev is not None:
+            return self._dev.status()
+        return torch.tensor([len(self._keys), 0], dtype=torch.int32)
+
+    def count(self):
+        """The distinct count (one synchronisation on a device set)."""
+        count, err = self.status().tolist()
+        _raise_set_error(err, "DistinctKeys")
+        return count
+
+
+def _take_draws(draws, n, B, attempts, device, what):
+    st, se = draw_shapes(n, B, attempts)
+    if draws is None:
+        u = torch.rand(int(np.prod(st)) + int(np.prod(se)), device=device)
+        return u[:int(np.prod(st))].view(st), u[int(np.prod(st)):].view(se)
+    if tuple(draws[0].shape) != st or tuple(draws[1].shape) != se:
+        raise ValueError("%s: draws must be shaped %s and %s" % (what, st, se))
+    return draws
+
+
+def extract_latent(model, graphs, batch_size=64):
+    """`extract_latent` of dvae/train.py:314-335 without the host round trip: mu [len(graphs), nz] of a data set,
+    encoded in batches of batch_size in evaluation mode, on the model's device.  The reference leaves the model in
+    evaluation mode; here the mode the model came in is restored, so a later `reparameterize` is not changed by the call."""
+    if int(batch_size) < 1:
+        raise ValueError("extract_latent(): batch_size must be >= 1 (got %d)" % batch_size)
+    was_training = model.training
+    model.eval()
+    try:
+        with torch.no_grad():
+            return torch.cat([model.encode(list(graphs[i:i + batch_size]))[0] for i in range(0, len(graphs), int(batch_size))])
+    finally:
+        model.train(was_training)
+
+
+def recon_accuracy(model, G, encode_times=10, decode_times=10, stochastic=True, draws=None, batch_size=None):
+    """The reconstruction accuracy `test()` of dvae/train.py:276-311 reports (its counting loop is gone there): per batch
+    of graphs `mu, logvar = model.encode(batch)`, encode_times times `z = model.reparameterize(mu, logvar)` (mu in
+    evaluation mode, a fresh sample in training mode, as the reference's), per z decode_times decodes - one
+    `decode_dense(attempts=decode_times)` call - and the count of decodes that are `is_same_DAG` to their input.
+    Returns (n_perfect, n_total, per_graph): per_graph [len(G)] int32 on the host, the perfect decodes of each graph out
+    of encode_times * decode_times; accuracy = n_perfect / n_total.
+
+    The uniforms of all decodes are drawn at once as `draw_shapes(max_n, len(G), encode_times * decode_times)` (attempt
+    e * decode_times + d is decode d of encode e), or given as `draws` in that shape; batches take their columns, so
+    batch_size (None: one batch) does not change the draws a graph gets, and torch.manual_seed reproduces a run.  With
+    agg='gated_sum' the result does not depend on batch_size at all.  With 'attn_h' it can, as it does on the reference's
+    infer_batch_size: that decoder's padded soft-max couples the rows of one decode call (the padding takes weight, and its
+    width is the call's largest predecessor count), so a graph's decode depends on the batch it is decoded in.
+    Comparing and counting run in HIP (dagnn_dvae_same_dag); the counts reach the host with one synchronisation."""
+    E, D, N, n = int(encode_times), int(decode_times), len(G), model.max_n
+    if E < 1 or D < 1 or N < 1:
+        raise ValueError("recon_accuracy(): encode_times, decode_times and len(G) must be >= 1 (got %d, %d, %d)" % (E, D, N))
+    step = N if batch_size is None else int(batch_size)
+    if step < 1:
+        raise ValueError("recon_accuracy(): batch_size must be >= 1 (got %d)" % step)
+    rows = dense_rows(G, n, model.nvt)
+    dev = model.get_device()
+    if dev.type != "cuda":
+        raise engine.DagnnHipError("recon_accuracy(): the model must live on a ROCm GPU - the decoder is HIP and has no CPU path")
+    true = [torch.from_numpy(x).pin_memory().to(dev, non_blocking=True) for x in rows]
+    u_type = u_edge = None
+    if stochastic:
+        u_type, u_edge = _take_draws(draws, n, N, E * D, dev, "recon_accuracy()")
+    per = []
+    with torch.no_grad():
+        for g0 in range(0, N, step):
+            g1 = min(N, g0 + step)
+            mu, logvar = model.encode(list(G[g0:g1]))
+            tt, pt, nt = (t[g0:g1] for t in true)
+            count = None
+            for e in range(E):
+                z = model.reparameterize(mu, logvar)
+                dr = (u_type[e * D:(e + 1) * D, :, g0:g1], u_edge[e * D:(e + 1) * D, :, g0:g1]) if stochastic else None
+                res = same_dag_dense(model.decode_dense(z, stochastic, D, dr), tt, pt, nt)
+                count = res.per_graph if count is None else count + res.per_graph
+            per.append(count)
+    per_graph = torch.cat(per).cpu()   # the one synchronisation
+    return int(per_graph.sum()), N * E * D, per_graph
+
+
+def prior_validity(model, train_set, n_latent_points=1000, decode_times=10, data_type="ENAS", z_mean=None, z_std=None,
+                   batch_size=None, z=None, draws=None):
+    """`prior_validity` of the D-VAE training script (the call dvae/train.py:411 comments out): decode_times decodes of
+    n_latent_points points z ~ N(0, I) - times z_std plus z_mean when given (`scale_to_train_range`: mean and std of
+    `extract_latent(model, train_graphs)`), or the rows of `z` - and from all of them
+        r_valid  = valid decodes (is_valid_ENAS / is_valid_BN) / all decodes,
+        r_unique = distinct strings (decode_igraph_to_ENAS / _BN_adj) among the valid decodes / valid decodes,
+        r_novel  = 1 - valid decodes that are `is_same_DAG` to a graph of `train_set` / valid decodes; `train_set` is a
+               GraphSet on the device the decodes live on (a host mirror with a GPU model is a ValueError).
+    Without a valid decode r_unique is 0.0 (the script's rule) and so is r_novel, where the script would divide by zero.
+    Returns PriorValidity(r_valid, r_unique, r_novel, n_valid, n_total, n_unique, n_in_train).
+
+    Points are decoded batch_size at a time (None: about SELECT_ROWS rows per call), each batch one
+    `decode_dense(attempts=decode_times)`; uniforms are drawn once as `draw_shapes(max_n, points, decode_times)`, or given
+    as `draws`, and batches take their columns, so batch_size does not change the draws a point gets; the decodes
+    themselves depend on it the way `recon_accuracy` describes (not for gated_sum; for attn_h through the batch's padding
+    width, as with the reference's infer_batch_size).  Validity and keys
+    (dagnn_dvae_select), the distinct count and the training-set lookup (csrc/dvae_match.hip) stay on the device; the four
+    counts reach the host with one synchronisation per call."""
+    kind, D = _kind(data_type), int(decode_times)
+    dev = model.get_device()
+    if z is None:
+        P = int(n_latent_points)
+        if P < 1:
+            raise ValueError("prior_validity(): n_latent_points must be >= 1 (got %d)" % P)
+        z = torch.randn(P, model.nz, device=dev)
+        if z_std is not None:
+            z = z * z_std
+        if z_mean is not None:
+            z = z + z_mean
+    elif not isinstance(z, torch.Tensor) or z.dim() != 2 or z.shape[0] == 0:
+        raise ValueError("prior_validity(): z must be a [points, nz] tensor with at least one row")
+    P, n = int(z.shape[0]), model.max_n
+    if D < 1:
+        raise ValueError("prior_validity(): decode_times must be >= 1 (got %d)" % D)
+    if P * D > _lib.DVAE_SET_MAX_ROWS:
+        raise ValueError("prior_validity(): at most %d decodes per call (got %d x %d)" % (_lib.DVAE_SET_MAX_ROWS, P, D))
+    if not isinstance(train_set, GraphSet) or train_set.n != n:
+        raise ValueError("prior_validity(): train_set must be a GraphSet of max_n=%d-vertex rows" % n)
+    if train_set.status().device != z.device:
+        raise ValueError("prior_validity(): train_set lives on %s, the decodes on %s - build it with "
+                         "GraphSet.from_graphs(..., device) / from_dense on the model's device"
+                         % (train_set.status().device, z.device))
+    step = max(1, SELECT_ROWS // D) if batch_size is None else int(batch_size)
+    if step < 1:
+        raise ValueError("prior_validity(): batch_size must be >= 1 (got %d)" % step)
+    u_type, u_edge = _take_draws(draws, n, P, D, z.device, "prior_validity()")
+    distinct = DistinctKeys(select_key_words(data_type, n, model.nvt), P * D, z.device)
+    n_valid = n_in = None
+    for p0 in range(0, P, step):
+        p1 = min(P, p0 + step)
+        d = model.decode_dense(z[p0:p1], True, D, (u_type[:, :, p0:p1], u_edge[:, :, p0:p1]))
+        sel = model.select_dense(d, data_type)
+        distinct.add(sel.keys, sel.valid)
+        _, hit = train_set.contains(d, sel.valid)
+        nv_, ni_ = sel.valid.sum().view(1).to(torch.int32), hit.view(1)
+        n_valid, n_in = (nv_, ni_) if n_valid is None else (n_valid + nv_, n_in + ni_)
+    host = torch.cat([n_valid, n_in, distinct.status(), train_set.status()[1:]]).cpu()   # the one synchronisation
+    n_valid, n_in, n_unique, err_keys, err_train = (int(x) for x in host)
+    _raise_set_error(err_keys, "prior_validity(): distinct keys")
+    _raise_set_error(err_train, "prior_validity(): training set")
+    total = P * D
+    return PriorValidity(n_valid / total, n_unique / n_valid if n_valid else 0.0, 1.0 - n_in / n_valid if n_valid else 0.0,
+                         n_valid, total, n_unique, n_in)

@@ -1801,3 +1801,112 @@ def dvae_select(types: torch.Tensor, preds: torch.Tensor, nv: torch.Tensor, nvt:
     a.work, a.work_bytes = keys.data_ptr(), nbytes
     check(lib.dagnn_dvae_select(C.byref(a), _stream(types)), "dagnn_dvae_select")
     return valid, out[0], out[1], out[2], keys
+
+
+def _dense_rows(types, preds, nv, what):
+    """types / preds [..., n] int32 and nv [...] int32 (or None) on one GPU, with equal leading shapes of 1 or 2 dims."""
+    types = _dev(types, "types", torch.int32)
+    preds = _dev(preds, "preds", torch.int32)
+    nv = None if nv is None else _dev(nv, "nv", torch.int32)
+    if types.dim() not in (2, 3) or tuple(preds.shape) != tuple(types.shape) or \
+            (nv is not None and tuple(nv.shape) != tuple(types.shape[:-1])):
+        raise ValueError("%s: types / preds [A,B,n] or [R,n] and nv [A,B] or [R] (got %s, %s, %s)"
+                         % (what, tuple(types.shape), tuple(preds.shape), None if nv is None else tuple(nv.shape)))
+    return types, preds, nv
+
+
+def dvae_same_dag(types: torch.Tensor, preds: torch.Tensor, nv: torch.Tensor, types_true: torch.Tensor,
+                  preds_true: torch.Tensor, nv_true: Optional[torch.Tensor] = None):
+    """One call of `dagnn_dvae_same_dag`: decode rows types / preds [A,B,n], nv [A,B] against true rows types_true /
+    preds_true [B,n], nv_true [B] (None: n vertices each).  Returns (same [A,B], per_graph [B], total [1]), int32 on the
+    rows' device, without synchronising."""
+    types, preds, nv = _dense_rows(types, preds, nv, "dagnn_dvae_same_dag")
+    tt, pt, nt = _dense_rows(types_true, preds_true, nv_true, "dagnn_dvae_same_dag")
+    if types.dim() != 3 or nv is None or tt.dim() != 2 or tuple(tt.shape) != tuple(types.shape[1:]) or tt.device != types.device:
+        raise ValueError("dagnn_dvae_same_dag: decode rows [A,B,n] with nv [A,B] against true rows [B,n] on one device "
+                         "(got %s and %s)" % (tuple(types.shape), tuple(tt.shape)))
+    A, B, n = types.shape
+    a = _lib.DvaeSameDagArgs()
+    a.A, a.B, a.n = A, B, n
+    same = torch.empty(A, B, dtype=torch.int32, device=types.device)
+    out = torch.empty(B + 1, dtype=torch.int32, device=types.device)
+    a.types, a.preds, a.nv = types.data_ptr(), preds.data_ptr(), nv.data_ptr()
+    a.types_true, a.preds_true, a.nv_true = tt.data_ptr(), pt.data_ptr(), _ptr(nt)
+    a.same, a.per_graph, a.total = same.data_ptr(), out.data_ptr(), out[B:].data_ptr()
+    check(_lib.load().dagnn_dvae_same_dag(C.byref(a), _stream(types)), "dagnn_dvae_same_dag")
+    return same, out[:B], out[B:]
+
+
+def dvae_set_words(form: int, width: int, max_rows: int) -> int:
+    """int32 words of a set's storage (dagnn_dvae_set_bytes / 4)."""
+    nbytes = _lib.load().dagnn_dvae_set_bytes(int(form), int(width), int(max_rows))
+    if nbytes == 0:
+        raise ValueError("dagnn_dvae_set: unsupported set (form=%d, width=%d, max_rows=%d; at most %d rows)"
+                         % (form, width, max_rows, _lib.DVAE_SET_MAX_ROWS))
+    return nbytes // 4
+
+
+def _set_desc(storage: torch.Tensor, form: int, width: int, max_rows: int) -> _lib.DvaeSet:
+    storage = _dev(storage, "set storage", torch.int32)
+    s = _lib.DvaeSet()
+    s.form, s.width, s.max_rows = int(form), int(width), int(max_rows)
+    s.data, s.bytes = storage.data_ptr(), storage.numel() * 4
+    return s
+
+
+def dvae_set_init(storage: torch.Tensor, form: int, width: int, max_rows: int) -> None:
+    """`dagnn_dvae_set_init` on `storage` (int32, at least dvae_set_words(...) words): an empty set."""
+    check(_lib.load().dagnn_dvae_set_init(C.byref(_set_desc(storage, form, width, max_rows)), _stream(storage)),
+          "dagnn_dvae_set_init")
+
+
+def _set_rows_args(storage, form, width, max_rows, A, B, mask, what):
+    a = _lib.DvaeSetRowsArgs()
+    a.set = _set_desc(storage, form, width, max_rows)
+    a.A, a.B = A, B
+    if mask is not None:
+        mask = _dev(mask, "mask", torch.int32)
+        if mask.numel() != A * B or mask.device != storage.device:
+            raise ValueError("%s: mask must hold one int32 per row (%d) on the set's device" % (what, A * B))
+    a.mask = _ptr(mask)
+    return a, mask
+
+
+def dvae_set_add(storage: torch.Tensor, form: int, width: int, max_rows: int, base: int, rows, mask=None) -> None:
+    """One call of `dagnn_dvae_set_add`.  form DVAE_SET_GRAPHS: rows = (types, preds, nv or None), [A,B,n] or [R,n];
+    DVAE_SET_KEYS: rows = keys [B,A,W] int64 (dagnn_dvae_select's).  mask: int32 per row ([A,B] / [R]) or None.  The rows
+    become records base .. base + A*B - 1; a storage that is too small, or rows beyond max_rows, raise DagnnHipError
+    before anything is launched.  Nothing synchronises."""
+    if form == _lib.DVAE_SET_GRAPHS:
+        types, preds, nv = _dense_rows(*rows, "dagnn_dvae_set_add")
+        if types.shape[-1] != width or types.device != storage.device:
+            raise ValueError("dagnn_dvae_set_add: rows of %d vertices on the set's device needed (got %s)" % (width, tuple(types.shape)))
+        A, B = (1, types.shape[0]) if types.dim() == 2 else tuple(types.shape[:2])
+        a, mask = _set_rows_args(storage, form, width, max_rows, A, B, mask, "dagnn_dvae_set_add")
+        a.types, a.preds, a.nv = types.data_ptr(), preds.data_ptr(), _ptr(nv)
+    else:
+        keys = _dev(rows, "keys", torch.int64)
+        if keys.dim() != 3 or keys.shape[2] != width or keys.device != storage.device:
+            raise ValueError("dagnn_dvae_set_add: keys [B,A,%d] on the set's device needed (got %s)" % (width, tuple(keys.shape)))
+        B, A = keys.shape[:2]
+        a, mask = _set_rows_args(storage, form, width, max_rows, A, B, mask, "dagnn_dvae_set_add")
+        a.keys = keys.data_ptr()
+    a.base = int(base)
+    check(_lib.load().dagnn_dvae_set_add(C.byref(a), _stream(storage)), "dagnn_dvae_set_add")
+
+
+def dvae_set_query(storage: torch.Tensor, width: int, max_rows: int, types: torch.Tensor, preds: torch.Tensor,
+                   nv: Optional[torch.Tensor], mask=None):
+    """One call of `dagnn_dvae_set_query` on a DVAE_SET_GRAPHS set: (member, count [1]) int32, member shaped as the
+    rows' leading dims, 1 where the masked row is_same_DAG-equal to a stored row.  Nothing synchronises."""
+    types, preds, nv = _dense_rows(types, preds, nv, "dagnn_dvae_set_query")
+    if types.shape[-1] != width or types.device != storage.device:
+        raise ValueError("dagnn_dvae_set_query: rows of %d vertices on the set's device needed (got %s)" % (width, tuple(types.shape)))
+    A, B = (1, types.shape[0]) if types.dim() == 2 else tuple(types.shape[:2])
+    a, mask = _set_rows_args(storage, _lib.DVAE_SET_GRAPHS, width, max_rows, A, B, mask, "dagnn_dvae_set_query")
+    a.types, a.preds, a.nv = types.data_ptr(), preds.data_ptr(), _ptr(nv)
+    member = torch.empty(types.shape[:-1], dtype=torch.int32, device=types.device)
+    count = torch.empty(1, dtype=torch.int32, device=types.device)
+    a.member, a.count = member.data_ptr(), count.data_ptr()
+    check(_lib.load().dagnn_dvae_set_query(C.byref(a), _stream(storage)), "dagnn_dvae_set_query")
+    return member, count

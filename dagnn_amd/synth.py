@@ -259,3 +259,92 @@ def decoded_rows(seed: int, kind: str, A: int, B: int, n: int, nvt: int, start: 
                 if k < n:
                     types[a, b, k] = int(rng.integers(0, nvt))
     return types, (preds & 0xFFFFFFFF).astype(np.uint32).view(np.int32), nv
+
+
+# --------------------------------------------------------------------------- decoded graphs against true / training graphs
+def match_rows(seed: int, kind: str, A: int, B: int, n: int, nvt: int, n_train: int = 300, start: int = 0, end: int = 1,
+               all_invalid: bool = False):
+    """Rows for the evaluation metrics (`is_same_DAG`, `ratio_same_DAG`, uniqueness) on top of `decoded_rows`: a dict of
+    decoded rows types / preds [A,B,n], nv [A,B]; true rows types_true / preds_true [B,n], nv_true [B]; training rows
+    types_train / preds_train [n_train,n], nv_train [n_train].  By construction (A >= 5, B >= 2):
+    true row b equals decode (b % A, b); the next four attempts of point b are that row with one middle type changed,
+    with one edge bit flipped, cut to one vertex less (equal in all vertices it keeps), and - when it has room - grown by
+    one vertex (equal in the first nv).  True and training rows carry junk past their end that must not take part.
+    Point 0 has no valid attempt (a second START); with all_invalid every point is spoiled that way (an empty valid
+    set).  The training set holds decoded rows of every kind - valid ones, invalid ones (in the set, but never counted:
+    novelty only looks at valid decodes), each BN graph in at most the vertex order it was drawn in (its other order
+    has the same string and is not the same DAG) - then rows of another seed that match nothing, and its second half
+    repeats rows of the first (duplicates)."""
+    if A < 5 or B < 2:
+        raise ValueError("match_rows: needs A >= 5 and B >= 2")
+    rng = np.random.default_rng(seed + 7919)
+    types, preds, nv = decoded_rows(seed, kind, A, B, n, nvt, start, end)
+    types, preds, nv = types.copy(), preds.view(np.uint32).astype(np.int64), nv.copy()
+    types_true = np.empty((B, n), dtype=np.int32)
+    preds_true = np.zeros((B, n), dtype=np.int64)
+    nv_true = np.empty(B, dtype=np.int32)
+
+    def junk(t, p, k):   # what the rules must ignore: entries past the end, bits at or above the vertex
+        for v in range(n):
+            p[v] |= int(rng.integers(0, 1 << 31)) & ~((1 << v) - 1) & 0xFFFFFFFF
+            if v >= k:
+                t[v] = int(rng.integers(0, nvt))
+                p[v] = int(rng.integers(0, 1 << 31))
+
+    for b in range(B):
+        a0 = b % A
+        k = int(nv[a0, b])
+        types_true[b], preds_true[b], nv_true[b] = types[a0, b], preds[a0, b], k
+        clean_t = types[a0, b].copy()
+        clean_t[k:] = -1
+        clean_p = preds[a0, b] & [((1 << v) - 1) if v < k else 0 for v in range(n)]
+        for j, how in enumerate(("type", "edge", "shorter", "longer")):
+            a = (a0 + 1 + j) % A
+            t, p, kk = clean_t.copy(), clean_p.copy(), k
+            v = int(rng.integers(1, max(2, k - 1))) if k > 2 else 0
+            if how == "type":
+                others = [x for x in range(nvt) if x != t[v]]
+                t[v] = others[int(rng.integers(0, len(others)))]
+            elif how == "edge":
+                v = max(v, 1) if k > 1 else 0
+                if v:
+                    p[v] ^= 1 << int(rng.integers(0, v))
+                else:
+                    t[0] = (t[0] + 1) % nvt
+            elif how == "shorter" and k > 1:
+                kk = k - 1
+                t[kk:], p[kk:] = -1, 0
+            elif how == "longer" and k < n:
+                kk = k + 1
+                t[k], p[k] = end, int(rng.integers(0, 1 << k))
+            else:
+                t[0] = (t[0] + 1) % nvt
+            types[a, b], preds[a, b], nv[a, b] = t, p, kk
+        junk(types_true[b], preds_true[b], k)
+    spoil = range(B) if all_invalid else [0]
+    for b in spoil:
+        for a in range(A):
+            if nv[a, b] >= 2:
+                types[a, b, 1] = start
+            else:
+                types[a, b, 0] = end
+    flat_t, flat_p, flat_k = types.reshape(A * B, n), preds.reshape(A * B, n), nv.reshape(A * B)
+    other = decoded_rows(seed + 100003, kind, 1, max(n_train, 1), n, nvt, start, end)
+    half = (n_train + 1) // 2
+    types_train = np.empty((n_train, n), dtype=np.int32)
+    preds_train = np.zeros((n_train, n), dtype=np.int64)
+    nv_train = np.empty(n_train, dtype=np.int32)
+    for i in range(n_train):
+        if i >= half:
+            src = int(rng.integers(0, half))
+            types_train[i], preds_train[i], nv_train[i] = types_train[src], preds_train[src], nv_train[src]
+        elif i % 3 != 2:
+            r = int(rng.integers(0, A * B))
+            types_train[i], preds_train[i], nv_train[i] = flat_t[r], flat_p[r], flat_k[r]
+        else:
+            types_train[i], preds_train[i], nv_train[i] = other[0][0, i], other[1].view(np.uint32)[0, i], other[2][0, i]
+        if i < half:
+            junk(types_train[i], preds_train[i], int(nv_train[i]))
+    as_i32 = lambda p: (p & 0xFFFFFFFF).astype(np.uint32).view(np.int32)  # noqa: E731
+    return dict(types=types, preds=as_i32(preds), nv=nv, types_true=types_true, preds_true=as_i32(preds_true), nv_true=nv_true,
+                types_train=types_train, preds_train=as_i32(preds_train), nv_train=nv_train)

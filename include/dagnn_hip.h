@@ -1038,6 +1038,89 @@ size_t dagnn_dvae_select_work_bytes(const dagnn_dvae_select_args* args /* host *
 int dagnn_dvae_select(const dagnn_dvae_select_args* args /* host */, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Graph identity of decoded D-VAE graphs (csrc/dvae_match.hip): what the reference's evaluation runs after the decode,
+ * on the dense layout of dagnn_dvae_sample (types / preds [A,B,n], nv [A,B]; bits of preds[.,v] at or above v ignored).
+ *
+ * dagnn_dvae_same_dag: `is_same_DAG` (dvae/util.py:576-585) of decode row (a, b) against true row b (types_true /
+ *   preds_true [B,n], nv_true [B] or NULL: n vertices each): equal vertex count, and for every v < nv equal type and
+ *   equal predecessor mask; entries at v >= nv take no part, no isomorphism.  Outputs, all int32, from one call: same
+ *   [A,B] (0 / 1), per_graph [B] (matching attempts of graph b), total [1].
+ *
+ * A SET of rows: `ratio_same_DAG`'s left-hand side (util.py:588-596; DAGNN_DVAE_SET_GRAPHS, width = n, membership =
+ *   is_same_DAG against any stored row), or the distinct canonical keys of dagnn_dvae_select, `len(set(G_valid_str))`
+ *   (DAGNN_DVAE_SET_KEYS, width = W 64-bit words).  Its storage is ONE caller-owned buffer of
+ *   dagnn_dvae_set_bytes(form, width, max_rows) bytes that outlives the calls: DAGNN_DVAE_SET_HEADER_WORDS int32 header
+ *   words, `cap` int32 slots, max_rows records.  Capacity rule: cap = the power of two >= 2 * max_rows (at least 64),
+ *   so the load factor never exceeds 1/2; the host refuses with DAGNN_ENOSPC, before any launch, a buffer smaller than
+ *   that and an add whose rows base .. base + A*B - 1 do not fit in max_rows.  Every probe loop runs at most cap steps;
+ *   one that runs out (possible only with a damaged header or table) sets DAGNN_DVAE_SET_ERR_FULL in header word
+ *   DAGNN_DVAE_SET_ERR, a header that does not match the descriptor DAGNN_DVAE_SET_ERR_HEADER; the caller reads the word
+ *   with its results.  The set is EXACT: the hash only chooses the first slot, a hit or a duplicate is reported after all
+ *   words of the row compared equal, and rows with equal hashes are all stored.  Header word DAGNN_DVAE_SET_COUNT is
+ *   the number of distinct rows added so far.  Flags and counts are bitwise repeatable (integer atomics on global memory;
+ *   which of several equal rows a slot names may differ, nothing returned shows it).
+ *   dagnn_dvae_set_init: empties the set (once, before the first add).
+ *   dagnn_dvae_set_add: adds the rows r = a * B + b with mask[r] != 0 (mask [A,B] int32 or NULL: all) as records
+ *     base + r; the caller gives every add a `base` behind the rows of the earlier ones.  GRAPHS: types / preds / nv
+ *     (nv NULL: n vertices each); KEYS: keys [B,A,W] as dagnn_dvae_select writes them (mask = its `valid`).
+ *   dagnn_dvae_set_query (GRAPHS): member [A,B] = 1 where mask[r] != 0 and the row is in the set, else 0; count [1] =
+ *     their number.  `base` is not read.
+ * No allocation, no synchronisation.  The size query returns 0 for descriptors the entry points refuse (DAGNN_EINVAL).
+ * ---------------------------------------------------------------------------------------- */
+#define DAGNN_DVAE_SET_GRAPHS 0
+#define DAGNN_DVAE_SET_KEYS 1
+#define DAGNN_DVAE_SET_MAX_ROWS ((int64_t)1 << 20)   /* per set, and per call (A * B) */
+#define DAGNN_DVAE_SET_HEADER_WORDS 16
+#define DAGNN_DVAE_SET_MAGIC 0    /* header words */
+#define DAGNN_DVAE_SET_K 1
+#define DAGNN_DVAE_SET_CAP 2
+#define DAGNN_DVAE_SET_ROWS 3
+#define DAGNN_DVAE_SET_COUNT 4
+#define DAGNN_DVAE_SET_ERR 5
+#define DAGNN_DVAE_SET_ERR_FULL 1
+#define DAGNN_DVAE_SET_ERR_HEADER 2
+typedef struct dagnn_dvae_same_dag_args {
+    int64_t A;               /* attempts */
+    int64_t B;               /* true graphs; A * B <= DAGNN_DVAE_SET_MAX_ROWS */
+    int n;                   /* max_n, 2..DAGNN_DVAE_MAX_N */
+    const int32_t* types;
+    const uint32_t* preds;
+    const int32_t* nv;
+    const int32_t* types_true;
+    const uint32_t* preds_true;
+    const int32_t* nv_true;  /* or NULL */
+    int32_t* same;
+    int32_t* per_graph;
+    int32_t* total;
+} dagnn_dvae_same_dag_args;
+int dagnn_dvae_same_dag(const dagnn_dvae_same_dag_args* args /* host */, void* stream);
+
+typedef struct dagnn_dvae_set {
+    int form;                /* DAGNN_DVAE_SET_GRAPHS or DAGNN_DVAE_SET_KEYS */
+    int width;               /* GRAPHS: n, 2..DAGNN_DVAE_MAX_N; KEYS: W, 1..16 */
+    int64_t max_rows;        /* 1..DAGNN_DVAE_SET_MAX_ROWS */
+    void* data;
+    size_t bytes;
+} dagnn_dvae_set;
+typedef struct dagnn_dvae_set_rows_args {
+    dagnn_dvae_set set;
+    int64_t base;            /* add: index of the call's first record */
+    int64_t A;
+    int64_t B;               /* A * B <= DAGNN_DVAE_SET_MAX_ROWS */
+    const int32_t* types;
+    const uint32_t* preds;
+    const int32_t* nv;       /* or NULL */
+    const uint64_t* keys;
+    const int32_t* mask;     /* or NULL */
+    int32_t* member;         /* query */
+    int32_t* count;          /* query */
+} dagnn_dvae_set_rows_args;
+size_t dagnn_dvae_set_bytes(int form, int width, int64_t max_rows);
+int dagnn_dvae_set_init(const dagnn_dvae_set* set /* host */, void* stream);
+int dagnn_dvae_set_add(const dagnn_dvae_set_rows_args* args /* host */, void* stream);
+int dagnn_dvae_set_query(const dagnn_dvae_set_rows_args* args /* host */, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Topological layering on the device: replaces `top_sort` / `add_order_info_01` (src/utils_dag.py:8-52) for a
  * whole collated batch.  layer_fwd[v] = longest-path distance of v from any source, layer_bwd[v] = the same on
  * the flipped edges; both int64 [N], i.e. `_bi_layer_idx0/1` (`_bi_layer_index0/1` is arange(N)).  `batch`
