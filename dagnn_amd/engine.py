@@ -879,6 +879,16 @@ class GranuleArena(object):
             self.err = torch.zeros(1, dtype=torch.int32, device=device)
         return self.err
 
+    def scratch(self, nbytes: int, device) -> torch.Tensor:
+        """At least `nbytes` of untyped device scratch (int64 words, 16-byte aligned by the allocator) that kernels of this
+        arena's stream fill and consume within one call: grown geometrically, never shrunk, contents undefined."""
+        t = getattr(self, "_scratch", None)
+        words = (int(nbytes) + 7) // 8
+        if t is None or t.device != device or t.numel() < words:
+            t = self._scratch = torch.empty(max(words, 0 if t is None or t.device != device else int(t.numel() * 1.5), 1),
+                                            dtype=torch.int64, device=device)
+        return t
+
     def xcc_table(self, device):
         """Tagged table the workgroups of a dataflow launch publish their XCD in (zero-initialised once, tagged with the
         arena's epochs like the granule buffers; re-created with them)."""
@@ -1910,3 +1920,64 @@ def dvae_set_query(storage: torch.Tensor, width: int, max_rows: int, types: torc
     a.member, a.count = member.data_ptr(), count.data_ptr()
     check(_lib.load().dagnn_dvae_set_query(C.byref(a), _stream(storage)), "dagnn_dvae_set_query")
     return member, count
+
+
+# ----------------------------------------------------------------------------- the TOK task's evaluation path (csrc/predict.hip)
+def heads_argmax(out: torch.Tensor, wcat: torch.Tensor, bcat: torch.Tensor, S: int, V: int,
+                 arena: Optional[GranuleArena] = None):
+    """`dagnn_heads_argmax`: (tok [B, S] int64, top [B, S, 2] float32 = winning logit and runner-up) of the S heads kept as one
+    matrix `wcat` [S V, D] / `bcat` [S V] on the pooled vectors `out` [B, D], without the logits.  The per-tile partials live
+    in `arena`'s scratch (a fresh tensor without one).  Nothing synchronises."""
+    out = _rows(out, "pooled graph vectors")
+    wcat, bcat = _rows(wcat, "head weights"), _dev(bcat, "head biases", torch.float32)
+    B, D = out.shape
+    if tuple(wcat.shape) != (S * V, D) or bcat.numel() != S * V or wcat.device != out.device or bcat.device != out.device:
+        raise DagnnHipError("heads_argmax: heads of shape [%d, %d] / [%d] on the device of `out` needed (got %s / %s)"
+                            % (S * V, D, S * V, tuple(wcat.shape), tuple(bcat.shape)))
+    lib = _lib.load()
+    tok = torch.empty(B, S, dtype=torch.int64, device=out.device)
+    top = torch.empty(B, S, 2, dtype=torch.float32, device=out.device)
+    nbytes = lib.dagnn_heads_argmax_bytes(B, S, V)
+    if nbytes == 0:
+        raise DagnnHipError("heads_argmax: unsupported shape (B=%d, S=%d, V=%d)" % (B, S, V))
+    work = arena.scratch(nbytes, out.device) if arena is not None else torch.empty(nbytes // 8, dtype=torch.int64, device=out.device)
+    with _span("heads_argmax", out):
+        check(lib.dagnn_heads_argmax(out.data_ptr(), out.stride(0), wcat.data_ptr(), wcat.stride(0), bcat.data_ptr(), B, D, S, V,
+                                     tok.data_ptr(), top.data_ptr(), work.data_ptr(), work.numel() * 8, _stream(out)),
+              "dagnn_heads_argmax")
+    return tok, top
+
+
+def rows_argmax(logits: torch.Tensor, S: int, V: int) -> torch.Tensor:
+    """`dagnn_rows_argmax`: tok [B, S] int64 of `logits` [B, S V] (fp32, unit column stride, any row pitch), one launch."""
+    if not isinstance(logits, torch.Tensor) or not logits.is_cuda:
+        _dev(logits, "logits")   # (raises: no CPU path)
+    if logits.dim() != 2 or logits.dtype != torch.float32 or logits.shape[1] != S * V:
+        raise DagnnHipError("rows_argmax: fp32 logits [B, %d] needed (got %s %s)" % (S * V, logits.dtype, tuple(logits.shape)))
+    if logits.stride(1) != 1 or (logits.shape[0] > 1 and logits.stride(0) < S * V):
+        logits = logits.contiguous()
+    B = logits.shape[0]
+    tok = torch.empty(B, S, dtype=torch.int64, device=logits.device)
+    check(_lib.load().dagnn_rows_argmax(logits.data_ptr(), logits.stride(0) if B > 1 else S * V, B, S, V, tok.data_ptr(),
+                                        _stream(logits)), "dagnn_rows_argmax")
+    return tok
+
+
+def seq_f1_counts(tok: torch.Tensor, eos_id: int, ref_ids: torch.Tensor, ref_extra: torch.Tensor,
+                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`dagnn_seq_f1_counts`: counts [B, 4] int32 = (true_positive, n_pred, n_ref, len) per graph (into `out` when given: a
+    contiguous int32 [B, 4] view whose start is 16-byte aligned).  Nothing synchronises."""
+    tok = _dev(tok, "tok", torch.int64)
+    ref_ids, ref_extra = _dev(ref_ids, "ref_ids", torch.int32), _dev(ref_extra, "ref_extra", torch.int32)
+    if tok.dim() != 2 or ref_ids.dim() != 2 or ref_ids.shape[0] != tok.shape[0] or ref_extra.numel() != tok.shape[0] or \
+            ref_ids.device != tok.device or ref_extra.device != tok.device:
+        raise DagnnHipError("seq_f1_counts: tok [B, S], ref_ids [B, R] and ref_extra [B] on one device needed (got %s, %s, %s)"
+                            % (tuple(tok.shape), tuple(ref_ids.shape), tuple(ref_extra.shape)))
+    B, S = tok.shape
+    if out is None:
+        out = torch.empty(B, 4, dtype=torch.int32, device=tok.device)
+    elif out.dtype != torch.int32 or tuple(out.shape) != (B, 4) or not out.is_contiguous() or out.device != tok.device:
+        raise DagnnHipError("seq_f1_counts: `out` must be a contiguous int32 [B, 4] tensor on tok's device")
+    check(_lib.load().dagnn_seq_f1_counts(tok.data_ptr(), B, S, int(eos_id), ref_ids.data_ptr(), ref_ids.shape[1],
+                                          ref_extra.data_ptr(), out.data_ptr(), _stream(tok)), "dagnn_seq_f1_counts")
+    return out

@@ -493,6 +493,24 @@ class DAGNN(HipModule):
 
     # ------------------------------------------------------------------------------ forward
     def forward(self, G):
+        return self._pass(G, self._heads)
+
+    def predict(self, G, return_top: bool = False):
+        """Evaluation passes of the TOK task (ogbg-code/main_pyg.py:101-109): the predicted token matrix [B, S] (int64) -
+        equal by contract to `torch.cat([torch.argmax(p, dim=1).view(-1, 1) for p in model(G)], dim=1)` under
+        `torch.no_grad()`, with `forward`'s side effects on `G` - from ONE pass over the heads that never writes the
+        [B, S V] logits (`dagnn_heads_argmax`, csrc/predict.hip; `num_class` models: [B, 1]).  Among equal logits the lowest
+        column wins and a NaN beats every number, as `torch.argmax` decides.  `return_top=True` also returns [B, S, 2]: the
+        winning logit and the runner-up.  Evaluation mode only (a training step has its logits: `evaluate.rows_argmax`)."""
+        if self.training:
+            raise RuntimeError("DAGNN.predict is an evaluation pass: call model.eval() first (the argmax of a training step's "
+                               "logits is dagnn_amd.evaluate.rows_argmax)")
+        with torch.no_grad():
+            tok, top = self._pass(G, self._heads_argmax)
+        return (tok, top) if return_top else tok
+
+    def _pass(self, G, head):
+        """`forward` up to the pooled graph vectors, then `head` on them (`_heads`: the logits; `_heads_argmax`: `predict`)."""
         L, H, dirs = self.num_layers, self.hidden_dim, self.dirs
         if not self._hip_supported():
             # constructor strings outside every BASELINE configuration (SURVEY §8 a12): same contract, torch-ROCm ops
@@ -511,14 +529,14 @@ class DAGNN(HipModule):
                     plan = self._plan_of(G, B)
                     flat_params = [p for d in self.dirs for i in range(L) for _, p in variants._cell_params(self, d, i)]
                     flat = variants.VariantRecurrence.apply(self, G, plan, G.x, *flat_params)
-                    return self._finish(G, None, G.x, self._unflatten(flat), B)
+                    return self._finish(G, None, G.x, self._unflatten(flat), B, head)
                 if self.variant_backend != "torch":   # (an explicit 'torch' backend is a choice, not a cliff)
                     variants.warn_torch_path(self, G)
-                return self._finish(G, None, G.x, variants.run(self, G, G.x), B)   # training: differentiable torch ops
+                return self._finish(G, None, G.x, variants.run(self, G, G.x), B, head)   # training: differentiable torch ops
             plan = self._plan_of(G, B)
             h = variants.run_hip(self, G, G.x, plan)
             self._guard_params(G.x)
-            return self._finish(G, plan, G.x, h, B)
+            return self._finish(G, plan, G.x, h, B, head)
         train = self._training_pass()
 
         B = num_graphs_of(G)
@@ -532,7 +550,7 @@ class DAGNN(HipModule):
                 h = run_stack(plan, x, cells, dirs, L, H, schedule=self.schedule, static_score=sscore,
                               arena=self._arena_for(x), gi0=gi0)
                 self._guard_params(x)
-                return self._finish(G, plan, x, h, B)
+                return self._finish(G, plan, x, h, B, head)
         # side effect 1 (dagnn.py:130-133) + the plan: on a side stream next to the encoder and the input GEMM, which do not
         # depend on them (`engine.PLAN_OVERLAP`); the caller's stream meets it again in front of the recurrence
         plan = self._plan_of(G, B, overlap=True)
@@ -549,14 +567,14 @@ class DAGNN(HipModule):
             h = self._unflatten(res[1:] if fused_readout else res)
             if fused_readout:
                 G.h = [[h[d][i] for i in range(L)] for d in dirs]
-                return self._heads(self.dropout(res[0]))
-            return self._finish(G, plan, x, h, B)
+                return head(self.dropout(res[0]))
+            return self._finish(G, plan, x, h, B, head)
         cells = self._cells()
         sscore = self._static_scores(x, cells)
         h = run_stack(plan, x, cells, dirs, L, H, schedule=self.schedule, static_score=sscore,
                       arena=self._arena_for(x), gi0=self._folded_gi0(x_idx, depth, cells))
         self._guard_params(x)
-        return self._finish(G, plan, x, h, B)
+        return self._finish(G, plan, x, h, B, head)
 
     def _head_storage(self):
         """The S vocabulary heads' weights and biases as ONE [S V, D] / [S V] pair: each head's parameter is (made) a VIEW of
@@ -604,8 +622,27 @@ class DAGNN(HipModule):
             return list(logits.split(self.num_vocab, dim=1))
         return [self.graph_pred_linear_list[i](out) for i in range(self.max_seq_len)]
 
-    def _finish(self, G, plan, x, h, B):
-        """Read-out + heads (dagnn.py:184-215) on the states h[d][i]."""
+    def _heads_argmax(self, out):
+        """(tok [B, S], top [B, S, 2]) of the heads on the pooled graph vectors: the head step of `predict`.  Plain `nn.Linear`
+        heads on an fp32 GPU `out` are one pass of `dagnn_heads_argmax`; anything else takes `_heads` + torch, as `_heads`
+        itself falls back."""
+        single = self.num_class > 0
+        heads = [self.graph_pred_linear] if single else list(self.graph_pred_linear_list)
+        if out.is_cuda and out.dtype == torch.float32 and all(
+                isinstance(hd, nn.Linear) and hd.bias is not None and hd.weight.dtype == torch.float32 and hd.weight.is_cuda
+                for hd in heads):
+            wcat, bcat = (heads[0].weight, heads[0].bias) if single else self._head_storage()
+            return engine.heads_argmax(out, wcat.detach(), bcat.detach(), len(heads), heads[0].weight.shape[0],
+                                       arena=self._arena_for(out))
+        pred = self._heads(out)
+        pred = [pred] if single else pred
+        tok = torch.cat([torch.argmax(p, dim=1).view(-1, 1) for p in pred], dim=1)
+        top = torch.stack([torch.cat([p.float(), p.new_full((p.shape[0], 1), float("-inf")).float()], 1).topk(2, dim=1).values
+                           for p in pred], dim=1)
+        return tok, top
+
+    def _finish(self, G, plan, x, h, B, head=None):
+        """Read-out + `head` (default `_heads`: dagnn.py:184-215) on the states h[d][i]."""
         L, dirs = self.num_layers, self.dirs
         G.h = [[h[d][i] for i in range(L)] for d in dirs]  # side effect 4 (dagnn.py:141-142,182)
 
@@ -642,4 +679,4 @@ class DAGNN(HipModule):
             if not hip_pool:
                 out = self._pool(G.h, G.batch, B)
 
-        return self._heads(self.dropout(out))
+        return (head or self._heads)(self.dropout(out))

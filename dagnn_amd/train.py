@@ -228,29 +228,39 @@ class _SeqCE(torch.autograd.Function):
         return torch.mul(dl, g, out=out), None, None, None
 
 
+def heads_base(pred_list):
+    """The ONE [B, S * V] fp32 GPU tensor `pred_list` is S views of - what `DAGNN.forward` returns on a GPU: the heads' outputs
+    side by side, head i at column i * V - or None for any other list."""
+    S = len(pred_list)
+    if S == 0:
+        return None
+    p0 = pred_list[0]
+    base = getattr(p0, "_base", None)
+    if base is None or not base.is_cuda or base.dtype != torch.float32 or base.dim() != 2 or base.stride(1) != 1 or p0.dim() != 2:
+        return None
+    V = p0.shape[1]
+    for i, p in enumerate(pred_list):
+        if getattr(p, "_base", None) is not base or p.shape != p0.shape or p.stride() != base.stride() or \
+                p.data_ptr() != base.data_ptr() + 4 * i * V:
+            return None
+    return base if base.shape[1] == S * V else None
+
+
 def seq_cross_entropy(pred_list, y_arr: torch.Tensor) -> torch.Tensor:
     """`sum_i CrossEntropyLoss()(pred_list[i], y_arr[:, i]) / len(pred_list)` - the loss of the reference's training loop
     (ogbg-code/main_pyg.py:55-60).  When the list is what `DAGNN.forward` returns on a GPU - views of one [B, S * V] tensor, the
     heads' outputs side by side - loss and gradient are ONE launch (`dagnn_seq_ce`) and the backward pass meets the heads as
     one matrix; any other list takes the plain loop.  Targets must lie in [0, V) (no `ignore_index`)."""
     S = len(pred_list)
-    p0 = pred_list[0]
-    base = getattr(p0, "_base", None)
-    fused = base is not None and base.is_cuda and base.dtype == torch.float32 and base.dim() == 2 and base.stride(1) == 1 \
-        and y_arr.is_cuda and y_arr.dtype == torch.int64 and y_arr.dim() == 2 and y_arr.shape[1] == S and y_arr.is_contiguous()
-    if fused:
-        V = p0.shape[1]
-        for i, p in enumerate(pred_list):
-            if getattr(p, "_base", None) is not base or p.shape != p0.shape or p.stride() != base.stride() or \
-                    p.data_ptr() != base.data_ptr() + 4 * i * V:
-                fused = False
-                break
-        fused = fused and base.shape[1] == S * V and y_arr.shape[0] == base.shape[0]
+    base = heads_base(pred_list)
+    fused = base is not None and y_arr.is_cuda and y_arr.dtype == torch.int64 and y_arr.dim() == 2 and y_arr.shape[1] == S \
+        and y_arr.is_contiguous() and y_arr.shape[0] == base.shape[0]
     if not fused:
         loss = 0
         for i in range(S):
             loss = loss + torch.nn.functional.cross_entropy(pred_list[i].to(torch.float32), y_arr[:, i])
         return loss / S
+    V = pred_list[0].shape[1]
     return _SeqCE.apply(base, y_arr, S, V)
 
 

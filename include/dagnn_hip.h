@@ -1170,6 +1170,38 @@ int dagnn_tn_product(const float* A, int64_t lda, const float* B, int64_t ldb, i
 int dagnn_seq_ce(const float* logits, int64_t ld, const int64_t* y, int B, int S, int V, float* dlogits, int64_t ld_dlogits,
                  float* row_loss, float* loss, unsigned* counter, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * The TOK task's evaluation path (csrc/predict.hip; ogbg-code/main_pyg.py:91-124): predicted tokens and the integer
+ * counts of the F1 evaluator (ogb/graphproppred/evaluate.py:231-267).
+ *
+ * Order of the logits everywhere below: a NaN is greater than every number and NaNs are equal to each other, -0 == +0,
+ * and among equal values the LOWEST column wins - what torch.argmax gives on the CPU.
+ *
+ * dagnn_heads_argmax: the S vocabulary heads (dagnn.py:212-215) and their argmax (main_pyg.py:106-109) without the
+ *   logits.  out [B, ld_out >= D] pooled graph vectors; wcat [S * V, ldw >= D] / bcat [S * V] the heads side by side
+ *   (head s: rows s V .. (s + 1) V - 1); tok [B, S] int64 = argmax_c (out[b] . wcat[s V + c] + bcat[s V + c]);
+ *   top [B, S, 2] (may be NULL) = that winning logit and the runner-up (the second in the order above, which EQUALS the
+ *   winner when two columns tie; -inf when V = 1).  fp32 MFMA accumulate; the sum over D is the same set of exact fp32
+ *   fmaf steps whatever B is.  `work` >= dagnn_heads_argmax_bytes(B, S, V) bytes: one 16-byte partial per (graph, head,
+ *   128-column tile), merged in ascending tile order by a second launch.  B = 0 returns at once; D is free (rows that
+ *   are not 16-byte aligned, or D % 4 != 0, take scalar loads).
+ * dagnn_rows_argmax: tok [B, S] from logits that exist, [B, ld >= S * V] with head s's V outputs of graph b at
+ *   b * ld + s * V (as dagnn_seq_ce reads them): one launch, a workgroup per (graph, head).
+ * dagnn_seq_f1_counts: counts [B, 4] int32 = (true_positive, n_pred, n_ref, len) per graph.  len = position of the first
+ *   eos_id in tok[b] (S if none: utils.py:166-179), n_pred = distinct ids in tok[b, :len], n_ref = distinct non-negative
+ *   ids in ref_ids[b] ([B, R] int32, padded with -1: the graph's in-vocabulary label words) + ref_extra[b] (its distinct
+ *   label words outside the vocabulary, which no prediction can match), true_positive = size of the intersection.
+ *   false_positive = n_pred - tp, false_negative = n_ref - tp.  A thread per graph.
+ * No allocation, no synchronisation, no float atomics: bitwise repeatable.  The size query returns 0 for arguments the
+ * entry point refuses with DAGNN_EINVAL.
+ * ---------------------------------------------------------------------------------------- */
+size_t dagnn_heads_argmax_bytes(int64_t B, int S, int V);
+int dagnn_heads_argmax(const float* out, int64_t ld_out, const float* wcat, int64_t ldw, const float* bcat, int64_t B, int D,
+                       int S, int V, int64_t* tok, float* top, void* work, size_t work_bytes, void* stream);
+int dagnn_rows_argmax(const float* logits, int64_t ld, int64_t B, int S, int V, int64_t* tok, void* stream);
+int dagnn_seq_f1_counts(const int64_t* tok, int64_t B, int S, int64_t eos_id, const int32_t* ref_ids, int R,
+                        const int32_t* ref_extra, int32_t* counts, void* stream);
+
 /* The tail of the reference's training step - `clip_grad_norm_(model.parameters(), clip)` + `optim.Adam.step()`
  * (ogbg-code/main_pyg.py:63-65,179) - over a table of fp32 tensors (csrc/optim.hip).  dagnn_grad_norm: the 2-norm of up to
  * DAGNN_MAX_OPT_TENSORS gradients (`partial`: scratch of dagnn_opt_chunks() floats; `accumulate` != 0 adds the tensors' sum of
