@@ -277,12 +277,13 @@ class VariantBwdCell(C.Structure):
                 ("recurrent", C.c_int32), ("reserved", C.c_int32)] + \
         [(k, C.c_void_p) for k in ("h", "a", "gi", "gh", "node0", "node1", "alpha", "edge_mat0", "edge_vec0", "edge_mat1",
                                    "edge_vec1", "w_node", "w_query", "w_hh", "w_ih", "g", "g_in", "da", "dgi", "dgh",
-                                   "dnode0", "dnode1", "dlogit", "esum")]
+                                   "dnode0", "dnode1", "dlogit", "esum", "w_node2")] + \
+        [("w_ld", C.c_int32), ("ld_in", C.c_int32)]
 
 
 class VariantBwdArgs(C.Structure):
     _fields_ = [("cell", (VariantBwdCell * MAX_STACKED) * MAX_DIRS), ("num_stacked", C.c_int), ("dir_mask", C.c_int),
-                ("H", C.c_int)]
+                ("H", C.c_int), ("ld", C.c_int)]
 
 
 class VariantArgs(C.Structure):
@@ -375,6 +376,7 @@ SYMBOLS = {
                                                     C.c_int32, C.c_void_p]),
     "dagnn_variant_backward_run": (C.c_int, [C.POINTER(Plan), C.POINTER(VariantBwdArgs), C.POINTER(C.POINTER(C.c_int32)),
                                              C.POINTER(C.c_int32), C.c_void_p]),
+    "dagnn_vid_colsums": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
     "dagnn_iprop_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.c_void_p, C.c_int, C.POINTER(IpropLayer), C.c_int, C.c_void_p, C.c_void_p]),
     "dagnn_encode_forward": (C.c_int, [C.POINTER(EncodeArgs), C.c_void_p]),

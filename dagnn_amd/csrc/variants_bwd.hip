@@ -24,6 +24,10 @@
 // are [K][J] for every product of a reverse pass).  No atomics, rows of a step are distinct nodes: deterministic.
 // Outputs for the parallel epilogue (weight gradients = transposed products over all nodes, edge-encoder gradients from
 // the per-node edge-feature sums): dgi, dgh, the projection gradients (dP|dM, dKr, dQl) and `esum`.
+// Width and row pitch are separate (gated_sum, add, max): state-like rows (h, a, g, da) are [N, ld] with H <= ld, the gate
+// blocks of gi / gh / dgi / dgh and the halves of P|M / dP|dM start at multiples of ld.  Only columns < H of a block are read
+// or written: the caller's zero padding stays zero.  D-VAE NA gated_sum: the one-hot vertex-id columns of gate / mapper are
+// a per-node bias the caller adds to P|M; their gradient is `dagnn_vid_colsums` of dP|dM (bottom of this file).
 #include "common.h"
 
 namespace {
@@ -43,7 +47,7 @@ __device__ __forceinline__ float vb_edge_term(const float* __restrict__ m, const
 struct VbStep {
     dagnn_variant_bwd_cell c[VBC];
     int dir[VBC], r0[VBC], r1[VBC];
-    int n, R, H;
+    int n, R, H, ld;   // ld: row pitch of the state-like buffers (>= H)
 };
 
 // ---- pull: one wave per frontier row
@@ -53,33 +57,33 @@ __global__ void __launch_bounds__(256) vb_pull_kernel(const int32_t* __restrict_
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int slot = S.r0[ci] + blockIdx.x * 4 + wave;
     if (slot >= S.r1[ci]) return;
-    const int d = S.dir[ci], od = 1 - d, R = S.R, H = S.H;
+    const int d = S.dir[ci], od = 1 - d, R = S.R, H = S.H, ld = S.ld;
     const int v = plan[L.rowrec[d] + 16 * (int64_t)slot];
     const int32_t* __restrict__ orec = plan + L.rowrec[od] + 16 * (int64_t)plan[L.pos[od] + v];
     const int eb = orec[1], ee = orec[2];
     const int32_t* __restrict__ col = plan + L.col[od];
     const int32_t* __restrict__ eidx = plan + L.eidx[od];
     const float* __restrict__ ea = reinterpret_cast<const float*>(plan + L.eattr[od]);
-    float* __restrict__ g = C.g + (int64_t)v * H;
+    float* __restrict__ g = C.g + (int64_t)v * ld;   // (mattn / additive attention: ld == H, checked by the host)
     if (C.mode == DAGNN_AGG_GIVEN) return;   // `agg_x`: the aggregate is an input of the recurrence - nothing to pull
     if (C.mode == DAGNN_AGG_GATED) {
-        const float* __restrict__ pq = C.node0 + (int64_t)v * 2 * H;
-        float* __restrict__ dpq = C.dnode0 + (int64_t)v * 2 * H;
+        const float* __restrict__ pq = C.node0 + (int64_t)v * 2 * ld;
+        float* __restrict__ dpq = C.dnode0 + (int64_t)v * 2 * ld;
         const bool es = C.esum != nullptr && R > 0 && R <= 2;
         for (int k = lane; k < H; k += 64) {
-            const float P = pq[k], M = pq[H + k];
+            const float P = pq[k], M = pq[ld + k];
             float aP = 0.f, aM = 0.f, eg[2] = {0.f, 0.f}, em[2] = {0.f, 0.f};
             for (int e = eb; e < ee; ++e) {
                 const float* attr = ea + (int64_t)e * R;
                 const float gt = vb_sigm(P + vb_edge_term(C.edge_mat0, C.edge_vec0, k, R, attr));
                 const float mp = M + vb_edge_term(C.edge_mat1, C.edge_vec1, k, R, attr);
-                const float dw = C.da[(int64_t)col[e] * H + k];
+                const float dw = C.da[(int64_t)col[e] * ld + k];
                 const float dg = dw * mp * gt * (1.0f - gt), dm = dw * gt;
                 aP += dg; aM += dm;
                 if (es)
                     for (int r = 0; r < R; ++r) { eg[r] = fmaf(dg, attr[r], eg[r]); em[r] = fmaf(dm, attr[r], em[r]); }
             }
-            dpq[k] = aP; dpq[H + k] = aM;
+            dpq[k] = aP; dpq[ld + k] = aM;
             if (es) {
                 float* o = C.esum + (int64_t)v * (2 * R * H);
                 for (int r = 0; r < R; ++r) { o[r * H + k] = eg[r]; o[(R + r) * H + k] = em[r]; }
@@ -91,12 +95,12 @@ __global__ void __launch_bounds__(256) vb_pull_kernel(const int32_t* __restrict_
         const bool is_max = C.mode == DAGNN_AGG_MAX;
         for (int k = lane; k < H; k += 64) {
             float acc = 0.f, eg[2] = {0.f, 0.f};
-            const float hv = C.h[(int64_t)v * H + k];
+            const float hv = C.h[(int64_t)v * ld + k];
             for (int e = eb; e < ee; ++e) {
-                float dw = C.da[(int64_t)col[e] * H + k];
+                float dw = C.da[(int64_t)col[e] * ld + k];
                 // max: the gradient of a_w[k] goes to the message that attained it - recomputed with the forward's own
                 // operations (variants.hip: vals + edge term), so the comparison with the stored maximum is exact
-                if (is_max && hv + vb_edge_term(C.edge_mat0, C.edge_vec0, k, R, ea + (int64_t)e * R) != C.a[(int64_t)col[e] * H + k])
+                if (is_max && hv + vb_edge_term(C.edge_mat0, C.edge_vec0, k, R, ea + (int64_t)e * R) != C.a[(int64_t)col[e] * ld + k])
                     dw = 0.f;
                 acc += dw;
                 if (es)
@@ -176,30 +180,40 @@ __global__ void __launch_bounds__(256) vb_gru_kernel(const int32_t* __restrict__
     const int ci = blockIdx.y;
     const dagnn_variant_bwd_cell& C = S.c[ci];
     if (!C.recurrent) return;   // Linear cell: its input gradients are plain maps of g
-    const int H = S.H, H3 = 3 * H;
+    const int H = S.H, ld = S.ld, H3 = 3 * ld;
     const int rows = S.r1[ci] - S.r0[ci];
     for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < (int64_t)rows * H; idx += (int64_t)gridDim.x * blockDim.x) {
         const int r = (int)(idx / H), k = (int)(idx - (int64_t)r * H);
         const int v = plan[L.rowrec[S.dir[ci]] + 16 * (int64_t)(S.r0[ci] + r)];
         const float* gi = C.gi + (int64_t)v * H3;
         const float* gh = C.gh + (int64_t)v * H3;
-        const float ghn = gh[2 * H + k];
-        const float rr = vb_sigm(gi[k] + gh[k]), zz = vb_sigm(gi[H + k] + gh[H + k]);
-        const float nn = tanhf(gi[2 * H + k] + rr * ghn);
-        const float G = C.g[(int64_t)v * H + k], av = C.a[(int64_t)v * H + k];
+        const float ghn = gh[2 * ld + k];
+        const float rr = vb_sigm(gi[k] + gh[k]), zz = vb_sigm(gi[ld + k] + gh[ld + k]);
+        const float nn = tanhf(gi[2 * ld + k] + rr * ghn);
+        const float G = C.g[(int64_t)v * ld + k], av = C.a[(int64_t)v * ld + k];
         const float dn = G * (1.0f - zz) * (1.0f - nn * nn);
         const float dz = G * (av - nn) * zz * (1.0f - zz);
         const float dr = dn * ghn * rr * (1.0f - rr);
         float* og = C.dgi + (int64_t)v * H3;
         float* oh = C.dgh + (int64_t)v * H3;
-        og[k] = dr; og[H + k] = dz; og[2 * H + k] = dn;
-        oh[k] = dr; oh[H + k] = dz; oh[2 * H + k] = dn * rr;
-        C.da[(int64_t)v * H + k] = G * zz;
+        og[k] = dr; og[ld + k] = dz; og[2 * ld + k] = dn;
+        oh[k] = dr; oh[ld + k] = dz; oh[2 * ld + k] = dn * rr;
+        C.da[(int64_t)v * ld + k] = G * zz;
     }
 }
 
-// ---- generic rows map: out[v, 0:J] += in[v, 0:K] W[K][J] for the frontier rows of a job
-struct VbMapJob { const float* in; const float* W; float* out; int K, J, dir, r0, r1; };
+// ---- generic rows map: out[v, 0:J] += in[v, 0:K] W[K][J] for the frontier rows of a job.  The weights are read in place:
+// `ld` = their row stride (0: J - a contiguous [K][J]), rows >= ksplit come from a second matrix W2 of the same stride (the
+// gate and the mapper of gated_sum are two parameters); the K logical input columns lie in blocks of kb at a pitch of kbp
+// (kb = 0: contiguous); ld_in / ld_out = row pitches of in / out (0: K / J)
+struct VbMapJob {
+    const float* in; const float* W; float* out; int K, J, dir, r0, r1;
+    const float* W2; int ld, ld_in, ld_out, kb, kbp, ksplit;
+};
+__host__ __device__ inline VbMapJob vb_job(const float* in, const float* W, float* out, int K, int J, int dir, int r0, int r1,
+                                           int ld_in = 0, int ld_out = 0, int kb = 0, int kbp = 0) {
+    return VbMapJob{in, W, out, K, J, dir, r0, r1, nullptr, 0, ld_in, ld_out, kb, kbp, 0};
+}
 struct VbMaps { VbMapJob j[VBC]; int n; };
 constexpr int VB_RT = 8;   // rows per workgroup
 
@@ -212,6 +226,8 @@ __global__ void __launch_bounds__(256) vb_map_kernel(const int32_t* __restrict__
     const int nrows = min(VB_RT, Jb.r1 - slot0);
     const int tid = threadIdx.x, j = blockIdx.y * 256 + tid;
     if (tid < VB_RT) s_node[tid] = tid < nrows ? plan[L.rowrec[Jb.dir] + 16 * (int64_t)(slot0 + tid)] : -1;
+    const int ldw = Jb.ld ? Jb.ld : Jb.J, ldi = Jb.ld_in ? Jb.ld_in : Jb.K, ldo = Jb.ld_out ? Jb.ld_out : Jb.J;
+    const int ksplit = Jb.W2 ? Jb.ksplit : Jb.K;
     float acc[VB_RT];
 #pragma unroll
     for (int r = 0; r < VB_RT; ++r) acc[r] = 0.f;
@@ -221,13 +237,15 @@ __global__ void __launch_bounds__(256) vb_map_kernel(const int32_t* __restrict__
         for (int idx = tid; idx < VB_RT * kc; idx += 256) {
             const int r = idx / kc, k = idx - r * kc;
             const int v = s_node[r];
-            s_in[r * kchunk + k] = v >= 0 ? Jb.in[(int64_t)v * Jb.K + k0 + k] : 0.f;
+            const int kk = k0 + k, c = Jb.kb ? (kk / Jb.kb) * Jb.kbp + kk % Jb.kb : kk;
+            s_in[r * kchunk + k] = v >= 0 ? Jb.in[(int64_t)v * ldi + c] : 0.f;
         }
         __syncthreads();
         if (j < Jb.J) {
-            const float* w = Jb.W + (int64_t)k0 * Jb.J + j;
+            const float* w = (k0 < ksplit ? Jb.W + (int64_t)k0 * ldw : Jb.W2 + (int64_t)(k0 - ksplit) * ldw) + j;
             for (int k = 0; k < kc; ++k) {
-                const float wv = w[(int64_t)k * Jb.J];
+                const float wv = *w;
+                w = k0 + k + 1 == ksplit ? Jb.W2 + j : w + ldw;   // (past the last row: never read)
 #pragma unroll
                 for (int r = 0; r < VB_RT; ++r) acc[r] = fmaf(s_in[r * kchunk + k], wv, acc[r]);
             }
@@ -237,7 +255,7 @@ __global__ void __launch_bounds__(256) vb_map_kernel(const int32_t* __restrict__
 #pragma unroll
         for (int r = 0; r < VB_RT; ++r) {
             const int v = s_node[r];
-            if (v >= 0) Jb.out[(int64_t)v * Jb.J + j] += acc[r];
+            if (v >= 0) Jb.out[(int64_t)v * ldo + j] += acc[r];
         }
     }
 }
@@ -367,7 +385,35 @@ int vb_launch_maps(const int32_t* plan, const PlanLayout& L, VbMaps& M, hipStrea
     return DAGNN_OK;
 }
 
+// gated_sum: g_v += [dP_v ; dM_v] [W_g ; W_m][:, :H] - the weights where they are: one stacked [2H, w_ld] matrix, or the gate's
+// rows at w_node and the mapper's at w_node2 (D-VAE NA: both [H, H + num_nodes], of which the first H columns are read)
+VbMapJob vb_gated_job(const dagnn_variant_bwd_cell& c, int H, int ld, int dir, int r0, int r1) {
+    VbMapJob j = vb_job(c.dnode0, c.w_node, c.g, 2 * H, H, dir, r0, r1, 2 * ld, ld, H, ld);
+    j.ld = c.w_ld;
+    j.W2 = c.w_node2; j.ksplit = H;
+    return j;
+}
+
+// ---- out[j, :] = sum over the rows v = j, j + n, j + 2 n, ... of in[v, :], added in that order by one thread per column:
+// no atomics, the same bits on every run
+__global__ void __launch_bounds__(256) vid_colsums_kernel(const float* __restrict__ in, int64_t ld_in, int64_t N, int J, int n,
+                                                          float* __restrict__ out, int64_t ld_out) {
+    const int c = blockIdx.x * 256 + threadIdx.x, j = blockIdx.y;
+    if (c >= J) return;
+    float acc = 0.f;
+    for (int64_t v = j; v < N; v += n) acc += in[v * ld_in + c];
+    out[(int64_t)j * ld_out + c] = acc;
+}
+
 }  // namespace
+
+extern "C" int dagnn_vid_colsums(const float* in, int64_t ld_in, int64_t N, int J, int n, float* out, int64_t ld_out, void* stream) {
+    if (!in || !out || N < 0 || J <= 0 || n <= 0 || n > 65535 || ld_in < J || ld_out < J) return DAGNN_EINVAL;
+    hipLaunchKernelGGL(vid_colsums_kernel, dim3((unsigned)((J + 255) / 256), (unsigned)n), dim3(256), 0, (hipStream_t)stream,
+                       in, ld_in, N, J, n, out, ld_out);
+    DAGNN_CHECK_LAUNCH();
+    return DAGNN_OK;
+}
 
 extern "C" int dagnn_variant_mattn_prepare(const dagnn_plan* pl, const dagnn_variant_bwd_cell* c, int dir, int H,
                                            int32_t row_begin, int32_t row_end, void* stream) {
@@ -391,8 +437,8 @@ extern "C" int dagnn_variant_mattn_prepare(const dagnn_plan* pl, const dagnn_var
 extern "C" int dagnn_variant_backward_run(const dagnn_plan* pl, const dagnn_variant_bwd_args* a, const int32_t* const* layer_ptr,
                                           const int32_t* num_layers, void* stream) {
     if (!pl || !a || !layer_ptr || !num_layers) return DAGNN_EINVAL;
-    const int Ls = a->num_stacked, H = a->H;
-    if (Ls <= 0 || Ls > DAGNN_MAX_STACKED || H <= 0 || !(a->dir_mask & 3)) return DAGNN_EINVAL;
+    const int Ls = a->num_stacked, H = a->H, ld = a->ld ? a->ld : a->H;
+    if (Ls <= 0 || Ls > DAGNN_MAX_STACKED || H <= 0 || ld < H || !(a->dir_mask & 3)) return DAGNN_EINVAL;
     if (pl->N == 0) return DAGNN_OK;
     if (!pl->data) return DAGNN_EINVAL;
     const int R = pl->num_edge_feats;
@@ -406,6 +452,8 @@ extern "C" int dagnn_variant_backward_run(const dagnn_plan* pl, const dagnn_vari
             if (c.mode != DAGNN_AGG_GATED && c.mode != DAGNN_AGG_MATTN && c.mode != DAGNN_AGG_ADD && c.mode != DAGNN_AGG_MAX &&
                 c.mode != DAGNN_AGG_ATTN && c.mode != DAGNN_AGG_GIVEN)
                 return DAGNN_EINVAL;
+            if ((c.mode == DAGNN_AGG_ATTN || c.mode == DAGNN_AGG_MATTN) && ld != H) return DAGNN_EINVAL;   // (their kernels know one stride)
+            if (c.ld_in < 0 || (c.ld_in && c.ld_in < c.in_dim) || c.w_ld < 0 || (c.w_ld && c.w_ld < H)) return DAGNN_EINVAL;
             if (c.mode == DAGNN_AGG_ATTN && (!c.alpha || !c.dnode0 || !c.w_node)) return DAGNN_EINVAL;
             if (!c.h || !c.a || !c.w_hh || !c.w_ih || !c.g || !c.g_in || !c.da || c.in_dim <= 0) return DAGNN_EINVAL;
             if (c.recurrent && (!c.gi || !c.gh || !c.dgi || !c.dgh)) return DAGNN_EINVAL;
@@ -420,7 +468,7 @@ extern "C" int dagnn_variant_backward_run(const dagnn_plan* pl, const dagnn_vari
     hipStream_t st = (hipStream_t)stream;
     for (int s = 0; s < maxT + Ls - 1; ++s) {
         VbStep S;
-        S.n = 0; S.R = R; S.H = H;
+        S.n = 0; S.R = R; S.H = H; S.ld = ld;
         int rows = 0;
         bool any_mattn = false;
         for (int d = 0; d < DAGNN_MAX_DIRS; ++d) {
@@ -448,8 +496,8 @@ extern "C" int dagnn_variant_backward_run(const dagnn_plan* pl, const dagnn_vari
         M.n = 0;
         for (int q = 0; q < S.n; ++q) {
             const dagnn_variant_bwd_cell& c = S.c[q];
-            if (c.mode == DAGNN_AGG_GATED) M.j[M.n++] = VbMapJob{c.dnode0, c.w_node, c.g, 2 * H, H, S.dir[q], S.r0[q], S.r1[q]};
-            else if (c.mode == DAGNN_AGG_MATTN) M.j[M.n++] = VbMapJob{c.dnode0, c.w_node, c.g, c.proj_dim, H, S.dir[q], S.r0[q], S.r1[q]};
+            if (c.mode == DAGNN_AGG_GATED) M.j[M.n++] = vb_gated_job(c, H, ld, S.dir[q], S.r0[q], S.r1[q]);
+            else if (c.mode == DAGNN_AGG_MATTN) M.j[M.n++] = vb_job(c.dnode0, c.w_node, c.g, c.proj_dim, H, S.dir[q], S.r0[q], S.r1[q]);
         }
         if (int rc = vb_launch_maps(plan, L, M, st)) return rc;
         // 3. GRU backward
@@ -459,14 +507,14 @@ extern "C" int dagnn_variant_backward_run(const dagnn_plan* pl, const dagnn_vari
         DAGNN_CHECK_LAUNCH();
         // 4. da += dgh W_hh   (Linear cell: da += g W[:, in_dim:])
         for (int q = 0; q < S.n; ++q)
-            M.j[M.n++] = S.c[q].recurrent ? VbMapJob{S.c[q].dgh, S.c[q].w_hh, S.c[q].da, 3 * H, H, S.dir[q], S.r0[q], S.r1[q]}
-                                          : VbMapJob{S.c[q].g, S.c[q].w_hh, S.c[q].da, H, H, S.dir[q], S.r0[q], S.r1[q]};
+            M.j[M.n++] = S.c[q].recurrent ? vb_job(S.c[q].dgh, S.c[q].w_hh, S.c[q].da, 3 * H, H, S.dir[q], S.r0[q], S.r1[q], 3 * ld, ld, H, ld)
+                                          : vb_job(S.c[q].g, S.c[q].w_hh, S.c[q].da, H, H, S.dir[q], S.r0[q], S.r1[q], ld, ld);
         if (int rc = vb_launch_maps(plan, L, M, st)) return rc;
         // 5. input gradient += dgi W_ih   (Linear cell: += g W[:, :in_dim])
         for (int q = 0; q < S.n; ++q)
             M.j[M.n++] = S.c[q].recurrent
-                ? VbMapJob{S.c[q].dgi, S.c[q].w_ih, S.c[q].g_in, 3 * H, S.c[q].in_dim, S.dir[q], S.r0[q], S.r1[q]}
-                : VbMapJob{S.c[q].g, S.c[q].w_ih, S.c[q].g_in, H, S.c[q].in_dim, S.dir[q], S.r0[q], S.r1[q]};
+                ? vb_job(S.c[q].dgi, S.c[q].w_ih, S.c[q].g_in, 3 * H, S.c[q].in_dim, S.dir[q], S.r0[q], S.r1[q], 3 * ld, S.c[q].ld_in, H, ld)
+                : vb_job(S.c[q].g, S.c[q].w_ih, S.c[q].g_in, H, S.c[q].in_dim, S.dir[q], S.r0[q], S.r1[q], ld, S.c[q].ld_in);
         if (int rc = vb_launch_maps(plan, L, M, st)) return rc;
         if (any_mattn) {
             // 6. dlogit of the in-edges, dQl; 7. input gradient += dQl W_l
@@ -474,8 +522,8 @@ extern "C" int dagnn_variant_backward_run(const dagnn_plan* pl, const dagnn_vari
             DAGNN_CHECK_LAUNCH();
             for (int q = 0; q < S.n; ++q)
                 if (S.c[q].mode == DAGNN_AGG_MATTN)
-                    M.j[M.n++] = VbMapJob{S.c[q].dnode1, S.c[q].w_query, S.c[q].g_in, S.c[q].proj_dim, S.c[q].in_dim, S.dir[q],
-                                          S.r0[q], S.r1[q]};
+                    M.j[M.n++] = vb_job(S.c[q].dnode1, S.c[q].w_query, S.c[q].g_in, S.c[q].proj_dim, S.c[q].in_dim, S.dir[q],
+                                        S.r0[q], S.r1[q], 0, S.c[q].ld_in);
             if (int rc = vb_launch_maps(plan, L, M, st)) return rc;
         }
     }
@@ -489,7 +537,7 @@ extern "C" int dagnn_variant_aggregator_backward(const dagnn_plan* pl, const dag
                                                  int32_t row_begin, int32_t row_end, void* stream) {
     if (!pl || !pl->data || !c || (dir != 0 && dir != 1) || width <= 0 || row_begin < 0 || row_end > pl->N) return DAGNN_EINVAL;
     if (!c->h || !c->a || !c->da || !c->g || !c->g_in) return DAGNN_EINVAL;
-    if (c->mode == DAGNN_AGG_GATED && (!c->node0 || !c->dnode0 || !c->w_node)) return DAGNN_EINVAL;
+    if (c->mode == DAGNN_AGG_GATED && (!c->node0 || !c->dnode0 || !c->w_node || c->w_ld < 0 || (c->w_ld && c->w_ld < width))) return DAGNN_EINVAL;
     if (c->mode == DAGNN_AGG_MATTN && (!c->node0 || !c->node1 || !c->dnode0 || !c->dnode1 || !c->w_node || !c->w_query || !c->alpha ||
                                        !c->dlogit || c->proj_dim <= 0))
         return DAGNN_EINVAL;
@@ -499,7 +547,7 @@ extern "C" int dagnn_variant_aggregator_backward(const dagnn_plan* pl, const dag
     const int32_t* plan = (const int32_t*)pl->data;
     hipStream_t st = (hipStream_t)stream;
     VbStep S;
-    S.n = 1; S.R = pl->num_edge_feats; S.H = width;
+    S.n = 1; S.R = pl->num_edge_feats; S.H = width; S.ld = width;
     S.c[0] = *c; S.dir[0] = dir; S.r0[0] = row_begin; S.r1[0] = row_end;
     const dim3 wgrid((unsigned)((row_end - row_begin + 3) / 4), 1);
     if (c->mode == DAGNN_AGG_MATTN) {   // dlogit of every edge first: the pull below reads it for the out-edges
@@ -510,11 +558,11 @@ extern "C" int dagnn_variant_aggregator_backward(const dagnn_plan* pl, const dag
     DAGNN_CHECK_LAUNCH();
     VbMaps M;
     M.n = 0;
-    if (c->mode == DAGNN_AGG_GATED) M.j[M.n++] = VbMapJob{c->dnode0, c->w_node, c->g, 2 * width, width, dir, row_begin, row_end};
-    else if (c->mode == DAGNN_AGG_MATTN) M.j[M.n++] = VbMapJob{c->dnode0, c->w_node, c->g, c->proj_dim, width, dir, row_begin, row_end};
+    if (c->mode == DAGNN_AGG_GATED) M.j[M.n++] = vb_gated_job(*c, width, width, dir, row_begin, row_end);
+    else if (c->mode == DAGNN_AGG_MATTN) M.j[M.n++] = vb_job(c->dnode0, c->w_node, c->g, c->proj_dim, width, dir, row_begin, row_end);
     if (int rc = vb_launch_maps(plan, L, M, st)) return rc;
     if (c->mode == DAGNN_AGG_MATTN) {
-        M.j[M.n++] = VbMapJob{c->dnode1, c->w_query, c->g_in, c->proj_dim, c->in_dim, dir, row_begin, row_end};
+        M.j[M.n++] = vb_job(c->dnode1, c->w_query, c->g_in, c->proj_dim, c->in_dim, dir, row_begin, row_end);
         if (int rc = vb_launch_maps(plan, L, M, st)) return rc;
     }
     return DAGNN_OK;

@@ -871,8 +871,9 @@ class _DvaeDagnn(_DvaeBase):
     def _gated_sum_states(self, G, x):
         """`gated_sum` on the NA encoder: the messages are gate(hs_j) * mapper(hs_j) with hs_j = [state ; one-hot vertex id]
         (dvae/dagnn.py:124-137, 269-299), i.e. per NODE P_j = W_g[:, :H] h_j + W_g[:, H + j mod n] + b_g (likewise the
-        mapper) - the vertex-id columns are a per-node bias.  Layer by layer on device-side torch ops (a D-VAE batch has
-        as many layers as a graph has vertices: <= ~10 steps; differentiable as it stands)."""
+        mapper) - the vertex-id columns are a per-node bias.  Layer by layer on differentiable torch ops, on whatever device
+        and precision `x` has: the fall-back of `_forward_plain_agg` where the HIP paths do not apply, and the restatement
+        the tests tie their float64 oracle to."""
         N, H, L, nn_ = x.shape[0], self.hidden_dim, self.num_layers, self.num_nodes
         dev = x.device
         vid = torch.arange(N, device=dev) % nn_
@@ -909,30 +910,32 @@ class _DvaeDagnn(_DvaeBase):
         return h
 
     def _forward_plain_agg(self, G, plan, x, B, train):
-        """`forward` for agg in {gated_sum, add, max}: `add` / `max` through the generic HIP kernels of csrc/variants.hip
-        (`dagnn_variant_run`; training: the reverse sweep of csrc/variants_bwd.hip where it applies, `variants.hip_backward_
-        supported`), `gated_sum` (NA) on torch ops; then the read-outs of `dvae/dagnn.py:147-172`."""
+        """`forward` for agg in {gated_sum, add, max}: the generic HIP kernels of csrc/variants.hip (`dagnn_variant_run`;
+        `gated_sum` (NA): the one-hot vertex-id columns of gate / mapper as a per-vertex-id bias), in training with the
+        reverse sweep of csrc/variants_bwd.hip behind them (`variants.VariantRecurrence`, any hidden width); then the
+        read-outs of `dvae/dagnn.py:147-172`.  Torch ops only where the sweep does not apply (`variants.hip_backward_
+        supported`, or a gate that is not hs + num_nodes wide): one `warn_torch_path` warning per model shape."""
         from . import variants
         L, H, nn_ = self.num_layers, self.hidden_dim, self.num_nodes
-        if self.agg == K.NA_GATED_SUM and (train or not self._gated_hip_ok()):
-            if train:   # differentiable device-side torch ops (the reverse sweep of csrc/variants_bwd.hip has no vertex-id columns)
+        view = self._agg_view()
+        gated = self.agg == K.NA_GATED_SUM
+        if gated and not self._gated_hip_ok():
+            if train:
+                variants.warn_torch_path(view, G)
                 h = self._gated_sum_states(G, x)
             else:
                 with torch.no_grad():
                     h = self._gated_sum_states(G, x)
-        elif self.agg == K.NA_GATED_SUM:   # evaluation: the generic HIP kernels, the one-hot columns as a per-vertex-id bias
-            h = variants.run_hip(self._agg_view(), G, x, plan)
+        elif not train:
+            h = variants.run_hip(view, G, x, plan)
+        elif variants.hip_backward_supported(view, G):
+            # (gated_sum: the view hands out gate / mapper at their full width [hs, hs + num_nodes] - the parameters themselves,
+            # so these gradients and the decoder's add up in one .grad)
+            flat_params = [p for d in self.dirs for i in range(L) for _, p in variants._cell_params(view, d, i)]
+            h = self._unflatten(variants.VariantRecurrence.apply(view, G, plan, x, *flat_params))
         else:
-            view = self._agg_view()
-            if train:
-                if variants.hip_backward_supported(view, G):
-                    flat_params = [p for d in self.dirs for i in range(L) for _, p in variants._cell_params(view, d, i)]
-                    h = self._unflatten(variants.VariantRecurrence.apply(view, G, plan, x, *flat_params))
-                else:
-                    variants.warn_torch_path(view, G)
-                    h = variants.run(view, G, x)
-            else:
-                h = variants.run_hip(view, G, x, plan)
+            variants.warn_torch_path(view, G)
+            h = self._gated_sum_states(G, x) if gated else variants.run(view, G, x)
         N = x.shape[0]
         if self.output_all:
             return self._pool_all(G, None, x, [h[d][i] for d in self.dirs for i in range(L)], B)

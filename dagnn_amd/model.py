@@ -11,8 +11,8 @@ Aggregators: the additive-attention family (`attn_h` - every BASELINE config - `
 `gated_sum`, `add`, `max`, `agg_x=True`, `recurr=0`; SURVEY.md §8(a) row a12: exercised by no BASELINE
 configuration) keep the same contract on the generic HIP kernels of `csrc/variants.hip` (forward) and
 `csrc/variants_bwd.hip` (the reverse sweep of a training step), marshalled by `dagnn_amd/variants.py`; only what those
-kernels do not take (more than 8 cells, widths that are not multiples of 4, more than two edge features behind an edge
-encoder) trains on torch-ROCm ops, and says so once (`variants.warn_torch_path`).
+kernels do not take (more than 8 cells, an input width that is no multiple of 4 - or a hidden width with `mattn_h` / additive
+attention -, more than two edge features behind an edge encoder) trains on torch-ROCm ops, and says so once (`variants.warn_torch_path`).
 """
 from __future__ import annotations
 

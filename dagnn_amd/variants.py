@@ -81,8 +81,8 @@ _TORCH_PATH_SEEN = set()
 def warn_torch_path(mod, G) -> None:
     """Say ONCE per model shape that a training step of this constructor string runs the reference's loop nest on torch
     ops (`run` below) instead of the HIP reverse sweep (`VariantRecurrence`): 10-100x slower per step, otherwise silent.
-    The HIP sweep covers up to 8 cells, widths that are multiples of 4 and at most two edge features behind an edge
-    encoder (`hip_backward_supported`)."""
+    The HIP sweep covers up to 8 cells, input widths that are multiples of 4 (hidden widths too for the attention
+    aggregators) and at most two edge features behind an edge encoder (`hip_backward_supported`)."""
     key = (mod.agg, bool(mod.agg_x), bool(mod.recurr), mod.hidden_dim, mod.emb_dim, mod.num_layers, len(mod.dirs))
     if key in _TORCH_PATH_SEEN:
         return
@@ -90,7 +90,8 @@ def warn_torch_path(mod, G) -> None:
     import warnings
     warnings.warn("dagnn_amd: training agg=%r (agg_x=%s, recurr=%s, hidden %d, %d stacked layers, %d direction(s)) runs on "
                   "torch ops, layer by layer - the HIP reverse sweep of the constructor-string variants takes at most 8 "
-                  "cells, widths that are multiples of 4 and at most two edge features; expect 10-100x the step time"
+                  "cells, input widths that are multiples of 4 (hidden widths too for mattn / attention aggregators) and at most "
+                  "two edge features; expect 10-100x the step time"
                   % (mod.agg, mod.agg_x, mod.recurr, mod.hidden_dim, mod.num_layers, len(mod.dirs)),
                   RuntimeWarning, stacklevel=3)
 
@@ -296,11 +297,19 @@ def run_plain_dataflow(mod, x: torch.Tensor, plan) -> Optional[List[List[Optiona
     return [[h[d][i][:, :H] if h[d][i] is not None else None for i in range(L)] for d in range(2)]
 
 
-def run_hip(mod, G, x: torch.Tensor, plan, dataflow: bool = True) -> List[List[Optional[torch.Tensor]]]:
+def row_pitch(width: int) -> int:
+    """Row pitch of the training buffers of a `width`-wide state: the next multiple of 4 floats (16-byte rows for
+    `engine.gemm_nt_bias` / `engine.wgrad`); the columns past `width` are zero and stay zero."""
+    return (width + 3) // 4 * 4
+
+
+def run_hip(mod, G, x: torch.Tensor, plan, dataflow: bool = True, pitch: int = 0,
+            bufs: Optional[dict] = None) -> List[List[Optional[torch.Tensor]]]:
     """h[d][i] ([N, hidden]) through `dagnn_variant_run` (csrc/variants.hip) - or, for `add` / `max` with GRU cells, through the
     persistent dataflow kernel (`run_plain_dataflow`; `dataflow=False`: never - a training pass, whose reverse sweep reads
     dense [N, hidden] state rows).  `plan`: engine.PlanHandle of the batch (with the edge features when the model has an edge
-    encoder)."""
+    encoder).  `pitch` > hidden: the states are the first `hidden` columns of zero-initialised [N, pitch] buffers, which
+    `bufs[(d, i)]` receives (the reverse sweep's row layout, `row_pitch`)."""
     fast = run_plain_dataflow(mod, engine._dev(x.detach(), "node inputs", torch.float32), plan) if dataflow else None
     if fast is not None:
         return fast
@@ -321,7 +330,12 @@ def run_hip(mod, G, x: torch.Tensor, plan, dataflow: bool = True) -> List[List[O
         for d in mod.dirs:
             lands = 0 if (shared_flow and d == 1) else 1
             for i in range(L):
-                h[d][i] = torch.empty(N, H, dtype=torch.float32, device=dev)
+                if pitch > H:
+                    h[d][i] = torch.zeros(N, pitch, dtype=torch.float32, device=dev)
+                else:
+                    h[d][i] = torch.empty(N, H, dtype=torch.float32, device=dev)
+                if bufs is not None:
+                    bufs[(d, i)] = h[d][i]
             given = None
             if mod.agg_x:
                 # the aggregator runs on the inputs (dagnn.py:159-169): all layers in one launch, reused by every cell
@@ -351,11 +365,11 @@ def run_hip(mod, G, x: torch.Tensor, plan, dataflow: bool = True) -> List[List[O
             for i in range(L):
                 p, vc = prm[(d, i)], args.cell[d][i]
                 inp = x if i == 0 else h[d][i - 1]
-                vc.recurrent, vc.in_dim = (1 if mod.recurr else 0), inp.shape[1]
-                vc.input, vc.ld_input = inp.data_ptr(), inp.shape[1]
+                vc.recurrent, vc.in_dim = (1 if mod.recurr else 0), (E if i == 0 else H)
+                vc.input, vc.ld_input = inp.data_ptr(), inp.stride(0)
                 vc.w_in_t, vc.w_agg_t = p["w_in_t"].data_ptr(), p["w_agg_t"].data_ptr()
                 vc.b_in, vc.b_agg = _ptr(p["b_in"]), _ptr(p["b_agg"])
-                vc.h, vc.ld_h = h[d][i].data_ptr(), H
+                vc.h, vc.ld_h = h[d][i].data_ptr(), h[d][i].stride(0)
                 a = vc.agg
                 a.out_dim, a.ld_out = H, H
                 if given is not None:
@@ -364,7 +378,7 @@ def run_hip(mod, G, x: torch.Tensor, plan, dataflow: bool = True) -> List[List[O
                 scratch = torch.empty(N, H, dtype=torch.float32, device=dev)
                 keep.append(scratch)
                 a.mode, a.lands, a.val_dim, a.out = mode, lands, H, scratch.data_ptr()
-                a.vals, a.ld_vals = h[d][i].data_ptr(), H
+                a.vals, a.ld_vals = h[d][i].data_ptr(), h[d][i].stride(0)
                 a.edge_mat0, a.edge_vec0 = _ptr(p.get("edge_mat0")), _ptr(p.get("edge_vec0"))
                 a.edge_mat1, a.edge_vec1 = _ptr(p.get("edge_mat1")), _ptr(p.get("edge_vec1"))
                 nm = 0
@@ -415,6 +429,8 @@ def run_hip(mod, G, x: torch.Tensor, plan, dataflow: bool = True) -> List[List[O
             engine.check(lib.dagnn_variant_run(C.byref(plan.desc), C.byref(args), ptrs, nl, stream),
                          "dagnn_variant_run")
     del keep
+    if pitch > H:
+        return [[t[:, :H] if t is not None else None for t in hd] for hd in h]
     return h
 
 
@@ -434,13 +450,17 @@ def _attn_slice(mod, i):
 def hip_backward_supported(mod, G) -> bool:
     """Every constructor-string variant trains through HIP (csrc/variants_bwd.hip): `gated_sum`, `mattn_h`, `add`, `max`
     with GRU or Linear (`recurr=0`) cells, the additive-attention aggregators on the Linear cell (with GRU cells they
-    are the tuned main path), and all of them with `agg_x`.  Left on the differentiable torch-ops path: more than 8
-    cells, widths that are not multiples of 4, more than two edge features with an edge encoder."""
+    are the tuned main path), and all of them with `agg_x`.  `gated_sum`, `add` and `max` take any hidden width (the
+    sweep's rows have a pitch of the next multiple of 4, `row_pitch`).  Left on the differentiable torch-ops path: more
+    than 8 cells, an input width (`emb_dim`) that is not a multiple of 4, a hidden width that is not one with `mattn_h` or
+    additive attention, more than two edge features with an edge encoder."""
     if mod.agg not in _BWD_MODES or len(mod.dirs) * mod.num_layers > 8:
         return False
     if _BWD_MODES[mod.agg] == _lib.AGG_ATTN and mod.recurr and not mod.agg_x:
         return False   # (never reached: that is the main path)
-    if mod.hidden_dim % 4 or mod.emb_dim % 4 or (mod.agg_x and mod.emb_dim > mod.hidden_dim):
+    if mod.emb_dim % 4 or (mod.agg_x and mod.emb_dim > mod.hidden_dim):
+        return False
+    if mod.hidden_dim % 4 and _BWD_MODES[mod.agg] not in (_lib.AGG_GATED, _lib.AGG_ADD, _lib.AGG_MAX):
         return False
     has_enc = getattr(mod.node_aggr_0[0], "wea", False)
     if has_enc and (getattr(G, "edge_attr", None) is None or G.edge_attr.view(G.edge_attr.shape[0], -1).shape[1] > 2):
@@ -475,9 +495,10 @@ def _cell_params(mod, d, i):
 def _setup_aggregator(mod, plan, bc, o, p, cp, mode, lands, d, i, vals, query, W, a_out, rows, stream, x):
     """Forward quantities of one aggregator for its reverse pass: the per-node projections (library GEMMs), the attention
     weights and the aggregate `a_out` [N, W] of the rows `rows` = (first slot, end slot) (HIP), and the fields of the C
-    struct `bc` that describe it.  `vals` [N, W] are the aggregated values (the cell's states, or x with `agg_x`)."""
+    struct `bc` that describe it.  `vals` [N, >= W] are the aggregated values (the cell's states at their row pitch, or x
+    with `agg_x`), of which the first W columns count; `a_out` has its own pitch."""
     lib = _lib.load()
-    N, R = vals.shape[0], plan.R
+    N, R, Wp = vals.shape[0], plan.R, vals.shape[1]
     f32 = dict(dtype=torch.float32, device=vals.device)
     has_enc = "we" in cp
     bc.mode, bc.lands = mode, lands
@@ -491,20 +512,31 @@ def _setup_aggregator(mod, plan, bc, o, p, cp, mode, lands, d, i, vals, query, W
             return
         ag = _lib.VariantAggregator()
         ag.mode, ag.lands, ag.val_dim, ag.out_dim = agg_mode, 1, W, W
-        ag.vals, ag.ld_vals, ag.out, ag.ld_out = vals.data_ptr(), W, a_out.data_ptr(), W
+        ag.vals, ag.ld_vals, ag.out, ag.ld_out = vals.data_ptr(), vals.stride(0), a_out.data_ptr(), a_out.stride(0)
         ag.node0, ag.node1, ag.ld_node = node0, node1, ld_node
         ag.edge_mat0, ag.edge_vec0, ag.edge_mat1, ag.edge_vec1 = bc.edge_mat0, bc.edge_vec0, bc.edge_mat1, bc.edge_vec1
         engine.check(lib.dagnn_variant_aggregate(C.byref(plan.desc), C.byref(ag), d, rows[0], rows[1], stream),
                      "dagnn_variant_aggregate")
 
     if mode == _lib.AGG_GATED:
-        pq = torch.addmm(p["pq_b"], vals, p["pq_w_t"])
-        o["node0"], o["dnode0"] = pq, torch.zeros(N, 2 * W, **f32)
-        o["w_node"] = torch.cat([cp["wg"], cp["wm"]], 0).contiguous()
-        bc.node0, bc.dnode0, bc.w_node, bc.proj_dim = pq.data_ptr(), o["dnode0"].data_ptr(), o["w_node"].data_ptr(), W
+        pq = torch.addmm(p["pq_b"], vals if Wp == W else vals[:, :W], p["pq_w_t"])
+        nv = p["pq_vid"].shape[0] if p.get("pq_vid") is not None else 0
+        if nv:   # D-VAE NA: the one-hot vertex-id columns of gate / mapper are a bias per vertex id (node v has id v mod nv)
+            pq += p["pq_vid"][torch.arange(N, device=vals.device) % nv]
+        if Wp != W:   # [P | M] with the mapper's half at column Wp, zero padding behind each half
+            pq, pq_c = torch.zeros(N, 2 * Wp, **f32), pq
+            pq.view(N, 2, Wp)[:, :, :W] = pq_c.view(N, 2, W)
+        o["node0"], o["dnode0"], o["vid"] = pq, torch.zeros(N, 2 * Wp, **f32), nv
+        # gate and mapper are read where they are: row stride = their own width (D-VAE NA: W + nv), first W columns
+        wg, wm = cp["wg"].contiguous(), cp["wm"].contiguous()
+        if wg.shape != wm.shape:
+            raise engine.DagnnHipError("gated_sum: gate %s and mapper %s weights differ in shape" % (tuple(wg.shape), tuple(wm.shape)))
+        o["w_node"] = (wg, wm)
+        bc.node0, bc.dnode0, bc.proj_dim = pq.data_ptr(), o["dnode0"].data_ptr(), W
+        bc.w_node, bc.w_node2, bc.w_ld = wg.data_ptr(), wm.data_ptr(), wg.shape[1]
         if has_enc and R > 0:
             o["esum"] = torch.zeros(N, 2 * R * W, **f32)
-        aggregate(_lib.AGG_GATED, pq.data_ptr(), pq.data_ptr() + 4 * W, 2 * W)
+        aggregate(_lib.AGG_GATED, pq.data_ptr(), pq.data_ptr() + 4 * Wp, 2 * Wp)
     elif mode in (_lib.AGG_ADD, _lib.AGG_MAX):
         if has_enc and R > 0 and lands:
             o["esum"] = torch.zeros(N, (R + 1) * W, **f32)
@@ -540,6 +572,33 @@ def _setup_aggregator(mod, plan, bc, o, p, cp, mode, lands, d, i, vals, query, W
     bc.esum = _ptr(o["esum"])
 
 
+def vid_colsums(t: torch.Tensor, n: int) -> torch.Tensor:
+    """out[j] = sum of the rows v of `t` [N, J] with v mod n == j, as [n, J] (`dagnn_vid_colsums`: rows added in ascending
+    order by one thread per element - no atomics, bitwise repeatable)."""
+    t = engine._dev(t, "vid_colsums input", torch.float32)
+    if t.dim() != 2 or n <= 0:
+        raise engine.DagnnHipError("vid_colsums: a [N, J] tensor and n > 0 (got %s, n = %d)" % (tuple(t.shape), n))
+    out = torch.empty(n, t.shape[1], dtype=torch.float32, device=t.device)
+    if t.shape[1] == 0:
+        return out
+    if t.stride(1) != 1:
+        t = t.contiguous()
+    engine.check(_lib.load().dagnn_vid_colsums(t.data_ptr(), t.stride(0) if t.shape[0] > 1 else t.shape[1], t.shape[0], t.shape[1],
+                                               n, out.data_ptr(), out.shape[1], engine._stream(t)), "dagnn_vid_colsums")
+    return out
+
+
+def _pad_gates(w: torch.Tensor, H: int, Hp: int, cols: int = 0) -> torch.Tensor:
+    """GRU weight [3H, in] / bias [3H] -> [3 Hp, cols] / [3 Hp]: gate block q at row q * Hp, zeros elsewhere."""
+    if w.dim() == 1:
+        out = w.new_zeros(3, Hp)
+        out[:, :H] = w.view(3, H)
+        return out.view(3 * Hp)
+    out = w.new_zeros(3, Hp, max(cols, w.shape[1]))
+    out[:, :H, :w.shape[1]] = w.view(3, H, w.shape[1])
+    return out.view(3 * Hp, -1)
+
+
 def _aggregator_grads(mod, mode, o, cp, vals, query, R, W, i, dx_d):
     """{name: gradient} of one aggregator's parameters from the sweep's per-node outputs (transposed products and sums
     over all nodes); `dx_d` additionally receives the key gradient of the `*_x` attention aggregators."""
@@ -547,10 +606,15 @@ def _aggregator_grads(mod, mode, o, cp, vals, query, R, W, i, dx_d):
     es = o.get("esum")
     f32 = dict(dtype=torch.float32, device=vals.device)
     if mode == _lib.AGG_GATED:
-        dpq = o["dnode0"]
-        prod = dpq.t() @ vals                       # [2W, W]: dP^T h | dM^T h
+        dpq = o["dnode0"]                          # [N, 2 Wp]: dP | dM, each half W wide at a pitch of Wp
+        Wp = dpq.shape[1] // 2
+        prod = dpq.t() @ vals                       # [2 Wp, W]: dP^T h | dM^T h
         sums = dpq.sum(0)
-        gwg, gwm, dPs, dMs = prod[:W], prod[W:], sums[:W], sums[W:]
+        gwg, gwm, dPs, dMs = prod[:W], prod[Wp:Wp + W], sums[:W], sums[Wp:Wp + W]
+        if o.get("vid"):   # the one-hot vertex-id columns: column W + j = the sum of dP (dM) over the nodes with id j
+            cs = vid_colsums(dpq, o["vid"])
+            gwg = torch.cat([gwg, cs[:, :W].t()], 1)
+            gwm = torch.cat([gwm, cs[:, Wp:Wp + W].t()], 1)
         if "we" in cp:
             We, be = cp["we"], cp["be"]
             gwg = gwg + torch.outer(dPs, be)
@@ -624,17 +688,19 @@ class VariantRecurrence(torch.autograd.Function):
         # it trains (dropout 0), and an optimizer step that does not bump version counters leaves the cache key where it was
         # (the backward below reuses what this call derives)
         mod._cache("variant").invalidate()
-        h = run_hip(mod, G, x, plan, dataflow=False)
-        ctx.mod, ctx.plan, ctx.h = mod, plan, h
+        bufs = {}
+        h = run_hip(mod, G, x, plan, dataflow=False, pitch=row_pitch(mod.hidden_dim), bufs=bufs)
+        ctx.mod, ctx.plan, ctx.h, ctx.hbuf = mod, plan, h, bufs
         ctx.save_for_backward(x, *params)
         return tuple(h[d][i] for d in mod.dirs for i in range(mod.num_layers))
 
     @staticmethod
     def backward(ctx, *gouts):
-        mod, plan, h = ctx.mod, ctx.plan, ctx.h
+        mod, plan, h, hb = ctx.mod, ctx.plan, ctx.h, ctx.hbuf
         saved = list(ctx.saved_tensors)
         x, params = saved[0].detach(), [p.detach() for p in saved[1:]]
         N, H, L, E = x.shape[0], mod.hidden_dim, mod.num_layers, mod.emb_dim
+        Hp = row_pitch(H)   # row pitch of every state-like buffer below; columns H..Hp-1 are zero and no kernel writes them
         f32 = dict(dtype=torch.float32, device=x.device)
         lib = _lib.load()
         mode = _BWD_MODES[mod.agg]
@@ -652,14 +718,19 @@ class VariantRecurrence(torch.autograd.Function):
                 names += [(d, i, n) for n, _ in spec]
                 k += len(spec)
         args = _lib.VariantBwdArgs()
-        args.num_stacked, args.H, args.dir_mask = L, H, sum(1 << d for d in mod.dirs)
+        args.num_stacked, args.H, args.ld, args.dir_mask = L, H, Hp, sum(1 << d for d in mod.dirs)
         g, res, aggx = {}, {}, {}
         q = 0
         for d in mod.dirs:
             for i in range(L):
                 go = gouts[q]
                 q += 1
-                g[(d, i)] = go.detach().float().contiguous().clone() if go is not None else torch.zeros(N, H, **f32)
+                if Hp == H:
+                    g[(d, i)] = go.detach().float().contiguous().clone() if go is not None else torch.zeros(N, H, **f32)
+                else:
+                    g[(d, i)] = torch.zeros(N, Hp, **f32)
+                    if go is not None:
+                        g[(d, i)][:, :H] = go.detach()
         dxd = {d: torch.zeros(N, E, **f32) for d in mod.dirs}
         with torch.no_grad():
             for d in mod.dirs:
@@ -674,33 +745,38 @@ class VariantRecurrence(torch.autograd.Function):
                     bca = _lib.VariantBwdCell()
                     bca.in_dim = E
                     _setup_aggregator(mod, plan, bca, ao, prm[(d, 0)], cellp[(d, 0)], mode, lands, d, 0, x, x, E, ao["a"], rows, stream, x)
-                    given = torch.zeros(N, H, **f32)
+                    given = torch.zeros(N, Hp, **f32)
                     given[:, :E] = ao["a"]
                     aggx[d] = (bca, ao)
                 for i in range(L):
                     p, cp, bc = prm[(d, i)], cellp[(d, i)], args.cell[d][i]
-                    hi = h[d][i]
-                    u = x if i == 0 else h[d][i - 1]
-                    in_dim = u.shape[1]
-                    o = dict(u=u, dgi=torch.zeros(N, 3 * H, **f32), dgh=torch.zeros(N, 3 * H, **f32), da=torch.zeros(N, H, **f32))
-                    bc.in_dim, bc.recurrent = in_dim, int(recurr)
+                    hi = hb[(d, i)]                             # [N, Hp]
+                    u = x if i == 0 else hb[(d, i - 1)]
+                    in_dim = E if i == 0 else H
+                    o = dict(u=u, dgi=torch.zeros(N, 3 * Hp, **f32), dgh=torch.zeros(N, 3 * Hp, **f32), da=torch.zeros(N, Hp, **f32))
+                    bc.in_dim, bc.recurrent, bc.ld_in = in_dim, int(recurr), (0 if i == 0 else Hp)
                     if agg_x:
                         o["a"] = given
                         bc.mode, bc.lands = _lib.AGG_GIVEN, 1
                         bc.h, bc.a = hi.data_ptr(), given.data_ptr()
                     else:
-                        o["a"] = torch.zeros(N, H, **f32)
+                        o["a"] = torch.zeros(N, Hp, **f32)
                         _setup_aggregator(mod, plan, bc, o, p, cp, mode, lands, d, i, hi, u, H, o["a"], rows, stream, x)
                     a = o["a"]
-                    if recurr:
+                    if recurr and Hp == H:
                         o["gi"] = engine.gemm_nt_bias([u], [cp["w_ih"]], [cp["b_ih"]])[0]
                         o["gh"] = engine.gemm_nt_bias([a], [cp["w_hh"]], [cp["b_hh"]])[0]
+                    elif recurr:   # gate blocks at a pitch of Hp: zero rows (and bias) between them leave the padding of gi / gh zero
+                        o["gi"] = engine.gemm_nt_bias([u], [_pad_gates(cp["w_ih"], H, Hp, u.shape[1])], [_pad_gates(cp["b_ih"], H, Hp)])[0]
+                        o["gh"] = engine.gemm_nt_bias([a], [_pad_gates(cp["w_hh"], H, Hp, Hp)], [_pad_gates(cp["b_hh"], H, Hp)])[0]
+                    if recurr:
                         bc.gi, bc.gh = o["gi"].data_ptr(), o["gh"].data_ptr()
                         bc.w_hh, bc.w_ih = cp["w_hh"].data_ptr(), cp["w_ih"].data_ptr()
                     else:   # Linear cell: W = [W_in | W_agg]
                         o["w_in"] = cp["w_lin"][:, :in_dim].contiguous()
                         o["w_agg"] = cp["w_lin"][:, in_dim:].contiguous()
                         bc.w_ih, bc.w_hh = o["w_in"].data_ptr(), o["w_agg"].data_ptr()
+                    o["in_dim"] = in_dim
                     bc.g = g[(d, i)].data_ptr()
                     bc.g_in = (g[(d, i - 1)] if i > 0 else dxd[d]).data_ptr()
                     bc.da, bc.dgi, bc.dgh = o["da"].data_ptr(), o["dgi"].data_ptr(), o["dgh"].data_ptr()
@@ -735,15 +811,15 @@ class VariantRecurrence(torch.autograd.Function):
                 for d in mod.dirs:
                     for i in range(L):
                         o = res[(d, i)]
-                        jobs += [(o["dgi"], o["u"], True), (o["dgh"], o["a"], True)]
-            wg = engine.wgrad(jobs, N, H, H) if (N > 0 and jobs) else None
+                        jobs += [(o["dgi"], o["u"][:, :o["in_dim"]], True), (o["dgh"], o["a"][:, :H], True)]
+            wg = engine.wgrad(jobs, N, Hp, H) if (N > 0 and jobs) else None
             kq = 0
             for d in mod.dirs:
                 for i in range(L):
                     o, cp = res[(d, i)], cellp[(d, i)]
                     if not recurr:   # Linear cell: dW = g^T [u ; a], db = sum g (g holds the total gradient of every row now)
-                        gt = g[(d, i)]
-                        grads[(d, i, "w_lin")] = torch.cat([gt.t() @ o["u"], gt.t() @ o["a"]], 1)
+                        gt = g[(d, i)][:, :H]
+                        grads[(d, i, "w_lin")] = torch.cat([gt.t() @ o["u"][:, :o["in_dim"]], gt.t() @ o["a"][:, :H]], 1)
                         grads[(d, i, "b_lin")] = gt.sum(0)
                     else:
                         if wg is not None:
@@ -761,7 +837,7 @@ class VariantRecurrence(torch.autograd.Function):
                                 if n not in ("w_ih", "w_hh", "b_ih", "b_hh", "w_lin", "b_lin"):
                                     grads[(d, i, n)] = ag.get(n, torch.zeros_like(cp[n]))
                     else:
-                        for n, v in _aggregator_grads(mod, mode, o, cp, h[d][i], o["u"], R, H, i, dxd[d]).items():
+                        for n, v in _aggregator_grads(mod, mode, o, cp, h[d][i], o["u"][:, :o["in_dim"]], R, H, i, dxd[d]).items():
                             grads[(d, i, n)] = v
             dx = None
             if ctx.needs_input_grad[3]:

@@ -790,7 +790,11 @@ int dagnn_variant_run(const dagnn_plan* plan /* host */, const dagnn_variant_arg
 
 /* Reverse sweep of the variants `gated_sum`, `mattn_h`, `add`, `max` with GRU or Linear cells (csrc/variants_bwd.hip): what
  * `loss.backward()` does to dagnn.py:144-182 with GatedSumConv (:254-276), MultAttnConv (:379-409) or AggConv add / max (:232-251).
- * Every buffer is indexed by node id and contiguous ([N, width]); weights are in their torch layouts.  The caller
+ * Every buffer is indexed by node id; weights are in their torch layouts.  Width and row pitch are separate for gated_sum,
+ * add and max: with ld = args->ld (0: H; mattn and additive attention need ld == H) the state-like buffers h, a, g, da are
+ * [N, ld], gi / gh / dgi / dgh are [N, 3 ld] with gate block q at column q * ld, gated node0 / dnode0 are [N, 2 ld] with the
+ * mapper's half at column ld; esum keeps the widths below.  Only columns < H of a block are read or written, so padding the
+ * caller zeroed stays zero (a pitch that is a multiple of 4 keeps dagnn_gemm_nt_bias / dagnn_wgrad_run on aligned rows).  The caller
  * provides the forward quantities (states h, aggregates a, pre-activations gi / gh, the per-node projections the forward
  * pass of dagnn_variant_run computed: node0 = [P | M] for gated_sum, Kr for mattn; node1 = Ql for mattn; mattn also the
  * attention weights alpha by original edge id - dagnn_variant_mattn_prepare computes a and alpha), `g` = the gradient
@@ -808,17 +812,22 @@ typedef struct dagnn_variant_bwd_cell {
     const float* h;  const float* a;  const float* gi;  const float* gh;
     const float* node0;  const float* node1;  const float* alpha;
     const float* edge_mat0;  const float* edge_vec0;  const float* edge_mat1;  const float* edge_vec1;
-    const float* w_node;     /* gated: [W_g ; W_m] [2H, H]; mattn: W_r [proj_dim, H] */
+    const float* w_node;     /* gated: [W_g ; W_m] [2H, H] - or, with w_node2, W_g alone; mattn: W_r [proj_dim, H] */
     const float* w_query;    /* mattn: W_l [proj_dim, in_dim] */
     const float* w_hh;       /* [3H, H] */
     const float* w_ih;       /* [3H, in_dim] */
     float* g;  float* g_in;  float* da;  float* dgi;  float* dgh;
     float* dnode0;  float* dnode1;  float* dlogit;  float* esum;
+    const float* w_node2;    /* gated: W_m [H, .] when gate and mapper are read in place as two matrices; NULL: stacked at w_node */
+    int32_t w_ld;            /* gated: row stride of w_node / w_node2, of which the first H columns are read (D-VAE NA: H +
+                              * num_nodes - the rest are the one-hot vertex-id columns); 0: H */
+    int32_t ld_in;           /* row pitch of g_in; 0: in_dim */
 } dagnn_variant_bwd_cell;
 
 typedef struct dagnn_variant_bwd_args {
     dagnn_variant_bwd_cell cell[DAGNN_MAX_DIRS][DAGNN_MAX_STACKED];
     int num_stacked, dir_mask, H;
+    int ld;                  /* row pitch of the state-like buffers, >= H; 0: H */
 } dagnn_variant_bwd_args;
 
 /* (also the additive-attention aggregators: mode DAGNN_AGG_ATTN) */
@@ -832,6 +841,11 @@ int dagnn_variant_backward_run(const dagnn_plan* plan /* host */, const dagnn_va
  * cells, g = g_in = the gradient of x (accumulated into). */
 int dagnn_variant_aggregator_backward(const dagnn_plan* plan /* host */, const dagnn_variant_bwd_cell* cell /* host */, int dir,
                                       int width, int32_t row_begin, int32_t row_end, void* stream);
+
+/* D-VAE NA gated_sum (dvae/dagnn.py:124-137): gate and mapper read [state ; one-hot(v mod n)], so the gradient of their one-hot
+ * column j is the sum of dP | dM over the nodes with v mod n == j:  out[j, 0:J] = sum_{v mod n == j} in[v, 0:J] for in [N, ld_in],
+ * out [n, ld_out].  One thread per output element adds its rows in ascending order: no atomics, bitwise repeatable. */
+int dagnn_vid_colsums(const float* in, int64_t ld_in, int64_t N, int J, int n, float* out, int64_t ld_out, void* stream);
 
 /* D-VAE read-out (dvae/dagnn.py:147-161, dvae/dagnn_bn.py:138-152): every graph has exactly
  * `stride` nodes; gather row g*stride + node_off of h [N,ld_h] into out[g, col_off : col_off+width]. */
