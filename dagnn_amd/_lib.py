@@ -250,6 +250,7 @@ class DvaeSelectArgs(C.Structure):
                 ("work_bytes", C.c_size_t)]
 
 
+LP_INT64, LP_FLOAT32, LP_FLOAT64 = 0, 1, 2         # DAGNN_LP_INT64 / DAGNN_LP_FLOAT32 / DAGNN_LP_FLOAT64
 DVAE_SET_GRAPHS, DVAE_SET_KEYS = 0, 1             # DAGNN_DVAE_SET_GRAPHS / DAGNN_DVAE_SET_KEYS
 DVAE_SET_MAX_ROWS = 1 << 20                      # DAGNN_DVAE_SET_MAX_ROWS
 DVAE_SET_HEADER_WORDS, DVAE_SET_COUNT, DVAE_SET_ERR = 16, 4, 5   # header words of a set's storage
@@ -405,6 +406,12 @@ SYMBOLS = {
     "dagnn_rows_argmax": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "dagnn_seq_f1_counts": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                       C.c_void_p]),
+    "dagnn_graph_depth": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
+    "dagnn_class_ce": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p,
+                                 C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dagnn_class_hits_bytes": (C.c_size_t, [C.c_int64, C.c_int]),
+    "dagnn_class_hits": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t,
+                                   C.c_void_p, C.c_void_p, C.c_void_p]),
     "dagnn_opt_chunks": (C.c_int64, [C.c_void_p, C.c_int]),
     "dagnn_grad_norm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "dagnn_clip_adam": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int64, C.c_float,

@@ -18,23 +18,28 @@ from .core import run_stack_lockstep
 
 class EncodeAST(torch.autograd.Function):
     """`ASTNodeEncoder.forward` (ogbg-code/utils.py:26-28) on the HIP kernel; backward = the three
-    embedding-table gradients (row sums of the incoming gradient by index)."""
+    embedding-table gradients (row sums of the incoming gradient by index).  `depth_w` None: `ASTNodeEncoder2`
+    (ogbg-code/utils2.py:26-28), two tables and two gradients."""
 
     @staticmethod
     def forward(ctx, x, depth, type_w, attr_w, depth_w, max_depth):
         out = engine.encode_ast(x, depth, type_w, attr_w, depth_w, max_depth)  # clamps `depth` in place
-        ctx.save_for_backward(x, depth.clone())
-        ctx.rows = (type_w.shape[0], attr_w.shape[0], depth_w.shape[0])
+        if depth_w is None:
+            ctx.save_for_backward(x)
+            ctx.rows = (type_w.shape[0], attr_w.shape[0])
+        else:
+            ctx.save_for_backward(x, depth.clone())
+            ctx.rows = (type_w.shape[0], attr_w.shape[0], depth_w.shape[0])
         return out
 
     @staticmethod
     def backward(ctx, g):
-        x, depth = ctx.saved_tensors
+        x = ctx.saved_tensors[0]
         g = g.contiguous()
         grads = []
-        for rows, idx in zip(ctx.rows, (x[:, 0], x[:, 1], depth)):
+        for rows, idx in zip(ctx.rows, (x[:, 0], x[:, 1]) + tuple(ctx.saved_tensors[1:])):
             grads.append(torch.zeros(rows, g.shape[1], dtype=g.dtype, device=g.device).index_add_(0, idx, g))
-        return (None, None, grads[0], grads[1], grads[2], None)
+        return (None, None, grads[0], grads[1], grads[2] if len(grads) > 2 else None, None)
 
 
 def _wgrad(dg: torch.Tensor, u: torch.Tensor, splits: int = 32) -> torch.Tensor:

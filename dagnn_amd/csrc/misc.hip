@@ -7,6 +7,8 @@ namespace {
 
 // out[v,:] = type_emb[x[v,0]] + attr_emb[x[v,1]] + depth_emb[min(depth[v], max_depth)]
 // (ogbg-code/utils.py:26-28).  depth is clamped in place like the reference does (:27).
+// DEPTH = false: the two-table encoder of the LP task (ogbg-code/utils2.py:26-28: type + attr, depth still clamped).
+template <bool DEPTH>
 __global__ void __launch_bounds__(256) encode_ast_kernel(const int64_t* __restrict__ x, int64_t* depth,
                                                           const float* __restrict__ type_emb,
                                                           const float* __restrict__ attr_emb,
@@ -22,13 +24,21 @@ __global__ void __launch_bounds__(256) encode_ast_kernel(const int64_t* __restri
         if (dp > max_depth) { dp = max_depth; if (lane == 0) depth[v] = dp; }
         const float4* pt = reinterpret_cast<const float4*>(type_emb + t * H);
         const float4* pa = reinterpret_cast<const float4*>(attr_emb + a * H);
-        const float4* pd = reinterpret_cast<const float4*>(depth_emb + dp * H);
         float4* po = reinterpret_cast<float4*>(out + v * ld_out);
-        for (int c = lane; c < H4; c += 64) {
-            float4 u = pt[c], w = pa[c], z = pd[c], r;
-            // same association as the reference: (type + attr) + depth
-            r.x = (u.x + w.x) + z.x; r.y = (u.y + w.y) + z.y; r.z = (u.z + w.z) + z.z; r.w = (u.w + w.w) + z.w;
-            po[c] = r;
+        if (DEPTH) {
+            const float4* pd = reinterpret_cast<const float4*>(depth_emb + dp * H);
+            for (int c = lane; c < H4; c += 64) {
+                float4 u = pt[c], w = pa[c], z = pd[c], r;
+                // same association as the reference: (type + attr) + depth
+                r.x = (u.x + w.x) + z.x; r.y = (u.y + w.y) + z.y; r.z = (u.z + w.z) + z.z; r.w = (u.w + w.w) + z.w;
+                po[c] = r;
+            }
+        } else {
+            for (int c = lane; c < H4; c += 64) {
+                float4 u = pt[c], w = pa[c], r;
+                r.x = u.x + w.x; r.y = u.y + w.y; r.z = u.z + w.z; r.w = u.w + w.w;
+                po[c] = r;
+            }
         }
     }
 }
@@ -296,11 +306,15 @@ extern "C" int dagnn_encode_ast(const int64_t* x, int64_t* depth, const float* t
                                 void* stream) {
     if (N < 0 || H <= 0 || (H & 3) || (ld_out & 3) || ld_out < H) return DAGNN_EINVAL;
     if (N == 0) return DAGNN_OK;
-    if (!x || !depth || !type_emb || !attr_emb || !depth_emb || !out) return DAGNN_EINVAL;
+    if (!x || !depth || !type_emb || !attr_emb || !out) return DAGNN_EINVAL;   // (depth_emb == NULL: two tables)
     int64_t blocks = (N + 3) / 4;  // 4 waves per block, one row per wave
     if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(encode_ast_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, depth,
-                       type_emb, attr_emb, depth_emb, max_depth, out, ld_out, N, H);
+    if (depth_emb)
+        hipLaunchKernelGGL(encode_ast_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, depth,
+                           type_emb, attr_emb, depth_emb, max_depth, out, ld_out, N, H);
+    else
+        hipLaunchKernelGGL(encode_ast_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, depth,
+                           type_emb, attr_emb, depth_emb, max_depth, out, ld_out, N, H);
     DAGNN_CHECK_LAUNCH();
     return DAGNN_OK;
 }

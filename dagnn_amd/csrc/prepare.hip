@@ -47,7 +47,7 @@ struct RowsShare { int64_t v0, v1; int first; };
 
 // Workgroup rb of nrb, nodes [v0, v1): the index stack as one flat coalesced copy, then one wave per node: indices read
 // once, out_k[v,:] = (type_k[x0] + attr_k[x1]) + depth_k[min(depth, max_depth)] for every table set k (the association of
-// utils.py:28; misc.hip's encode_ast_kernel is the single-table form).
+// utils.py:28; misc.hip's encode_ast_kernel is the single-table form; a set without a depth table is type_k + attr_k).
 __device__ __forceinline__ void rows_body(const PrepRows& J, const int64_t rb, const int64_t nrb, const int64_t v0, const int64_t v1,
                                           const bool with_stack) {
     const int64_t N = J.N;
@@ -66,15 +66,22 @@ __device__ __forceinline__ void rows_body(const PrepRows& J, const int64_t rb, c
             const int W = J.width[k], W4 = W >> 2;
             const float4* pt = reinterpret_cast<const float4*>(J.type_emb[k] + t * W);
             const float4* pa = reinterpret_cast<const float4*>(J.attr_emb[k] + a * W);
-            const float4* pd = reinterpret_cast<const float4*>(J.depth_emb[k] + dp * W);
             float4* po = reinterpret_cast<float4*>(J.out[k] + v * J.ld_out[k]);
+            typedef float prep_v4f __attribute__((ext_vector_type(4)));
+            if (!J.depth_emb[k]) {   // (the two-table encoder of the LP task, utils2.py:28: type + attr; uniform per launch)
+                for (int c = lane; c < W4; c += 64) {
+                    const float4 u = pt[c], w = pa[c];
+                    __builtin_nontemporal_store(prep_v4f{u.x + w.x, u.y + w.y, u.z + w.z, u.w + w.w}, reinterpret_cast<prep_v4f*>(po + c));
+                }
+                continue;
+            }
+            const float4* pd = reinterpret_cast<const float4*>(J.depth_emb[k] + dp * W);
             for (int c = lane; c < W4; c += 64) {
                 const float4 u = pt[c], w = pa[c], z = pd[c];
                 float4 r;
                 r.x = (u.x + w.x) + z.x; r.y = (u.y + w.y) + z.y; r.z = (u.z + w.z) + z.z; r.w = (u.w + w.w) + z.w;
                 // (non-temporal: the rows are read next by the recurrence, a whole launch later - they need not push the
                 // tables out of the L2 on their way to memory; measured -5 us per forward)
-                typedef float prep_v4f __attribute__((ext_vector_type(4)));
                 __builtin_nontemporal_store(prep_v4f{r.x, r.y, r.z, r.w}, reinterpret_cast<prep_v4f*>(po + c));
             }
         }
@@ -237,7 +244,7 @@ static int prep_rows_of(const dagnn_prepare_rows* rows, int64_t N, PrepRows* J) 
         J->x = rows->x; J->depth = rows->depth; J->max_depth = rows->max_depth; J->ntab = rows->num_tables;
         for (int k = 0; k < rows->num_tables; ++k) {
             const auto& t = rows->table[k];
-            if (!t.type_emb || !t.attr_emb || !t.depth_emb || !t.out || t.width <= 0 || (t.width & 3) || (t.ld_out & 3) || t.ld_out < t.width)
+            if (!t.type_emb || !t.attr_emb || !t.out || t.width <= 0 || (t.width & 3) || (t.ld_out & 3) || t.ld_out < t.width)
                 return DAGNN_EINVAL;
             J->type_emb[k] = t.type_emb; J->attr_emb[k] = t.attr_emb; J->depth_emb[k] = t.depth_emb; J->out[k] = t.out;
             J->width[k] = t.width; J->ld_out[k] = t.ld_out;

@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import List, Optional, Sequence
+from typing import List, Optional, Sequence, Tuple
 
 import torch
 
@@ -282,7 +282,7 @@ class PlanHandle(object):
     def launch_prepare(self, groups: int = 0, enc=None, stack=None) -> None:
         """The fused pipeline (`dagnn_prepare`, csrc/prepare.hip): this plan, its dataflow schedule for `groups` groups
         (0: none) and the row work that rides along - `enc` = (x [N,2], depth [N], max_depth, [(type, attr, depth tables, out),
-        ...]): encoder rows of up to three table sets; `stack` = (four [N] int64 tensors, out [4, N]): side effect 1."""
+        ...]): encoder rows of up to three table sets (depth table None: type + attr); `stack` = (four [N] int64 tensors, out [4, N]): side effect 1."""
         lib = _lib.load()
         edge_index, layer_fwd, layer_bwd, batch, edge_attr = self._keep
         rows = _lib.PrepareRows()
@@ -294,10 +294,11 @@ class PlanHandle(object):
                 raise DagnnHipError("node_depth must be a contiguous int64 GPU tensor (it is clamped in place)")
             rows.x, rows.depth, rows.max_depth, rows.num_tables = x.data_ptr(), depth.data_ptr(), int(max_depth), len(tables)
             for k, (tw, aw, dw, out) in enumerate(tables):
-                tw, aw, dw = _dev(tw, "type table", torch.float32), _dev(aw, "attribute table", torch.float32), _dev(dw, "depth table", torch.float32)
+                tw, aw = _dev(tw, "type table", torch.float32), _dev(aw, "attribute table", torch.float32)
+                dw = None if dw is None else _dev(dw, "depth table", torch.float32)   # (None: the two-table encoder, utils2.py:28)
                 keep += [tw, aw, dw]
                 t = rows.table[k]
-                t.type_emb, t.attr_emb, t.depth_emb, t.out = tw.data_ptr(), aw.data_ptr(), dw.data_ptr(), out.data_ptr()
+                t.type_emb, t.attr_emb, t.depth_emb, t.out = tw.data_ptr(), aw.data_ptr(), _ptr(dw), out.data_ptr()
                 t.width, t.ld_out = tw.shape[1], out.stride(0)
             keep.append(x)
         if stack is not None:
@@ -444,8 +445,9 @@ def build_plan(edge_index: torch.Tensor, layer_fwd: torch.Tensor, layer_bwd: tor
 
 
 def encode_ast(x: torch.Tensor, depth: torch.Tensor, type_w: torch.Tensor, attr_w: torch.Tensor,
-               depth_w: torch.Tensor, max_depth: int) -> torch.Tensor:
-    """out = type_emb[x0] + attr_emb[x1] + depth_emb[min(depth, max_depth)]; clamps `depth` in place."""
+               depth_w: Optional[torch.Tensor], max_depth: int) -> torch.Tensor:
+    """out = type_emb[x0] + attr_emb[x1] + depth_emb[min(depth, max_depth)]; clamps `depth` in place.  `depth_w` None: the
+    two-table encoder (ogbg-code/utils2.py:26-28), out = type_emb[x0] + attr_emb[x1]."""
     x = _dev(x, "x", torch.int64)
     if not (depth.is_cuda and depth.dtype == torch.int64 and depth.is_contiguous()):
         raise DagnnHipError("node_depth must be a contiguous int64 GPU tensor (it is clamped in place)")
@@ -453,7 +455,7 @@ def encode_ast(x: torch.Tensor, depth: torch.Tensor, type_w: torch.Tensor, attr_
     out = torch.empty(N, H, dtype=torch.float32, device=x.device)
     check(_lib.load().dagnn_encode_ast(x.data_ptr(), depth.data_ptr(), _dev(type_w, "type table").data_ptr(),
                                        _dev(attr_w, "attribute table").data_ptr(),
-                                       _dev(depth_w, "depth table").data_ptr(), int(max_depth), out.data_ptr(), H,
+                                       None if depth_w is None else _dev(depth_w, "depth table").data_ptr(), int(max_depth), out.data_ptr(), H,
                                        N, H, _stream(x)), "dagnn_encode_ast")
     return out
 
@@ -1980,4 +1982,87 @@ def seq_f1_counts(tok: torch.Tensor, eos_id: int, ref_ids: torch.Tensor, ref_ext
         raise DagnnHipError("seq_f1_counts: `out` must be a contiguous int32 [B, 4] tensor on tok's device")
     check(_lib.load().dagnn_seq_f1_counts(tok.data_ptr(), B, S, int(eos_id), ref_ids.data_ptr(), ref_ids.shape[1],
                                           ref_extra.data_ptr(), out.data_ptr(), _stream(tok)), "dagnn_seq_f1_counts")
+    return out
+
+
+# ----------------------------------------------------------------------------- the LP task's tail (csrc/lp.hip)
+_LP_KINDS = {torch.int64: _lib.LP_INT64, torch.float32: _lib.LP_FLOAT32, torch.float64: _lib.LP_FLOAT64}
+_LP_WORDS = {}
+
+
+def lp_target(targ: torch.Tensor, B: int, device) -> Tuple[torch.Tensor, int]:
+    """(`targ` as a contiguous [B] tensor on `device`, its DAGNN_LP_* kind): int64 / float32 / float64 as they are, any other
+    dtype as int64 (integers) or float32 (floats)."""
+    if targ.numel() != B:
+        raise DagnnHipError("LP targets: %d values for %d graphs" % (targ.numel(), B))
+    if targ.dtype not in _LP_KINDS:
+        targ = targ.to(torch.float32 if targ.is_floating_point() else torch.int64)
+    if targ.device != device:
+        targ = targ.to(device, non_blocking=True)
+    return targ.reshape(B).contiguous(), _LP_KINDS[targ.dtype]
+
+
+def _lp_counter(t: torch.Tensor) -> torch.Tensor:
+    """The zeroed device word the last-workgroup-in kernels of csrc/lp.hip count on (they leave it zero), one per stream."""
+    key = (t.device.index, _stream(t))
+    cnt = _LP_WORDS.get(key)
+    if cnt is None:
+        cnt = _LP_WORDS[key] = torch.zeros(1, dtype=torch.int32, device=t.device)
+    return cnt
+
+
+def graph_depth(layer: torch.Tensor, batch: torch.Tensor, num_graphs: int) -> torch.Tensor:
+    """`dagnn_graph_depth`: [num_graphs] int64, the largest `layer` value among each graph's nodes (`batch` sorted; 0 for a
+    graph without nodes).  One launch, nothing synchronises."""
+    layer, batch = _dev(layer, "layer ids", torch.int64), _dev(batch, "batch", torch.int64)
+    if layer.numel() != batch.numel() or layer.device != batch.device:
+        raise DagnnHipError("graph_depth: layer ids and batch must have one entry per node on one device")
+    out = torch.empty(int(num_graphs), dtype=torch.int64, device=layer.device)
+    check(_lib.load().dagnn_graph_depth(layer.data_ptr(), batch.data_ptr(), layer.numel(), int(num_graphs), out.data_ptr(),
+                                        _stream(layer)), "dagnn_graph_depth")
+    return out
+
+
+def class_ce(pred: torch.Tensor, targ: torch.Tensor, need_grad: bool):
+    """`dagnn_class_ce`: (loss [1], d loss / d logits [B, C] in rows pitched to a multiple of 4 floats, or None) for fp32 GPU
+    logits `pred` [B, C] with unit column stride.  One launch, nothing synchronises."""
+    B, C = pred.shape
+    dev = pred.device
+    targ, kind = lp_target(targ, B, dev)
+    dl = torch.empty(B, (C + 3) // 4 * 4, dtype=torch.float32, device=dev)[:, :C] if need_grad else None
+    row = torch.empty(B, dtype=torch.float32, device=dev)
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    check(_lib.load().dagnn_class_ce(pred.data_ptr(), pred.stride(0) if B > 1 else C, targ.data_ptr(), kind, B, C, _ptr(dl),
+                                     0 if dl is None else dl.stride(0), row.data_ptr(), loss.data_ptr(),
+                                     _lp_counter(pred).data_ptr(), _stream(pred)), "dagnn_class_ce")
+    return loss, dl
+
+
+def class_hits(pred: torch.Tensor, targ: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`dagnn_class_hits`: [2] int64 = (hits, labelled) of one batch.  `pred`: fp32 logits [B, C] (argmax fused) or int64
+    tokens [B] / [B, 1].  One launch, nothing synchronises."""
+    if not isinstance(pred, torch.Tensor) or not pred.is_cuda:
+        _dev(pred, "predictions")   # (raises: no CPU path)
+    lib = _lib.load()
+    dev = pred.device
+    if pred.is_floating_point():
+        if pred.dim() != 2 or pred.dtype != torch.float32:
+            raise DagnnHipError("class_hits: fp32 logits [B, C] needed (got %s %s)" % (pred.dtype, tuple(pred.shape)))
+        B, C = pred.shape
+        if pred.stride(1) != 1 or (B > 1 and pred.stride(0) < C):
+            pred = pred.contiguous()
+        logits, ld, tok = pred.data_ptr(), (pred.stride(0) if B > 1 else C), None
+    else:
+        if pred.dim() > 2 or (pred.dim() == 2 and pred.shape[1] != 1):
+            raise DagnnHipError("class_hits: tokens [B] or [B, 1] needed (got %s)" % (tuple(pred.shape),))
+        pred = _dev(pred.reshape(-1), "tokens", torch.int64)
+        B, C = pred.shape[0], 0
+        logits, ld, tok = None, 0, pred.data_ptr()
+    targ, kind = lp_target(targ, B, dev)
+    if out is None:
+        out = torch.empty(2, dtype=torch.int64, device=dev)
+    nbytes = lib.dagnn_class_hits_bytes(B, 1 if tok is None else 0)
+    work = torch.empty(max(nbytes // 8, 2), dtype=torch.int64, device=dev)
+    check(lib.dagnn_class_hits(logits, ld, tok, B, C, targ.data_ptr(), kind, work.data_ptr(), work.numel() * 8,
+                               _lp_counter(pred).data_ptr(), out.data_ptr(), _stream(pred)), "dagnn_class_hits")
     return out

@@ -1,0 +1,181 @@
+"""The longest-path (LP) task of ogbg-code2 (ogbg-code/main_pyg_lp.py) around the model, on the device.
+
+The reference predicts `len_longest_path` of every AST as one of 275 classes: one `[B, num_class]` head, `CrossEntropyLoss`
+against `targ.to(torch.long)` (main_pyg_lp.py:56-58), accuracy through `Evaluator("ogbg-ppa")` - `_eval_acc` of
+ogb/graphproppred/evaluate.py:221-229 - on the argmax and the targets of every batch, copied to the host batch by batch
+(main_pyg_lp.py:66-74, 93-107).  Here: `lp_targets` (the attribute, or the per-graph maximum of `_bi_layer_idx0` in one
+launch when the dataset is a stock one), `class_cross_entropy` (loss and d logits in one launch), `ClassAccuracy` (one
+launch per batch, one copy to the host at the end), with the model built as `DAGNN(..., encoder=ASTNodeEncoder2(...),
+num_class=275)`.  Kernels: csrc/lp.hip.
+
+    for batch in lp_batches(loader, training=True):
+        loss = class_cross_entropy(model(batch), lp_targets(batch)); loss.backward(); optimizer.step()
+    metric = evaluate_lp(model, lp_batches(valid_loader, training=False))       # {'acc', 'n'}
+"""
+from __future__ import annotations
+
+from typing import Iterable, Iterator, Optional
+
+import numpy as np
+import torch
+
+from . import engine
+from .core import num_graphs_of
+
+__all__ = ["lp_targets", "graph_depth_host", "class_cross_entropy", "class_hits_host", "ClassAccuracy", "lp_batches",
+           "evaluate_lp"]
+
+
+# ----------------------------------------------------------------------------- targets
+def graph_depth_host(layer, batch, num_graphs: Optional[int] = None) -> np.ndarray:
+    """The definition `dagnn_graph_depth` implements, in numpy: [num_graphs] int64, the largest `layer` value among the nodes
+    whose `batch` id is g; 0 for an id without nodes; ids outside [0, num_graphs) are ignored.  `num_graphs` None: the
+    largest id + 1."""
+    layer = np.asarray(layer.cpu() if isinstance(layer, torch.Tensor) else layer).reshape(-1)
+    batch = np.asarray(batch.cpu() if isinstance(batch, torch.Tensor) else batch).reshape(-1)
+    if num_graphs is None:
+        num_graphs = int(batch.max()) + 1 if batch.size else 0
+    out = np.zeros(int(num_graphs), dtype=np.int64)
+    keep = (batch >= 0) & (batch < num_graphs)
+    np.maximum.at(out, batch[keep], layer[keep].astype(np.int64))
+    return out
+
+
+def lp_targets(batch, num_graphs: Optional[int] = None) -> torch.Tensor:
+    """The LP task's targets of a batch, [B] int64 on the batch's device: `batch.len_longest_path` as the reference casts it
+    (`.to(torch.long)`, main_pyg_lp.py:56-58) when the batch carries it - the reference's patched reader stores it,
+    ogb/io/read_graph_pyg.py:51-54 - else what that reader computes, the maximum of `_bi_layer_idx0` per graph, from the
+    layer ids the batch already holds (`dagnn_graph_depth` on the GPU: one launch, no host read when `num_graphs` is given
+    or the batch knows its `num_graphs`; `graph_depth_host` for a CPU batch)."""
+    llp = getattr(batch, "len_longest_path", None)
+    if llp is not None:
+        return llp.reshape(-1).to(batch.batch.device).to(torch.long)
+    B = int(num_graphs) if num_graphs is not None else num_graphs_of(batch)
+    layer = batch._bi_layer_idx0
+    if layer.is_cuda:
+        return engine.graph_depth(layer, batch.batch, B)
+    return torch.from_numpy(graph_depth_host(layer, batch.batch, B))
+
+
+# ----------------------------------------------------------------------------- loss
+class _ClassCE(torch.autograd.Function):
+    """Mean cross-entropy of one [B, C] head, loss and gradient in one HIP launch (`dagnn_class_ce`, csrc/lp.hip); the backward
+    is one multiplication by the incoming scalar, into rows of the pitch `_HeadsLinear.backward` reads."""
+
+    @staticmethod
+    def forward(ctx, pred, targ):
+        loss, ctx.dl = engine.class_ce(pred, targ, pred.requires_grad)
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        # out of place (`backward(retain_graph=True)` may run this again on the same `ctx.dl`), into rows of the same pitch
+        dl = ctx.dl
+        out = torch.empty(dl.shape[0], dl.stride(0), dtype=dl.dtype, device=dl.device)[:, :dl.shape[1]]
+        return torch.mul(dl, g, out=out), None
+
+
+def class_cross_entropy(pred: torch.Tensor, targ: torch.Tensor) -> torch.Tensor:
+    """`torch.nn.CrossEntropyLoss()(pred, targ.to(torch.long))` - the loss of the reference's LP loop (main_pyg_lp.py:56-58), a
+    mean over the graphs.  `pred` [B, C] fp32 on the GPU with unit column stride: loss and d logits are ONE launch
+    (`dagnn_class_ce`).  `targ` [B] (or [B, 1]) may be int64 or the float tensor the reference concatenates; the kernel
+    truncates toward zero as `.to(torch.long)` does.  A target outside [0, C) - a NaN included - makes the loss NaN (the
+    contract of `dagnn_seq_ce`; there is no `ignore_index`), where torch raises.  Anything else (CPU, other dtypes, strided
+    columns) takes `F.cross_entropy`."""
+    fused = isinstance(pred, torch.Tensor) and pred.is_cuda and pred.dtype == torch.float32 and pred.dim() == 2 and \
+        pred.shape[0] > 0 and pred.shape[1] > 0 and pred.stride(1) == 1 and (pred.shape[0] == 1 or pred.stride(0) >= pred.shape[1]) \
+        and targ.numel() == pred.shape[0]
+    if not fused:
+        return torch.nn.functional.cross_entropy(pred, targ.reshape(-1).to(pred.device).to(torch.long))
+    return _ClassCE.apply(pred, targ)
+
+
+# ----------------------------------------------------------------------------- accuracy
+def _as_np(t):
+    return np.asarray(t.detach().cpu() if isinstance(t, torch.Tensor) else t)
+
+
+def class_hits_host(pred, targ) -> np.ndarray:
+    """The definition `dagnn_class_hits` implements, in numpy: [2] int64 = (hits, labelled) of one batch.  `pred`: float logits
+    [B, C] - argmax with the lowest column among equals, a NaN beating every number (`torch.argmax`) - or integer tokens [B] /
+    [B, 1]; `targ` [B] / [B, 1].  `Evaluator._eval_acc`'s own operations: labelled where the target equals itself (not NaN),
+    hit where target and prediction are equal as values."""
+    pred, targ = _as_np(pred), _as_np(targ).reshape(-1)
+    if pred.dtype.kind == "f":
+        nan = np.isnan(pred)
+        tok = np.where(nan.any(axis=1), nan.argmax(axis=1), np.where(nan, -np.inf, pred).argmax(axis=1)).astype(np.int64)
+    else:
+        tok = pred.reshape(-1).astype(np.int64)
+    is_labeled = targ == targ
+    correct = targ[is_labeled] == tok[is_labeled]
+    return np.array([int(np.sum(correct)), int(len(correct))], dtype=np.int64)
+
+
+class ClassAccuracy(object):
+    """The accuracy evaluator of the LP task (`Evaluator("ogbg-ppa")`: `_eval_acc`) as an accumulator, in the shape of `SeqF1`.
+    `update(pred_or_tok, targ)`: one launch of `dagnn_class_hits` for GPU predictions - [B, C] fp32 logits (argmax fused) or
+    the [B] / [B, 1] int64 tokens of `DAGNN.predict` - writing one (hits, labelled) int64 pair into device memory (the numpy
+    mirror `class_hits_host` for CPU predictions); nothing synchronises.  `compute()`: the one copy to the host, then
+    `float(hits) / labelled` -> {'acc', 'n'}; without a labelled graph the evaluator divides by zero: `ValueError`."""
+
+    def __init__(self):
+        self.reset()
+
+    def reset(self) -> None:
+        self._parts = []
+
+    def update(self, pred: torch.Tensor, targ: torch.Tensor) -> None:
+        B = pred.shape[0] if pred.dim() else 1
+        if targ.numel() != B:
+            raise ValueError("ClassAccuracy.update: %d targets for %d predictions" % (targ.numel(), B))
+        if B == 0:
+            return
+        if pred.is_cuda:
+            self._parts.append(engine.class_hits(pred.detach(), targ))
+        else:
+            self._parts.append(torch.from_numpy(class_hits_host(pred, targ)))
+
+    def counts(self) -> np.ndarray:
+        """(hits, labelled) of every update so far, [updates, 2] int64 on the host (one blocking copy)."""
+        if not self._parts:
+            return np.zeros((0, 2), dtype=np.int64)
+        if len({p.device for p in self._parts}) > 1:
+            return np.stack([p.cpu().numpy() for p in self._parts])
+        return torch.stack(self._parts).cpu().numpy()
+
+    def compute(self) -> dict:
+        hits, labelled = (int(v) for v in self.counts().sum(axis=0)) if self._parts else (0, 0)
+        if labelled == 0:
+            raise ValueError("ClassAccuracy.compute: no labelled graph (the evaluator's division by zero)")
+        return {"acc": float(hits) / labelled, "n": labelled}
+
+
+# ----------------------------------------------------------------------------- the loops
+def lp_batches(batches: Iterable, training: bool) -> Iterator:
+    """The reference's filters on its batches (main_pyg_lp.py:51, 84): a batch with ONE node is dropped; a training loop also
+    drops a batch with ONE graph (its `batch.batch[-1] == 0`).  The graph count is the batch's host attribute `num_graphs`
+    (`core.num_graphs_of`: a batch without it costs the device read the reference's test costs)."""
+    for b in batches:
+        if b.x.shape[0] == 1:
+            continue
+        if training and num_graphs_of(b) == 1:
+            continue
+        yield b
+
+
+def evaluate_lp(model, batches: Iterable) -> dict:
+    """The evaluation loop of main_pyg_lp.py:77-107: `predict`, `lp_targets`, `ClassAccuracy.update` per batch and one
+    `compute()` - the loop's only synchronisation besides what the passes themselves need - at the end -> {'acc', 'n'}.
+    Filtering (`lp_batches`) stays with the caller; the model's mode is restored."""
+    was_training = model.training
+    model.eval()
+    metric = ClassAccuracy()
+    try:
+        for batch in batches:
+            B = num_graphs_of(batch)
+            targ = lp_targets(batch, B)   # (before the pass: `forward` may replace `batch.batch`)
+            metric.update(model.predict(batch), targ)
+    finally:
+        if was_training:
+            model.train()
+    return metric.compute()

@@ -50,6 +50,39 @@ class ASTNodeEncoder(nn.Module):
         return self.type_encoder(x[:, 0]) + self.attribute_encoder(x[:, 1]) + self.depth_encoder(depth)
 
 
+class ASTNodeEncoder2(nn.Module):
+    """Node embedding of the LP task, `ogbg-code/utils2.py:6-28` (same parameter names): type + attribute and NO depth table
+    - the depth would leak `len_longest_path`.  `depth` is still clamped in place (utils2.py:27)."""
+
+    def __init__(self, emb_dim, num_nodetypes, num_nodeattributes, max_depth):
+        super().__init__()
+        self.max_depth = max_depth
+        self.type_encoder = nn.Embedding(num_nodetypes, emb_dim)
+        self.attribute_encoder = nn.Embedding(num_nodeattributes, emb_dim)
+
+    def forward(self, x, depth):
+        if x.is_cuda and self.type_encoder.weight.shape[1] % 4 == 0 and depth.dtype == torch.int64 \
+                and depth.is_contiguous():
+            tables = (self.type_encoder.weight, self.attribute_encoder.weight)
+            if torch.is_grad_enabled() and any(t.requires_grad for t in tables):
+                from .autograd import EncodeAST
+                return EncodeAST.apply(x, depth, *tables, None, self.max_depth)
+            return engine.encode_ast(x, depth, *tables, None, self.max_depth)
+        # generic torch path (odd widths): same math as utils2.py:27-28
+        depth[depth > self.max_depth] = self.max_depth
+        return self.type_encoder(x[:, 0]) + self.attribute_encoder(x[:, 1])
+
+
+def _ast_tables(enc):
+    """(type, attribute, depth) tables of the two encoders the row kernels know - depth None for `ASTNodeEncoder2` - or None
+    for an encoder of any other class (a user's own module, a subclass included: its `forward` may do anything)."""
+    if type(enc) is ASTNodeEncoder:
+        return enc.type_encoder.weight, enc.attribute_encoder.weight, enc.depth_encoder.weight
+    if type(enc) is ASTNodeEncoder2:
+        return enc.type_encoder.weight, enc.attribute_encoder.weight, None
+    return None
+
+
 class _EdgeAttnParams(nn.Module):
     """Parameter holder with the names of the reference's `AttnConv` (`dagnn.py:347-359`)."""
 
@@ -285,26 +318,27 @@ class DAGNN(HipModule):
         `W_ih x_v + b_ih = (T W_ih^T)[type_v] + (A W_ih^T)[attr_v] + (D W_ih^T + b_ih)[depth_v]`: the three products depend on
         the PARAMETERS only and are made once per weight version (kept on the derived cell, like the packed matrices); per batch the
         [N, emb] x [emb, 3H] GEMM of every direction becomes the encoder's own row kernel on the folded tables.  Per
-        direction (type, attribute, depth) tables of width 3Hp, or None where it does not apply (other encoders, odd widths;
-        training passes never ask)."""
-        if not engine.FOLD_INPUT or type(self.encoder) is not ASTNodeEncoder or self.schedule != "lockstep" or self.agg_x:
+        direction (type, attribute, depth) tables of width 3Hp - depth None for `ASTNodeEncoder2`, whose two products are
+        `T W_ih^T` and `A W_ih^T + b_ih` -, or None where it does not apply (other encoders, odd widths; training passes never ask)."""
+        tabs = _ast_tables(self.encoder)
+        if not engine.FOLD_INPUT or tabs is None or self.schedule != "lockstep" or self.agg_x:
             return None
         if self.training:
             # a no-grad pass on a module left in train() mode (validation without eval(), MC dropout): the derived cells are
             # rebuilt on every pass there, and re-folding three tables per direction each time costs what the fold saves
             return None
-        enc = self.encoder
-        tabs = [enc.type_encoder.weight, enc.attribute_encoder.weight, enc.depth_encoder.weight]
         if tabs[0].shape[1] % 4 or not tabs[0].is_cuda:
             return None
-        key = tuple((p.data_ptr(), p._version) for p in tabs)
+        # (every node takes exactly one row of the LAST table - depth, or attribute for `ASTNodeEncoder2`: the bias rides on it)
+        last = 2 if tabs[2] is not None else 1
+        key = tuple((p.data_ptr(), p._version) for p in tabs[:last + 1])
         out = []
         with torch.no_grad():
             for d in self.dirs:
                 c = cells[(d, 0)]   # (the folded tables live and die with the derived cell: same invalidation rules, same width)
                 if c.fold is None or c.fold[0] != key:
-                    t, a, dp = (engine.gemm_nt_bias([tab.detach()], [c.w_ih], [b])[0]
-                                for tab, b in zip(tabs, (None, None, c.b_ih)))   # (every node takes exactly one depth row: the bias rides on it)
+                    t, a, dp = (None if tab is None else engine.gemm_nt_bias([tab.detach()], [c.w_ih], [c.b_ih if j == last else None])[0]
+                                for j, tab in enumerate(tabs))
                     c.fold = (key, (t, a, dp), built_marker(t))
                 else:
                     meet_built(c.fold[2])   # (built by a pass on another stream, perhaps still in flight)
@@ -330,12 +364,13 @@ class DAGNN(HipModule):
         """Evaluation passes: plan + dataflow schedule + encoder rows (+ folded gi0 rows) + side effect 1 as ONE pipeline of 7
         launches (`dagnn_prepare`, csrc/prepare.hip).  Returns (plan, gi0 or None) with `G.x` / `G.bi_layer_index` set, or None
         where the pipeline does not apply (the caller then takes the separate calls)."""
-        if not engine.PREPARE_FUSED or self.schedule != "lockstep" or type(self.encoder) is not ASTNodeEncoder or \
+        tabs = _ast_tables(self.encoder)
+        if not engine.PREPARE_FUSED or self.schedule != "lockstep" or tabs is None or \
                 getattr(G, "_dagnn_plan", None) is not None:
             return None
         x_idx, depth = G.x, G.node_depth.view(-1, )
         enc = self.encoder
-        if not (self._rows_ok(x_idx, depth) and enc.type_encoder.weight.shape[1] % 4 == 0 and G.edge_index.is_cuda):
+        if not (self._rows_ok(x_idx, depth) and tabs[0].shape[1] % 4 == 0 and G.edge_index.is_cuda):
             return None
         has_edge_enc = getattr(self.node_aggr_0[0], "wea", False)
         ea = G.edge_attr if has_edge_enc else None
@@ -344,8 +379,7 @@ class DAGNN(HipModule):
         wide_ok = has_edge_enc and not (self.agg_x or self.agg_attn_x)
         Hp = engine.state_width(self.hidden_dim, self.num_layers, R, wide_ok=wide_ok)
         groups = engine.dataflow_groups(dev, len(self.dirs), self.num_layers, Hp, B, training=False)
-        tables = [(enc.type_encoder.weight, enc.attribute_encoder.weight, enc.depth_encoder.weight,
-                   torch.empty(N, enc.type_encoder.weight.shape[1], dtype=torch.float32, device=dev))]
+        tables = [(*tabs, torch.empty(N, tabs[0].shape[1], dtype=torch.float32, device=dev))]
         folded = self._folded_tables(cells)
         gi0 = None
         if folded is not None:

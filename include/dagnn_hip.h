@@ -91,6 +91,8 @@ int dagnn_plan_build(const dagnn_plan* plan /* host */,
  *   out[v,:] = type_emb[x[v,0]] + attr_emb[x[v,1]] + depth_emb[min(depth[v], max_depth)]
  * and clamps depth[v] IN PLACE to max_depth, as the reference does (utils.py:27).
  *   x [N,2] int64, depth [N] int64, tables [*,H] fp32, out [N,ld_out] fp32 (ld_out >= H).
+ * depth_emb == NULL is the two-table encoder of the LP task (ogbg-code/utils2.py:26-28): out = type + attr, one fp32
+ * add; depth is clamped all the same (utils2.py:27).
  * ---------------------------------------------------------------------------------------- */
 int dagnn_encode_ast(const int64_t* x, int64_t* depth, const float* type_emb, const float* attr_emb,
                      const float* depth_emb, int max_depth, float* out, int ld_out,
@@ -115,7 +117,7 @@ typedef struct dagnn_prepare_rows {
     int max_depth;
     int num_tables;              /* 1..DAGNN_PREPARE_MAX_TABLES */
     struct {
-        const float *type_emb, *attr_emb, *depth_emb;   /* [*, width] each */
+        const float *type_emb, *attr_emb, *depth_emb;   /* [*, width] each; depth_emb NULL: type + attr rows (utils2.py:28) */
         float* out;                                     /* [N, ld_out]: (type + attr) + depth rows */
         int width, ld_out;                              /* multiples of 4 */
     } table[DAGNN_PREPARE_MAX_TABLES];
@@ -1215,6 +1217,37 @@ int dagnn_heads_argmax(const float* out, int64_t ld_out, const float* wcat, int6
 int dagnn_rows_argmax(const float* logits, int64_t ld, int64_t B, int S, int V, int64_t* tok, void* stream);
 int dagnn_seq_f1_counts(const int64_t* tok, int64_t B, int S, int64_t eos_id, const int32_t* ref_ids, int R,
                         const int32_t* ref_extra, int32_t* counts, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * The LP task's tail (csrc/lp.hip; ogbg-code/main_pyg_lp.py): predict `len_longest_path` of every graph as a class.
+ *
+ * dagnn_graph_depth: depth [B] int64 = max over the nodes of graph g of layer[v] (`_bi_layer_idx0`: the target the
+ *   reference's patched reader stores, ogb/io/read_graph_pyg.py:51-54); batch [N] int64 sorted ascending, so a graph is one
+ *   contiguous range, found by bisection; ids outside [0, B) are ignored, a graph without nodes gives 0.  One launch, a
+ *   wave per graph, no atomics.  B = 0 returns at once.
+ * Targets below are int64, float32 or float64 [B] (`targ_kind`): what the reference concatenates and hands to
+ *   `.to(torch.long)` / to the evaluator.
+ * dagnn_class_ce: `CrossEntropyLoss()(pred, targ.to(torch.long))` (main_pyg_lp.py:56-58) = dagnn_seq_ce with S = 1 - same
+ *   arguments, same sums in the same order, same counter protocol - with the target truncated toward zero in the kernel.
+ *   dlogits = (softmax - onehot) / B.  A target outside [0, C) (a NaN included) makes the loss NaN.
+ * dagnn_class_hits: out [2] int64 = (hits, labelled) of `Evaluator._eval_acc` (ogb/graphproppred/evaluate.py:221-229) over
+ *   one batch.  Predictions are EITHER logits [B, ld >= C] - argmax in the order stated above dagnn_heads_argmax: lowest
+ *   column among equals, a NaN beats every number - OR tok [B] int64 (what DAGNN.predict returns); the other pointer is
+ *   NULL.  A NaN target is unlabelled and counts in neither; target and prediction are compared as values (3.0 matches
+ *   class 3, 3.5 nothing).  `work` >= dagnn_class_hits_bytes(B, logits != NULL) bytes, 8-byte aligned: one partial pair per
+ *   workgroup, added by the last workgroup in (integers: exact in any order); counter [1] device word, zero before the first
+ *   call (the kernel leaves it zero).  One launch.
+ * No allocation, no synchronisation, no float atomics: bitwise repeatable.
+ * ---------------------------------------------------------------------------------------- */
+#define DAGNN_LP_INT64 0
+#define DAGNN_LP_FLOAT32 1
+#define DAGNN_LP_FLOAT64 2
+int dagnn_graph_depth(const int64_t* layer, const int64_t* batch, int64_t N, int64_t B, int64_t* depth, void* stream);
+int dagnn_class_ce(const float* logits, int64_t ld, const void* targ, int targ_kind, int B, int C, float* dlogits,
+                   int64_t ld_dlogits, float* row_loss, float* loss, unsigned* counter, void* stream);
+size_t dagnn_class_hits_bytes(int64_t B, int from_logits);
+int dagnn_class_hits(const float* logits, int64_t ld, const int64_t* tok, int64_t B, int C, const void* targ, int targ_kind,
+                     void* work, size_t work_bytes, unsigned* counter, int64_t* out, void* stream);
 
 /* The tail of the reference's training step - `clip_grad_norm_(model.parameters(), clip)` + `optim.Adam.step()`
  * (ogbg-code/main_pyg.py:63-65,179) - over a table of fp32 tensors (csrc/optim.hip).  dagnn_grad_norm: the 2-norm of up to
