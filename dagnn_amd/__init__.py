@@ -7,6 +7,7 @@ Drop-in modules with the reference's constructor / state_dict / forward(G) contr
     from dagnn_amd import DataParallel                 # ogbg-code/tg/data_parallel.py (list[Batch] caller)
     from dagnn_amd import evaluate, SeqF1              # ogbg-code/main_pyg.py:91-124 (predicted tokens, the F1 evaluator)
     from dagnn_amd import ASTNodeEncoder2, lp          # ogbg-code/utils2.py, ogbg-code/main_pyg_lp.py (the LP task)
+    from dagnn_amd import GraphStore                   # the loader side: the dataset on the device, a batch per launch
 
 The hot path runs in libdagnn_hip.so (hand-written HIP, C ABI in include/dagnn_hip.h); importing
 this package does not need a GPU, calling `forward` does.
@@ -23,5 +24,6 @@ from .evaluate import SeqF1  # noqa: F401
 from . import lp  # noqa: F401
 from .lp import ClassAccuracy, class_cross_entropy, evaluate_lp, lp_batches, lp_targets  # noqa: F401
 from .data_parallel import DataParallel  # noqa: F401
+from .store import GraphStore  # noqa: F401
 
 __version__ = "0.1.0"

@@ -306,8 +306,18 @@ class PrepareRows(C.Structure):
                 ("table", PrepTable * PREPARE_MAX_TABLES), ("stack_src", C.c_void_p * 4), ("stack_out", C.c_void_p)]
 
 
+class StoreGatherArgs(C.Structure):   # dagnn_store_gather_args: every field 8 bytes, in the header's order
+    _fields_ = [(k, C.c_void_p) for k in ("node_ptr", "edge_ptr", "tok_ptr", "x", "depth", "layer_f", "layer_b", "src", "dst",
+                                          "tok", "depth_max", "y_arr", "ref_ids", "ref_extra", "idx", "offsets")] + \
+        [(k, C.c_int64) for k in ("ld_offsets", "B", "N", "E", "S", "R")] + \
+        [(k, C.c_void_p) for k in ("out_x", "out_depth", "out_edge_index", "out_edge_attr", "out_batch", "out_ptr",
+                                   "out_index0", "out_index1", "out_layer_f", "out_layer_b", "out_llp", "out_y_arr",
+                                   "out_ref_ids", "out_ref_extra")]
+
+
 SYMBOLS = {
     "dagnn_version": (C.c_char_p, []),
+    "dagnn_store_gather": (C.c_int, [C.POINTER(StoreGatherArgs), C.c_void_p]),
     "dagnn_plan_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int64, C.c_int]),
     "dagnn_plan_is_small": (C.c_int, [C.c_int64, C.c_int64, C.c_int64]),
     "dagnn_plan_layout": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.c_int, C.POINTER(C.c_int64)]),

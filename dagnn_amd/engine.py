@@ -2066,3 +2066,54 @@ def class_hits(pred: torch.Tensor, targ: torch.Tensor, out: Optional[torch.Tenso
     check(lib.dagnn_class_hits(logits, ld, tok, B, C, targ.data_ptr(), kind, work.data_ptr(), work.numel() * 8,
                                _lp_counter(pred).data_ptr(), out.data_ptr(), _stream(pred)), "dagnn_class_hits")
     return out
+
+
+# ----------------------------------------------------------------------------- the graph store's batch (csrc/store.hip)
+_STORE_SOURCES = ("node_ptr", "edge_ptr", "tok_ptr", "x", "depth", "layer_f", "layer_b", "src", "dst", "tok", "depth_max",
+                  "y_arr", "ref_ids", "ref_extra")
+
+
+def store_gather(packed: dict, table: torch.Tensor, B: int, N: int, E: int, layers: bool = True, llp: bool = True,
+                 labels: bool = True, refs: bool = True) -> dict:
+    """`dagnn_store_gather`: one batch of a packed graph store, every tensor freshly allocated, in ONE launch; nothing
+    synchronises.  `packed`: the store's device arrays under the names of `dagnn_store_gather_args` (an absent or None
+    optional array is NULL); `table`: device int64 [4, B + 1] - row 0 the graph ids (B used), rows 1-3 the node / AST-edge /
+    next-token-edge offsets of the batch - the caller has checked the ids.  `layers`, `llp`, `labels`, `refs` switch the
+    optional outputs (given only where the store has their source).  Returns the batch's attributes by name."""
+    table = _dev(table, "store batch table", torch.int64)
+    B, N, E = int(B), int(N), int(E)
+    if table.dim() != 2 or table.shape[0] != 4 or table.shape[1] < B + 1 or B <= 0:
+        raise DagnnHipError("store_gather: table int64 [4, >= B + 1] and B > 0 needed (got %s, B = %d)" % (tuple(table.shape), B))
+    dev = table.device
+    a = _lib.StoreGatherArgs()
+    for k in _STORE_SOURCES:
+        t = packed.get(k)
+        if t is not None and (not t.is_cuda or t.device != dev or not t.is_contiguous()):
+            raise DagnnHipError("store_gather: packed array %s must be contiguous on %s" % (k, dev))
+        setattr(a, k, _ptr(t))
+    y_arr, ref_ids = packed.get("y_arr"), packed.get("ref_ids")
+    S = y_arr.shape[1] if (labels and y_arr is not None) else 0
+    R = ref_ids.shape[1] if (refs and ref_ids is not None) else 0
+    a.idx, a.offsets, a.ld_offsets = table.data_ptr(), table.data_ptr() + 8 * table.stride(0), table.stride(0)
+    a.B, a.N, a.E, a.S, a.R = B, N, E, S, R
+    i64 = dict(dtype=torch.int64, device=dev)
+    out = {"x": torch.empty(N, 2, **i64), "node_depth": torch.empty(N, 1, **i64), "edge_index": torch.empty(2, E, **i64),
+           "edge_attr": torch.empty(E, 2, dtype=torch.float32, device=dev), "batch": torch.empty(N, **i64),
+           "ptr": torch.empty(B + 1, **i64), "_bi_layer_index0": torch.empty(N, **i64), "_bi_layer_index1": torch.empty(N, **i64)}
+    if layers and packed.get("layer_f") is not None:
+        out["_bi_layer_idx0"], out["_bi_layer_idx1"] = torch.empty(N, **i64), torch.empty(N, **i64)
+    if llp and packed.get("depth_max") is not None:
+        out["len_longest_path"] = torch.empty(B, dtype=torch.float32, device=dev)
+    if S:
+        out["y_arr"] = torch.empty(B, S, **i64)
+    if R:
+        out["ref_ids"] = torch.empty(B, R, dtype=torch.int32, device=dev)
+        out["ref_extra"] = torch.empty(B, dtype=torch.int32, device=dev)
+    for field, key in (("out_x", "x"), ("out_depth", "node_depth"), ("out_edge_index", "edge_index"), ("out_edge_attr", "edge_attr"),
+                       ("out_batch", "batch"), ("out_ptr", "ptr"), ("out_index0", "_bi_layer_index0"),
+                       ("out_index1", "_bi_layer_index1"), ("out_layer_f", "_bi_layer_idx0"), ("out_layer_b", "_bi_layer_idx1"),
+                       ("out_llp", "len_longest_path"), ("out_y_arr", "y_arr"), ("out_ref_ids", "ref_ids"),
+                       ("out_ref_extra", "ref_extra")):
+        setattr(a, field, _ptr(out.get(key)))
+    check(_lib.load().dagnn_store_gather(C.byref(a), _stream(table)), "dagnn_store_gather")
+    return out

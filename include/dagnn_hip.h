@@ -1249,6 +1249,74 @@ size_t dagnn_class_hits_bytes(int64_t B, int from_logits);
 int dagnn_class_hits(const float* logits, int64_t ld, const int64_t* tok, int64_t B, int C, const void* targ, int targ_kind,
                      void* work, size_t work_bytes, unsigned* counter, int64_t* out, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * The device-resident graph store (csrc/store.hip; dagnn_amd/store.py): a dataset of raw ogbg-code2 graphs packed once
+ * into int32 arrays, and any batch of it - the collation of ogbg-code/tg/dataloader.py:13-35 over graphs that went through
+ * `augment_edge2` (utils2.py:31-79) and `add_order_info_01` (src/utils_dag.py:39-52) - written by ONE launch.
+ *
+ * Packed form (G graphs; every pointer a device pointer): node_ptr / edge_ptr / tok_ptr [G+1] int64 (offsets of a graph's
+ * nodes, AST edges and attributed nodes); per node x [., 2], depth, layer_f, layer_b int32; per AST edge src, dst int32
+ * (node ids inside the graph); per attributed node tok int32 (its id inside the graph, ascending) - next-token edge k of a
+ * graph is (tok[k], tok[k+1]); per graph depth_max int32, y_arr [G, S] int32, ref_ids [G, R] int32, ref_extra [G] int32.
+ *
+ * The batch: idx [B] int64 graph ids (any order, repeats allowed; the CALLER has checked them against G) and
+ * offsets [3, ld_offsets] int64, rows (node, AST edge, next-token edge) of B+1 exclusive prefix sums over the batch's
+ * graphs: graph slot b owns nodes [node[b], node[b+1]) and edges [ast[b] + nxt[b], ast[b+1] + nxt[b+1]), its AST edges in
+ * stored order first.  N = node[B], E = ast[B] + nxt[B].
+ *
+ * Outputs, each written exactly over its extent, every word by one thread (no atomics, no hand-offs; work is divided by
+ * OUTPUT element, so a batch of one large graph uses as many threads as a batch of many small ones): out_x [N, 2] int64
+ * (one 16-byte store per row), out_depth [N] int64 (`node_depth` [N, 1]), out_edge_index [2, E] int64 (shifted by the
+ * slot's node offset), out_edge_attr [E, 2] fp32 (rows [0, 0] / [1, 0], one 8-byte store), out_batch [N] int64,
+ * out_ptr [B+1] int64, out_index0 / out_index1 [N] int64 (= 0..N-1).  Optional, NULL = not written: out_layer_f /
+ * out_layer_b [N] int64 (need layer_f / layer_b), out_llp [B] fp32 (`len_longest_path` = depth_max as a float),
+ * out_y_arr [B, S] int64, out_ref_ids [B, R] int32 with out_ref_extra [B] int32 (both or neither).
+ *
+ * Arguments are validated before any HIP call: DAGNN_EINVAL for a NULL required pointer (the edge arrays only when
+ * E > 0), a negative count, ld_offsets < B + 1, B = 0 with N > 0 or E > 0, an optional output without its source or with
+ * S / R = 0, out_x not 16-byte or x / out_edge_attr not 8-byte aligned.  B = 0 returns at once.  No allocation, no
+ * synchronisation.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct dagnn_store_gather_args {
+    const int64_t* node_ptr;
+    const int64_t* edge_ptr;
+    const int64_t* tok_ptr;
+    const int32_t* x;
+    const int32_t* depth;
+    const int32_t* layer_f;
+    const int32_t* layer_b;
+    const int32_t* src;
+    const int32_t* dst;
+    const int32_t* tok;
+    const int32_t* depth_max;
+    const int32_t* y_arr;
+    const int32_t* ref_ids;
+    const int32_t* ref_extra;
+    const int64_t* idx;
+    const int64_t* offsets;
+    int64_t ld_offsets;
+    int64_t B;
+    int64_t N;
+    int64_t E;
+    int64_t S;
+    int64_t R;
+    int64_t* out_x;
+    int64_t* out_depth;
+    int64_t* out_edge_index;
+    float* out_edge_attr;
+    int64_t* out_batch;
+    int64_t* out_ptr;
+    int64_t* out_index0;
+    int64_t* out_index1;
+    int64_t* out_layer_f;
+    int64_t* out_layer_b;
+    float* out_llp;
+    int64_t* out_y_arr;
+    int32_t* out_ref_ids;
+    int32_t* out_ref_extra;
+} dagnn_store_gather_args;
+int dagnn_store_gather(const dagnn_store_gather_args* args /* host */, void* stream);
+
 /* The tail of the reference's training step - `clip_grad_norm_(model.parameters(), clip)` + `optim.Adam.step()`
  * (ogbg-code/main_pyg.py:63-65,179) - over a table of fp32 tensors (csrc/optim.hip).  dagnn_grad_norm: the 2-norm of up to
  * DAGNN_MAX_OPT_TENSORS gradients (`partial`: scratch of dagnn_opt_chunks() floats; `accumulate` != 0 adds the tensors' sum of
