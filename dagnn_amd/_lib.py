@@ -315,9 +315,18 @@ class StoreGatherArgs(C.Structure):   # dagnn_store_gather_args: every field 8 b
                                    "out_ref_ids", "out_ref_extra")]
 
 
+class DagStoreGatherArgs(C.Structure):   # dagnn_dag_store_gather_args: every field 8 bytes, in the header's order
+    _fields_ = [(k, C.c_void_p) for k in ("types", "preds", "succs", "layer_f", "layer_b", "y", "idx", "offsets")] + \
+        [(k, C.c_int64) for k in ("B", "n", "nvt", "E")] + \
+        [(k, C.c_void_p) for k in ("out_x", "out_edge_index", "out_bi_layer_index", "out_batch", "out_ptr", "out_types",
+                                   "out_preds", "out_y")]
+
+
 SYMBOLS = {
     "dagnn_version": (C.c_char_p, []),
     "dagnn_store_gather": (C.c_int, [C.POINTER(StoreGatherArgs), C.c_void_p]),
+    "dagnn_dag_store_gather": (C.c_int, [C.POINTER(DagStoreGatherArgs), C.c_void_p]),
+    "dagnn_dag_store_layers": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "dagnn_plan_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int64, C.c_int]),
     "dagnn_plan_is_small": (C.c_int, [C.c_int64, C.c_int64, C.c_int64]),
     "dagnn_plan_layout": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.c_int, C.POINTER(C.c_int64)]),

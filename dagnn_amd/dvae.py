@@ -597,6 +597,10 @@ def _make_decode(spec, types, preds, h0, params):
     return engine.DvaeDecode(spec["n"], spec["nvt"], spec["start_type"], spec["bn"], t)
 
 
+_LOSS_NEEDS_GPU = ("loss(): the model must live on a ROCm GPU - the teacher-forced decoder is HIP "
+                   "(csrc/dvae_decode.hip) and has no CPU path")
+
+
 class _DvaeBase(HipModule):
     """Parameters of `DVAE_PYG.__init__` (`dvae/models_pyg.py:18-85`), same names and order."""
 
@@ -1032,6 +1036,12 @@ class _DvaeDagnn(_DvaeBase):
         Hg = self(b)
         return self.fc1(Hg), self.fc2(Hg)
 
+    def encode_batch(self, b):
+        """(mu, logvar) of an already collated batch - `DagStore.batch(idx)`, or `GraphBatch.from_data_list` of D-VAE graphs:
+        what `encode` does after its collation.  The pass may rewrite attributes of `b` (`batch`, `h`)."""
+        Hg = self(b)
+        return self.fc1(Hg), self.fc2(Hg)
+
 
     # ------------------------------------------------------------------ teacher-forced decoder loss (dvae/models_pyg.py:324-456)
     def reparameterize(self, mu, logvar, eps_scale=0.01):
@@ -1055,19 +1065,34 @@ class _DvaeDagnn(_DvaeBase):
         types, preds = decode_schedule(G_true, self.max_n, self.nvt, int(self.START_TYPE))
         if len(G_true) != mu.shape[0]:
             raise ValueError("loss(): %d graphs for %d latent rows" % (len(G_true), mu.shape[0]))
+        if not (mu.is_cuda and self.fc3.weight.is_cuda):
+            raise engine.DagnnHipError(_LOSS_NEEDS_GPU)
+        t_types = torch.from_numpy(types).pin_memory().to(mu.device, non_blocking=True)
+        t_preds = torch.from_numpy(preds).pin_memory().to(mu.device, non_blocking=True)
+        return self.loss_dense(mu, logvar, t_types, t_preds, beta)
+
+    def loss_dense(self, mu, logvar, types, preds, beta=0.005):
+        """`loss()` on a schedule that is on the device already: types / preds int32 [B, max_n] as `decode_schedule`
+        describes them (`DagStore.batch(idx).types` / `.preds`).  The rows are taken as they are - a DagStore checked them
+        when it packed them; `loss()` checks its graphs per call - and nothing is built on or copied from the host."""
+        self._check_decoder_agg("loss(): the teacher-forced decoder")
+        B = mu.shape[0]
+        for t, what in ((types, "types"), (preds, "preds")):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or tuple(t.shape) != (B, self.max_n):
+                raise ValueError("loss_dense(): %s must be an int32 tensor [%d, max_n=%d] (got %s)"
+                                 % (what, B, self.max_n, getattr(t, "shape", type(t))))
         z = self.reparameterize(mu, logvar)
         H0 = self.tanh(self.fc3(z))
         if not H0.is_cuda:
-            raise engine.DagnnHipError("loss(): the model must live on a ROCm GPU - the teacher-forced decoder is HIP "
-                                       "(csrc/dvae_decode.hip) and has no CPU path")
-        dev = H0.device
-        t_types = torch.from_numpy(types).pin_memory().to(dev, non_blocking=True)
-        t_preds = torch.from_numpy(preds).pin_memory().to(dev, non_blocking=True)
+            raise engine.DagnnHipError(_LOSS_NEEDS_GPU)
+        if types.device != H0.device or preds.device != H0.device:
+            raise ValueError("loss_dense(): types and preds must be on the model's device %s" % H0.device)
+        types, preds = types.contiguous(), preds.contiguous()
         spec, params = self._decode_loss_inputs()
         if torch.is_grad_enabled() and any(t.requires_grad for t in [H0] + params):
-            res = _DecodeLoss.apply(spec, t_types, t_preds, H0, *params)
+            res = _DecodeLoss.apply(spec, types, preds, H0, *params)
         else:   # (no autograd record: the saved activations die with this call)
-            res = _make_decode(spec, t_types, t_preds, H0, params).forward()[2 * H0.shape[0]].clone()
+            res = _make_decode(spec, types, preds, H0, params).forward()[2 * H0.shape[0]].clone()
         kld = -0.5 * torch.sum(1 + logvar - mu.pow(2) - logvar.exp())
         return res + beta * kld, res, kld
 
@@ -1564,16 +1589,28 @@ def _take_draws(draws, n, B, attempts, device, what):
     return draws
 
 
+def _store_pair(G):
+    """(store, ids) when `G` is the pair that stands for a list of graphs - a DagStore (dagnn_amd/dvae_store.py) and the
+    ids of its graphs - else None."""
+    if isinstance(G, tuple) and len(G) == 2 and hasattr(G[0], "batch") and hasattr(G[0], "loader") and hasattr(G[0], "arrays"):
+        return G[0], G[0]._ids(G[1])
+    return None
+
+
 def extract_latent(model, graphs, batch_size=64):
-    """`extract_latent` of dvae/train.py:314-335 without the host round trip: mu [len(graphs), nz] of a data set,
+    """`extract_latent` of dvae/train.py:314-335 without the host round trip: mu [len(graphs), nz] of a data set (a list
+    of graphs, or the pair `(store, ids)` of a DagStore and graph ids, which takes every batch from the store),
     encoded in batches of batch_size in evaluation mode, on the model's device.  The reference leaves the model in
     evaluation mode; here the mode the model came in is restored, so a later `reparameterize` is not changed by the call."""
     if int(batch_size) < 1:
         raise ValueError("extract_latent(): batch_size must be >= 1 (got %d)" % batch_size)
+    pair = _store_pair(graphs)
     was_training = model.training
     model.eval()
     try:
         with torch.no_grad():
+            if pair is not None:   # (the per-batch host work is `store.batch`: one small copy, one launch)
+                return torch.cat([model.encode_batch(b)[0] for b in pair[0].loader(pair[1], int(batch_size))])
             return torch.cat([model.encode(list(graphs[i:i + batch_size]))[0] for i in range(0, len(graphs), int(batch_size))])
     finally:
         model.train(was_training)
@@ -1581,7 +1618,7 @@ def extract_latent(model, graphs, batch_size=64):
 
 def recon_accuracy(model, G, encode_times=10, decode_times=10, stochastic=True, draws=None, batch_size=None):
     """The reconstruction accuracy `test()` of dvae/train.py:276-311 reports (its counting loop is gone there): per batch
-    of graphs `mu, logvar = model.encode(batch)`, encode_times times `z = model.reparameterize(mu, logvar)` (mu in
+    of graphs (`G`: a list, or the pair `(store, ids)` of a DagStore and graph ids) `mu, logvar = model.encode(batch)`, encode_times times `z = model.reparameterize(mu, logvar)` (mu in
     evaluation mode, a fresh sample in training mode, as the reference's), per z decode_times decodes - one
     `decode_dense(attempts=decode_times)` call - and the count of decodes that are `is_same_DAG` to their input.
     Returns (n_perfect, n_total, per_graph): per_graph [len(G)] int32 on the host, the perfect decodes of each graph out
@@ -1594,17 +1631,20 @@ def recon_accuracy(model, G, encode_times=10, decode_times=10, stochastic=True, 
     infer_batch_size: that decoder's padded soft-max couples the rows of one decode call (the padding takes weight, and its
     width is the call's largest predecessor count), so a graph's decode depends on the batch it is decoded in.
     Comparing and counting run in HIP (dagnn_dvae_same_dag); the counts reach the host with one synchronisation."""
-    E, D, N, n = int(encode_times), int(decode_times), len(G), model.max_n
+    pair = _store_pair(G)
+    E, D, N, n = int(encode_times), int(decode_times), len(G) if pair is None else int(pair[1].size), model.max_n
     if E < 1 or D < 1 or N < 1:
         raise ValueError("recon_accuracy(): encode_times, decode_times and len(G) must be >= 1 (got %d, %d, %d)" % (E, D, N))
     step = N if batch_size is None else int(batch_size)
     if step < 1:
         raise ValueError("recon_accuracy(): batch_size must be >= 1 (got %d)" % step)
-    rows = dense_rows(G, n, model.nvt)
+    rows = dense_rows(G, n, model.nvt) if pair is None else None
     dev = model.get_device()
     if dev.type != "cuda":
         raise engine.DagnnHipError("recon_accuracy(): the model must live on a ROCm GPU - the decoder is HIP and has no CPU path")
-    true = [torch.from_numpy(x).pin_memory().to(dev, non_blocking=True) for x in rows]
+    if pair is not None and (pair[0].n != n or pair[0].arrays["types"].device != dev):
+        raise ValueError("recon_accuracy(): the store must hold max_n=%d-vertex graphs on the model's device %s" % (n, dev))
+    true = [torch.from_numpy(x).pin_memory().to(dev, non_blocking=True) for x in rows] if pair is None else None
     u_type = u_edge = None
     if stochastic:
         u_type, u_edge = _take_draws(draws, n, N, E * D, dev, "recon_accuracy()")
@@ -1612,8 +1652,13 @@ def recon_accuracy(model, G, encode_times=10, decode_times=10, stochastic=True, 
     with torch.no_grad():
         for g0 in range(0, N, step):
             g1 = min(N, g0 + step)
-            mu, logvar = model.encode(list(G[g0:g1]))
-            tt, pt, nt = (t[g0:g1] for t in true)
+            if pair is None:
+                mu, logvar = model.encode(list(G[g0:g1]))
+                tt, pt, nt = (t[g0:g1] for t in true)
+            else:   # (the true rows are the batch's own schedule: n vertices each)
+                b = pair[0].batch(pair[1][g0:g1])
+                tt, pt, nt = b.types, b.preds, None
+                mu, logvar = model.encode_batch(b)
             count = None
             for e in range(E):
                 z = model.reparameterize(mu, logvar)

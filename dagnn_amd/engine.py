@@ -2117,3 +2117,55 @@ def store_gather(packed: dict, table: torch.Tensor, B: int, N: int, E: int, laye
         setattr(a, field, _ptr(out.get(key)))
     check(_lib.load().dagnn_store_gather(C.byref(a), _stream(table)), "dagnn_store_gather")
     return out
+
+
+# ----------------------------------------------------------------------------- the D-VAE store (csrc/dvae_store.hip)
+_DAG_STORE_SOURCES = ("types", "preds", "succs", "layer_f", "layer_b", "y")
+
+
+def dag_store_layers(preds: torch.Tensor, succs: torch.Tensor):
+    """`dagnn_dag_store_layers`: (layer_f, layer_b) int32 [M, n] of M dense graphs given as predecessor / successor masks
+    int32 [M, n] (n <= 32, read as unsigned words).  One launch, nothing synchronises."""
+    preds, succs = _dev(preds, "preds", torch.int32), _dev(succs, "succs", torch.int32)
+    if preds.dim() != 2 or preds.shape != succs.shape or not 1 <= preds.shape[1] <= 32 or succs.device != preds.device:
+        raise DagnnHipError("dag_store_layers: preds and succs int32 [M, n <= 32] on one device needed (got %s, %s)"
+                            % (tuple(preds.shape), tuple(succs.shape)))
+    lf, lb = torch.empty_like(preds), torch.empty_like(preds)
+    check(_lib.load().dagnn_dag_store_layers(_ptr(preds), _ptr(succs), preds.shape[0], preds.shape[1], _ptr(lf), _ptr(lb),
+                                             _stream(preds)), "dagnn_dag_store_layers")
+    return lf, lb
+
+
+def dag_store_gather(packed: dict, table: torch.Tensor, B: int, E: int, nvt: int, schedule: bool = True) -> dict:
+    """`dagnn_dag_store_gather`: one batch of a packed D-VAE store, every tensor freshly allocated, in ONE launch; nothing
+    synchronises.  `packed`: the store's device arrays under the names of `dagnn_dag_store_gather_args` (`y` may be absent);
+    `table`: device int64 [2, B + 1] - row 0 the graph ids (B used), row 1 the batch's edge offsets - the caller has checked
+    the ids.  `schedule` False leaves `types` / `preds` out.  Returns the batch's attributes by name."""
+    table = _dev(table, "store batch table", torch.int64)
+    B, E, nvt = int(B), int(E), int(nvt)
+    if table.dim() != 2 or table.shape[0] != 2 or table.shape[1] < B + 1 or B <= 0:
+        raise DagnnHipError("dag_store_gather: table int64 [2, >= B + 1] and B > 0 needed (got %s, B = %d)" % (tuple(table.shape), B))
+    dev = table.device
+    a = _lib.DagStoreGatherArgs()
+    for k in _DAG_STORE_SOURCES:
+        t = packed.get(k)
+        if t is not None and (not t.is_cuda or t.device != dev or not t.is_contiguous()):
+            raise DagnnHipError("dag_store_gather: packed array %s must be contiguous on %s" % (k, dev))
+        setattr(a, k, _ptr(t))
+    n = int(packed["types"].shape[1])
+    N = B * n
+    a.idx, a.offsets = table.data_ptr(), table.data_ptr() + 8 * table.stride(0)
+    a.B, a.n, a.nvt, a.E = B, n, nvt, E
+    i64 = dict(dtype=torch.int64, device=dev)
+    out = {"x": torch.empty(N, nvt, dtype=torch.float32, device=dev), "edge_index": torch.empty(2, E, **i64),
+           "bi_layer_index": torch.empty(2, 2, N, **i64), "batch": torch.empty(N, **i64), "ptr": torch.empty(B + 1, **i64)}
+    if schedule:
+        out["types"] = torch.empty(B, n, dtype=torch.int32, device=dev)
+        out["preds"] = torch.empty(B, n, dtype=torch.int32, device=dev)
+    if packed.get("y") is not None:
+        out["y"] = torch.empty(B, dtype=torch.float32, device=dev)
+    for field, key in (("out_x", "x"), ("out_edge_index", "edge_index"), ("out_bi_layer_index", "bi_layer_index"),
+                       ("out_batch", "batch"), ("out_ptr", "ptr"), ("out_types", "types"), ("out_preds", "preds"), ("out_y", "y")):
+        setattr(a, field, _ptr(out.get(key)))
+    check(_lib.load().dagnn_dag_store_gather(C.byref(a), _stream(table)), "dagnn_dag_store_gather")
+    return out

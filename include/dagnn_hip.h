@@ -1317,6 +1317,60 @@ typedef struct dagnn_store_gather_args {
 } dagnn_store_gather_args;
 int dagnn_store_gather(const dagnn_store_gather_args* args /* host */, void* stream);
 
+/* -------------------------------------------------------------------------------------------
+ * The device-resident store of a D-VAE data set (csrc/dvae_store.hip; host side dagnn_amd/dvae_store.py): a batch of
+ * ENAS / BN graphs - what `Batch.from_data_list` (dvae/batch.py:26-146) makes of the graphs of `decode_ENAS_to_pygraph` /
+ * `decode_BN_to_pygraph` (dvae/util.py:290-385), plus the decoder's schedule of `loss()` (models_pyg.py:405-420) - written
+ * by ONE launch.
+ *
+ * Packed form (M graphs of exactly n vertices, n <= 32, every edge u -> v with u < v; every pointer a device pointer;
+ * [M, n] int32 row-major): types; preds (bit u of word v: the edge u -> v); succs, its transpose (bit v of word u: the same
+ * edge); layer_f / layer_b (longest-path layer over the edges / the reversed edges); y [M] fp32 (optional).  Mask words are
+ * read as UNSIGNED: with 32 vertices bit 31 is an edge.
+ *
+ * The batch: idx [B] int64 graph ids (any order, repeats allowed; the CALLER has checked them against M) and offsets [B+1]
+ * int64, the exclusive prefix sums of the graphs' edge counts; E = offsets[B].  N = B * n.
+ *
+ * Outputs, each written exactly over its extent, every word by one thread (no atomics; work is divided by OUTPUT element):
+ * out_x [N, nvt] fp32 one-hot of the types; out_edge_index [2, E] int64, per graph slot source-major (source ascending,
+ * then target ascending), shifted by b * n; out_bi_layer_index [2, 2, N] int64 ([d][0] the layer of direction d, [d][1]
+ * the node id 0..N-1); out_batch [N] int64; out_ptr [B+1] int64 (= b * n).  Optional, NULL = not written: out_types /
+ * out_preds [B, n] int32 (the decoder's schedule), out_y [B] fp32 (needs y).
+ *
+ * dagnn_dag_store_layers: layer_f[v] = 1 + max(layer_f[u]) over the predecessors u < v of v (0 without one), walking v
+ * ascending; layer_b the same over succs, descending.  Bits at or above v in preds[v] (at or below u, or from n up, in
+ * succs[u]) are ignored.
+ *
+ * Arguments are validated before any HIP call: DAGNN_EINVAL for a NULL required pointer (succs / out_edge_index only when
+ * E > 0), a negative count, n outside [1, 32], nvt < 1, B = 0 with E > 0, E > B n (n - 1) / 2, out_preds without preds,
+ * out_y without y.  B = 0 / M = 0 returns at once.  No allocation, no synchronisation.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct dagnn_dag_store_gather_args {
+    const int32_t* types;
+    const int32_t* preds;
+    const int32_t* succs;
+    const int32_t* layer_f;
+    const int32_t* layer_b;
+    const float* y;
+    const int64_t* idx;
+    const int64_t* offsets;
+    int64_t B;
+    int64_t n;
+    int64_t nvt;
+    int64_t E;
+    float* out_x;
+    int64_t* out_edge_index;
+    int64_t* out_bi_layer_index;
+    int64_t* out_batch;
+    int64_t* out_ptr;
+    int32_t* out_types;
+    int32_t* out_preds;
+    float* out_y;
+} dagnn_dag_store_gather_args;
+int dagnn_dag_store_gather(const dagnn_dag_store_gather_args* args /* host */, void* stream);
+int dagnn_dag_store_layers(const int32_t* preds, const int32_t* succs, int64_t M, int n, int32_t* layer_f, int32_t* layer_b,
+                           void* stream);
+
 /* The tail of the reference's training step - `clip_grad_norm_(model.parameters(), clip)` + `optim.Adam.step()`
  * (ogbg-code/main_pyg.py:63-65,179) - over a table of fp32 tensors (csrc/optim.hip).  dagnn_grad_norm: the 2-norm of up to
  * DAGNN_MAX_OPT_TENSORS gradients (`partial`: scratch of dagnn_opt_chunks() floats; `accumulate` != 0 adds the tensors' sum of
