@@ -9,6 +9,7 @@ Drop-in modules with the reference's constructor / state_dict / forward(G) contr
     from dagnn_amd import ASTNodeEncoder2, lp          # ogbg-code/utils2.py, ogbg-code/main_pyg_lp.py (the LP task)
     from dagnn_amd import GraphStore                   # the loader side: the dataset on the device, a batch per launch
     from dagnn_amd import DagStore                     # the same for D-VAE data sets (ENAS / BN rows), dvae/train.py's loops
+    from dagnn_amd import attach_predictor             # dvae/train.py --predictor: the MLP on mu, its MSE and gradients
 
 The hot path runs in libdagnn_hip.so (hand-written HIP, C ABI in include/dagnn_hip.h); importing
 this package does not need a GPU, calling `forward` does.
@@ -27,5 +28,7 @@ from .lp import ClassAccuracy, class_cross_entropy, evaluate_lp, lp_batches, lp_
 from .data_parallel import DataParallel  # noqa: F401
 from .store import GraphStore  # noqa: F401
 from .dvae_store import DagStore  # noqa: F401
+from . import predictor  # noqa: F401
+from .predictor import attach_predictor, predict_latent, predictor_mse, predictor_report  # noqa: F401
 
 __version__ = "0.1.0"

@@ -251,6 +251,7 @@ class DvaeSelectArgs(C.Structure):
 
 
 LP_INT64, LP_FLOAT32, LP_FLOAT64 = 0, 1, 2         # DAGNN_LP_INT64 / DAGNN_LP_FLOAT32 / DAGNN_LP_FLOAT64
+PREDICTOR_MAX_NZ, PREDICTOR_MAX_HS, PREDICTOR_ROWS = 128, 1024, 8   # DAGNN_PREDICTOR_MAX_NZ / _MAX_HS / _ROWS
 DVAE_SET_GRAPHS, DVAE_SET_KEYS = 0, 1             # DAGNN_DVAE_SET_GRAPHS / DAGNN_DVAE_SET_KEYS
 DVAE_SET_MAX_ROWS = 1 << 20                      # DAGNN_DVAE_SET_MAX_ROWS
 DVAE_SET_HEADER_WORDS, DVAE_SET_COUNT, DVAE_SET_ERR = 16, 4, 5   # header words of a set's storage
@@ -431,6 +432,15 @@ SYMBOLS = {
     "dagnn_class_hits_bytes": (C.c_size_t, [C.c_int64, C.c_int]),
     "dagnn_class_hits": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t,
                                    C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dagnn_predictor_mse_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "dagnn_predictor_mse": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int,
+                                      C.c_void_p]),
+    "dagnn_predictor_forward": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dagnn_fit_sums_bytes": (C.c_size_t, [C.c_int64]),
+    "dagnn_fit_sums": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_double, C.c_double, C.c_void_p, C.c_void_p,
+                                 C.c_size_t, C.c_void_p, C.c_void_p]),
     "dagnn_opt_chunks": (C.c_int64, [C.c_void_p, C.c_int]),
     "dagnn_grad_norm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "dagnn_clip_adam": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int64, C.c_float,

@@ -18,6 +18,7 @@ store has it.  `gather_host` is the definition the kernel implements, in numpy; 
     for epoch in range(E):
         loss, recon, kld = train_epoch(model, optimizer, store, train_ids, 32, seed=epoch)
     nll = test_nll(model, store, test_ids, 64)
+    # with `predictor.attach_predictor(model)`: train_epoch(..., predictor=True) -> (loss, recon, kld, pred); test_predictor(...)
     Z = extract_latent(model, (store, train_ids), 64)
 """
 from __future__ import annotations
@@ -33,7 +34,7 @@ from . import engine
 from .data import GraphBatch
 from .dvae import GraphSet, dense_rows
 
-__all__ = ["DagStore", "gather_host", "layers_host", "train_epoch", "test_nll"]
+__all__ = ["DagStore", "gather_host", "layers_host", "train_epoch", "test_nll", "test_predictor"]
 
 MAX_N = 32
 BATCH_KEYS = ("x", "edge_index", "bi_layer_index", "batch", "ptr", "types", "preds")
@@ -321,11 +322,21 @@ class DagStore(object):
 
 # --------------------------------------------------------------------------------- the loops of dvae/train.py
 def train_epoch(model, optimizer, store: DagStore, idx, batch_size: int, clip: float = 0.0, beta: float = 0.005,
-                seed: Optional[int] = None):
-    """`train()` of dvae/train.py:218-273 (without its predictor branch) over the graphs `idx` of a store: per batch
-    zero_grad, `encode_batch`, `loss_dense`, backward, `clip_grad_norm_` when clip > 0, step.  `seed` None keeps the order
-    of `idx`; a number shuffles it as `store.loader` does (the reference shuffles its list every epoch).  Returns the sums
-    (loss, recon, kld) over the batches as floats - added up on the device and read once, at the end."""
+                seed: Optional[int] = None, predictor: bool = False):
+    """`train()` of dvae/train.py:218-273 over the graphs `idx` of a store: per batch zero_grad, `encode_batch`, `loss_dense`,
+    backward, `clip_grad_norm_` when clip > 0, step.  `seed` None keeps the order of `idx`; a number shuffles it as
+    `store.loader` does (the reference shuffles its list every epoch).  Returns the sums (loss, recon, kld) over the batches
+    as floats - added up on the device and read once, at the end.
+
+    `predictor` True is the reference's `--predictor` branch (train.py:243-250, 262-263): every batch adds
+    `predictor_mse(model, mu, b.y)[0]` - the summed squared error of `model.predictor` (see `predictor.attach_predictor`)
+    against the graphs' scores - to the loss before backward, and the call returns the four sums (loss, recon, kld, pred)
+    of train.py:272.  A store without `y` raises ValueError."""
+    if predictor:
+        from .predictor import _predictor_of, predictor_mse
+        if "y" not in store.arrays:
+            raise ValueError("train_epoch(predictor=True): the store holds no y (pass y= to DagStore)")
+        _predictor_of(model, "train_epoch(predictor=True)")
     model.train()
     sums = None
     for b in store.loader(idx, batch_size, shuffle=seed is not None, seed=0 if seed is None else seed):
@@ -333,10 +344,15 @@ def train_epoch(model, optimizer, store: DagStore, idx, batch_size: int, clip: f
         types, preds = b.types, b.preds
         mu, logvar = model.encode_batch(b)
         loss, recon, kld = model.loss_dense(mu, logvar, types, preds, beta)
+        parts = [recon, kld]
+        if predictor:
+            pred = predictor_mse(model, mu, b.y)[0]
+            loss = loss + pred
+            parts.append(pred)
         loss.backward()
         if clip > 0:
             torch.nn.utils.clip_grad_norm_(model.parameters(), clip)
-        part = torch.stack([loss.detach().reshape(()), recon.detach().reshape(()), kld.detach().reshape(())])
+        part = torch.stack([t.detach().reshape(()) for t in [loss] + parts])
         sums = part if sums is None else sums + part
         optimizer.step()
     return tuple(float(v) for v in sums.tolist())   # the one read
@@ -362,4 +378,30 @@ def test_nll(model, store: DagStore, idx, batch_size: int) -> float:
     return float(total) / ids.size
 
 
-test_nll.__test__ = False   # (a loop of the library, not a test for pytest to collect)
+def test_predictor(model, store: DagStore, idx, batch_size: int) -> float:
+    """The `pred rmse` of `test()` (dvae/train.py:276-308) as that line is plainly meant: in evaluation mode and without
+    gradients, sqrt(sum (y_pred - y)^2 / len(idx)) over the graphs `idx`, the batches' squared errors added up on the device
+    and read once.  The reference prints it from a `pred_loss` that its loop never accumulates (train.py:282, 302-303): there
+    the figure is always 0.  The mode the model came in is restored; a store without `y` raises ValueError."""
+    from .predictor import _predictor_of, predictor_mse
+    if "y" not in store.arrays:
+        raise ValueError("test_predictor: the store holds no y (pass y= to DagStore)")
+    _predictor_of(model, "test_predictor")
+    ids = store._ids(idx)
+    was_training = model.training
+    model.eval()
+    total = None
+    try:
+        with torch.no_grad():
+            for b in store.loader(ids, batch_size):
+                y = b.y
+                mu, _ = model.encode_batch(b)
+                se = predictor_mse(model, mu, y)[0].reshape(())
+                total = se if total is None else total + se
+    finally:
+        model.train(was_training)
+    return float(np.sqrt(float(total) / ids.size))
+
+
+test_nll.__test__ = False   # (loops of the library, not tests for pytest to collect)
+test_predictor.__test__ = False

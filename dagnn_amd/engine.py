@@ -2068,6 +2068,109 @@ def class_hits(pred: torch.Tensor, targ: torch.Tensor, out: Optional[torch.Tenso
     return out
 
 
+# ----------------------------------------------------------------------------- the D-VAE predictor (csrc/predictor.hip)
+def _predictor_params(W1, b1, W2, b2, nz: int, dev):
+    """The four parameters as they lie (contiguous fp32 on `dev`; nothing is derived or cached) and hs."""
+    if W1.dim() != 2 or W1.shape[1] != nz:
+        raise DagnnHipError("predictor: W1 [hs, nz=%d] needed (got %s)" % (nz, tuple(W1.shape)))
+    hs = W1.shape[0]
+    if not (1 <= nz <= _lib.PREDICTOR_MAX_NZ and 1 <= hs <= _lib.PREDICTOR_MAX_HS):
+        raise DagnnHipError("predictor: 1 <= nz <= %d and 1 <= hs <= %d needed (got nz=%d, hs=%d)"
+                            % (_lib.PREDICTOR_MAX_NZ, _lib.PREDICTOR_MAX_HS, nz, hs))
+    if b1.numel() != hs or W2.numel() != hs or b2.numel() != 1:
+        raise DagnnHipError("predictor: b1 [hs], W2 [1, hs], b2 [1] needed with hs = %d (got %s, %s, %s)"
+                            % (hs, tuple(b1.shape), tuple(W2.shape), tuple(b2.shape)))
+    out = []
+    for t, what in ((W1, "W1"), (b1, "b1"), (W2, "W2"), (b2, "b2")):
+        if not t.is_cuda or t.device != dev or t.dtype != torch.float32:
+            raise DagnnHipError("predictor: %s must be fp32 on %s (got %s on %s)" % (what, dev, t.dtype, t.device))
+        out.append(t.detach() if t.is_contiguous() else t.detach().contiguous())
+    return out, hs
+
+
+def _predictor_rows(x: torch.Tensor, what: str) -> torch.Tensor:
+    """fp32 GPU matrix with unit column stride; a row pitch above the width (a view of a wider tensor) is kept."""
+    if not isinstance(x, torch.Tensor) or not x.is_cuda:
+        _dev(x, what)   # (raises: no CPU path)
+    if x.dtype != torch.float32:
+        x = x.to(torch.float32)
+    if x.dim() != 2 or x.shape[1] < 1:
+        raise DagnnHipError("predictor: %s [rows, nz] needed (got %s)" % (what, tuple(x.shape)))
+    if x.stride(1) != 1 or (x.shape[0] > 1 and x.stride(0) < x.shape[1]):
+        x = x.contiguous()
+    return x
+
+
+def predictor_mse(mu: torch.Tensor, y: torch.Tensor, W1, b1, W2, b2, need_grads: bool, need_dmu: bool):
+    """`dagnn_predictor_mse`: (y_pred [B], loss [1], (d W1, d b1, d W2, d b2) or None, d mu [B, nz] or None) of
+    sum (W2 tanh(W1 mu + b1) + b2 - y)^2 for an upstream gradient of 1.  `mu` [B, nz] fp32 (row pitch kept), `y` [B] fp32
+    on mu's device.  One launch, nothing synchronises."""
+    mu = _predictor_rows(mu, "mu")
+    B, nz = mu.shape
+    dev = mu.device
+    if B < 1:
+        raise DagnnHipError("predictor_mse: no row")
+    (W1, b1, W2, b2), hs = _predictor_params(W1, b1, W2, b2, nz, dev)
+    y = _dev(y, "y", torch.float32)
+    if y.numel() != B or y.device != dev:
+        raise DagnnHipError("predictor_mse: y must hold one value per row of mu on its device (got %s for %d rows)"
+                            % (tuple(y.shape), B))
+    lib = _lib.load()
+    f32 = dict(dtype=torch.float32, device=dev)
+    P = hs * nz + 2 * hs + 2 if need_grads else 1
+    y_pred, out = torch.empty(B, **f32), torch.empty(P, **f32)
+    dmu = torch.empty(B, nz, **f32) if (need_grads and need_dmu) else None
+    nbytes = lib.dagnn_predictor_mse_bytes(B, nz, hs, 1 if need_grads else 0)
+    work = torch.empty(max(nbytes // 4, 1), **f32)
+    check(lib.dagnn_predictor_mse(mu.data_ptr(), mu.stride(0) if B > 1 else nz, y.data_ptr(), B, nz, hs, W1.data_ptr(),
+                                  b1.data_ptr(), W2.data_ptr(), b2.data_ptr(), y_pred.data_ptr(), out.data_ptr(), _ptr(dmu),
+                                  work.data_ptr(), work.numel() * 4, _lp_counter(mu).data_ptr(), 1 if need_grads else 0,
+                                  _stream(mu)), "dagnn_predictor_mse")
+    if not need_grads:
+        return y_pred, out, None, None
+    n1 = hs * nz
+    grads = (out[:n1].view(hs, nz), out[n1:n1 + hs], out[n1 + hs:n1 + 2 * hs].view(1, hs), out[P - 2:P - 1])
+    return y_pred, out[P - 1:], grads, dmu
+
+
+def predictor_forward(Z: torch.Tensor, W1, b1, W2, b2, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`dagnn_predictor_forward`: pred [M] of the rows of Z [M, nz] (into `out` when given: a contiguous fp32 [M] view).  One
+    launch, nothing synchronises."""
+    Z = _predictor_rows(Z, "Z")
+    M, nz = Z.shape
+    (W1, b1, W2, b2), hs = _predictor_params(W1, b1, W2, b2, nz, Z.device)
+    if out is None:
+        out = torch.empty(M, dtype=torch.float32, device=Z.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (M,) or not out.is_contiguous() or out.device != Z.device:
+        raise DagnnHipError("predictor_forward: `out` must be a contiguous fp32 [M] tensor on Z's device")
+    if M:
+        check(_lib.load().dagnn_predictor_forward(Z.data_ptr(), Z.stride(0) if M > 1 else nz, M, nz, hs, W1.data_ptr(),
+                                                  b1.data_ptr(), W2.data_ptr(), b2.data_ptr(), out.data_ptr(), _stream(Z)),
+              "dagnn_predictor_forward")
+    return out
+
+
+def fit_sums(pred: torch.Tensor, y: torch.Tensor, mean: float, std: float) -> torch.Tensor:
+    """`dagnn_fit_sums`: float64 [6] on the device = sum p, sum y, sum p^2, sum y^2, sum p y, sum (p - y)^2 with
+    p = (-pred - mean) / std; `pred` [M] fp32, `y` [M] fp32 or float64 (anything else as float64).  One launch, nothing
+    synchronises."""
+    pred = _dev(pred.reshape(-1), "pred", torch.float32)
+    M = pred.numel()
+    y = y.reshape(-1)
+    if y.dtype not in (torch.float32, torch.float64):
+        y = y.to(torch.float64)
+    y = _dev(y, "y")
+    if M < 1 or y.numel() != M or y.device != pred.device:
+        raise DagnnHipError("fit_sums: pred [M >= 1] and y [M] on one device needed (got %d and %d)" % (M, y.numel()))
+    lib = _lib.load()
+    out = torch.empty(6, dtype=torch.float64, device=pred.device)
+    work = torch.empty(max(lib.dagnn_fit_sums_bytes(M) // 8, 6), dtype=torch.float64, device=pred.device)
+    check(lib.dagnn_fit_sums(pred.data_ptr(), y.data_ptr(), 1 if y.dtype == torch.float64 else 0, M, float(mean), float(std),
+                             out.data_ptr(), work.data_ptr(), work.numel() * 8, _lp_counter(pred).data_ptr(), _stream(pred)),
+          "dagnn_fit_sums")
+    return out
+
+
 # ----------------------------------------------------------------------------- the graph store's batch (csrc/store.hip)
 _STORE_SOURCES = ("node_ptr", "edge_ptr", "tok_ptr", "x", "depth", "layer_f", "layer_b", "src", "dst", "tok", "depth_max",
                   "y_arr", "ref_ids", "ref_extra")

@@ -1371,6 +1371,39 @@ int dagnn_dag_store_gather(const dagnn_dag_store_gather_args* args /* host */, v
 int dagnn_dag_store_layers(const int32_t* preds, const int32_t* succs, int64_t M, int n, int32_t* layer_f, int32_t* layer_b,
                            void* stream);
 
+/* -------------------------------------------------------------------------------------------
+ * The D-VAE performance predictor (csrc/predictor.hip; dvae/train.py:184-191, 243-250, bayesian_optimization/bo.py:250-286):
+ *   y_pred = W2 tanh(W1 mu + b1) + b2   with W1 [hs, nz], b1 [hs], W2 [1, hs], b2 [1], read in place on every call.
+ * 1 <= nz <= DAGNN_PREDICTOR_MAX_NZ, 1 <= hs <= DAGNN_PREDICTOR_MAX_HS; any other width is DAGNN_EINVAL.
+ *
+ * dagnn_predictor_mse: ONE launch.  mu [B, nz] fp32 with row pitch ld_mu >= nz, y [B] fp32 -> y_pred [B] and
+ *   want_grads == 0:  out [1] = loss = sum_b (y_pred_b - y_b)^2                                   (dmu must be NULL)
+ *   want_grads != 0:  out [hs nz + 2 hs + 2] = d W1 [hs, nz] | d b1 [hs] | d W2 [hs] | d b2 | loss,  the gradients of the loss
+ *                     for an upstream gradient of 1; dmu [B, nz] contiguous, or NULL to skip it.
+ *   y_pred and the loss are the same bits in both forms.  A workgroup owns tiles of DAGNN_PREDICTOR_ROWS rows; `work` (4-byte
+ *   aligned, >= dagnn_predictor_mse_bytes(B, nz, hs, want_grads) bytes, any content) takes one partial of `out` per workgroup,
+ *   which the last workgroup in - an integer ticket on `counter` - adds in workgroup order.  counter [1]: device word, zero
+ *   before the first call (the kernel leaves it zero).
+ * dagnn_predictor_forward: pred [M] of the rows of Z [M, nz] (row pitch ld_z >= nz), many workgroups over the rows; a row has
+ *   the arithmetic of dagnn_predictor_mse, in the same order: the same bits.  M = 0 returns at once.
+ * dagnn_fit_sums: with p_i = (-pred_i - mean) / std (bo.py:253) in float64,
+ *   out [6] float64 = sum p, sum y, sum p^2, sum y^2, sum p y, sum (p - y)^2   over pred [M] fp32 and y [M] (fp32, or float64
+ *   with y_is_f64 != 0); `work`: 8-byte aligned, >= dagnn_fit_sums_bytes(M) bytes; counter as above.  One launch.
+ * No allocation, no synchronisation, no float atomics, every sum in one fixed order: bitwise repeatable.
+ * ---------------------------------------------------------------------------------------- */
+#define DAGNN_PREDICTOR_MAX_NZ 128
+#define DAGNN_PREDICTOR_MAX_HS 1024
+#define DAGNN_PREDICTOR_ROWS 8
+size_t dagnn_predictor_mse_bytes(int B, int nz, int hs, int want_grads);
+int dagnn_predictor_mse(const float* mu, int64_t ld_mu, const float* y, int B, int nz, int hs, const float* W1, const float* b1,
+                        const float* W2, const float* b2, float* y_pred, float* out, float* dmu, void* work, size_t work_bytes,
+                        unsigned* counter, int want_grads, void* stream);
+int dagnn_predictor_forward(const float* Z, int64_t ld_z, int64_t M, int nz, int hs, const float* W1, const float* b1,
+                            const float* W2, const float* b2, float* pred, void* stream);
+size_t dagnn_fit_sums_bytes(int64_t M);
+int dagnn_fit_sums(const float* pred, const void* y, int y_is_f64, int64_t M, double mean, double std, double* out, void* work,
+                   size_t work_bytes, unsigned* counter, void* stream);
+
 /* The tail of the reference's training step - `clip_grad_norm_(model.parameters(), clip)` + `optim.Adam.step()`
  * (ogbg-code/main_pyg.py:63-65,179) - over a table of fp32 tensors (csrc/optim.hip).  dagnn_grad_norm: the 2-norm of up to
  * DAGNN_MAX_OPT_TENSORS gradients (`partial`: scratch of dagnn_opt_chunks() floats; `accumulate` != 0 adds the tensors' sum of
