@@ -323,6 +323,15 @@ class DagStoreGatherArgs(C.Structure):   # dagnn_dag_store_gather_args: every fi
                                    "out_preds", "out_y")]
 
 
+BN_TABLE_CELLS, BN_MAX_VARS = 8192, 30             # DAGNN_BN_TABLE_CELLS / DAGNN_BN_MAX_VARS
+BN_STAGE_AUTO, BN_STAGE_LDS, BN_STAGE_GLOBAL = 0, 1, 2   # DAGNN_BN_STAGE_*
+
+
+class BnData(C.Structure):   # dagnn_bn_data
+    _fields_ = [("cols", C.c_void_p), ("ld", C.c_int64), ("S", C.c_int64), ("n_var", C.c_int32), ("reserved", C.c_int32),
+                ("cards", C.c_int32 * BN_MAX_VARS)]
+
+
 SYMBOLS = {
     "dagnn_version": (C.c_char_p, []),
     "dagnn_store_gather": (C.c_int, [C.POINTER(StoreGatherArgs), C.c_void_p]),
@@ -441,6 +450,10 @@ SYMBOLS = {
     "dagnn_fit_sums_bytes": (C.c_size_t, [C.c_int64]),
     "dagnn_fit_sums": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_double, C.c_double, C.c_void_p, C.c_void_p,
                                  C.c_size_t, C.c_void_p, C.c_void_p]),
+    "dagnn_bn_stage_fits": (C.c_int, [C.POINTER(BnData)]),
+    "dagnn_bn_score": (C.c_int, [C.POINTER(BnData), C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dagnn_bn_rows_to_parents": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int,
+                                           C.c_void_p, C.c_void_p, C.c_void_p]),
     "dagnn_opt_chunks": (C.c_int64, [C.c_void_p, C.c_int]),
     "dagnn_grad_norm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "dagnn_clip_adam": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int64, C.c_float,

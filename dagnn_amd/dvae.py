@@ -1330,6 +1330,13 @@ def decode_from_latent_space(latent_points, model, decode_attempts=500, n_nodes=
     torch.manual_seed reproduces the result), or given as `draws` shaped as `draw_shapes(max_n, B, decode_attempts)`;
     the decode runs in chunks of `chunk` attempts (default: about SELECT_ROWS rows per call), which does not change the
     result.  Validity, keys and selection are one HIP call; the result reaches the host with one synchronisation."""
+    return _decode_and_pick(latent_points, model, decode_attempts, n_nodes, return_igraph, data_type, select, chunk, draws)[0]
+
+
+def _decode_and_pick(latent_points, model, decode_attempts, n_nodes, return_igraph, data_type, select, chunk, draws, extra=None):
+    """The body of `decode_from_latent_space`.  `extra(d, sel, pick)` - d the DecodedDense [A, B, ...] of all attempts, sel
+    the SelectedDense, pick [B] int64 the picked attempt per point (0 where none is valid) - may return an int32 [B, E]
+    device tensor that rides to the host in the call's one copy.  Returns (result, extra columns on the host or None)."""
     kind = _kind(data_type)
     if n_nodes != "variable" and kind == 0:
         _n_nodes(n_nodes)
@@ -1362,20 +1369,25 @@ def decode_from_latent_space(latent_points, model, decode_attempts=500, n_nodes=
     if return_igraph:
         last = _last_occurrence(sel, pick, B, A)
         cols.append(_gather_rows(d, last % A, last // A))
+    more = None if extra is None else extra(d, sel, pick)
+    if more is not None:
+        cols.append(more)
     host = torch.cat(cols, 1).cpu().numpy()   # the one synchronisation
+    if more is not None:
+        host, more = host[:, :host.shape[1] - more.shape[1]], np.ascontiguousarray(host[:, host.shape[1] - more.shape[1]:])
     form = enas_string if kind == 0 else bn_adj_string
     w = 2 * n + 1
     strings = [None if host[b, 0] < 0 else form(host[b, 1:1 + n], host[b, 1 + n:1 + 2 * n], host[b, 2 * n + 1])
                for b in range(B)]
     if not return_igraph:
-        return strings
+        return strings, more
     rows = host[:, 1 + w:]
     keep = [b for b in range(B) if host[b, 0] >= 0]
     built = graphs_from_dense(rows[keep, :n], rows[keep, n:2 * n], rows[keep, 2 * n], model.END_TYPE) if keep else []
     graphs = [None] * B
     for b, g in zip(keep, built):
         graphs[b] = g
-    return graphs, strings
+    return (graphs, strings), more
 
 
 # ------------------------------------------------------------------ evaluation metrics (dvae/train.py:276-311, prior_validity)

@@ -2272,3 +2272,38 @@ def dag_store_gather(packed: dict, table: torch.Tensor, B: int, E: int, nvt: int
         setattr(a, field, _ptr(out.get(key)))
     check(_lib.load().dagnn_dag_store_gather(C.byref(a), _stream(table)), "dagnn_dag_store_gather")
     return out
+
+
+def bn_score(desc: "_lib.BnData", parents: torch.Tensor, valid: Optional[torch.Tensor] = None, stage: int = 0):
+    """`dagnn_bn_score`: the BIC scores of M structures - `parents` int32 / uint32 [M, n_var] parent masks on the device of
+    the packed table `desc` describes, `valid` None or int32 [M] - as (scores float64 [M], n_over int32 [1]) on that device.
+    One launch, nothing synchronises.  stage: _lib.BN_STAGE_AUTO / _LDS / _GLOBAL."""
+    if not isinstance(parents, torch.Tensor) or not parents.is_cuda or parents.dim() != 2 or parents.shape[1] != desc.n_var \
+            or parents.dtype not in (torch.int32, torch.uint32):
+        raise DagnnHipError("bn_score: parents must be a 32-bit integer [M, n_var=%d] tensor on the GPU" % desc.n_var)
+    parents = parents if parents.is_contiguous() else parents.contiguous()
+    M, dev = parents.shape[0], parents.device
+    if valid is not None:
+        valid = _dev(valid, "valid", torch.int32)
+        if valid.numel() != M or valid.device != dev:
+            raise DagnnHipError("bn_score: valid must hold one flag per structure on the parents' device")
+    scores = torch.empty(M, dtype=torch.float64, device=dev)
+    n_over = torch.zeros(1, dtype=torch.int32, device=dev)
+    check(_lib.load().dagnn_bn_score(C.byref(desc), _ptr(parents), _ptr(valid), M, int(stage), _ptr(scores), _ptr(n_over),
+                                     _stream(parents)), "dagnn_bn_score")
+    return scores, n_over
+
+
+def bn_rows_to_parents(types: torch.Tensor, preds: torch.Tensor, nv: torch.Tensor, nvt: int, start_type: int, end_type: int):
+    """`dagnn_bn_rows_to_parents`: dense rows types / preds int32 [R, n], nv int32 [R] -> (parents int32 [R, nvt - 2] - the
+    masks read as unsigned words -, valid int32 [R]).  One launch, nothing synchronises."""
+    types, preds, nv = _dev(types, "types", torch.int32), _dev(preds, "preds", torch.int32), _dev(nv, "nv", torch.int32)
+    if types.dim() != 2 or tuple(preds.shape) != tuple(types.shape) or nv.numel() != types.shape[0]:
+        raise DagnnHipError("bn_rows_to_parents: types / preds [R, n] and nv [R] needed (got %s, %s, %s)"
+                            % (tuple(types.shape), tuple(preds.shape), tuple(nv.shape)))
+    R, n = types.shape
+    parents = torch.empty(R, max(int(nvt) - 2, 0), dtype=torch.int32, device=types.device)
+    valid = torch.empty(R, dtype=torch.int32, device=types.device)
+    check(_lib.load().dagnn_bn_rows_to_parents(_ptr(types), _ptr(preds), _ptr(nv), R, n, int(nvt), int(start_type), int(end_type),
+                                               _ptr(parents), _ptr(valid), _stream(types)), "dagnn_bn_rows_to_parents")
+    return parents, valid

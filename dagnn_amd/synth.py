@@ -142,6 +142,23 @@ def bn_rows(seed: int, num_graphs: int) -> list:
     return out
 
 
+def asia_samples(seed: int, S: int) -> np.ndarray:
+    """S samples int64 [S, 8] of the textbook Asia network (Lauritzen and Spiegelhalter 1988), columns A, S, T, L, B, E, X, D,
+    1 = yes: a workload for `bn_score` where bnlearn's `data(asia)` - the table the reference scores on - is not at hand.
+    It is drawn here from the network's published probabilities, so scores on it are NOT the reference's numbers."""
+    rng = np.random.default_rng(seed)
+    u = rng.random((int(S), 8))
+    a = u[:, 0] < 0.01
+    s = u[:, 1] < 0.5
+    t = u[:, 2] < np.where(a, 0.05, 0.01)
+    l = u[:, 3] < np.where(s, 0.1, 0.01)   # noqa: E741
+    b = u[:, 4] < np.where(s, 0.6, 0.3)
+    e = t | l
+    x = u[:, 6] < np.where(e, 0.98, 0.05)
+    d = u[:, 7] < np.where(b, np.where(e, 0.9, 0.8), np.where(e, 0.7, 0.1))
+    return np.stack([a, s, t, l, b, e, x, d], axis=1).astype(np.int64)
+
+
 def dvae_batch(graphs: Sequence[GraphData]) -> GraphBatch:
     """Collate D-VAE graphs the way `dvae/batch.py:26-146` does (`bi_layer_index` row 1 shifted)."""
     return GraphBatch.from_data_list([g for g in graphs])

@@ -1404,6 +1404,58 @@ size_t dagnn_fit_sums_bytes(int64_t M);
 int dagnn_fit_sums(const float* pred, const void* y, int y_is_f64, int64_t M, double mean, double std, double* out, void* work,
                    size_t work_bytes, unsigned* counter, void* stream);
 
+/* The BIC score of Bayesian-network structures on a table of discrete samples (csrc/bn_score.hip): the target y of the
+ * D-VAE's BN data set and the objective of its BO loop - what the reference obtains from one R process per structure
+ * (bayesian_optimization/evaluate_BN.py: bnlearn's score(net, data), type "bic").
+ *
+ * Data: S samples of n_var <= DAGNN_BN_MAX_VARS discrete variables, variable i with values in [0, cards[i]), cards[i] in
+ * 1..255, S < 2^31; on the device column-major, one byte per value: value (s, i) at cols[i * ld + s], ld >= S a multiple of
+ * 16, cols 16-byte aligned, the padding bytes zero.  A structure is n_var parent masks: bit j of parents[m * n_var + i] is
+ * the arc j -> i (bits at or above n_var are ignored; the masks of one structure must describe a DAG - this is NOT checked,
+ * a cyclic structure gets the number the formula gives).  With q_i the product of the parents' cardinalities (1 without a
+ * parent; every configuration counts, observed or not), N_ijk the samples with parent configuration j and x_i = k, and N_ij
+ * the sum of N_ijk over k:
+ *     family_i = sum over (j, k) with N_ijk > 0 of N_ijk (log N_ijk - log N_ij)  -  0.5 log(S) q_i (cards[i] - 1)
+ *     score[m] = sum over i of family_i
+ * Counts are int32, everything after them float64, added in one fixed order (cells ascending through a fixed tree, then the
+ * families in node order; no float atomics): scores are bitwise equal from run to run, under any permutation of the samples
+ * and on both staging paths.
+ *
+ * Capacity: a family's count table holds at most DAGNN_BN_TABLE_CELLS cells.  A structure with a family of q_i cards[i] cells
+ * beyond that is NOT scored: its score is NaN and *n_over (device int32, zeroed by the caller) is incremented once for the
+ * structure.  `valid` (may be NULL) marks structures to skip: valid[m] == 0 gives NaN and does not count in *n_over.
+ *
+ * stage: DAGNN_BN_STAGE_LDS - a workgroup copies the table (n_var * ld bytes) into LDS once and scores many structures from
+ * it; refused (DAGNN_EINVAL) when the bn_stage_fits query says 0.  DAGNN_BN_STAGE_GLOBAL - the columns are read from global
+ * memory.  DAGNN_BN_STAGE_AUTO - LDS when it fits.
+ *
+ * The rows_to_parents entry turns R dense decoder rows (types / preds [R, n] int32, preds as predecessor bitmasks, nv [R];
+ * 3 <= nvt <= n <= 32) into parent masks [R, nvt - 2] and valid [R]: a row is valid under the reference's BN rules (exactly nvt
+ * vertices, every type in [0, nvt) exactly once, one start and one end type); the first and last vertex are dropped and a
+ * middle vertex becomes the variable given by the rank of its type among the middle types (np.argsort in
+ * decode_igraph_to_BN_adj, dvae/util.py:388-394).  Invalid rows get zero masks and valid = 0.
+ *
+ * Borrowed pointers, the caller's stream, no allocation, no synchronisation; arguments are validated before any HIP call
+ * (DAGNN_EINVAL). */
+#define DAGNN_BN_TABLE_CELLS 8192
+#define DAGNN_BN_MAX_VARS 30
+#define DAGNN_BN_STAGE_AUTO 0
+#define DAGNN_BN_STAGE_LDS 1
+#define DAGNN_BN_STAGE_GLOBAL 2
+typedef struct dagnn_bn_data {
+    const uint8_t* cols;
+    int64_t ld;
+    int64_t S;
+    int32_t n_var;
+    int32_t reserved;
+    int32_t cards[DAGNN_BN_MAX_VARS];
+} dagnn_bn_data;
+int dagnn_bn_stage_fits(const dagnn_bn_data* d);   /* 1 / 0, DAGNN_EINVAL for a bad descriptor */
+int dagnn_bn_score(const dagnn_bn_data* d, const uint32_t* parents, const int32_t* valid, int64_t M, int stage, double* scores,
+                   int32_t* n_over, void* stream);
+int dagnn_bn_rows_to_parents(const int32_t* types, const int32_t* preds, const int32_t* nv, int64_t R, int n, int nvt,
+                             int start_type, int end_type, uint32_t* parents, int32_t* valid, void* stream);
+
 /* The tail of the reference's training step - `clip_grad_norm_(model.parameters(), clip)` + `optim.Adam.step()`
  * (ogbg-code/main_pyg.py:63-65,179) - over a table of fp32 tensors (csrc/optim.hip).  dagnn_grad_norm: the 2-norm of up to
  * DAGNN_MAX_OPT_TENSORS gradients (`partial`: scratch of dagnn_opt_chunks() floats; `accumulate` != 0 adds the tensors' sum of
