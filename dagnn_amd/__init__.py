@@ -11,6 +11,7 @@ Drop-in modules with the reference's constructor / state_dict / forward(G) contr
     from dagnn_amd import DagStore                     # the same for D-VAE data sets (ENAS / BN rows), dvae/train.py's loops
     from dagnn_amd import attach_predictor             # dvae/train.py --predictor: the MLP on mu, its MSE and gradients
     from dagnn_amd import BnData, bn_scores            # bayesian_optimization/evaluate_BN.py: BIC scores of BN structures
+    from dagnn_amd import SparseGP, bo_round           # bayesian_optimization/sparse_gp.py: the model that proposes BO points
 
 The hot path runs in libdagnn_hip.so (hand-written HIP, C ABI in include/dagnn_hip.h); importing
 this package does not need a GPU, calling `forward` does.
@@ -33,5 +34,7 @@ from . import predictor  # noqa: F401
 from .predictor import attach_predictor, predict_latent, predictor_mse, predictor_report  # noqa: F401
 from . import bn_score  # noqa: F401
 from .bn_score import BnData, BnEvaluator, bn_scores, decode_and_score, score_dense, score_strings, store_scores  # noqa: F401
+from . import sgp  # noqa: F401
+from .sgp import SparseGP, bo_round  # noqa: F401
 
 __version__ = "0.1.0"

@@ -332,6 +332,9 @@ class BnData(C.Structure):   # dagnn_bn_data
                 ("cards", C.c_int32 * BN_MAX_VARS)]
 
 
+SGP_MAX_M, SGP_MAX_D, SGP_MAX_Q = 512, 128, 128   # DAGNN_SGP_MAX_M / _MAX_D / _MAX_Q
+SGP_ARGMIN_MEAN, SGP_ARGMIN_EI = 0, 1             # DAGNN_SGP_ARGMIN_*
+
 SYMBOLS = {
     "dagnn_version": (C.c_char_p, []),
     "dagnn_store_gather": (C.c_int, [C.POINTER(StoreGatherArgs), C.c_void_p]),
@@ -454,6 +457,13 @@ SYMBOLS = {
     "dagnn_bn_score": (C.c_int, [C.POINTER(BnData), C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "dagnn_bn_rows_to_parents": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int,
                                            C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dagnn_sgp_project": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_float,
+                                    C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dagnn_sgp_ei_step_bytes": (C.c_size_t, [C.c_int64]),
+    "dagnn_sgp_ei_step": (C.c_int, [C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_int64, C.c_int, C.c_void_p,
+                                    C.c_float, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "dagnn_opt_chunks": (C.c_int64, [C.c_void_p, C.c_int]),
     "dagnn_grad_norm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "dagnn_clip_adam": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int64, C.c_float,

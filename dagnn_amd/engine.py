@@ -2307,3 +2307,82 @@ def bn_rows_to_parents(types: torch.Tensor, preds: torch.Tensor, nv: torch.Tenso
     check(_lib.load().dagnn_bn_rows_to_parents(_ptr(types), _ptr(preds), _ptr(nv), R, n, int(nvt), int(start_type), int(end_type),
                                                _ptr(parents), _ptr(valid), _stream(types)), "dagnn_bn_rows_to_parents")
     return parents, valid
+
+
+# ----------------------------------------------------------------------------- the sparse GP's grids (csrc/sgp.hip)
+def sgp_project(X: torch.Tensor, zt: torch.Tensor, inv_ls: torch.Tensor, sf: float, Tt: Optional[torch.Tensor], Mt: int, split: int,
+                a: Optional[torch.Tensor], U: Optional[torch.Tensor] = None, u_col0: int = 0, want_var0: bool = False,
+                want_var1: bool = False):
+    """`dagnn_sgp_project` over the rows of X [N, d] (fp32, a row pitch is read in place): (mean, var0, var1), each fp32 [N] or
+    None - mean with `a`, var0 / var1 as asked; the columns u_col0.. of U = k(X, z) T^T go into `U` [N, >= Mt - u_col0] when
+    given.  zt [d, M], inv_ls [d], Tt [M, >= Mt] (T transposed), a [M]: fp32 on X's device.  One launch, nothing synchronises."""
+    X = _rows(X, "X")
+    if X.dim() != 2:
+        raise DagnnHipError("sgp_project: X must be [N, d] (got %s)" % (tuple(X.shape),))
+    N, d = X.shape
+    dev = X.device
+    zt, inv_ls = _dev(zt, "zt", torch.float32), _dev(inv_ls, "inv_ls", torch.float32)
+    M = zt.shape[1]
+    if zt.dim() != 2 or zt.shape[0] != d or inv_ls.numel() != d or zt.device != dev or inv_ls.device != dev:
+        raise DagnnHipError("sgp_project: zt [d, M] and inv_ls [d] on X's device needed")
+    Mt, ld_t = int(Mt), 0
+    if Mt > 0:
+        Tt = _dev(Tt, "Tt", torch.float32)
+        if Tt.dim() != 2 or Tt.shape[0] != M or Tt.shape[1] < Mt or Tt.device != dev:
+            raise DagnnHipError("sgp_project: Tt must be [M=%d, >= Mt=%d] on X's device (got %s)" % (M, Mt, tuple(Tt.shape)))
+        ld_t = Tt.shape[1]
+    if a is not None:
+        a = _dev(a, "a", torch.float32)
+        if a.numel() != M or a.device != dev:
+            raise DagnnHipError("sgp_project: a must hold M = %d values on X's device" % M)
+    ld_u = 0
+    if U is not None:
+        if not U.is_cuda or U.device != dev or U.dtype != torch.float32 or U.dim() != 2 or U.shape[0] != N or U.stride(1) != 1 \
+                or U.shape[1] < Mt - int(u_col0) or (N > 1 and U.stride(0) < U.shape[1]):
+            raise DagnnHipError("sgp_project: U must be fp32 [N, >= Mt - u_col0] with contiguous rows on X's device")
+        ld_u = U.stride(0) if N > 1 else U.shape[1]
+    mean = torch.empty(N, dtype=torch.float32, device=dev) if a is not None else None
+    var0 = torch.empty(N, dtype=torch.float32, device=dev) if want_var0 else None
+    var1 = torch.empty(N, dtype=torch.float32, device=dev) if want_var1 else None
+    check(_lib.load().dagnn_sgp_project(X.data_ptr(), X.stride(0) if N > 1 else d, N, d, M, zt.data_ptr(), M, inv_ls.data_ptr(), float(sf),
+                                        _ptr(Tt) if Mt > 0 else None, ld_t, Mt, int(split), _ptr(a), _ptr(U), ld_u, int(u_col0),
+                                        _ptr(var0), _ptr(var1), _ptr(mean), _stream(X)), "dagnn_sgp_project")
+    return mean, var0, var1
+
+
+def sgp_ei_step(mode: int, mean: torch.Tensor, r: torch.Tensor, incumbent: float = 0.0, update=None, want_keys: bool = False):
+    """`dagnn_sgp_ei_step`: the argmin of the mean (mode _lib.SGP_ARGMIN_MEAN) or of -log EI (SGP_ARGMIN_EI) over the N rows -
+    `mean`, `r` contiguous fp32 [N] on the GPU - as (result int64 [4] on the device: index, rows without a positive variance,
+    the winning key's bits, 0; keys float64 [N] or None).  `update` = (X [N, d], inv_ls [d], sf, p [d], U [N, > Me], Me, c [Me],
+    inv_delta) first appends the point p to the factor: column Me of U is written and `r` is lowered IN PLACE.  One launch,
+    nothing synchronises."""
+    for t, what in ((mean, "mean"), (r, "r")):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or t.dim() != 1 or not t.is_contiguous():
+            raise DagnnHipError("sgp_ei_step: %s must be a contiguous fp32 [N] tensor on the GPU" % what)
+    N, dev = mean.numel(), mean.device
+    if N < 1 or r.numel() != N or r.device != dev:
+        raise DagnnHipError("sgp_ei_step: mean and r must hold N >= 1 rows on one device")
+    X = inv_ls = p = U = c = None
+    ld_x = ld_u = d = Me = 0
+    sf = inv_delta = 0.0
+    if update is not None:
+        X, inv_ls, sf, p, U, Me, c, inv_delta = update
+        X = _rows(X, "X")
+        d, Me = X.shape[1], int(Me)
+        ok = X.dim() == 2 and X.shape[0] == N and X.device == dev
+        for t, n in ((inv_ls, d), (p, d), (c, Me)):
+            ok = ok and isinstance(t, torch.Tensor) and t.is_cuda and t.device == dev and t.dtype == torch.float32 and \
+                t.is_contiguous() and t.numel() >= n
+        ok = ok and isinstance(U, torch.Tensor) and U.is_cuda and U.device == dev and U.dtype == torch.float32 and U.dim() == 2 \
+            and U.shape[0] == N and U.stride(1) == 1 and U.shape[1] > Me and (N == 1 or U.stride(0) >= U.shape[1])
+        if not ok:
+            raise DagnnHipError("sgp_ei_step: update needs X [N, d], inv_ls [d], p [d], c [Me] and U [N, > Me] as fp32 on one GPU")
+        ld_x, ld_u = (X.stride(0) if N > 1 else d), (U.stride(0) if N > 1 else U.shape[1])
+    lib = _lib.load()
+    result = torch.empty(4, dtype=torch.int64, device=dev)
+    keys = torch.empty(N, dtype=torch.float64, device=dev) if want_keys else None
+    work = torch.empty(max(lib.dagnn_sgp_ei_step_bytes(N) // 8, 4), dtype=torch.int64, device=dev)
+    check(lib.dagnn_sgp_ei_step(int(mode), N, mean.data_ptr(), r.data_ptr(), float(incumbent), _ptr(X), ld_x, d, _ptr(inv_ls), float(sf),
+                                _ptr(p), _ptr(U), ld_u, Me, _ptr(c), float(inv_delta), _ptr(keys), result.data_ptr(), work.data_ptr(),
+                                work.numel() * 8, _lp_counter(mean).data_ptr(), _stream(mean)), "dagnn_sgp_ei_step")
+    return result, keys

@@ -1,0 +1,608 @@
+"""The sparse GP of the D-VAE BO loop (bayesian_optimization/sparse_gp.py, sparse_gp_theano_internal.py, gauss.py; used by
+bo.py:256-261, 289): the model that proposes the points of a round.
+
+    sgp = SparseGP(X_train, y_train, 500, device="cuda")
+    sgp.train_via_adam(X_test, y_test, max_iterations=100, minibatch_size=1000, learning_rate=5e-4, rng=rng)    # bo.py:257
+    mean, var = sgp.predict(X_test)                                                                             # bo.py:261
+    fit = sgp.report(X_test, y_test)                     # {'rmse', 'll', 'pearson', 'n'} of bo.py:265-270
+    points = sgp.batched_greedy_ei(50, lower, upper, mean, std, sample="normal", rng=rng)                       # bo.py:289
+    points, strings, scores = bo_round(sgp, model, 50, lower, upper, mean, std, data=bn_data)                   # bo.py:289-306
+
+The model (ignore_variances = True, the only path of the reference that bo.py runs): sf = exp(lsf), ls = exp(lls),
+    k(x, z) = sf exp(-1/2 sum_c (x_c - z_c)^2 / ls_c),      Kzz = k(z, z) + 1e-3 sf I,      P = LParamPost LParamPost^T,
+    covPost = (Kzz^-1 + P)^-1,      a = Kzz^-1 covPost mParamPost,      B = Kzz^-1 covPost Kzz^-1 - Kzz^-1,
+    mean(x) = k(x, z) a,      var(x) = |sf + k B k^T| + exp(lvar_noise).
+Training is plumbing on torch ops in float64 (`energy`, `train_via_adam`): the factorisation of a 500 x 500 matrix is the
+library's job.  The hot side - every `predict` and every grid of `batched_greedy_ei` - runs in csrc/sgp.hip on matrices derived
+once per parameter version in float64 and handed over rounded to fp32, in the whitened form:
+    Kzz = L L^T,   A = L^T P L,   I - (I + A)^-1 = R^T R,   G = R L^-1,   var = sf - |G k|^2,   a = L^-T (I + A)^-1 L^T mParamPost
+and for the averaged EI, W = L^-1 extended by one row per chosen point.  A model on the CPU goes through the float64 numpy
+mirrors of this module (`*_host`); a model on the GPU never does.
+"""
+from __future__ import annotations
+
+import math
+from types import SimpleNamespace
+from typing import Optional
+
+import numpy as np
+import torch
+
+from . import _lib, core, engine
+
+__all__ = ["SparseGP", "bo_round", "MAX_M", "MAX_D", "MAX_Q", "JITTER", "kernel_host", "predict_host", "log_ei_host",
+           "greedy_host"]
+
+MAX_M = _lib.SGP_MAX_M   # DAGNN_SGP_MAX_M: inducing points
+MAX_D = _lib.SGP_MAX_D   # DAGNN_SGP_MAX_D: input columns
+MAX_Q = _lib.SGP_MAX_Q   # DAGNN_SGP_MAX_Q: points of one greedy batch
+JITTER = 1e-3
+_HALF_LOG_2PI = 0.5 * math.log(2.0 * math.pi)
+_SQRT_2PI = math.sqrt(2.0 * math.pi)
+
+
+# --------------------------------------------------------------------------------- the host mirrors (float64 numpy)
+def kernel_host(lls, lsf, x, z) -> np.ndarray:
+    """k(x, z) [Nx, Nz] in float64, from the differences (the reference expands the square: gauss.py:11-29)."""
+    x, z = np.atleast_2d(np.asarray(x, dtype=np.float64)), np.atleast_2d(np.asarray(z, dtype=np.float64))
+    il = np.exp(-np.asarray(lls, dtype=np.float64)).reshape(-1)
+    out = np.empty((x.shape[0], z.shape[0]), dtype=np.float64)
+    for i in range(0, x.shape[0], 256):   # (bounded scratch: [256, Nz, d])
+        df = x[i:i + 256, None, :] - z[None, :, :]
+        out[i:i + 256] = np.einsum("nmc,c,nmc->nm", df, il, df)
+    return math.exp(float(lsf)) * np.exp(-0.5 * out)
+
+
+def _erfc(x: np.ndarray) -> np.ndarray:
+    return torch.special.erfc(torch.from_numpy(np.ascontiguousarray(x, dtype=np.float64))).numpy()
+
+
+def log_ei_host(mean, var, incumbent: float) -> np.ndarray:
+    """The row epilogue of `dagnn_sgp_ei_step` in float64 numpy: with s = (incumbent - mean) / sqrt(var),
+        log EI = log((incumbent - mean) ratio(s) + sqrt(var)) - 1/2 log(2 pi) - 1/2 s^2,
+    ratio(s) the reference's series below s = -10 and Phi(s) / phi(s) with Phi(s) = 1/2 erfc(-s / sqrt 2) otherwise; NaN where
+    var is not positive."""
+    m, v = np.asarray(mean, dtype=np.float64).reshape(-1), np.asarray(var, dtype=np.float64).reshape(-1)
+    out = np.full(m.shape, np.nan)
+    ok = v > 0
+    sd = np.sqrt(v[ok])
+    u = float(incumbent) - m[ok]
+    s = u / sd
+    with np.errstate(all="ignore"):
+        far = s < -10.0
+        x = np.where(far, s, -11.0)
+        x2 = x * x
+        x3 = x2 * x
+        x5 = x3 * x2
+        x7 = x5 * x2
+        series = -(1.0 / x - 1.0 / x3 + 3.0 / x5 - 15.0 / x7)
+        near = (0.5 * _erfc(-s * math.sqrt(0.5))) / (np.exp(-0.5 * s * s) / _SQRT_2PI)
+        out[ok] = np.log(u * np.where(far, series, near) + sd) - _HALF_LOG_2PI - 0.5 * s * s
+    return out
+
+
+def _neg_log_ei_point(m: float, v: float, inc: float):
+    """(-log EI, d / d mean, d / d var) at one point, of the expression `log_ei_host` evaluates (the series branch is
+    differentiated as the series it is)."""
+    if not v > 0:
+        return float("nan"), 0.0, 0.0
+    sd = math.sqrt(v)
+    s = (inc - m) / sd
+    if s < -10.0:
+        rho = -(1.0 / s - 1.0 / s ** 3 + 3.0 / s ** 5 - 15.0 / s ** 7)
+        drho = 1.0 / s ** 2 - 3.0 / s ** 4 + 15.0 / s ** 6 - 105.0 / s ** 8
+    else:
+        phi = math.exp(-0.5 * s * s) / _SQRT_2PI
+        if phi == 0.0:
+            return float("-inf"), 0.0, 0.0   # (s beyond 38: the formula's own overflow)
+        rho = 0.5 * math.erfc(-s * math.sqrt(0.5)) / phi
+        drho = 1.0 + s * rho
+    h = (inc - m) * rho + sd
+    if not h > 0:
+        return float("nan"), 0.0, 0.0
+    lei = math.log(h) - _HALF_LOG_2PI - 0.5 * s * s
+    gs = (rho + s * drho) / (s * rho + 1.0) - s
+    return -lei, gs / sd, -(1.0 - gs * s) / (2.0 * v)
+
+
+def predict_host(D, X):
+    """(mean [N], var0 [N]) of the rows of X from the derived matrices `D` (`SparseGP.derived()`), float64:
+    mean = k a and var0 = sf - |G k|^2, the posterior variance without |.| and without the noise."""
+    K = kernel_host(D.lls, D.lsf, X, D.z)
+    GK = K @ D.G.T
+    return K @ D.a, D.sf - np.einsum("nm,nm->n", GK, GK)
+
+
+class _Factor(object):
+    """The inverse Cholesky factor of Kzz_expanded = k(z_e, z_e) + jitter sf I, z_e = [z; chosen points], in float64 on the
+    host: W_e = L_e^-1, extended by one row per point (never re-inverted)."""
+
+    def __init__(self, D, q: int):
+        M = D.z.shape[0]
+        self.D, self.M, self.Me = D, M, M
+        self.ze = np.zeros((M + q, D.z.shape[1]))
+        self.ze[:M] = D.z
+        self.W = np.zeros((M + q, M + q))
+        self.W[:M, :M] = D.W
+
+    def extend(self, p: np.ndarray):
+        """Append the point p: returns (c [Me], delta) with c = L_e^-1 k(p, z_e), delta = sqrt(sf + jitter sf - c^T c)."""
+        D, Me = self.D, self.Me
+        kv = kernel_host(D.lls, D.lsf, p[None, :], self.ze[:Me])[0]
+        c = self.W[:Me, :Me] @ kv
+        d2 = D.sf * (1.0 + JITTER) - float(c @ c)
+        if not d2 > 0:
+            raise FloatingPointError("batched_greedy_ei: Kzz_expanded is not positive definite at point %d" % (Me - self.M))
+        delta = math.sqrt(d2)
+        self.W[Me, :Me] = -(c @ self.W[:Me, :Me]) / delta
+        self.W[Me, Me] = 1.0 / delta
+        self.ze[Me] = p
+        self.Me = Me + 1
+        return c, delta
+
+    def point(self, x: np.ndarray):
+        """(mean, r, d mean / dx, d r / dx) at one point: r = sf - |W_e k(x, z_e)|^2 - O(Me^2)."""
+        D, Me, M = self.D, self.Me, self.M
+        ke = kernel_host(D.lls, D.lsf, x[None, :], self.ze[:Me])[0]
+        dk = -ke[:, None] * (x[None, :] - self.ze[:Me]) * D.inv_ls[None, :]
+        u = self.W[:Me, :Me] @ ke
+        return float(ke[:M] @ D.a), D.sf - float(u @ u), D.a @ dk[:M], -2.0 * ((u @ self.W[:Me, :Me]) @ dk)
+
+
+def _posterior_point(D, x: np.ndarray):
+    """(mean, var0, d mean / dx, d var0 / dx) at one point under the posterior (compute_log_ei)."""
+    k = kernel_host(D.lls, D.lsf, x[None, :], D.z)[0]
+    dk = -k[:, None] * (x[None, :] - D.z) * D.inv_ls[None, :]
+    u = D.G @ k
+    return float(k @ D.a), D.sf - float(u @ u), D.a @ dk, -2.0 * ((u @ D.G) @ dk)
+
+
+def _ei_objective(point_fn, inc: float):
+    def fun(x):
+        m, v, dm, dv = point_fn(np.asarray(x, dtype=np.float64).reshape(-1))
+        f, fm, fv = _neg_log_ei_point(m, v, inc)
+        return f, fm * dm + fv * dv
+    return fun
+
+
+def _scipy_optimize():
+    try:
+        import scipy.optimize as spo
+    except ImportError as e:   # pragma: no cover - scipy is an optional dependency
+        raise ImportError("refine='lbfgs' runs the reference's scipy.optimize.fmin_l_bfgs_b and scipy is not installed: "
+                          "install scipy, or pass refine=None to take the best grid rows") from e
+    return spo
+
+
+def _refine(fun, x0: np.ndarray, lower: np.ndarray, upper: np.ndarray):
+    """global_optimization's second half (sparse_gp.py:31-43): L-BFGS-B from the best grid row inside the bounds, maxiter 150.
+    Returns (x, f); never worse than the (clipped) start."""
+    spo = _scipy_optimize()
+    x0 = np.clip(x0, lower, upper)
+    f0 = fun(x0)[0]
+    x, f, _ = spo.fmin_l_bfgs_b(fun, x0, bounds=list(zip(lower.tolist(), upper.tolist())), maxiter=150)
+    x = np.clip(np.asarray(x, dtype=np.float64).reshape(-1), lower, upper)
+    if not f <= f0:
+        return x0, f0
+    return x, float(f)
+
+
+def _check_refine(refine):
+    if refine not in (None, "lbfgs"):
+        raise ValueError("refine must be None or 'lbfgs' (got %r)" % (refine,))
+    if refine == "lbfgs":
+        _scipy_optimize()
+
+
+def greedy_host(D, grid: np.ndarray, q: int, refine=None, lower=None, upper=None):
+    """The numpy mirror of the device flow of `batched_greedy_ei` over `grid` [N, d], in float64: incumbent (argmin of the
+    mean), first point (posterior log EI), q - 1 points by the averaged EI with the incrementally extended factor.  Returns
+    (points [q, d], info): info['incumbent'], info['index'] (the grid row of every step), info['r'] (the residual variance
+    [N] after the last step), info['bad'] (rows without a positive variance, per step)."""
+    grid = np.asarray(grid, dtype=np.float64)
+    N = grid.shape[0]
+    K = kernel_host(D.lls, D.lsf, grid, D.z)
+    mean = K @ D.a
+    GK, U0 = K @ D.G.T, K @ D.W.T
+    var0 = D.sf - np.einsum("nm,nm->n", GK, GK)
+    r = D.sf - np.einsum("nm,nm->n", U0, U0)
+    i0 = int(np.argmin(mean))
+    inc = float(mean[i0])
+    if refine:
+        inc = _refine(lambda x: _posterior_point(D, np.asarray(x, dtype=np.float64).reshape(-1))[0::2], grid[i0], lower, upper)[1]
+    keys = -log_ei_host(mean, var0, inc)
+    idx, bad = [int(np.argmin(keys))], [int((~(var0 > 0)).sum())]
+    p = grid[idx[0]]
+    if refine:
+        p = _refine(_ei_objective(lambda x: _posterior_point(D, x), inc), p, lower, upper)[0]
+    points = [p]
+    fac = _Factor(D, q)
+    U = np.zeros((N, D.z.shape[0] + q))
+    U[:, :D.z.shape[0]] = U0
+    for _ in range(1, q):
+        Me = fac.Me
+        c, delta = fac.extend(p)
+        w = (kernel_host(D.lls, D.lsf, grid, p[None, :])[:, 0] - U[:, :Me] @ c) / delta
+        U[:, Me] = w
+        r = r - w * w
+        keys = -log_ei_host(mean, r, inc)
+        idx.append(int(np.argmin(keys)))
+        bad.append(int((~(r > 0)).sum()))
+        p = grid[idx[-1]]
+        if refine:
+            p = _refine(_ei_objective(fac.point, inc), p, lower, upper)[0]
+        points.append(p)
+    return np.stack(points), {"incumbent": inc, "index": idx, "r": r, "bad": bad}
+
+
+# --------------------------------------------------------------------------------- the model
+def _as_rows(X, d: int, what: str) -> torch.Tensor:
+    if not isinstance(X, torch.Tensor):
+        X = torch.from_numpy(np.ascontiguousarray(np.asarray(X, dtype=np.float64)))
+    if X.dim() != 2 or X.shape[1] != d or not X.is_floating_point():
+        raise ValueError("%s: a floating-point [N, d=%d] matrix needed (got %s %s)" % (what, d, tuple(X.shape), X.dtype))
+    if not X.is_cuda and bool(torch.isnan(X).any()):
+        raise ValueError("%s: X holds NaN" % what)
+    return X
+
+
+def _bounds(v, d: int, what: str) -> np.ndarray:
+    a = np.asarray(v, dtype=np.float64).reshape(-1)
+    if a.size == 1:
+        a = np.full(d, float(a[0]))
+    if a.size != d:
+        raise ValueError("batched_greedy_ei: %s must hold one value per column (d=%d, got %d)" % (what, d, a.size))
+    return a
+
+
+class SparseGP(object):
+    """The reference's `SparseGP(input_means, input_vars, training_targets, n_inducing_points)` without the input variances
+    (bo.py passes zeros; ignore_variances is true).  The six parameters are float64 tensors on `device` under the reference's
+    names: lls [d], lsf [], z [M, d], mParamPost [M, 1], LParamPost [M, M], lvar_noise []."""
+
+    def __init__(self, X, y, n_inducing: int, device=None):
+        X = np.asarray(X.detach().cpu() if isinstance(X, torch.Tensor) else X, dtype=np.float64)
+        y = np.asarray(y.detach().cpu() if isinstance(y, torch.Tensor) else y, dtype=np.float64)
+        if X.ndim != 2 or X.shape[0] < 1 or X.shape[1] < 1:
+            raise ValueError("SparseGP: X must be [n >= 1, d >= 1] (got %s)" % (X.shape,))
+        if y.size != X.shape[0] or y.ndim > 2 or (y.ndim == 2 and y.shape[1] != 1):
+            raise ValueError("SparseGP: y must be [n] or [n, 1] for n = %d rows (got %s)" % (X.shape[0], y.shape))
+        if np.isnan(X).any() or np.isnan(y).any():
+            raise ValueError("SparseGP: X or y holds NaN")
+        M = int(n_inducing)
+        if not 1 <= M <= MAX_M:
+            raise ValueError("SparseGP: 1 <= n_inducing <= %d needed (got %d)" % (MAX_M, M))
+        if X.shape[1] > MAX_D:
+            raise ValueError("SparseGP: at most %d input columns (got %d)" % (MAX_D, X.shape[1]))
+        if device is None:
+            device = "cuda" if torch.cuda.is_available() else "cpu"
+        self.device = torch.device(device)
+        self.n_points, self.d_input, self.n_inducing = int(X.shape[0]), int(X.shape[1]), M
+        self.X = torch.from_numpy(np.ascontiguousarray(X)).to(self.device)
+        self.y = torch.from_numpy(np.ascontiguousarray(y.reshape(-1, 1))).to(self.device)
+        kw = dict(dtype=torch.float64, device=self.device)
+        self.lls, self.lsf = torch.zeros(self.d_input, **kw), torch.zeros((), **kw)
+        self.z, self.mParamPost = torch.zeros(M, self.d_input, **kw), torch.zeros(M, 1, **kw)
+        self.LParamPost, self.lvar_noise = torch.zeros(M, M, **kw), torch.zeros((), **kw)
+        self._cache = core.DerivedCache()
+
+    @property
+    def on_gpu(self) -> bool:
+        return self.device.type == "cuda"
+
+    def get_params(self):
+        return [self.lls, self.lsf, self.z, self.mParamPost, self.LParamPost, self.lvar_noise]
+
+    def set_params(self, params) -> None:
+        params = list(params)
+        if len(params) != 6:
+            raise ValueError("set_params: six arrays in the order of get_params() needed (got %d)" % len(params))
+        with torch.no_grad():
+            for p, v in zip(self.get_params(), params):
+                v = torch.as_tensor(np.asarray(v.detach().cpu() if isinstance(v, torch.Tensor) else v, dtype=np.float64))
+                if v.numel() != p.numel():
+                    raise ValueError("set_params: %d values for a parameter of shape %s" % (v.numel(), tuple(p.shape)))
+                p.copy_(v.reshape(p.shape))
+        self._cache.invalidate()
+
+    def initialize(self, rng=None, minibatch_size: int = 4000) -> None:
+        """The start of `train_via_ADAM` (sparse_gp.py:202-210, sparse_gp_theano_internal.py:203-234), drawing from `rng` (a
+        numpy RandomState; default: numpy's global one, as the reference) in the reference's order: the minibatch subset, the
+        inducing rows out of it, then L ~ N(0, 1)."""
+        rng = np.random if rng is None else rng
+        n, M = self.n_points, self.n_inducing
+        sub = rng.choice(n, n, replace=False)[0:min(n, int(minibatch_size))]
+        if sub.shape[0] < M:
+            raise ValueError("initialize: %d inducing points need at least as many rows (the subset has %d)" % (M, sub.shape[0]))
+        Xs, ys = self.X.cpu().numpy()[sub, :], self.y.cpu().numpy()[sub, :]
+        sel = rng.choice(Xs.shape[0], M, replace=False)
+        sq = np.outer(np.sum(Xs ** 2, 1), np.ones(Xs.shape[0]))
+        dist = sq - 2 * np.dot(Xs, Xs.T) + sq.T
+        tri = dist[np.triu_indices(Xs.shape[0], 1)]
+        med = float(np.median(tri)) if tri.size else 0.0
+        L = rng.normal(size=(M, M)) * 1.0
+        self.set_params([np.log(0.5 * (med + 1e-3)) * np.ones(self.d_input), 0.0, Xs[sel, :], ys[sel, :], L, 0.0])
+
+    # ----------------------------------------------------------------------------- training: torch ops, float64
+    def energy(self, X: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+        """The energy of one minibatch (getContributionToEnergy, sparse_gp_theano_internal.py:163-198, 255-257) with the
+        training graph's cavity factor (n - 1) / n, as a float64 scalar that autograd differentiates."""
+        n, M = float(self.n_points), self.n_inducing
+        cav = (n - 1.0) / n
+        sf, il = torch.exp(self.lsf), torch.exp(-self.lls)
+
+        def kern(a, b):   # (the reference's expansion, gauss.py:22-27: smooth where a row of a equals a row of b)
+            r2 = (a * a * il).sum(1, keepdim=True) - 2.0 * (a * il) @ b.T + ((b * b) @ il)[None, :]
+            return sf * torch.exp(-0.5 * r2)
+
+        def inv_psd(S):
+            return torch.cholesky_inverse(torch.linalg.cholesky(0.5 * (S + S.T)))
+
+        def logdet_psd(S):
+            return 2.0 * torch.log(torch.diagonal(torch.linalg.cholesky(0.5 * (S + S.T)))).sum()
+
+        eye = torch.eye(M, dtype=torch.float64, device=self.z.device)
+        Kzz = kern(self.z, self.z) + eye * (JITTER * sf)
+        KzzInv = inv_psd(Kzz)
+        LLt = self.LParamPost @ self.LParamPost.T
+        covCavInv = KzzInv + LLt * cav
+        covCav = inv_psd(covCavInv)
+        meanCav = covCav @ (cav * self.mParamPost)
+        covPostInv = KzzInv + LLt
+        covPost = inv_psd(covPostInv)
+        meanPost = covPost @ self.mParamPost
+        Kxz = kern(X, self.z)
+        B = KzzInv @ covCav @ KzzInv - KzzInv
+        v_out = sf + ((Kxz @ B) * Kxz).sum(1, keepdim=True)
+        out_mean = Kxz @ (KzzInv @ meanCav)
+        out_var = v_out.abs() + torch.exp(self.lvar_noise)
+        half = 0.5 * M * math.log(2.0 * math.pi)
+        logZcav = half + 0.5 * logdet_psd(covCav) + 0.5 * (meanCav.T @ covCavInv @ meanCav)[0, 0]
+        logZprior = half - 0.5 * logdet_psd(KzzInv)
+        logZpost = half + 0.5 * logdet_psd(covPost) + 0.5 * (meanPost.T @ covPostInv @ meanPost)[0, 0]
+        logZ = -0.5 * torch.log(2.0 * math.pi * out_var) - 0.5 * (y.reshape(-1, 1) - out_mean) ** 2 / out_var
+        return ((logZcav - logZpost) + logZpost / n - logZprior / n) * float(X.shape[0]) + logZ.sum()
+
+    def train_via_adam(self, X_test=None, y_test=None, max_iterations: int = 500, minibatch_size: int = 4000,
+                       learning_rate: float = 1e-3, rng=None, verbose: bool = True, initialize: bool = True):
+        """`train_via_ADAM` (sparse_gp.py:195-270): `initialize`, then per epoch the reference's shuffle and minibatches, every
+        minibatch one step of `torch.optim.Adam` (default betas, eps = 1e-8: the rule of `adam_theano`) on minus the energy.
+        With `verbose` (and a test set) the epoch's train / test RMSE and test log-likelihood are printed, through `predict`.
+        Returns the last minibatch's energy."""
+        rng = np.random if rng is None else rng
+        mb = int(minibatch_size)
+        if mb < 1 or int(max_iterations) < 0:
+            raise ValueError("train_via_adam: minibatch_size >= 1 and max_iterations >= 0 needed")
+        if initialize:
+            self.initialize(rng, mb)
+        Xt = yt = None
+        if X_test is not None:
+            Xt = _as_rows(X_test, self.d_input, "train_via_adam").to(self.device, torch.float64)
+            yt = torch.as_tensor(np.asarray(y_test.cpu() if isinstance(y_test, torch.Tensor) else y_test, dtype=np.float64)).reshape(-1, 1).to(self.device)
+        params = self.get_params()
+        for p in params:
+            p.requires_grad_(True)
+        opt = torch.optim.Adam(params, lr=float(learning_rate), betas=(0.9, 0.999), eps=1e-8)
+        X, y, n = self.X, self.y, self.n_points
+        n_batches = int(np.ceil(1.0 * n / mb))
+        last = None
+        try:
+            for j in range(int(max_iterations)):
+                perm = torch.from_numpy(np.asarray(rng.choice(n, n, replace=False), dtype=np.int64)).to(self.device)
+                X, y = X[perm], y[perm]
+                for i in range(n_batches):
+                    opt.zero_grad(set_to_none=True)
+                    loss = -self.energy(X[i * mb:min((i + 1) * mb, n)], y[i * mb:min((i + 1) * mb, n)])
+                    loss.backward()
+                    opt.step()
+                    last = loss.detach()
+                self._cache.invalidate()
+                if verbose:
+                    tr = self.report(X, y)
+                    msg = "Epoch %d, Train error: %.4f" % (j, tr["rmse"])
+                    if Xt is not None:
+                        te = self.report(Xt, yt)
+                        msg += " Test error: %.4f Test ll: %.4f" % (te["rmse"], te["ll"])
+                    print(msg, flush=True)
+        finally:
+            for p in params:
+                p.requires_grad_(False)
+            self._cache.invalidate()
+        return None if last is None else -float(last)
+
+    # ----------------------------------------------------------------------------- derived matrices
+    def derived(self):
+        """The matrices the prediction side runs on, derived in float64 (torch.linalg on the model's device) once per
+        parameter version (`core.DerivedCache`): host copies (z, ls, a, G, W = L^-1: numpy float64) and, on the GPU, the
+        kernels' operands rounded to fp32 (zt, inv_ls, Tt = [G; W]^T, a)."""
+        return self._cache.get(self.get_params(), self._derive)
+
+    def _derive(self):
+        M = self.n_inducing
+        z, il, sf = self.z.detach(), torch.exp(-self.lls.detach()), torch.exp(self.lsf.detach())
+        eye = torch.eye(M, dtype=torch.float64, device=z.device)
+        df = z[:, None, :] - z[None, :, :]
+        Kzz = sf * torch.exp(-0.5 * (df * df * il).sum(-1)) + eye * (JITTER * sf)
+        L = torch.linalg.cholesky(Kzz)
+        W = torch.linalg.solve_triangular(L, eye, upper=False)
+        Lp = self.LParamPost.detach()
+        A = L.T @ (Lp @ Lp.T) @ L
+        lam, V = torch.linalg.eigh(0.5 * (A + A.T))
+        lam = lam.clamp_min(0.0)
+        G = (torch.sqrt(lam / (1.0 + lam))[:, None] * V.T) @ W              # R L^-1, R^T R = I - (I + A)^-1
+        S = (V / (1.0 + lam)[None, :]) @ V.T                                  # (I + A)^-1
+        a = torch.linalg.solve_triangular(L.T, S @ (L.T @ self.mParamPost.detach()), upper=True).reshape(-1)
+        h = lambda t: t.cpu().numpy()   # noqa: E731
+        D = SimpleNamespace(lls=h(self.lls.detach()), lsf=float(self.lsf), sf=float(sf), inv_ls=h(il), z=h(z), a=h(a), G=h(G), W=h(W),
+                            noise=math.exp(float(self.lvar_noise)), M=M, d=self.d_input)
+        if self.on_gpu:
+            f = lambda t: t.to(torch.float32).contiguous()   # noqa: E731
+            D.zt, D.inv_ls32, D.a32, D.Tt = f(z.T), f(il), f(a), f(torch.cat([G, W], 0).T)
+        return D
+
+    # ----------------------------------------------------------------------------- prediction
+    def _rows32(self, X, what: str) -> torch.Tensor:
+        X = _as_rows(X, self.d_input, what)
+        return X.to(self.device, torch.float32, non_blocking=True)
+
+    def predict(self, X):
+        """(mean, var) of the rows of X, float64 [N, 1] on the model's device: var = |sf - |G k|^2| + exp(lvar_noise).  On the GPU
+        one launch of `dagnn_sgp_project` (fp32), nothing synchronises."""
+        D = self.derived()
+        if not self.on_gpu:
+            X = _as_rows(X, self.d_input, "predict")
+            m, v = predict_host(D, X.detach().numpy())
+            return torch.from_numpy(m).reshape(-1, 1), torch.from_numpy(np.abs(v) + D.noise).reshape(-1, 1)
+        X = self._rows32(X, "predict")
+        m, v, _ = engine.sgp_project(X, D.zt, D.inv_ls32, D.sf, D.Tt, D.M, D.M, D.a32, want_var0=True)
+        return m.double().reshape(-1, 1), (v.double().abs() + D.noise).reshape(-1, 1)
+
+    def report(self, X, y) -> dict:
+        """What the reference prints of a fit (sparse_gp.py:250-252, bo.py:265-270): rmse = sqrt(mean (pred - y)^2), ll = mean
+        log N(pred - y; 0, var), pearson = pearsonr(pred, y)[0], n.  On the GPU the sums are `dagnn_fit_sums` and the call
+        synchronises once."""
+        m, v = self.predict(X)
+        y = torch.as_tensor(np.asarray(y, dtype=np.float64)) if not isinstance(y, torch.Tensor) else y
+        y = y.reshape(-1, 1).to(m.device, torch.float64)
+        n = m.shape[0]
+        if y.shape[0] != n or n < 1:
+            raise ValueError("report: y must hold one value per row of X (got %d for %d rows)" % (y.shape[0], n))
+        ll = (-0.5 * torch.log(2.0 * math.pi * v) - 0.5 * (m - y) ** 2 / v).sum().reshape(1)
+        if self.on_gpu:   # p = (-pred - 0) / 1 of dagnn_fit_sums: hand it minus the mean
+            s = torch.cat([engine.fit_sums((-m).reshape(-1).float(), y.reshape(-1), 0.0, 1.0), ll]).tolist()
+        else:
+            p, t = m.reshape(-1).numpy(), y.reshape(-1).numpy()
+            s = [p.sum(), t.sum(), (p * p).sum(), (t * t).sum(), (p * t).sum(), ((p - t) ** 2).sum(), float(ll)]
+        sp, sy, spp, syy, spy, sd, sll = (float(x) for x in s)
+        cov, vp, vy = spy - sp * sy / n, spp - sp * sp / n, syy - sy * sy / n
+        return {"rmse": math.sqrt(sd / n), "ll": sll / n, "pearson": cov / math.sqrt(vp * vy) if vp > 0 and vy > 0 else float("nan"),
+                "n": n}
+
+    # ----------------------------------------------------------------------------- the acquisition
+    def log_ei(self, X, incumbent: float) -> torch.Tensor:
+        """`compute_log_ei(x, incumbent)` per row of X, float64 [N] on the model's device: the posterior mean and variance
+        (no |.|, no noise), NaN where the variance is not positive."""
+        D = self.derived()
+        if not self.on_gpu:
+            X = _as_rows(X, self.d_input, "log_ei")
+            m, v = predict_host(D, X.detach().numpy())
+            return torch.from_numpy(log_ei_host(m, v, incumbent))
+        X = self._rows32(X, "log_ei")
+        m, v, _ = engine.sgp_project(X, D.zt, D.inv_ls32, D.sf, D.Tt, D.M, D.M, D.a32, want_var0=True)
+        return -engine.sgp_ei_step(_lib.SGP_ARGMIN_EI, m, v, float(incumbent), want_keys=True)[1]
+
+    def get_incumbent(self, grid, lower=None, upper=None, refine="lbfgs") -> float:
+        """`get_incumbent` (sparse_gp.py:272-283): the smallest predictive mean - over the grid, then refined from the best row
+        by L-BFGS-B inside the bounds (refine=None: the best grid row's mean)."""
+        _check_refine(refine)
+        D = self.derived()
+        grid = _as_rows(grid, self.d_input, "get_incumbent")
+        if self.on_gpu:
+            g32 = grid.to(self.device, torch.float32)
+            m, _, _ = engine.sgp_project(g32, D.zt, D.inv_ls32, D.sf, None, 0, 0, D.a32)
+            res = engine.sgp_ei_step(_lib.SGP_ARGMIN_MEAN, m, m)[0].cpu().numpy()
+            i0, inc = int(res[0]), float(res[2:3].view(np.float64)[0])
+            x0 = g32[i0].double().cpu().numpy() if refine else None
+        else:
+            mean = predict_host(D, grid.detach().numpy().astype(np.float64))[0]
+            i0 = int(np.argmin(mean))
+            inc, x0 = float(mean[i0]), grid[i0].detach().numpy().astype(np.float64)
+        if refine:
+            d = self.d_input
+            inc = _refine(lambda x: _posterior_point(D, np.asarray(x, dtype=np.float64).reshape(-1))[0::2], x0,
+                          _bounds(lower, d, "lower"), _bounds(upper, d, "upper"))[1]
+        return inc
+
+    def batched_greedy_ei(self, q: int, lower, upper, mean=None, std=None, sample: str = "normal", grid=None,
+                          grid_size: int = 10000, rng=None, refine="lbfgs", return_info: bool = False):
+        """`batched_greedy_ei` (sparse_gp.py:296-335): q points [q, d] (float64 numpy) - the incumbent, the first point by
+        `compute_log_ei`, q - 1 points by `compute_log_averaged_ei` (n_samples = 1, zero randomness: the posterior mean and the
+        prior variance given z and the points chosen so far).  grid=None draws the reference's grid from `rng`
+        (sample='normal': mean + randn std; 'uniform': lower + rand (upper - lower)).  Every step is one grid evaluation
+        (`dagnn_sgp_ei_step` on the GPU: one launch and one 32-byte read) and, with refine='lbfgs', the reference's L-BFGS-B from
+        the best grid row (float64 on the host, scipy); refine=None returns the best grid rows."""
+        _check_refine(refine)
+        q, d = int(q), self.d_input
+        if not 1 <= q <= MAX_Q:
+            raise ValueError("batched_greedy_ei: 1 <= q <= %d needed (got %d)" % (MAX_Q, q))
+        lo, up = _bounds(lower, d, "lower"), _bounds(upper, d, "upper")
+        if grid is None:
+            rng = np.random if rng is None else rng
+            if sample == "normal":
+                if mean is None or std is None:
+                    raise ValueError("batched_greedy_ei: sample='normal' needs mean and std")
+                grid = np.asarray(mean, dtype=np.float64) + rng.randn(int(grid_size), d) * np.asarray(std, dtype=np.float64)
+            elif sample == "uniform":
+                grid = lo + rng.rand(int(grid_size), d) * (up - lo)
+            else:
+                raise ValueError("batched_greedy_ei: sample must be 'normal' or 'uniform' (got %r)" % (sample,))
+        grid = _as_rows(grid, d, "batched_greedy_ei")
+        if grid.shape[0] < 1:
+            raise ValueError("batched_greedy_ei: the grid has no row")
+        D = self.derived()
+        if not self.on_gpu:
+            points, info = greedy_host(D, grid.detach().numpy(), q, refine, lo, up)
+            return (points, info) if return_info else points
+        return self._greedy_gpu(D, grid, q, refine, lo, up, return_info)
+
+    def _greedy_gpu(self, D, grid, q, refine, lo, up, return_info):
+        M, N, dev = D.M, grid.shape[0], self.device
+        g32 = grid.to(dev, torch.float32).contiguous()
+        host = g32.double().cpu().numpy()   # the rows as the kernels see them
+        U = torch.empty(N, M + q, dtype=torch.float32, device=dev)
+        mean, var0, r = engine.sgp_project(g32, D.zt, D.inv_ls32, D.sf, D.Tt, 2 * M, M, D.a32, U=U, u_col0=M, want_var0=True,
+                                           want_var1=True)
+
+        def read(res):
+            res = res.cpu().numpy()   # the step's one read
+            return int(res[0]), int(res[1]), float(res[2:3].view(np.float64)[0])
+
+        i0, _, inc = read(engine.sgp_ei_step(_lib.SGP_ARGMIN_MEAN, mean, var0)[0])
+        if refine:
+            inc = _refine(lambda x: _posterior_point(D, np.asarray(x, dtype=np.float64).reshape(-1))[0::2], host[i0], lo, up)[1]
+        i, nb, _ = read(engine.sgp_ei_step(_lib.SGP_ARGMIN_EI, mean, var0, inc)[0])
+        idx, bad = [i], [nb]
+        p = host[i]
+        if refine:
+            p = _refine(_ei_objective(lambda x: _posterior_point(D, x), inc), p, lo, up)[0]
+        points = [p]
+        fac = _Factor(D, q)
+        stage = torch.empty(q, self.d_input + M + q, dtype=torch.float32).pin_memory()   # (a row per step: p, then c)
+        for j in range(1, q):
+            Me = fac.Me
+            c, delta = fac.extend(p)
+            row = stage[j]
+            row[:self.d_input] = torch.from_numpy(p)
+            row[self.d_input:self.d_input + Me] = torch.from_numpy(c)
+            pc = row.to(dev, non_blocking=True)
+            res = engine.sgp_ei_step(_lib.SGP_ARGMIN_EI, mean, r, inc,
+                                     update=(g32, D.inv_ls32, D.sf, pc[:self.d_input], U, Me, pc[self.d_input:], 1.0 / delta))[0]
+            i, nb, _ = read(res)
+            idx.append(i)
+            bad.append(nb)
+            p = host[i]
+            if refine:
+                p = _refine(_ei_objective(fac.point, inc), p, lo, up)[0]
+            points.append(p)
+        points = np.stack(points)
+        if return_info:
+            return points, {"incumbent": inc, "index": idx, "r": r, "bad": bad}
+        return points
+
+
+# --------------------------------------------------------------------------------- a BO round
+def bo_round(sgp: SparseGP, model, q: int, lower, upper, mean=None, std=None, data=None, decode_attempts: int = 500,
+             data_type: Optional[str] = None, **greedy):
+    """bo.py:289-306 as two calls: `batched_greedy_ei` proposes q latent points, then `decode_and_score` (with a `BnData`: the
+    BN objective) or `decode_from_latent_space` decodes them on `model`.  Returns (points [q, nz] float64 numpy, strings,
+    scores float64 numpy [q] or None).  `greedy`: further arguments of `batched_greedy_ei` (sample, grid, grid_size, rng,
+    refine)."""
+    from . import bn_score, dvae
+    points = sgp.batched_greedy_ei(q, lower, upper, mean, std, **greedy)
+    dev = next(model.parameters()).device
+    zq = torch.from_numpy(np.ascontiguousarray(points, dtype=np.float32)).to(dev)
+    if data is not None:
+        strings, scores = bn_score.decode_and_score(zq, model, data, decode_attempts=decode_attempts)
+        return points, strings, scores
+    strings = dvae.decode_from_latent_space(zq, model, decode_attempts=decode_attempts, data_type=data_type or "ENAS")
+    return points, strings, None

@@ -1456,6 +1456,47 @@ int dagnn_bn_score(const dagnn_bn_data* d, const uint32_t* parents, const int32_
 int dagnn_bn_rows_to_parents(const int32_t* types, const int32_t* preds, const int32_t* nv, int64_t R, int n, int nvt,
                              int start_type, int end_type, uint32_t* parents, int32_t* valid, void* stream);
 
+/* The sparse GP of the D-VAE BO loop (csrc/sgp.hip): what `SparseGP.predict` and `batched_greedy_ei` of
+ * bayesian_optimization/sparse_gp.py evaluate on every grid row.  Kernel: k(x, z_m) = sf exp(-1/2 sum_c (x_c - z_mc)^2 / ls_c)
+ * over M <= DAGNN_SGP_MAX_M inducing rows of d <= DAGNN_SGP_MAX_D columns.
+ *
+ * dagnn_sgp_project: for the N rows of X (fp32, row pitch ld_x >= d) the tile k(X, z) is built in LDS and multiplied on the
+ * fp32 matrix cores by a matrix T [Mt, M], Mt <= 2 DAGNN_SGP_MAX_M; k never goes to memory.  Derived operands, all fp32:
+ *     zt [d, ld_z]  the inducing rows transposed (zt[c * ld_z + m] = z[m][c]),   inv_ls [d] = 1 / ls,
+ *     Tt [M, ld_t]  T transposed (Tt[k * ld_t + j] = T[j][k]),                   a [M].
+ * With u = T k(x, z), each output may be NULL:
+ *     U    [N, ld_u]: the columns j >= u_col0 of u at U[x * ld_u + j - u_col0]  (ld_u >= Mt - u_col0),
+ *     var0 [N] = sf - sum over j <  split of u_j^2,      var1 [N] = sf - sum over split <= j < Mt of u_j^2,
+ *     mean [N] = k(x, z) . a   (a may be NULL only with mean).
+ * Every sum has one fixed order and there is no atomic: the outputs are bitwise repeatable, and a row's value does not
+ * depend on N or on the other rows.
+ *
+ * dagnn_sgp_ei_step: one greedy step over the whole grid and the argmin behind it.  With U != NULL the launch first appends
+ * a chosen point p [d] to the factor: for every row, w = (k(x, p) - U[x, 0:Me] . c) * inv_delta (c [Me] = L_e^-1 k(p, z_e) and
+ * delta from the host, in fp32), U[x, Me] = w (ld_u > Me) and r[x] -= w^2.  Then per row, in float64 from the fp32 mean[x] and
+ * r[x]: mode DAGNN_SGP_ARGMIN_MEAN: the key is mean[x]; mode DAGNN_SGP_ARGMIN_EI: with v = r[x], s = (incumbent - mean) / sqrt(v),
+ *     log EI = log((incumbent - mean) ratio(s) + sqrt(v)) - 1/2 log(2 pi) - 1/2 s^2,
+ *     ratio(s) = -(1/s - 1/s^3 + 3/s^5 - 15/s^7) for s < -10, else (1/2 erfc(-s / sqrt 2)) / (exp(-s^2 / 2) / sqrt(2 pi)),
+ * the key is -log EI, NaN where v is not positive.  keys (may be NULL) [N] receives every key.  result [4] int64:
+ * {argmin as numpy.argmin gives it - the lowest index wins a tie, the first NaN wins -, rows whose v is not positive (mode EI),
+ *  the bits of the winning key, 0}.  Workgroup partials are merged by the last workgroup to draw a ticket on `counter` (a
+ * zeroed device word, left zero); work: dagnn_sgp_ei_step_bytes(N) bytes, 8-byte aligned.
+ *
+ * Borrowed pointers, the caller's stream, no allocation, no synchronisation; arguments are validated before any HIP call. */
+#define DAGNN_SGP_MAX_M 512
+#define DAGNN_SGP_MAX_D 128
+#define DAGNN_SGP_MAX_Q 128
+#define DAGNN_SGP_ARGMIN_MEAN 0
+#define DAGNN_SGP_ARGMIN_EI 1
+int dagnn_sgp_project(const float* X, int64_t ld_x, int64_t N, int d, int M, const float* zt, int64_t ld_z, const float* inv_ls,
+                      float sf, const float* Tt, int64_t ld_t, int Mt, int split, const float* a, float* U, int64_t ld_u,
+                      int u_col0, float* var0, float* var1, float* mean, void* stream);
+size_t dagnn_sgp_ei_step_bytes(int64_t N);
+int dagnn_sgp_ei_step(int mode, int64_t N, const float* mean, float* r, double incumbent, const float* X, int64_t ld_x, int d,
+                      const float* inv_ls, float sf, const float* p, float* U, int64_t ld_u, int Me, const float* c,
+                      float inv_delta, double* keys, int64_t* result, void* work, size_t work_bytes, unsigned* counter,
+                      void* stream);
+
 /* The tail of the reference's training step - `clip_grad_norm_(model.parameters(), clip)` + `optim.Adam.step()`
  * (ogbg-code/main_pyg.py:63-65,179) - over a table of fp32 tensors (csrc/optim.hip).  dagnn_grad_norm: the 2-norm of up to
  * DAGNN_MAX_OPT_TENSORS gradients (`partial`: scratch of dagnn_opt_chunks() floats; `accumulate` != 0 adds the tensors' sum of
