@@ -41,14 +41,8 @@ namespace {
 
 typedef float bf4 __attribute__((ext_vector_type(4)));
 
-#ifndef BD_NSLOT_V
-#define BD_NSLOT_V 3
-#endif
-constexpr int BD_NSLOT = BD_NSLOT_V;   // LDS ring depth per stream (a slot holds 3 operand rows per block row; 2 / 3 / 4: the same time)
-#ifndef BD_WPS_V
-#define BD_WPS_V 4
-#endif
-constexpr int BD_WPS = BD_WPS_V;     // loader waves per stream (4: one row of a block each; 2: the 8-wave shape of H = 320, two rows each)
+constexpr int BD_NSLOT = 3;          // LDS ring depth per stream (a slot holds 3 operand rows per block row; 2 / 3 / 4: the same time)
+constexpr int BD_WPS = 4;            // loader waves per stream: one row of a block each
 constexpr int BD_RPW = DF_RB / BD_WPS;   // rows of a block per loader wave, one after the other
 constexpr int BD_NLW = DF_NLS * BD_WPS;
 constexpr int BD_THREADS = 64 * (DF_NCW + BD_NLW);
@@ -66,7 +60,7 @@ constexpr int BD_RECW = 64;
 // rows) and dgh; a block costs the compute waves more than a row costs its loader, and they serve two streams (measured per
 // workgroup shape in round 4; the compute-wave forms of these stores live in scripts/experiments/).  The compute
 // wave of row r keeps sigma_v and the edge-feature sums of slice BD_SCAL_SL.
-static_assert(BD_WPS_V == 4, "the workgroup shape: 4 compute + 2 x 4 loader waves (the 8-wave shape of round 4 is in scripts/experiments/)");
+static_assert(BD_WPS == 4, "the workgroup shape: 4 compute + 2 x 4 loader waves (the 8-wave shape of round 4 is in scripts/experiments/)");
 constexpr int BD_SCAL_SL = 1;        // slice whose compute waves store sigma_v and the edge-feature sums (slice 0 stores q_v)
 enum { BD_DA = 0, BD_DU = 1 };
 enum { ST_GEXT = DF_ST_GEXT, ST_H = DF_ST_H, ST_CR = DF_ST_CR, ST_CZ = DF_ST_CZ, ST_CNR = DF_ST_CNR, ST_CN = DF_ST_CN, ST_Z = DF_ST_Z, ST_CQ = DF_ST_CQ };
@@ -1039,7 +1033,6 @@ __device__ __forceinline__ void bd_compute(const BdArgs& S, const BdCell& C, int
             float gsum;
             {
                 bf4 acc[3] = {(bf4){0.f, 0.f, 0.f, 0.f}, (bf4){0.f, 0.f, 0.f, 0.f}, (bf4){0.f, 0.f, 0.f, 0.f}};
-#ifndef BD_EXP_NOMFMA   // (timing experiment, scripts/build_variant.sh)
 #pragma unroll
                 for (int q = 0; q < NK4; ++q) {
                     const float4 b0 = *reinterpret_cast<const float4*>(a_seg + 4 * q);
@@ -1053,7 +1046,6 @@ __device__ __forceinline__ void bd_compute(const BdArgs& S, const BdCell& C, int
                         acc[2] = __builtin_amdgcn_mfma_f32_4x4x1f32(wn[4 * q + e], q2[e], acc[2], 0, 0, 0);
                     }
                 }
-#endif
                 // the look for the NEXT block: issued behind the last product, read at the top of the next iteration
                 __builtin_amdgcn_sched_barrier(0);
                 const i4v r0 = rdy_p[0], r1 = rdy_p[1];

@@ -7,10 +7,7 @@
 //     waves, two rows of a block per loader wave, one after the other).  The lean compute loop of round 6 fits 168 once the
 //     operand reads are left to stream two registers ahead of the products (df_compute: no early-read barrier above H = 256),
 //     so the kernel has the 12-wave shape of H <= 256 again - one row per loader wave: recurrence 2.18 -> 1.75 ms on the
-//     emb_dim-300 bench batch (B = 160), bitwise the same results.  -DDF_NLW_V=4 still builds the 8-wave shape;
+//     emb_dim-300 bench batch (B = 160), bitwise the same results (the 8-wave shape: scripts/experiments/dataflow_8wave.patch);
 //   * a loader lane carries five column blocks of a row (five 8-byte loads per polled row).
 #define DF_WIDE_TU 1
-#ifndef DF_NLW_V
-#define DF_NLW_V 8
-#endif
 #include "dataflow.hip"

@@ -14,12 +14,9 @@ constexpr int DF_NLS = 2;          // streams per workgroup = loader sets: set s
 constexpr int DF_NSLOT = 4;             // LDS ring depth (blocks the loaders may run ahead)
 // (Measured and removed: two chunks per trip for rows with > 4 in-edges - the second sweep's 32 registers spilled the
 // loader at 3 waves per SIMD.)
-#ifndef DF_NLW_V
-#define DF_NLW_V (12 - DF_NCW)
-#endif
-constexpr int DF_NLW = DF_NLW_V;                 // loader waves per workgroup (12 waves = 3 per SIMD at <= 168 VGPRs)
+constexpr int DF_NLW = 12 - DF_NCW;         // loader waves per workgroup (12 waves = 3 per SIMD at <= 168 VGPRs)
 constexpr int DF_WPS = DF_NLW / DF_NLS;     // ... per stream
-constexpr int DF_RPW = DF_RB / DF_WPS;      // rows of a block per loader wave (one after the other)
+constexpr int DF_RPW = DF_RB / DF_WPS;      // rows of a block per loader wave: one
 // group served by stream `set` of workgroup set `pair` (-1: none)
 __device__ __host__ __forceinline__ int df_group_of_stream(int pair, int set, int groups) {
     const int g = DF_NLS * pair + set;

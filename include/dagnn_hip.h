@@ -386,10 +386,6 @@ typedef struct dagnn_dataflow_args {
                             * adds the external-gradient row (dagnn_bwd_dataflow_args.stat_rows_written).  The records are
                             * addressed with 32-bit byte offsets: N x 4 x (8 x 256) bytes (H <= 256) or N x 4 x (8 x 320) bytes
                             * (H = 320) must stay below 2^32, otherwise the call returns DAGNN_EINVAL */
-    int slices64;           /* nonzero and H = 256 / 320: the workgroup shape of csrc/dataflow_x.hip - 64 hidden units, 8 compute
-                            * waves and one stream per workgroup, `groups` workgroup sets of (kernel cells x H / 64) workgroups
-                            * (the caller guarantees they fit the device: groups <= 2 * floor(CUs / (cells x H / 32)), what
-                            * dagnn_dataflow_groups returns).  Same schedule, same results */
 } dagnn_dataflow_args;
 
 int dagnn_dataflow_groups(int num_cus, int num_dirs, int num_stacked, int H, int64_t B);
@@ -398,11 +394,10 @@ int dagnn_dataflow_schedule(const dagnn_plan* plan /* host */, void* workspace, 
                             int cost_layer, int cost_row, const int32_t* plan_status /* device, or NULL */, void* stream);
 int dagnn_dataflow_run(const dagnn_plan* plan /* host */, const dagnn_dataflow_args* args /* host */, void* stream);
 /* H = 320 (hidden sizes 257..320, zero-padded by the caller: the reference trains at emb_dim = 300, scripts/ogb_tok.sh:17): the
- * same launch in an 8-wave workgroup shape (csrc/dataflow_w.hip).  Exactly two edge features, no static scores, no vertex-id
+ * same launch, same workgroup shape, in a translation unit of its own (csrc/dataflow_w.hip).  Exactly two edge features, no static scores, no vertex-id
  * key biases (anything else: DAGNN_EINVAL - the caller keeps such models on the other paths).  dagnn_dataflow_run forwards
  * H > 256 here; dagnn_dataflow_groups / dagnn_pack_dataflow accept H = 320. */
 int dagnn_dataflow_run_wide(const dagnn_plan* plan /* host */, const dagnn_dataflow_args* args /* host */, void* stream);
-int dagnn_dataflow_run_x(const dagnn_plan* plan /* host */, const dagnn_dataflow_args* args /* host */, void* stream);   /* slices64 */
 int dagnn_pack_dataflow(const float* w /* [3H,H] */, float* out /* 3H*H floats */, int H, void* stream);
 /* the same order of the gate-wise transposed matrix W'[g H + j][u] = W[g H + u][j] (reverse sweep, dagnn_bwd_dataflow_run) */
 int dagnn_pack_dataflow_transposed(const float* w /* [3H,H] */, float* out /* 3H*H floats */, int H, void* stream);

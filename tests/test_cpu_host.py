@@ -93,7 +93,7 @@ def test_host_only_entry_points_without_gpu():
 
 def test_dataflow_argument_structs_carry_the_round6_fields():
     """`dagnn_dataflow_args.stat_rows` (the forward launch of a training pass writes the reverse sweep's static rows into the
-    buffers passed as `gh_out`; `gi_out` must then be NULL) and `slices64`, `dagnn_bwd_dataflow_args.stat_rows_written`: the
+    buffers passed as `gh_out`; `gi_out` must then be NULL), `dagnn_bwd_dataflow_args.stat_rows_written`: the
     ctypes mirrors end where the C structs end, and the one bad value each case plants is refused before any HIP call."""
     lib = _lib.load()
     plan = _lib.Plan(64, 0, 4, 3, 1, 2, 0)
@@ -111,19 +111,19 @@ def test_dataflow_argument_structs_carry_the_round6_fields():
     assert lib.dagnn_dataflow_run(ctypes.byref(plan), ctypes.byref(a), None) == -22
     a.cell[0][1].gi_out, a.cell[0][1].gh_out = None, None   # a cell without its record buffer
     assert lib.dagnn_dataflow_run(ctypes.byref(plan), ctypes.byref(a), None) == -22
-    a.cell[0][1].gh_out, a.slices64, a.H = 64, 1, 192       # the 64-unit shape exists for H = 256 / 320: other widths take the 32-unit one
+    a.cell[0][1].gh_out, a.H = 64, 192                      # the same at another width
     a.cell[0][1].gi_out = 64
     assert lib.dagnn_dataflow_run(ctypes.byref(plan), ctypes.byref(a), None) == -22
-    a.H = 128                                                # ... and its own entry point refuses them
-    assert lib.dagnn_dataflow_run_x(ctypes.byref(plan), ctypes.byref(a), None) == -22
-    assert _lib.DataflowArgs.slices64.offset == ctypes.sizeof(_lib.DataflowArgs) - 8 or _lib.DataflowArgs.slices64.offset == ctypes.sizeof(_lib.DataflowArgs) - 4
+    # `stat_rows` is the last field: the mirror ends where the C struct ends (up to the tail padding of its 8-byte alignment)
+    assert _lib.DataflowArgs._fields_[-1][0] == "stat_rows"
+    assert _lib.DataflowArgs.stat_rows.offset + 4 in (ctypes.sizeof(_lib.DataflowArgs), ctypes.sizeof(_lib.DataflowArgs) - 4)
     assert _lib.BwdDataflowArgs.stat_rows_written.offset >= _lib.BwdDataflowArgs.xcd_first.offset + 4
 
 
 @pytest.mark.parametrize("H,N", [(256, 600000), (256, 524288), (320, 420000)])
 def test_dataflow_refuses_static_rows_beyond_32_bit_record_offsets(H, N):
     """With `stat_rows` the forward launch addresses every node's static record (8 rows of 256 floats, 320 for H = 320) with
-    a 32-bit byte offset: all three entry points refuse a batch whose records reach 2^32 bytes before any HIP call.  The same
+    a 32-bit byte offset: both entry points refuse a batch whose records reach 2^32 bytes before any HIP call.  The same
     struct is otherwise valid (N x granule pitch < 2^31, N < 2^24)."""
     lib = _lib.load()
     plan = _lib.Plan(64, 0, N, 2 * N, 1000, 2, 0)
@@ -137,11 +137,8 @@ def test_dataflow_refuses_static_rows_beyond_32_bit_record_offsets(H, N):
     a.stat_rows = 1
     assert N * 8 * (320 if H > 256 else 256) * 4 >= 1 << 32 and N * gld < 1 << 31
     assert lib.dagnn_dataflow_run(ctypes.byref(plan), ctypes.byref(a), None) == -22
-    entry = lib.dagnn_dataflow_run_wide if H > 256 else lib.dagnn_dataflow_run_x
-    assert entry(ctypes.byref(plan), ctypes.byref(a), None) == -22
-    a.slices64 = 1
-    assert lib.dagnn_dataflow_run(ctypes.byref(plan), ctypes.byref(a), None) == -22
-    assert lib.dagnn_dataflow_run_x(ctypes.byref(plan), ctypes.byref(a), None) == -22
+    if H > 256:
+        assert lib.dagnn_dataflow_run_wide(ctypes.byref(plan), ctypes.byref(a), None) == -22
 
 
 def test_engine_refuses_cpu_tensors():

@@ -854,45 +854,6 @@ def test_static_rows_from_the_forward_launch_feed_the_reverse_sweep(device, monk
         assert Hh.maxdiff(g, ref) <= 2e-5 * max(float(ref.abs().max()), 1e-3), k
 
 
-@pytest.mark.parametrize("H,L", [(256, 2), (320, 1)])
-def test_sixty_four_unit_slices_are_the_same_pass(device, monkeypatch, H, L):
-    """`DAGNN_AMD_DF_SLICES64=1` (csrc/dataflow_x.hip): the forward dataflow kernel with 64 hidden units, 8 compute waves and one
-    stream per workgroup - the same schedule, packed weights and arithmetic, so logits, loss and every gradient of a training
-    step (its forward writes the reverse sweep's static rows from that shape) agree with the 32-unit shape to the last bit; the
-    entry point really ran."""
-    from dagnn_amd import _lib
-    lib = _lib.load()
-    model = _headline_model(H=H, L=L, V=32, seed=8).to(device)
-    b = synth.code2_batch(14, 96, 125)
-    y = torch.randint(0, 32, (96, 5), generator=torch.Generator().manual_seed(3)).to(device)
-    seen = []
-    orig = lib.dagnn_dataflow_run
-
-    class _Spy(object):
-        def __call__(self, plan, args, stream):
-            seen.append(int(args._obj.slices64))
-            return orig(plan, args, stream)
-    monkeypatch.setattr(lib, "dagnn_dataflow_run", _Spy(), raising=False)
-    got = {}
-    for flag in (0, 1):
-        monkeypatch.setattr(engine, "DF_SLICES64", flag)
-        model.eval()
-        with torch.no_grad():
-            logits = torch.stack(model(b.clone().to(device)))
-        model.check()
-        loss, grads = _train_step(model, b.clone().to(device), y)
-        model.check()
-        got[flag] = (logits.clone(), loss.clone(), {k: v.clone() for k, v in grads.items()})
-    assert 0 in seen and 1 in seen, seen
-    assert torch.equal(got[0][0], got[1][0])
-    assert torch.equal(got[0][1], got[1][1])
-    for k, g in got[1][2].items():
-        if "encoder." in k:   # (torch's embedding backward accumulates with atomics)
-            assert Hh.maxdiff(g, got[0][2][k]) <= 1e-6 * max(1.0, float(got[0][2][k].abs().max())), k
-        else:
-            assert torch.equal(g, got[0][2][k]), k
-
-
 def _degenerate_batch(extra=()):
     """Single-node graphs, a chain, stars with a 200-way fan-in / fan-out, a graph with no edges, a duplicate edge
     (`extra`: more graphs behind them)."""
@@ -2371,7 +2332,7 @@ def _spy_entries(monkeypatch, fields):
     return seen
 
 
-_TRAIN_ENTRIES = {"dagnn_dataflow_run": ("H", "stat_rows", "slices64"), "dagnn_bwd_dataflow_prepare": ("H", "stat_rows_written"),
+_TRAIN_ENTRIES = {"dagnn_dataflow_run": ("H", "stat_rows"), "dagnn_bwd_dataflow_prepare": ("H", "stat_rows_written"),
                   "dagnn_bwd_dataflow_run": ("H",), "dagnn_backward_run": ("H",)}
 
 
@@ -2396,15 +2357,14 @@ def _full_size_training_step(device, model, b, y, key):
     return worst
 
 
-@pytest.mark.parametrize("path", ["default", "stat_fwd0", "bwd_per_layer", "slices64"])
+@pytest.mark.parametrize("path", ["default", "stat_fwd0", "bwd_per_layer"])
 def test_headline_training_step_matches_float64_autograd(device, monkeypatch, path):
     """The bench's training leg at its own shape (B = 128, N = 16 561, T = 374 layers; h = 256, L = 2, 5 heads of 5002) against
     float64 autograd: the reverse sweep (csrc/bwd_dataflow.hip) fed by the forward launch's static rows (the default), by
-    `bd_stat_kernel`'s records (`STAT_FWD=0`), the per-layer and persistent-tail launches of csrc/backward.hip
-    (`BWD_DATAFLOW=0`), and the 64-unit forward shape (csrc/dataflow_x.hip) - each against the same reference, and each
-    really on the path it names."""
-    flags = dict(BWD_DATAFLOW=1, STAT_FWD=1, DF_SLICES64=0)
-    flags.update({"stat_fwd0": dict(STAT_FWD=0), "bwd_per_layer": dict(BWD_DATAFLOW=0), "slices64": dict(DF_SLICES64=1)}.get(path, {}))
+    `bd_stat_kernel`'s records (`STAT_FWD=0`) and the per-layer and persistent-tail launches of csrc/backward.hip
+    (`BWD_DATAFLOW=0`) - each against the same reference, and each really on the path it names."""
+    flags = dict(BWD_DATAFLOW=1, STAT_FWD=1)
+    flags.update({"stat_fwd0": dict(STAT_FWD=0), "bwd_per_layer": dict(BWD_DATAFLOW=0)}.get(path, {}))
     for k, v in flags.items():
         monkeypatch.setattr(engine, k, v)
     model = _headline_model(H=256, L=2, V=5002)
@@ -2413,14 +2373,14 @@ def test_headline_training_step_matches_float64_autograd(device, monkeypatch, pa
     seen = _spy_entries(monkeypatch, _TRAIN_ENTRIES)
     _full_size_training_step(device, model, b, y, "cfg2_train_f64")
     fwd = seen["dagnn_dataflow_run"]
-    assert fwd and all(h == 256 and s64 == flags["DF_SLICES64"] for h, _, s64 in fwd), fwd
+    assert fwd and all(h == 256 for h, _ in fwd), fwd
     if path == "bwd_per_layer":
         assert seen["dagnn_backward_run"] and not seen["dagnn_bwd_dataflow_run"], seen
-        assert [s for _, s, _ in fwd] == [0], fwd
+        assert [s for _, s in fwd] == [0], fwd
     else:
         assert seen["dagnn_bwd_dataflow_run"] == [(256,)] and not seen["dagnn_backward_run"], seen
         assert seen["dagnn_bwd_dataflow_prepare"] == [(256, flags["STAT_FWD"])], seen
-        assert [s for _, s, _ in fwd] == [flags["STAT_FWD"]], fwd
+        assert [s for _, s in fwd] == [flags["STAT_FWD"]], fwd
 
 
 def test_reference_training_shape_step_matches_float64_autograd(device, monkeypatch):
@@ -2432,7 +2392,7 @@ def test_reference_training_shape_step_matches_float64_autograd(device, monkeypa
     y = torch.randint(0, 5002, (160, 5), generator=torch.Generator().manual_seed(160))
     seen = _spy_entries(monkeypatch, _TRAIN_ENTRIES)
     _full_size_training_step(device, model, b, y, "ogb_tok_h300_B160_train_f64")
-    assert seen["dagnn_dataflow_run"] == [(320, 1, 0)], seen
+    assert seen["dagnn_dataflow_run"] == [(320, 1)], seen
     assert seen["dagnn_bwd_dataflow_prepare"] == [(320, 1)] and seen["dagnn_bwd_dataflow_run"] == [(320,)], seen
     assert not seen["dagnn_backward_run"], seen
 
