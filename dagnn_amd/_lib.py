@@ -463,6 +463,9 @@ SYMBOLS = {
     "dagnn_sgp_ei_step": (C.c_int, [C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_int64, C.c_int, C.c_void_p,
                                     C.c_float, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "dagnn_sgp_energy_grad_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int64]),
+    "dagnn_sgp_energy_grad": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_double] + [C.c_void_p] * 14 +
+                              [C.c_size_t, C.c_void_p, C.c_void_p]),
     "dagnn_opt_chunks": (C.c_int64, [C.c_void_p, C.c_int]),
     "dagnn_grad_norm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "dagnn_clip_adam": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int64, C.c_float,

@@ -2381,3 +2381,53 @@ def sgp_ei_step(mode: int, mean: torch.Tensor, r: torch.Tensor, incumbent: float
                                 _ptr(p), _ptr(U), ld_u, Me, _ptr(c), float(inv_delta), _ptr(keys), result.data_ptr(), work.data_ptr(),
                                 work.numel() * 8, _lp_counter(mean).data_ptr(), _stream(mean)), "dagnn_sgp_ei_step")
     return result, keys
+
+
+# ----------------------------------------------------------------------------- the sparse GP's training step (csrc/sgp_train.hip)
+def sgp_energy_grad(X: torch.Tensor, y: torch.Tensor, params, n_points: int, fail: torch.Tensor, work: Optional[torch.Tensor] = None):
+    """`dagnn_sgp_energy_grad`: (E [1], [g_lls, g_lsf, g_z, g_mParamPost, g_LParamPost, g_lvar_noise]) of the minibatch X [b, d],
+    y [b] (float64 on the GPU, a row pitch of X is read in place) at `params` (the six float64 tensors of
+    `SparseGP.get_params()`, read in place).  `fail`: an int32 device word that counts failed pivots (the caller zeroes and
+    reads it); `work`: a float64 scratch tensor of at least `sgp_energy_grad_words(M, d, b)` values, allocated when None.  No
+    synchronisation; M > 512 or d > 128 raises ValueError."""
+    lls, lsf, z, mP, Lp, lvn = params
+    for t, what in ((X, "X"), (y, "y"), (lls, "lls"), (lsf, "lsf"), (z, "z"), (mP, "mParamPost"), (Lp, "LParamPost"), (lvn, "lvar_noise")):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float64 or t.device != X.device:
+            raise DagnnHipError("sgp_energy_grad: %s must be a float64 tensor on X's GPU: this path is HIP only" % what)
+    if X.dim() != 2 or z.dim() != 2 or X.shape[1] != z.shape[1] or X.shape[0] < 1:
+        raise ValueError("sgp_energy_grad: X [b >= 1, d] and z [M, d] needed (got %s, %s)" % (tuple(X.shape), tuple(z.shape)))
+    (b, d), M = X.shape, z.shape[0]
+    words = sgp_energy_grad_words(M, d, b)
+    if X.stride(1) != 1 or (b > 1 and X.stride(0) < d):
+        X = X.contiguous()
+    y = y.reshape(-1)
+    y = y if y.is_contiguous() else y.contiguous()
+    if y.numel() != b or lls.numel() != d or lsf.numel() != 1 or lvn.numel() != 1 or mP.numel() != M or tuple(Lp.shape) != (M, M) \
+            or not all(t.is_contiguous() for t in (lls, z, mP, Lp)):
+        raise ValueError("sgp_energy_grad: y [b], lls [d], lsf [], z [M, d], mParamPost [M, 1], LParamPost [M, M], lvar_noise [] "
+                         "contiguous needed")
+    if fail.dtype != torch.int32 or not fail.is_cuda or fail.device != X.device or fail.numel() < 1:
+        raise DagnnHipError("sgp_energy_grad: fail must be an int32 word on X's GPU")
+    dev = X.device
+    if work is None:
+        work = torch.empty(words, dtype=torch.float64, device=dev)
+    elif work.dtype != torch.float64 or work.device != dev or work.numel() < words or not work.is_contiguous():
+        raise DagnnHipError("sgp_energy_grad: work must hold %d float64 values on X's GPU" % words)
+    E = torch.empty(1, dtype=torch.float64, device=dev)
+    grads = [torch.empty_like(p) for p in params]
+    check(_lib.load().dagnn_sgp_energy_grad(X.data_ptr(), X.stride(0) if b > 1 else d, y.data_ptr(), b, M, d, float(n_points),
+                                            lls.data_ptr(), lsf.data_ptr(), z.data_ptr(), mP.data_ptr(), Lp.data_ptr(), lvn.data_ptr(),
+                                            E.data_ptr(), *[g.data_ptr() for g in grads], work.data_ptr(), work.numel() * 8,
+                                            fail.data_ptr(), _stream(X)), "dagnn_sgp_energy_grad")
+    return E, grads
+
+
+def sgp_energy_grad_words(M: int, d: int, b: int) -> int:
+    """The float64 values of `dagnn_sgp_energy_grad`'s workspace; ValueError for a shape the kernels do not take."""
+    if not 1 <= int(M) <= _lib.SGP_MAX_M or not 1 <= int(d) <= _lib.SGP_MAX_D:
+        raise ValueError("sgp_energy_grad: 1 <= M <= %d and 1 <= d <= %d needed (got M = %d, d = %d)"
+                         % (_lib.SGP_MAX_M, _lib.SGP_MAX_D, M, d))
+    nbytes = _lib.load().dagnn_sgp_energy_grad_bytes(int(M), int(d), int(b))
+    if nbytes == 0:
+        raise ValueError("sgp_energy_grad: 1 <= b <= 2^24 rows needed (got %d)" % b)
+    return nbytes // 8

@@ -12,8 +12,9 @@ The model (ignore_variances = True, the only path of the reference that bo.py ru
     k(x, z) = sf exp(-1/2 sum_c (x_c - z_c)^2 / ls_c),      Kzz = k(z, z) + 1e-3 sf I,      P = LParamPost LParamPost^T,
     covPost = (Kzz^-1 + P)^-1,      a = Kzz^-1 covPost mParamPost,      B = Kzz^-1 covPost Kzz^-1 - Kzz^-1,
     mean(x) = k(x, z) a,      var(x) = |sf + k B k^T| + exp(lvar_noise).
-Training is plumbing on torch ops in float64 (`energy`, `train_via_adam`): the factorisation of a 500 x 500 matrix is the
-library's job.  The hot side - every `predict` and every grid of `batched_greedy_ei` - runs in csrc/sgp.hip on matrices derived
+Training (`energy`, `train_via_adam`) runs by default on torch ops in float64 with autograd; `train_via_adam(grad="hip")` and
+`energy_and_grad` take the fused step of csrc/sgp_train.hip instead: energy and the six gradients by analytic adjoints in one
+library call.  Every `predict` and every grid of `batched_greedy_ei` runs in csrc/sgp.hip on matrices derived
 once per parameter version in float64 and handed over rounded to fp32, in the whitened form:
     Kzz = L L^T,   A = L^T P L,   I - (I + A)^-1 = R^T R,   G = R L^-1,   var = sf - |G k|^2,   a = L^-T (I + A)^-1 L^T mParamPost
 and for the averaged EI, W = L^-1 extended by one row per chosen point.  A model on the CPU goes through the float64 numpy
@@ -31,7 +32,7 @@ import torch
 from . import _lib, core, engine
 
 __all__ = ["SparseGP", "bo_round", "MAX_M", "MAX_D", "MAX_Q", "JITTER", "kernel_host", "predict_host", "log_ei_host",
-           "greedy_host"]
+           "greedy_host", "energy_grad_host"]
 
 MAX_M = _lib.SGP_MAX_M   # DAGNN_SGP_MAX_M: inducing points
 MAX_D = _lib.SGP_MAX_D   # DAGNN_SGP_MAX_D: input columns
@@ -235,6 +236,90 @@ def greedy_host(D, grid: np.ndarray, q: int, refine=None, lower=None, upper=None
     return np.stack(points), {"incumbent": inc, "index": idx, "r": r, "bad": bad}
 
 
+# --------------------------------------------------------------------------------- the training step's host mirror (float64 torch)
+def _kernel_diff(il: torch.Tensor, sf: torch.Tensor, x: torch.Tensor, z: torch.Tensor) -> torch.Tensor:
+    """k(x, z) [Nx, Nz] from the differences, in chunks of 128 rows (bounded scratch)."""
+    out = torch.empty(x.shape[0], z.shape[0], dtype=torch.float64)
+    for i in range(0, x.shape[0], 128):
+        df = x[i:i + 128, None, :] - z[None, :, :]
+        out[i:i + 128] = torch.einsum("nmc,c,nmc->nm", df, il, df)
+    return sf * torch.exp(-0.5 * out)
+
+
+def _kernel_adjoint(il: torch.Tensor, g: torch.Tensor, x: torch.Tensor, z: torch.Tensor):
+    """With g = Kbar o K [Nx, Nz]: (sum_r g_rm (x_rc - z_mc) [Nz, d], sum_rm g_rm (x_rc - z_mc)^2 [d]), from the differences."""
+    dz, dl = torch.zeros_like(z), torch.zeros_like(il)
+    for i in range(0, x.shape[0], 128):
+        df = x[i:i + 128, None, :] - z[None, :, :]
+        dz += torch.einsum("nm,nmc->mc", g[i:i + 128], df)
+        dl += torch.einsum("nm,nmc,nmc->c", g[i:i + 128], df, df)
+    return dz, dl
+
+
+def energy_grad_host(params, X, y, n_points: int):
+    """The energy of one minibatch and its six gradients (in `get_params()` order) in float64 torch on the CPU, by the analytic
+    adjoints of the whitened form - the mirror of `dagnn_sgp_energy_grad`, product by product; no autograd.
+    Returns (E [], [g_lls, g_lsf, g_z, g_mParamPost, g_LParamPost, g_lvar_noise])."""
+    lls, lsf, z, mP, Lp, lvn = [torch.as_tensor(p).detach().to("cpu", torch.float64) for p in params]
+    X = torch.as_tensor(X).detach().to("cpu", torch.float64)
+    y = torch.as_tensor(y).detach().to("cpu", torch.float64).reshape(-1)
+    M, b, n = z.shape[0], X.shape[0], float(n_points)
+    mP = mP.reshape(M, 1)
+    c = (n - 1.0) / n
+    sf, il, noise = torch.exp(lsf), torch.exp(-lls), torch.exp(lvn)
+    eye = torch.eye(M, dtype=torch.float64)
+    inv = lambda T: torch.linalg.solve_triangular(T, eye, upper=False)   # noqa: E731
+    # forward
+    Kzz = _kernel_diff(il, sf, z, z) + eye * (JITTER * sf)
+    L = torch.linalg.cholesky(Kzz)
+    W = inv(L)
+    C = Lp.T @ L
+    A = C.T @ C
+    Lc, L1 = torch.linalg.cholesky(eye + c * A), torch.linalg.cholesky(eye + A)
+    Wc, W1 = inv(Lc), inv(L1)
+    Sci, S1i = Wc.T @ Wc, W1.T @ W1
+    t = L.T @ mP
+    al, be = Sci @ t, S1i @ t
+    G = -torch.log(torch.diagonal(Lc)).sum() + 0.5 * c * c * (t * al).sum() \
+        - c * (-torch.log(torch.diagonal(L1)).sum() + 0.5 * (t * be).sum())
+    Kx = _kernel_diff(il, sf, X, z)
+    U = W @ Kx.T
+    R = Sci @ U
+    v = sf - (U * U).sum(0) + (U * R).sum(0)
+    mean = c * (al * U).sum(0)
+    out = v.abs() + noise
+    r = y - mean
+    E = b * G + (-0.5 * torch.log(2.0 * math.pi * out) - 0.5 * r * r / out).sum()
+    # adjoints of the rows
+    d_out = -0.5 / out + 0.5 * r * r / (out * out)
+    d_v, d_mean = d_out * torch.sign(v), r / out
+    Ub = (2.0 * (R - U)) * d_v + (c * al) * d_mean
+    rho = R @ d_mean.reshape(b, 1)
+    T3 = (R * d_v) @ R.T
+    # adjoints of S_c, S_1 -> A, t
+    Ab = c * (-0.5 * b * Sci - 0.5 * b * c * c * (al @ al.T) - T3 - 0.5 * c * (rho @ al.T + al @ rho.T)) \
+        + 0.5 * c * b * (S1i + be @ be.T)
+    tb = b * c * c * al + c * rho - c * b * be
+    X1 = C @ Ab
+    g_Lp = 2.0 * (L @ X1.T)
+    g_m = L @ tb
+    KxbT = W.T @ Ub
+    Lb = torch.tril(2.0 * (Lp @ X1) - KxbT @ U.T + mP @ tb.T)
+    # the Cholesky adjoint: Kzz_bar = L^-T Phi(L^T L_bar) L^-1, Phi = the lower triangle with half the diagonal
+    Phi = torch.tril(L.T @ Lb)
+    Phi.diagonal().mul_(0.5)
+    Kb = W.T @ (Phi @ W)
+    # the kernel's own derivative
+    gz, gx = (Kb + Kb.T) * Kzz, KxbT.T * Kx
+    dz1, dl1 = _kernel_adjoint(il, gz, z, z)
+    dz2, dl2 = _kernel_adjoint(il, gx, X, z)
+    g_z = (dz1 + dz2) * il
+    g_lls = 0.5 * il * (0.5 * dl1 + dl2)
+    g_lsf = 0.5 * gz.sum() + gx.sum() + sf * d_v.sum()
+    g_noise = noise * d_out.sum()
+    return E, [g_lls, g_lsf.reshape(()), g_z, g_m.reshape(M, 1), g_Lp, g_noise.reshape(())]
+
+
 # --------------------------------------------------------------------------------- the model
 def _as_rows(X, d: int, what: str) -> torch.Tensor:
     if not isinstance(X, torch.Tensor):
@@ -363,16 +448,53 @@ class SparseGP(object):
         logZ = -0.5 * torch.log(2.0 * math.pi * out_var) - 0.5 * (y.reshape(-1, 1) - out_mean) ** 2 / out_var
         return ((logZcav - logZpost) + logZpost / n - logZprior / n) * float(X.shape[0]) + logZ.sum()
 
+    def energy_and_grad(self, X, y, fail: Optional[torch.Tensor] = None, work: Optional[torch.Tensor] = None):
+        """(E, [six gradients in `get_params()` order]) of one minibatch, float64 on the model's device, by the analytic
+        adjoints of the whitened form; no autograd graph.  On a GPU model one call of `dagnn_sgp_energy_grad`
+        (csrc/sgp_train.hip), nothing synchronises: a pivot that is not positive gives NaN outputs and counts on `fail` (an int32
+        device word; default: the model's own, `train_failures()` reads it).  On a CPU model `energy_grad_host`."""
+        X = _as_rows(X, self.d_input, "energy_and_grad")
+        y = y if isinstance(y, torch.Tensor) else torch.as_tensor(np.asarray(y, dtype=np.float64))
+        if y.numel() != X.shape[0] or X.shape[0] < 1:
+            raise ValueError("energy_and_grad: y must hold one value per row of X, at least one (got %d for %d rows)"
+                             % (y.numel(), X.shape[0]))
+        params = [p.detach() for p in self.get_params()]
+        if not self.on_gpu:
+            return energy_grad_host(params, X, y, self.n_points)
+        X, y = X.detach().to(self.device, torch.float64), y.detach().to(self.device, torch.float64)
+        E, grads = engine.sgp_energy_grad(X, y, params, self.n_points, self._fail_word() if fail is None else fail, work)
+        return E.reshape(()), grads
+
+    def _fail_word(self) -> torch.Tensor:
+        if getattr(self, "_fail", None) is None:
+            self._fail = torch.zeros(1, dtype=torch.int32, device=self.device)
+        return self._fail
+
+    def train_failures(self) -> int:
+        """The failed pivots counted by `energy_and_grad` on the GPU since the last call of this method (one device read)."""
+        if not self.on_gpu or getattr(self, "_fail", None) is None:
+            return 0
+        n = int(self._fail.item())
+        self._fail.zero_()
+        return n
+
     def train_via_adam(self, X_test=None, y_test=None, max_iterations: int = 500, minibatch_size: int = 4000,
-                       learning_rate: float = 1e-3, rng=None, verbose: bool = True, initialize: bool = True):
+                       learning_rate: float = 1e-3, rng=None, verbose: bool = True, initialize: bool = True,
+                       grad: str = "autograd"):
         """`train_via_ADAM` (sparse_gp.py:195-270): `initialize`, then per epoch the reference's shuffle and minibatches, every
         minibatch one step of `torch.optim.Adam` (default betas, eps = 1e-8: the rule of `adam_theano`) on minus the energy.
         With `verbose` (and a test set) the epoch's train / test RMSE and test log-likelihood are printed, through `predict`.
-        Returns the last minibatch's energy."""
+        grad='autograd' differentiates `energy`; grad='hip' writes the gradients of `energy_and_grad` (one library call per
+        minibatch on a GPU model; the same draws, minibatches and optimiser) - the failure counter is read once, at the end,
+        and a non-zero count raises DagnnHipError.  Returns the last minibatch's energy."""
         rng = np.random if rng is None else rng
         mb = int(minibatch_size)
         if mb < 1 or int(max_iterations) < 0:
             raise ValueError("train_via_adam: minibatch_size >= 1 and max_iterations >= 0 needed")
+        if grad not in ("autograd", "hip"):
+            raise ValueError("train_via_adam: grad must be 'autograd' or 'hip' (got %r)" % (grad,))
+        if grad == "hip":
+            return self._train_analytic(X_test, y_test, int(max_iterations), mb, float(learning_rate), rng, verbose, initialize)
         if initialize:
             self.initialize(rng, mb)
         Xt = yt = None
@@ -409,6 +531,53 @@ class SparseGP(object):
                 p.requires_grad_(False)
             self._cache.invalidate()
         return None if last is None else -float(last)
+
+    def _train_analytic(self, X_test, y_test, max_iterations, mb, learning_rate, rng, verbose, initialize):
+        """`train_via_adam(grad='hip')`: the same loop with `p.grad` written from `energy_and_grad`."""
+        if initialize:
+            self.initialize(rng, mb)
+        Xt = yt = None
+        if X_test is not None:
+            Xt = _as_rows(X_test, self.d_input, "train_via_adam").to(self.device, torch.float64)
+            yt = torch.as_tensor(np.asarray(y_test.cpu() if isinstance(y_test, torch.Tensor) else y_test, dtype=np.float64)).reshape(-1, 1).to(self.device)
+        params = self.get_params()
+        opt = torch.optim.Adam(params, lr=learning_rate, betas=(0.9, 0.999), eps=1e-8)
+        X, y, n = self.X, self.y, self.n_points
+        n_batches = int(np.ceil(1.0 * n / mb))
+        fail = work = None
+        if self.on_gpu:
+            fail = torch.zeros(1, dtype=torch.int32, device=self.device)
+            work = torch.empty(engine.sgp_energy_grad_words(self.n_inducing, self.d_input, min(mb, n)), dtype=torch.float64,
+                               device=self.device)
+        last = None
+        try:
+            for j in range(max_iterations):
+                perm = torch.from_numpy(np.asarray(rng.choice(n, n, replace=False), dtype=np.int64)).to(self.device)
+                X, y = X[perm], y[perm]
+                for i in range(n_batches):
+                    E, grads = self.energy_and_grad(X[i * mb:min((i + 1) * mb, n)], y[i * mb:min((i + 1) * mb, n)], fail, work)
+                    for p, g in zip(params, grads):
+                        p.grad = g.neg_()   # (the optimiser minimises minus the energy)
+                    opt.step()
+                    last = E
+                self._cache.invalidate()
+                if verbose:
+                    tr = self.report(X, y)
+                    msg = "Epoch %d, Train error: %.4f" % (j, tr["rmse"])
+                    if Xt is not None:
+                        te = self.report(Xt, yt)
+                        msg += " Test error: %.4f Test ll: %.4f" % (te["rmse"], te["ll"])
+                    print(msg, flush=True)
+        finally:
+            for p in params:
+                p.grad = None
+            self._cache.invalidate()
+        if fail is not None:
+            bad = int(fail.item())   # the call's one read of the counter
+            if bad:
+                raise _lib.DagnnHipError("train_via_adam(grad='hip'): %d Cholesky pivots were not positive: the parameters "
+                                         "hold NaN from the first of them on" % bad)
+        return None if last is None else float(last)
 
     # ----------------------------------------------------------------------------- derived matrices
     def derived(self):

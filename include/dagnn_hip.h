@@ -1492,6 +1492,25 @@ int dagnn_sgp_ei_step(int mode, int64_t N, const float* mean, float* r, double i
                       float inv_delta, double* keys, int64_t* result, void* work, size_t work_bytes, unsigned* counter,
                       void* stream);
 
+/* One training step of that sparse GP (csrc/sgp_train.hip): the energy of a minibatch (getContributionToEnergy with the cavity
+ * factor c = (n_points - 1) / n_points; `SparseGP.energy`) and its gradients, all float64, by analytic adjoints of the whitened
+ * form: Kzz = k(z, z) + 1e-3 sf I = L L^T, C = Lp^T L, A = C^T C, S_c = I + c A, S_1 = I + A, t = L^T m, U = L^-1 k(X, z)^T,
+ *     v_i = sf - |U_i|^2 + U_i^T S_c^-1 U_i,   mean_i = c U_i^T S_c^-1 t,   out_i = |v_i| + exp(lvar_noise),
+ *     E = b (-1/2 logdet S_c + 1/2 c^2 t^T S_c^-1 t - c (-1/2 logdet S_1 + 1/2 t^T S_1^-1 t))
+ *         + sum_i (-1/2 log(2 pi out_i) - 1/2 (y_i - mean_i)^2 / out_i).
+ * X [b, d] (row pitch ld_x >= d), y [b], lls [d], lsf [1], z [M, d], mP [M], Lp [M, M], lvar_noise [1] are read in place;
+ * E [1], g_lls [d], g_lsf [1], g_z [M, d], g_m [M], g_Lp [M, M], g_noise [1] are written.  M <= DAGNN_SGP_MAX_M,
+ * d <= DAGNN_SGP_MAX_D, 1 <= b <= 2^24, n_points >= 1.  work: dagnn_sgp_energy_grad_bytes(M, d, b) bytes (0 for a shape out of
+ * range), 8-byte aligned.  The three Cholesky factorisations run a fixed number of steps: a pivot that is not positive (or
+ * NaN) becomes NaN - the outputs are then NaN - and adds one to *fail, a device word the caller zeroes and reads when it
+ * likes.  The products run on v_mfma_f64_16x16x4_f64; every sum has one fixed order and there is no floating-point atomic:
+ * two calls on the same inputs are bitwise equal.  Borrowed pointers, the caller's stream, no allocation, no synchronisation. */
+size_t dagnn_sgp_energy_grad_bytes(int M, int d, int64_t b);
+int dagnn_sgp_energy_grad(const double* X, int64_t ld_x, const double* y, int64_t b, int M, int d, double n_points,
+                          const double* lls, const double* lsf, const double* z, const double* mP, const double* Lp,
+                          const double* lvar_noise, double* E, double* g_lls, double* g_lsf, double* g_z, double* g_m,
+                          double* g_Lp, double* g_noise, void* work, size_t work_bytes, unsigned* fail, void* stream);
+
 /* The tail of the reference's training step - `clip_grad_norm_(model.parameters(), clip)` + `optim.Adam.step()`
  * (ogbg-code/main_pyg.py:63-65,179) - over a table of fp32 tensors (csrc/optim.hip).  dagnn_grad_norm: the 2-norm of up to
  * DAGNN_MAX_OPT_TENSORS gradients (`partial`: scratch of dagnn_opt_chunks() floats; `accumulate` != 0 adds the tensors' sum of

@@ -8,12 +8,15 @@
   batched_greedy_ei  q = --q points on a --grid-row grid: the HIP flow without refinement, the same loop on torch ops (one
                      grid evaluation, the argmin and one read per step), and the HIP flow with the L-BFGS-B refinement; wall
                      clock including every synchronisation
-  train_via_adam     wall time per Adam step at minibatch --minibatch (float64 torch ops)
+  train_via_adam     wall time per Adam step at minibatch --minibatch: the default path (float64 torch ops under autograd) and
+                     grad="hip" (csrc/sgp_train.hip) in the same run; one energy + gradient evaluation of each path alone
+                     (`energy_grad_*_ms`, their largest relative difference per parameter before anything is timed); and one
+                     bo.py-sized fit, --fit-rows rows for --fit-epochs epochs, on each path (--fit-epochs 0 skips it)
 
 Median (and 90th percentile) over --steps windows after --warmup (a `predict` window is 20 calls); the results are checked against each other before anything is
 timed.  One JSON line at the end.
 
-    python scripts/bench_sgp.py [--steps 10] [--warmup 3] [--q 50] [--grid 10000]
+    python scripts/bench_sgp.py [--steps 10] [--warmup 3] [--q 50] [--grid 10000] [--train-only]
 """
 from __future__ import annotations
 
@@ -123,6 +126,9 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--no-refine", action="store_true")
+    ap.add_argument("--train-only", action="store_true")
+    ap.add_argument("--fit-rows", type=int, default=5000)
+    ap.add_argument("--fit-epochs", type=int, default=100)
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     rng = np.random.RandomState(0)
@@ -143,6 +149,51 @@ def main():
         if k >= a.warmup:
             t.append((time.perf_counter() - t0) * 1e3 / int(np.ceil(n / a.minibatch)))
     out["adam_step_ms"] = [round(float(np.median(t)), 3), round(float(np.percentile(t, 90)), 3)]
+    t = []
+    for k in range(a.warmup + a.steps):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        g.train_via_adam(max_iterations=1, minibatch_size=a.minibatch, learning_rate=5e-4, rng=rng, verbose=False, initialize=False,
+                         grad="hip")   # (reads the failure counter once per call: every synchronisation is inside the window)
+        torch.cuda.synchronize()
+        if k >= a.warmup:
+            t.append((time.perf_counter() - t0) * 1e3 / int(np.ceil(n / a.minibatch)))
+    out["adam_step_hip_ms"] = [round(float(np.median(t)), 3), round(float(np.percentile(t, 90)), 3)]
+
+    # one energy + gradient evaluation of each path, no optimiser
+    Xb, yb = g.X[:a.minibatch], g.y[:a.minibatch]
+
+    def autograd_step():
+        ps = g.get_params()
+        for p in ps:
+            p.requires_grad_(True)
+        try:
+            return torch.autograd.grad(g.energy(Xb, yb), ps)
+        finally:
+            for p in ps:
+                p.requires_grad_(False)
+
+    ga, (_, gh) = autograd_step(), g.energy_and_grad(Xb, yb)
+    out["energy_grad_maxreldiff"] = [float((u - v).abs().max() / u.abs().max()) for u, v in zip(ga, gh)]
+    out["energy_grad_autograd_ms"] = wall_ms(autograd_step, a.steps, a.warmup)
+    out["energy_grad_hip_ms"] = wall_ms(lambda: g.energy_and_grad(Xb, yb), a.steps, a.warmup)
+    out["train_failures"] = g.train_failures()
+
+    if a.fit_epochs > 0:   # bo.py:256-260 at the BN loop's size
+        Xf = rng.randn(a.fit_rows, d)
+        yf = np.sin(Xf[:, :4].sum(1)) + 0.1 * rng.randn(a.fit_rows)
+        for path in ("hip", "autograd"):
+            f = sgp.SparseGP(Xf, yf, M, device=dev)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            f.train_via_adam(max_iterations=a.fit_epochs, minibatch_size=a.minibatch, learning_rate=5e-4, rng=np.random.RandomState(1),
+                             verbose=False, grad=path)
+            torch.cuda.synchronize()
+            out["fit_%dx%d_%s_s" % (a.fit_rows, a.fit_epochs, path)] = round(time.perf_counter() - t0, 3)
+            out["fit_%s_rmse" % path] = round(f.report(f.X, f.y)["rmse"], 6)
+    if a.train_only:
+        print(json.dumps(out))
+        return
     D = g.derived()
 
     for N in a.rows:
