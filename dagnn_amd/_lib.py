@@ -334,6 +334,9 @@ class BnData(C.Structure):   # dagnn_bn_data
 
 SGP_MAX_M, SGP_MAX_D, SGP_MAX_Q = 512, 128, 128   # DAGNN_SGP_MAX_M / _MAX_D / _MAX_Q
 SGP_ARGMIN_MEAN, SGP_ARGMIN_EI = 0, 1             # DAGNN_SGP_ARGMIN_*
+SGP_REFINE_MAX_STARTS, SGP_REFINE_HISTORY = 32, 8    # DAGNN_SGP_REFINE_MAX_STARTS / _HISTORY
+SGP_REFINE_MEAN, SGP_REFINE_EI = 0, 1                # DAGNN_SGP_REFINE_MEAN / _EI (the objective)
+SGP_REFINE_STATUS = ("running", "converged", "stalled", "budget", "dead")   # DAGNN_SGP_REFINE_RUNNING .. _DEAD
 
 SYMBOLS = {
     "dagnn_version": (C.c_char_p, []),
@@ -466,6 +469,11 @@ SYMBOLS = {
     "dagnn_sgp_energy_grad_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int64]),
     "dagnn_sgp_energy_grad": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_double] + [C.c_void_p] * 14 +
                               [C.c_size_t, C.c_void_p, C.c_void_p]),
+    "dagnn_sgp_refine_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "dagnn_sgp_refine_eval": (C.c_int, [C.c_int] * 5 + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_int64,
+                                        C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "dagnn_sgp_refine_run": (C.c_int, [C.c_int] * 5 + [C.c_void_p] * 6 + [C.c_int64, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_int64, C.c_int,
+                                       C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "dagnn_opt_chunks": (C.c_int64, [C.c_void_p, C.c_int]),
     "dagnn_grad_norm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "dagnn_clip_adam": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int64, C.c_float,

@@ -2383,6 +2383,96 @@ def sgp_ei_step(mode: int, mean: torch.Tensor, r: torch.Tensor, incumbent: float
     return result, keys
 
 
+# ----------------------------------------------------------------------------- the sparse GP's refinement (csrc/sgp_refine.hip)
+def _sgp_refine_args(what: str, mode: int, X: torch.Tensor, ze: torch.Tensor, zet, inv_ls: torch.Tensor, a: torch.Tensor, T, Me: int):
+    """The shared checks of `sgp_refine_eval` / `sgp_refine_run`: float64 contiguous operands on X's GPU, shapes in range.
+    `zet` [d, >= Me] is ze transposed (None: made here).  Returns (S, d, M, Me, ld_t, zet)."""
+    if mode not in (_lib.SGP_REFINE_MEAN, _lib.SGP_REFINE_EI):
+        raise ValueError("%s: mode must be SGP_REFINE_MEAN or SGP_REFINE_EI (got %r)" % (what, mode))
+    for t, name in ((X, "X"), (ze, "ze"), (inv_ls, "inv_ls"), (a, "a")) + (((T, "T"),) if mode == _lib.SGP_REFINE_EI else ()):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float64 or t.device != X.device or not t.is_contiguous():
+            raise DagnnHipError("%s: %s must be a contiguous float64 tensor on X's GPU: this path is HIP only" % (what, name))
+    if X.dim() != 2 or ze.dim() != 2 or ze.shape[1] != X.shape[1] or inv_ls.numel() != X.shape[1]:
+        raise ValueError("%s: X [S, d], ze [>= Me, d] and inv_ls [d] needed (got %s, %s, %s)"
+                         % (what, tuple(X.shape), tuple(ze.shape), tuple(inv_ls.shape)))
+    (S, d), M, Me = X.shape, a.numel(), int(Me)
+    if not 1 <= S <= _lib.SGP_REFINE_MAX_STARTS or not 1 <= d <= _lib.SGP_MAX_D or not 1 <= M <= _lib.SGP_MAX_M \
+            or not M <= Me <= min(M + _lib.SGP_MAX_Q, ze.shape[0]):
+        raise ValueError("%s: 1 <= S <= %d, 1 <= d <= %d, 1 <= M <= %d and M <= Me <= min(M + %d, rows of ze) needed (got S = %d, "
+                         "d = %d, M = %d, Me = %d, %d rows)" % (what, _lib.SGP_REFINE_MAX_STARTS, _lib.SGP_MAX_D, _lib.SGP_MAX_M,
+                                                                _lib.SGP_MAX_Q, S, d, M, Me, ze.shape[0]))
+    ld_t = 0
+    if mode == _lib.SGP_REFINE_EI:
+        if T.dim() != 2 or T.shape[0] < Me or T.shape[1] < Me:
+            raise ValueError("%s: T must be [>= Me, >= Me] for Me = %d (got %s)" % (what, Me, tuple(T.shape)))
+        ld_t = T.shape[1]
+    if zet is None:
+        zet = ze[:Me].t().contiguous()
+    elif not isinstance(zet, torch.Tensor) or not zet.is_cuda or zet.dtype != torch.float64 or zet.device != X.device \
+            or not zet.is_contiguous() or zet.dim() != 2 or zet.shape[0] != d or zet.shape[1] < Me:
+        raise DagnnHipError("%s: zet must be a contiguous float64 [d = %d, >= Me = %d] tensor on X's GPU" % (what, d, Me))
+    return S, d, M, Me, ld_t, zet
+
+
+def _sgp_refine_work(S: int, d: int, Me: int, dev, work: Optional[torch.Tensor]) -> torch.Tensor:
+    words = _lib.load().dagnn_sgp_refine_bytes(Me, d, S) // 8
+    if work is None:
+        return torch.empty(words, dtype=torch.float64, device=dev)
+    if work.dtype != torch.float64 or work.device != dev or work.numel() < words or not work.is_contiguous():
+        raise DagnnHipError("sgp_refine: work must hold %d float64 values on X's GPU" % words)
+    return work
+
+
+def sgp_refine_words(M: int, q: int, d: int, S: int) -> int:
+    """The float64 values of the refinement's workspace for up to M + q expanded rows."""
+    return _lib.load().dagnn_sgp_refine_bytes(int(M) + int(q), int(d), int(S)) // 8
+
+
+def sgp_refine_eval(mode: int, X: torch.Tensor, ze: torch.Tensor, inv_ls: torch.Tensor, sf: float, a: torch.Tensor,
+                    T: Optional[torch.Tensor] = None, Me: Optional[int] = None, tri: bool = False, incumbent: float = 0.0,
+                    work: Optional[torch.Tensor] = None, zet: Optional[torch.Tensor] = None):
+    """`dagnn_sgp_refine_eval`: the refinement's objective at the S rows of X [S, d] in float64 - (f [S], mean [S], v [S],
+    d mean / dx [S, d], d v / dx [S, d]) over the first Me rows of ze (default: a.numel() = M) with T [>= Me, >= Me] (tri: lower
+    triangular); mode SGP_REFINE_MEAN: f = mean, T unused; SGP_REFINE_EI: f = -log EI against `incumbent`.  Four launches,
+    nothing synchronises."""
+    S, d, M, Me, ld_t, zet = _sgp_refine_args("sgp_refine_eval", mode, X, ze, zet, inv_ls, a, T, a.numel() if Me is None else Me)
+    work = _sgp_refine_work(S, d, Me, X.device, work)
+    out = torch.empty(S, 4 + 2 * d, dtype=torch.float64, device=X.device)
+    check(_lib.load().dagnn_sgp_refine_eval(int(mode), S, d, M, Me, X.data_ptr(), ze.data_ptr(), zet.data_ptr(), zet.shape[1], inv_ls.data_ptr(), float(sf),
+                                            a.data_ptr(),
+                                            _ptr(T) if ld_t else None, ld_t, int(bool(tri)), float(incumbent), out.data_ptr(),
+                                            work.data_ptr(), work.numel() * 8, _stream(X)), "dagnn_sgp_refine_eval")
+    return out[:, 0], out[:, 1], out[:, 2], out[:, 4:4 + d], out[:, 4 + d:]
+
+
+def sgp_refine_run(mode: int, X0: torch.Tensor, lower: torch.Tensor, upper: torch.Tensor, ze: torch.Tensor, inv_ls: torch.Tensor,
+                   sf: float, a: torch.Tensor, T: Optional[torch.Tensor] = None, Me: Optional[int] = None, tri: bool = False,
+                   incumbent: float = 0.0, max_evals: int = 64, nstart: Optional[torch.Tensor] = None,
+                   work: Optional[torch.Tensor] = None, want_points: bool = False, zet: Optional[torch.Tensor] = None):
+    """`dagnn_sgp_refine_run`: the S rows of X0 [S, d] (clipped into [lower, upper], float64 [d] each) advanced in lock-step for
+    `max_evals` evaluations on the objective of `sgp_refine_eval`; `nstart` (an int32 device word): the rows from it on are
+    dead.  Returns float64 [2 + d + 3 S] on the device: the best start (-1: none), its objective, its point, then status,
+    evaluations and objective per start - with `want_points` a pair of it and every start's accepted point [S, d] (NaN: dead).  1 + 3 max_evals + 1 launches (1 + max_evals + 1 for SGP_REFINE_MEAN), nothing synchronises."""
+    S, d, M, Me, ld_t, zet = _sgp_refine_args("sgp_refine_run", mode, X0, ze, zet, inv_ls, a, T, a.numel() if Me is None else Me)
+    for t, name in ((lower, "lower"), (upper, "upper")):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float64 or t.device != X0.device \
+                or not t.is_contiguous() or t.numel() != d:
+            raise DagnnHipError("sgp_refine_run: %s must hold d = %d float64 values on X0's GPU" % (name, d))
+    if not 4 <= int(max_evals) <= 1024:
+        raise ValueError("sgp_refine_run: 4 <= max_evals <= 1024 needed (got %d)" % max_evals)
+    if nstart is not None and (not isinstance(nstart, torch.Tensor) or nstart.dtype != torch.int32 or nstart.device != X0.device
+                               or nstart.numel() < 1):
+        raise DagnnHipError("sgp_refine_run: nstart must be an int32 word on X0's GPU")
+    work = _sgp_refine_work(S, d, Me, X0.device, work)
+    out = torch.empty(2 + d + 3 * S, dtype=torch.float64, device=X0.device)
+    xs = torch.empty(S, d, dtype=torch.float64, device=X0.device) if want_points else None
+    check(_lib.load().dagnn_sgp_refine_run(int(mode), S, d, M, Me, X0.data_ptr(), _ptr(nstart), lower.data_ptr(), upper.data_ptr(),
+                                           ze.data_ptr(), zet.data_ptr(), zet.shape[1], inv_ls.data_ptr(), float(sf), a.data_ptr(), _ptr(T) if ld_t else None, ld_t,
+                                           int(bool(tri)), float(incumbent), int(max_evals), out.data_ptr(), _ptr(xs),
+                                           work.data_ptr(), work.numel() * 8, _stream(X0)), "dagnn_sgp_refine_run")
+    return (out, xs) if want_points else out
+
+
 # ----------------------------------------------------------------------------- the sparse GP's training step (csrc/sgp_train.hip)
 def sgp_energy_grad(X: torch.Tensor, y: torch.Tensor, params, n_points: int, fail: torch.Tensor, work: Optional[torch.Tensor] = None):
     """`dagnn_sgp_energy_grad`: (E [1], [g_lls, g_lsf, g_z, g_mParamPost, g_LParamPost, g_lvar_noise]) of the minibatch X [b, d],

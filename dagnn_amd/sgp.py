@@ -6,6 +6,7 @@ bo.py:256-261, 289): the model that proposes the points of a round.
     mean, var = sgp.predict(X_test)                                                                             # bo.py:261
     fit = sgp.report(X_test, y_test)                     # {'rmse', 'll', 'pearson', 'n'} of bo.py:265-270
     points = sgp.batched_greedy_ei(50, lower, upper, mean, std, sample="normal", rng=rng)                       # bo.py:289
+    points = sgp.batched_greedy_ei(50, lower, upper, mean, std, refine="multistart", starts=16, max_evals=64)   # on the device
     points, strings, scores = bo_round(sgp, model, 50, lower, upper, mean, std, data=bn_data)                   # bo.py:289-306
 
 The model (ignore_variances = True, the only path of the reference that bo.py runs): sf = exp(lsf), ls = exp(lls),
@@ -17,7 +18,9 @@ Training (`energy`, `train_via_adam`) runs by default on torch ops in float64 wi
 library call.  Every `predict` and every grid of `batched_greedy_ei` runs in csrc/sgp.hip on matrices derived
 once per parameter version in float64 and handed over rounded to fp32, in the whitened form:
     Kzz = L L^T,   A = L^T P L,   I - (I + A)^-1 = R^T R,   G = R L^-1,   var = sf - |G k|^2,   a = L^-T (I + A)^-1 L^T mParamPost
-and for the averaged EI, W = L^-1 extended by one row per chosen point.  A model on the CPU goes through the float64 numpy
+and for the averaged EI, W = L^-1 extended by one row per chosen point.  refine="multistart" replaces the reference's one
+L-BFGS-B run per step by `starts` projected L-BFGS runs in lock-step (`refine_host` is the definition; on the GPU
+csrc/sgp_refine.hip, float64, no scipy).  A model on the CPU goes through the float64 numpy
 mirrors of this module (`*_host`); a model on the GPU never does.
 """
 from __future__ import annotations
@@ -32,11 +35,13 @@ import torch
 from . import _lib, core, engine
 
 __all__ = ["SparseGP", "bo_round", "MAX_M", "MAX_D", "MAX_Q", "JITTER", "kernel_host", "predict_host", "log_ei_host",
-           "greedy_host", "energy_grad_host"]
+           "greedy_host", "energy_grad_host", "refine_host", "REFINE_STATUS", "MAX_STARTS"]
 
 MAX_M = _lib.SGP_MAX_M   # DAGNN_SGP_MAX_M: inducing points
 MAX_D = _lib.SGP_MAX_D   # DAGNN_SGP_MAX_D: input columns
 MAX_Q = _lib.SGP_MAX_Q   # DAGNN_SGP_MAX_Q: points of one greedy batch
+MAX_STARTS = _lib.SGP_REFINE_MAX_STARTS   # DAGNN_SGP_REFINE_MAX_STARTS: starts of refine="multistart"
+REFINE_STATUS = _lib.SGP_REFINE_STATUS    # the names of a start's status, by its number
 JITTER = 1e-3
 _HALF_LOG_2PI = 0.5 * math.log(2.0 * math.pi)
 _SQRT_2PI = math.sqrt(2.0 * math.pi)
@@ -188,19 +193,159 @@ def _refine(fun, x0: np.ndarray, lower: np.ndarray, upper: np.ndarray):
     return x, float(f)
 
 
-def _check_refine(refine):
-    if refine not in (None, "lbfgs"):
-        raise ValueError("refine must be None or 'lbfgs' (got %r)" % (refine,))
+_RUNNING, _CONVERGED, _STALLED, _BUDGET, _DEAD = range(5)   # DAGNN_SGP_REFINE_RUNNING .. _DEAD
+_HISTORY, _MAX_HALVINGS = _lib.SGP_REFINE_HISTORY, 20
+
+
+def _refine_start(objective, x0: np.ndarray, lo: np.ndarray, up: np.ndarray, max_evals: int):
+    """One start of `refine_host`: (x, f, status, evals), x = None for a dead start."""
+    clip = lambda v: np.minimum(np.maximum(v, lo), up)   # noqa: E731
+    xt = clip(x0)
+    x = g = p = None
+    f, t, halv, evals, status = float("nan"), 0.0, 0, 0, _RUNNING
+    S, Y, SY = [], [], []
+    while evals < max_evals and status == _RUNNING:
+        ft, gt = objective(xt)
+        ft, gt = float(ft), np.asarray(gt, dtype=np.float64).reshape(-1)
+        evals += 1
+        took = False
+        if evals == 1:
+            if not math.isfinite(ft):
+                status = _DEAD
+                break
+            x, f, g, took = xt, ft, gt, True
+        else:
+            s = xt - x
+            if math.isfinite(ft) and ft <= f + 1e-4 * float(g @ s):
+                y = gt - g
+                sy = float(s @ y)
+                if sy > 1e-10 * math.sqrt(float(s @ s)) * math.sqrt(float(y @ y)):
+                    S, Y, SY = (S + [s])[-_HISTORY:], (Y + [y])[-_HISTORY:], (SY + [sy])[-_HISTORY:]
+                if f - ft <= 2.2e-9 * max(abs(f), abs(ft), 1.0):   # scipy's default factr
+                    status = _CONVERGED
+                x, f, g, took = xt, ft, gt, True
+            elif halv >= _MAX_HALVINGS:
+                status = _STALLED
+            else:
+                halv, t = halv + 1, 0.5 * t
+                xt = clip(x + t * p)
+        if took and status == _RUNNING:
+            if float(np.max(np.abs(x - clip(x - g)))) <= 1e-5:       # scipy's pgtol
+                status = _CONVERGED
+                continue
+            free = ~(((x <= lo) & (g > 0)) | ((x >= up) & (g < 0)))
+            qv = np.where(free, g, 0.0)
+            alpha = [0.0] * len(S)
+            for i in range(len(S) - 1, -1, -1):
+                alpha[i] = float(S[i] @ qv) / SY[i]
+                qv = qv - alpha[i] * Y[i]
+            r = qv * (SY[-1] / float(Y[-1] @ Y[-1])) if S else qv
+            for i in range(len(S)):
+                beta = float(Y[i] @ r) / SY[i]
+                r = r + S[i] * (alpha[i] - beta)
+            p = np.where(free, -r, 0.0)
+            if not float(g @ p) < 0:
+                S, Y, SY = [], [], []
+                p = np.where(free, -g, 0.0)
+            if S:
+                t = 1.0
+            else:
+                pn = math.sqrt(float(p @ p))
+                t = min(1.0, 1.0 / pn) if pn > 0 else 1.0
+            halv = 0
+            xt = clip(x + t * p)
+    if status == _RUNNING:
+        status = _BUDGET
+    return x, f, status, evals
+
+
+def refine_host(objective, X0, lower, upper, max_evals: int = 64):
+    """The definition of refine="multistart" (csrc/sgp_refine.hip implements the same state machine): every row of X0 [S, d],
+    clipped into [lower, upper], is one start of a projected L-BFGS with 8 curvature pairs on `objective` (x -> (f, grad)),
+    one evaluation per tick for at most `max_evals` ticks.  Per start: the first tick evaluates clip(x0) - not finite: the start
+    is dead.  After an accepted point x: stop `converged` if max |x - clip(x - g)| <= 1e-5; coordinate i is fixed if it sits on
+    a bound with the gradient pointing outward; p = -H g by the two-loop recursion on g with the fixed coordinates zeroed
+    (scaling s.y / y.y of the newest pair), fixed coordinates of p zeroed; if g.p is not below 0 the pairs are dropped and
+    p = -g on the free set; t = 1 with pairs, else min(1, 1 / |p|).  A trial xt = clip(x + t p) is accepted if f(xt) is finite
+    and f(xt) <= f + 1e-4 g.(xt - x), else t halves (`stalled` after 20 halvings).  On acceptance the pair (xt - x, gt - g) is
+    kept if s.y > 1e-10 |s| |y|, and the start stops `converged` if f - f(xt) <= 2.2e-9 max(|f|, |f(xt)|, 1); the point is taken
+    either way.  A start out of ticks stops with `budget`.  The result is the accepted point with the smallest f (ties: the
+    lower start).  Returns (x [d] or None, f, info): info['best'] (-1: no start has a finite objective), info['status'] and
+    info['evals'] per start, info['x'] [S, d] and info['f'] [S] (NaN for a dead start)."""
+    X0 = np.atleast_2d(np.asarray(X0, dtype=np.float64))
+    d = X0.shape[1]
+    lo, up = _bounds(lower, d, "lower"), _bounds(upper, d, "upper")
+    max_evals = int(max_evals)
+    if not 4 <= max_evals <= 1024:
+        raise ValueError("refine_host: 4 <= max_evals <= 1024 needed (got %d)" % max_evals)
+    xs, fs, status, evals = np.full(X0.shape, np.nan), np.full(X0.shape[0], np.nan), [], []
+    best = -1
+    for k in range(X0.shape[0]):
+        x, f, st, ne = _refine_start(objective, X0[k], lo, up, max_evals)
+        status.append(st)
+        evals.append(ne)
+        if x is not None:
+            xs[k], fs[k] = x, f
+            if math.isfinite(f) and (best < 0 or f < fs[best]):
+                best = k
+    info = {"best": best, "status": status, "evals": evals, "x": xs, "f": fs}
+    if best < 0:
+        return None, float("nan"), info
+    return xs[best].copy(), float(fs[best]), info
+
+
+def _pick_starts(keys: np.ndarray, starts: int) -> np.ndarray:
+    """The rows of the `starts` smallest finite keys, ties to the lower row."""
+    keys = np.asarray(keys, dtype=np.float64)
+    fin = np.isfinite(keys)
+    return np.argsort(np.where(fin, keys, np.inf), kind="stable")[:min(int(starts), int(fin.sum()))]
+
+
+def _multistart(objective, grid: np.ndarray, keys: np.ndarray, i0: int, lo, up, starts: int, max_evals: int):
+    """(x, f, info) of one greedy step under refine="multistart": `refine_host` from the best rows of the grid; without a start
+    of finite objective the clipped grid row i0, as `_refine` falls back to."""
+    rows = _pick_starts(keys, starts)
+    x, f, info = None, float("nan"), {"best": -1, "status": [], "evals": []}
+    if rows.size:
+        x, f, info = refine_host(objective, grid[rows], lo, up, max_evals)
+    if x is None:
+        x = np.clip(grid[i0], lo, up)
+        f = float(objective(x)[0])
+    return x, f, info
+
+
+def _check_refine(refine, lower=None, upper=None, starts: int = 16, max_evals: int = 64):
+    if refine not in (None, "lbfgs", "multistart"):
+        raise ValueError("refine must be None, 'lbfgs' or 'multistart' (got %r)" % (refine,))
     if refine == "lbfgs":
         _scipy_optimize()
+    if refine == "multistart":
+        if not 1 <= int(starts) <= MAX_STARTS:
+            raise ValueError("refine='multistart': 1 <= starts <= %d needed (got %r)" % (MAX_STARTS, starts))
+        if not 4 <= int(max_evals) <= 1024:
+            raise ValueError("refine='multistart': 4 <= max_evals <= 1024 needed (got %r)" % (max_evals,))
+        if lower is None or upper is None:
+            raise ValueError("refine='multistart' needs the bounds lower and upper")
 
 
-def greedy_host(D, grid: np.ndarray, q: int, refine=None, lower=None, upper=None):
+def greedy_host(D, grid: np.ndarray, q: int, refine=None, lower=None, upper=None, starts: int = 16, max_evals: int = 64):
     """The numpy mirror of the device flow of `batched_greedy_ei` over `grid` [N, d], in float64: incumbent (argmin of the
     mean), first point (posterior log EI), q - 1 points by the averaged EI with the incrementally extended factor.  Returns
     (points [q, d], info): info['incumbent'], info['index'] (the grid row of every step), info['r'] (the residual variance
-    [N] after the last step), info['bad'] (rows without a positive variance, per step)."""
+    [N] after the last step), info['bad'] (rows without a positive variance, per step).  refine='multistart' runs
+    `refine_host` from the `starts` best rows of every step (the rows as given: float64) and adds info['starts'], the info of
+    `refine_host` per step, the incumbent's first."""
     grid = np.asarray(grid, dtype=np.float64)
+    multi = refine == "multistart"
+    if multi:
+        _check_refine(refine, lower, upper, starts, max_evals)
+        lower, upper = _bounds(lower, grid.shape[1], "lower"), _bounds(upper, grid.shape[1], "upper")
+        runs = []
+
+        def ms(fun, keys, i):
+            x, f, info = _multistart(fun, grid, keys, i, lower, upper, starts, max_evals)
+            runs.append(info)
+            return x, f
     N = grid.shape[0]
     K = kernel_host(D.lls, D.lsf, grid, D.z)
     mean = K @ D.a
@@ -209,12 +354,16 @@ def greedy_host(D, grid: np.ndarray, q: int, refine=None, lower=None, upper=None
     r = D.sf - np.einsum("nm,nm->n", U0, U0)
     i0 = int(np.argmin(mean))
     inc = float(mean[i0])
-    if refine:
+    if multi:
+        inc = ms(lambda x: _posterior_point(D, np.asarray(x, dtype=np.float64).reshape(-1))[0::2], mean, i0)[1]
+    elif refine:
         inc = _refine(lambda x: _posterior_point(D, np.asarray(x, dtype=np.float64).reshape(-1))[0::2], grid[i0], lower, upper)[1]
     keys = -log_ei_host(mean, var0, inc)
     idx, bad = [int(np.argmin(keys))], [int((~(var0 > 0)).sum())]
     p = grid[idx[0]]
-    if refine:
+    if multi:
+        p = ms(_ei_objective(lambda x: _posterior_point(D, x), inc), keys, idx[0])[0]
+    elif refine:
         p = _refine(_ei_objective(lambda x: _posterior_point(D, x), inc), p, lower, upper)[0]
     points = [p]
     fac = _Factor(D, q)
@@ -230,10 +379,15 @@ def greedy_host(D, grid: np.ndarray, q: int, refine=None, lower=None, upper=None
         idx.append(int(np.argmin(keys)))
         bad.append(int((~(r > 0)).sum()))
         p = grid[idx[-1]]
-        if refine:
+        if multi:
+            p = ms(_ei_objective(fac.point, inc), keys, idx[-1])[0]
+        elif refine:
             p = _refine(_ei_objective(fac.point, inc), p, lower, upper)[0]
         points.append(p)
-    return np.stack(points), {"incumbent": inc, "index": idx, "r": r, "bad": bad}
+    info = {"incumbent": inc, "index": idx, "r": r, "bad": bad}
+    if multi:
+        info["starts"] = runs
+    return np.stack(points), info
 
 
 # --------------------------------------------------------------------------------- the training step's host mirror (float64 torch)
@@ -660,12 +814,26 @@ class SparseGP(object):
         m, v, _ = engine.sgp_project(X, D.zt, D.inv_ls32, D.sf, D.Tt, D.M, D.M, D.a32, want_var0=True)
         return -engine.sgp_ei_step(_lib.SGP_ARGMIN_EI, m, v, float(incumbent), want_keys=True)[1]
 
-    def get_incumbent(self, grid, lower=None, upper=None, refine="lbfgs") -> float:
+    def get_incumbent(self, grid, lower=None, upper=None, refine="lbfgs", starts: int = 16, max_evals: int = 64) -> float:
         """`get_incumbent` (sparse_gp.py:272-283): the smallest predictive mean - over the grid, then refined from the best row
-        by L-BFGS-B inside the bounds (refine=None: the best grid row's mean)."""
-        _check_refine(refine)
+        by L-BFGS-B inside the bounds (refine=None: the best grid row's mean; refine='multistart': `refine_host`'s flow from the
+        `starts` best rows, on the device for a GPU model)."""
+        _check_refine(refine, lower, upper, starts, max_evals)
         D = self.derived()
         grid = _as_rows(grid, self.d_input, "get_incumbent")
+        if refine == "multistart":
+            d = self.d_input
+            lo, up = _bounds(lower, d, "lower"), _bounds(upper, d, "upper")
+            if not self.on_gpu:
+                g64 = grid.detach().numpy().astype(np.float64)
+                mean = predict_host(D, g64)[0]
+                return _multistart(lambda x: _posterior_point(D, np.asarray(x, dtype=np.float64).reshape(-1))[0::2], g64, mean,
+                                   int(np.argmin(mean)), lo, up, starts, max_evals)[1]
+            g32 = grid.to(self.device, torch.float32).contiguous()
+            m, _, _ = engine.sgp_project(g32, D.zt, D.inv_ls32, D.sf, None, 0, 0, D.a32)
+            ctx = self._multistart_ctx(D, g32, 0, lo, up, int(starts), int(max_evals))
+            _, _, key, _, f, _ = self._multistart_step(ctx, _lib.SGP_ARGMIN_MEAN, m, m, 0.0, None, _lib.SGP_REFINE_MEAN, None, D.M, False)
+            return f if math.isfinite(f) else key
         if self.on_gpu:
             g32 = grid.to(self.device, torch.float32)
             m, _, _ = engine.sgp_project(g32, D.zt, D.inv_ls32, D.sf, None, 0, 0, D.a32)
@@ -683,14 +851,19 @@ class SparseGP(object):
         return inc
 
     def batched_greedy_ei(self, q: int, lower, upper, mean=None, std=None, sample: str = "normal", grid=None,
-                          grid_size: int = 10000, rng=None, refine="lbfgs", return_info: bool = False):
+                          grid_size: int = 10000, rng=None, refine="lbfgs", return_info: bool = False, starts: int = 16,
+                          max_evals: int = 64):
         """`batched_greedy_ei` (sparse_gp.py:296-335): q points [q, d] (float64 numpy) - the incumbent, the first point by
         `compute_log_ei`, q - 1 points by `compute_log_averaged_ei` (n_samples = 1, zero randomness: the posterior mean and the
         prior variance given z and the points chosen so far).  grid=None draws the reference's grid from `rng`
         (sample='normal': mean + randn std; 'uniform': lower + rand (upper - lower)).  Every step is one grid evaluation
         (`dagnn_sgp_ei_step` on the GPU: one launch and one 32-byte read) and, with refine='lbfgs', the reference's L-BFGS-B from
-        the best grid row (float64 on the host, scipy); refine=None returns the best grid rows."""
-        _check_refine(refine)
+        the best grid row (float64 on the host, scipy); refine=None returns the best grid rows.  refine='multistart' refines
+        on the device instead (csrc/sgp_refine.hip; no scipy): the `starts` <= 32 rows with the smallest finite key of the
+        step, each a projected L-BFGS run of at most `max_evals` evaluations (`refine_host` is the definition), advanced in
+        lock-step in float64; the step's point is the best of them, and the step still reads the device once.  Both defaults
+        come from a CPU prototype on synthetic models, not from a BO run on the real latent spaces."""
+        _check_refine(refine, lower, upper, starts, max_evals)
         q, d = int(q), self.d_input
         if not 1 <= q <= MAX_Q:
             raise ValueError("batched_greedy_ei: 1 <= q <= %d needed (got %d)" % (MAX_Q, q))
@@ -710,9 +883,102 @@ class SparseGP(object):
             raise ValueError("batched_greedy_ei: the grid has no row")
         D = self.derived()
         if not self.on_gpu:
-            points, info = greedy_host(D, grid.detach().numpy(), q, refine, lo, up)
+            points, info = greedy_host(D, grid.detach().numpy(), q, refine, lo, up, starts, max_evals)
             return (points, info) if return_info else points
+        if refine == "multistart":
+            return self._greedy_gpu_multistart(D, grid, q, lo, up, int(starts), int(max_evals), return_info)
         return self._greedy_gpu(D, grid, q, refine, lo, up, return_info)
+
+    # ----------------------------------------------------------------------------- refine="multistart" on the device
+    def _derived64(self, D):
+        """The float64 device operands of csrc/sgp_refine.hip, built when refine='multistart' first asks for them and kept
+        with `D` for the parameter version (the other paths never pay for them)."""
+        if getattr(D, "z64", None) is None:
+            t = lambda v: torch.from_numpy(np.ascontiguousarray(v, dtype=np.float64)).to(self.device)   # noqa: E731
+            D.z64, D.inv_ls64, D.a64, D.G64, D.W64 = t(D.z), t(D.inv_ls), t(D.a), t(D.G), t(D.W)
+        return D
+
+    def _multistart_ctx(self, D, g32, q: int, lo, up, starts: int, max_evals: int):
+        """What the steps of one call share: the expanded operands ze [M + q, d] (and its transpose) and W_e [M + q, M + q], the bounds and the
+        workspace, float64 on the device."""
+        self._derived64(D)
+        M, d, dev = D.M, self.d_input, self.device
+        ze = torch.zeros(M + q, d, dtype=torch.float64, device=dev)
+        ze[:M] = D.z64
+        zet = torch.zeros(d, M + q, dtype=torch.float64, device=dev)   # the same rows transposed: the kernel columns read them
+        zet[:, :M] = D.z64.t()
+        We = None
+        if q > 0:
+            We = torch.zeros(M + q, M + q, dtype=torch.float64, device=dev)
+            We[:M, :M] = D.W64
+        return SimpleNamespace(D=D, g32=g32, lo=lo, up=up, lo_t=torch.from_numpy(lo.copy()).to(dev), up_t=torch.from_numpy(up.copy()).to(dev),
+                               ze=ze, zet=zet, We=We, S=starts, max_evals=max_evals, d=d,
+                               inf=torch.full((), float("inf"), dtype=torch.float64, device=dev),
+                               work=torch.empty(engine.sgp_refine_words(M, q, d, starts), dtype=torch.float64, device=dev))
+
+    def _multistart_step(self, ctx, grid_mode, mean, r, incumbent, update, mode, T, Me, tri):
+        """One greedy step: the grid step with its keys, the starts (a stable sort, nothing synchronises), the refinement, and
+        the step's one read.  Returns (grid row, rows without a positive variance, the row's key, x [d], f, info); without a
+        start of finite objective x is the clipped grid row and f is NaN."""
+        D, S, d = ctx.D, ctx.S, ctx.d
+        res, keys = engine.sgp_ei_step(grid_mode, mean, r, incumbent, update=update, want_keys=True)
+        fin = torch.isfinite(keys)
+        rows = torch.sort(torch.where(fin, keys, ctx.inf), stable=True)[1][:S]
+        nstart = fin.sum().clamp(max=S).to(torch.int32).reshape(1)
+        X0 = torch.zeros(S, d, dtype=torch.float64, device=keys.device)
+        X0[:rows.numel()] = ctx.g32[rows].double()   # the rows as the kernels see them; the run clips them
+        out = engine.sgp_refine_run(mode, X0, ctx.lo_t, ctx.up_t, ctx.ze, D.inv_ls64, D.sf, D.a64, T, Me, tri, incumbent, ctx.max_evals,
+                                    nstart, ctx.work, zet=ctx.zet)
+        both = torch.cat([res, out.view(torch.int64)]).cpu().numpy()   # the step's one read
+        i, nb, key = int(both[0]), int(both[1]), float(both[2:3].view(np.float64)[0])
+        o = both[4:].view(np.float64)
+        best = int(o[0])
+        info = {"best": best, "status": [int(v) for v in o[2 + d:2 + d + S]], "evals": [int(v) for v in o[2 + d + S:2 + d + 2 * S]],
+                "f": o[2 + d + 2 * S:2 + d + 3 * S].copy()}
+        if best >= 0:
+            return i, nb, key, o[2:2 + d].copy(), float(o[1]), info
+        return i, nb, key, np.clip(ctx.g32[i].double().cpu().numpy(), ctx.lo, ctx.up), float("nan"), info
+
+    def _greedy_gpu_multistart(self, D, grid, q, lo, up, starts, max_evals, return_info):
+        M, N, dev, d = D.M, grid.shape[0], self.device, self.d_input
+        g32 = grid.to(dev, torch.float32).contiguous()
+        ctx = self._multistart_ctx(D, g32, q, lo, up, starts, max_evals)
+        U = torch.empty(N, M + q, dtype=torch.float32, device=dev)
+        mean, var0, r = engine.sgp_project(g32, D.zt, D.inv_ls32, D.sf, D.Tt, 2 * M, M, D.a32, U=U, u_col0=M, want_var0=True,
+                                           want_var1=True)
+        runs = []
+        _, _, key, _, f, info = self._multistart_step(ctx, _lib.SGP_ARGMIN_MEAN, mean, var0, 0.0, None, _lib.SGP_REFINE_MEAN, None, M, False)
+        runs.append(info)
+        inc = f if math.isfinite(f) else key
+        i, nb, _, p, _, info = self._multistart_step(ctx, _lib.SGP_ARGMIN_EI, mean, var0, inc, None, _lib.SGP_REFINE_EI, D.G64, M, False)
+        runs.append(info)
+        idx, bad, points = [i], [nb], [p]
+        fac = _Factor(D, q)
+        stage = torch.empty(q, d + M + q, dtype=torch.float32).pin_memory()      # (a row per step: p, then c)
+        stage64 = torch.empty(q, d + M + q, dtype=torch.float64).pin_memory()    # (p, then the new row of W_e)
+        for j in range(1, q):
+            Me = fac.Me
+            c, delta = fac.extend(p)
+            row, row64 = stage[j], stage64[j]
+            row[:d] = torch.from_numpy(p)
+            row[d:d + Me] = torch.from_numpy(c)
+            row64[:d] = torch.from_numpy(p)
+            row64[d:d + Me + 1] = torch.from_numpy(fac.W[Me, :Me + 1])
+            pc, pw = row.to(dev, non_blocking=True), row64.to(dev, non_blocking=True)
+            ctx.ze[Me].copy_(pw[:d])
+            ctx.zet[:, Me].copy_(pw[:d])
+            ctx.We[Me, :Me + 1].copy_(pw[d:d + Me + 1])
+            i, nb, _, p, _, info = self._multistart_step(ctx, _lib.SGP_ARGMIN_EI, mean, r, inc,
+                                                         (g32, D.inv_ls32, D.sf, pc[:d], U, Me, pc[d:], 1.0 / delta),
+                                                         _lib.SGP_REFINE_EI, ctx.We, Me + 1, True)
+            runs.append(info)
+            idx.append(i)
+            bad.append(nb)
+            points.append(p)
+        points = np.stack(points)
+        if return_info:
+            return points, {"incumbent": inc, "index": idx, "r": r, "bad": bad, "starts": runs}
+        return points
 
     def _greedy_gpu(self, D, grid, q, refine, lo, up, return_info):
         M, N, dev = D.M, grid.shape[0], self.device
@@ -765,7 +1031,7 @@ def bo_round(sgp: SparseGP, model, q: int, lower, upper, mean=None, std=None, da
     """bo.py:289-306 as two calls: `batched_greedy_ei` proposes q latent points, then `decode_and_score` (with a `BnData`: the
     BN objective) or `decode_from_latent_space` decodes them on `model`.  Returns (points [q, nz] float64 numpy, strings,
     scores float64 numpy [q] or None).  `greedy`: further arguments of `batched_greedy_ei` (sample, grid, grid_size, rng,
-    refine)."""
+    refine, starts, max_evals)."""
     from . import bn_score, dvae
     points = sgp.batched_greedy_ei(q, lower, upper, mean, std, **greedy)
     dev = next(model.parameters()).device

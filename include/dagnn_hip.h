@@ -1511,6 +1511,46 @@ int dagnn_sgp_energy_grad(const double* X, int64_t ld_x, const double* y, int64_
                           const double* lvar_noise, double* E, double* g_lls, double* g_lsf, double* g_z, double* g_m,
                           double* g_Lp, double* g_noise, void* work, size_t work_bytes, unsigned* fail, void* stream);
 
+/* The refinement of that sparse GP's greedy proposals (csrc/sgp_refine.hip; the reference's `global_optimization`,
+ * sparse_gp.py:24-43, is one L-BFGS-B run of scipy from the best grid row): S <= DAGNN_SGP_REFINE_MAX_STARTS starts advanced
+ * in lock-step by a projected L-BFGS with DAGNN_SGP_REFINE_HISTORY curvature pairs and a halving Armijo search, everything in
+ * float64.  The objective at a column of points x_s, over the Me = M + j rows of ze [Me, d] (the inducing rows, then the chosen
+ * points; zet [d, ld_zt >= Me] holds the same rows transposed, zet[c ld_zt + m] = ze[m][c]), with k_m = sf exp(-1/2 sum_c (x_c - ze_mc)^2 inv_ls_c):
+ *     mean = sum_{m < M} a_m k_m,   v = sf - |T k|^2,   T [Me, Me] with row pitch ld_t (tri != 0: lower triangular, the tiles
+ *     above the diagonal are skipped),
+ * mode DAGNN_SGP_REFINE_MEAN: f = mean (T is not read); mode DAGNN_SGP_REFINE_EI: f = -log EI(mean, v, incumbent), the branch
+ * expression of dagnn_sgp_ei_step with its partials (NaN where v or the argument of the logarithm is not positive, -inf where
+ * exp(-s^2 / 2) underflows).  K = k(x, ze) [Me, S], U = T K and C = T^T U are tile products on v_mfma_f64_16x16x4_f64; every
+ * sum has one fixed order and there is no floating-point atomic, no ticket and no spinning: two calls are bitwise equal.
+ *
+ * dagnn_sgp_refine_eval: one evaluation.  X [S, d]; out [S, 4 + 2 d]: f, mean, v, 0, d mean / dx [d], d v / dx [d].
+ * dagnn_sgp_refine_run: X0 [S, d] (clipped into [lower, upper] on entry); nstart (a device word, may be NULL: S) - the starts
+ * from *nstart on are dead.  max_evals ticks are enqueued without a look at the device, a tick being the two products (mode
+ * EI only) and one launch that reduces, advances every start by one transition and builds the next column of K.  out
+ * [2 + d + 3 S]: the best start (-1: no start has a finite objective), its objective, its point [d], then per start the status
+ * (DAGNN_SGP_REFINE_*), the evaluations it used and its objective, as doubles; xs (may be NULL) [S, d]: every start's accepted
+ * point (NaN for a dead start).
+ * work: dagnn_sgp_refine_bytes(Me, d, S) bytes (0 for a shape out of range), 8-byte aligned.  Borrowed pointers, the caller's
+ * stream, no allocation, no synchronisation; arguments are validated before any HIP call. */
+#define DAGNN_SGP_REFINE_MAX_STARTS 32
+#define DAGNN_SGP_REFINE_HISTORY 8
+#define DAGNN_SGP_REFINE_MEAN 0
+#define DAGNN_SGP_REFINE_EI 1
+#define DAGNN_SGP_REFINE_RUNNING 0
+#define DAGNN_SGP_REFINE_CONVERGED 1
+#define DAGNN_SGP_REFINE_STALLED 2
+#define DAGNN_SGP_REFINE_BUDGET 3
+#define DAGNN_SGP_REFINE_DEAD 4
+size_t dagnn_sgp_refine_bytes(int Me, int d, int S);
+int dagnn_sgp_refine_eval(int mode, int S, int d, int M, int Me, const double* X, const double* ze, const double* zet,
+                          int64_t ld_zt, const double* inv_ls, double sf, const double* a, const double* T, int64_t ld_t, int tri, double incumbent, double* out, void* work,
+                          size_t work_bytes, void* stream);
+int dagnn_sgp_refine_run(int mode, int S, int d, int M, int Me, const double* X0, const int* nstart, const double* lower,
+                         const double* upper, const double* ze, const double* zet, int64_t ld_zt, const double* inv_ls, double sf,
+                         const double* a, const double* T,
+                         int64_t ld_t, int tri, double incumbent, int max_evals, double* out, double* xs, void* work,
+                         size_t work_bytes, void* stream);
+
 /* The tail of the reference's training step - `clip_grad_norm_(model.parameters(), clip)` + `optim.Adam.step()`
  * (ogbg-code/main_pyg.py:63-65,179) - over a table of fp32 tensors (csrc/optim.hip).  dagnn_grad_norm: the 2-norm of up to
  * DAGNN_MAX_OPT_TENSORS gradients (`partial`: scratch of dagnn_opt_chunks() floats; `accumulate` != 0 adds the tensors' sum of

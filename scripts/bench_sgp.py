@@ -6,8 +6,9 @@
                      same GPU and the same fp32 operands - distances from the differences as the kernel has them, and
                      (`torch_mm`) from the expanded square on a matmul as the reference has them
   batched_greedy_ei  q = --q points on a --grid-row grid: the HIP flow without refinement, the same loop on torch ops (one
-                     grid evaluation, the argmin and one read per step), and the HIP flow with the L-BFGS-B refinement; wall
-                     clock including every synchronisation
+                     grid evaluation, the argmin and one read per step), the HIP flow with the L-BFGS-B refinement (scipy, on
+                     the host) and with refine="multistart" (--starts starts, --max-evals ticks, on the device); wall clock
+                     including every synchronisation
   train_via_adam     wall time per Adam step at minibatch --minibatch: the default path (float64 torch ops under autograd) and
                      grad="hip" (csrc/sgp_train.hip) in the same run; one energy + gradient evaluation of each path alone
                      (`energy_grad_*_ms`, their largest relative difference per parameter before anything is timed); and one
@@ -126,6 +127,8 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--no-refine", action="store_true")
+    ap.add_argument("--starts", type=int, default=16)
+    ap.add_argument("--max-evals", type=int, default=64)
     ap.add_argument("--train-only", action="store_true")
     ap.add_argument("--fit-rows", type=int, default=5000)
     ap.add_argument("--fit-epochs", type=int, default=100)
@@ -221,6 +224,16 @@ def main():
     out["greedy_torch_ms"] = wall_ms(lambda: torch_greedy(D, g32, a.q), steps, warm)
     if not a.no_refine:
         out["greedy_hip_lbfgs_ms"] = wall_ms(lambda: g.batched_greedy_ei(a.q, lo, up, grid=g32, refine="lbfgs"), 3, 1)
+        # the same call refined on the device: `--starts` starts in lock-step, `--max-evals` ticks of three launches each
+        # (two for the products, one that reduces, advances and builds the next kernel columns; one for the incumbent's mean)
+        ms = dict(refine="multistart", starts=a.starts, max_evals=a.max_evals)
+        _, minfo = g.batched_greedy_ei(a.q, lo, up, grid=g32, return_info=True, **ms)
+        runs = minfo["starts"]
+        out["greedy_multistart"] = {"starts": a.starts, "max_evals": a.max_evals, "launches_per_tick": 3,
+                                    "status": {name: sum(r["status"].count(k) for r in runs) for k, name in enumerate(sgp.REFINE_STATUS)},
+                                    "evals_of_the_best_median": float(np.median([r["evals"][r["best"]] for r in runs if r["best"] >= 0])),
+                                    "best_is_start_0": sum(int(r["best"] == 0) for r in runs), "steps": len(runs)}
+        out["greedy_hip_multistart_ms"] = wall_ms(lambda: g.batched_greedy_ei(a.q, lo, up, grid=g32, **ms), 3, 1)
     print(json.dumps(out))
 
 
