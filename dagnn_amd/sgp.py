@@ -328,6 +328,203 @@ def _check_refine(refine, lower=None, upper=None, starts: int = 16, max_evals: i
             raise ValueError("refine='multistart' needs the bounds lower and upper")
 
 
+# --------------------------------------------------------------------------------- the greedy flow and its step providers
+def _posterior_mean(D):
+    """x -> (mean, d mean / dx) under the posterior: the objective of the incumbent's refinement."""
+    return lambda x: _posterior_point(D, np.asarray(x, dtype=np.float64).reshape(-1))[0::2]
+
+
+def _incumbent(prov, D):
+    """Stage 0 of a greedy batch, and all of `get_incumbent`: (the incumbent, the step's run info).  The incumbent is the
+    refined objective, and the best row's mean where no refinement has one (none asked for, or no live start)."""
+    _, _, key, _, f, run = prov.incumbent(_posterior_mean(D))
+    return (f if math.isfinite(f) else key), run
+
+
+def _greedy_flow(prov, D, q: int):
+    """The order of a greedy batch, written once for the host mirror and the device: the incumbent, the first point by the
+    posterior EI under G, then per further point the factor extended by the previous point and the averaged EI under it.
+    `prov` evaluates the grid and picks the points - `incumbent(fun)`, `posterior(inc, fun)`, `averaged(inc, fun, fac, c, delta)`,
+    each returning (grid row, rows without a positive variance, the row's key, x, f, run info or None); `fun` is the step's
+    float64 objective on the host, for a provider that refines there.  Returns (points [q, d], info) as `greedy_host` has them."""
+    inc, run = _incumbent(prov, D)
+    steps = [prov.posterior(inc, _ei_objective(lambda x: _posterior_point(D, x), inc))]
+    fac = _Factor(D, q)
+    for _ in range(1, q):
+        c, delta = fac.extend(steps[-1][3])
+        steps.append(prov.averaged(inc, _ei_objective(fac.point, inc), fac, c, delta))
+    info = {"incumbent": inc, "index": [s[0] for s in steps], "r": prov.r, "bad": [s[1] for s in steps]}
+    if run is not None:
+        info["starts"] = [run] + [s[5] for s in steps]
+    return np.stack([s[3] for s in steps]), info
+
+
+def _from_row(refine, fun, x: np.ndarray, key: float, lower, upper):
+    """(x, f, None) of a step that starts from its best grid row x alone: the row with its key, or `_refine` from it."""
+    return _refine(fun, x, lower, upper) + (None,) if refine else (x, key, None)
+
+
+def _decode(res: np.ndarray):
+    """(grid row, rows without a positive variance, the row's key) of the result words of `dagnn_sgp_ei_step`."""
+    return int(res[0]), int(res[1]), float(res[2:3].view(np.float64)[0])
+
+
+def _stage(row: torch.Tensor, dev, *parts):
+    """Fills the front of one pinned staging row with `parts`, back to back, and sends it: the row on the device."""
+    v = np.concatenate(parts)
+    row[:v.size] = torch.from_numpy(v)
+    return row.to(dev, non_blocking=True)
+
+
+class _HostGrid(object):
+    """The steps of a CPU model and of `greedy_host`: the grid in float64 numpy, the point by `_refine` (refine='lbfgs') or
+    `_multistart` from the rows as given."""
+
+    def __init__(self, D, grid, q: int, refine, lower, upper, starts: int, max_evals: int):
+        grid = np.asarray(grid, dtype=np.float64)
+        if refine == "multistart":
+            _check_refine(refine, lower, upper, starts, max_evals)
+        if refine:
+            lower, upper = _bounds(lower, grid.shape[1], "lower"), _bounds(upper, grid.shape[1], "upper")
+        self.D, self.grid, self.q, self.refine, self.point_args = D, grid, q, refine, (lower, upper, starts, max_evals)
+        self.K = kernel_host(D.lls, D.lsf, grid, D.z)
+        self.mean = self.K @ D.a
+
+    def _step(self, keys, fun, var=None):
+        i = int(np.argmin(keys))
+        key = float(keys[i])
+        if self.refine == "multistart":
+            point = _multistart(fun, self.grid, keys, i, *self.point_args)
+        else:
+            point = _from_row(self.refine, fun, self.grid[i], key, *self.point_args[:2])
+        return (i, 0 if var is None else int((~(var > 0)).sum()), key) + point
+
+    def incumbent(self, fun):
+        return self._step(self.mean, fun)
+
+    def posterior(self, inc, fun):
+        D, K, M = self.D, self.K, self.D.z.shape[0]
+        GK, U0 = K @ D.G.T, K @ D.W.T
+        var0 = D.sf - np.einsum("nm,nm->n", GK, GK)
+        self.r = D.sf - np.einsum("nm,nm->n", U0, U0)
+        self.U = np.zeros((K.shape[0], M + self.q))
+        self.U[:, :M] = U0
+        return self._step(-log_ei_host(self.mean, var0, inc), fun, var0)
+
+    def averaged(self, inc, fun, fac, c, delta):
+        D, Me = self.D, fac.Me - 1   # (fac holds the previous point as row Me of z_e)
+        w = (kernel_host(D.lls, D.lsf, self.grid, fac.ze[Me:Me + 1])[:, 0] - self.U[:, :Me] @ c) / delta
+        self.U[:, Me] = w
+        self.r = self.r - w * w
+        return self._step(-log_ei_host(self.mean, self.r, inc), fun, self.r)
+
+
+_INCUMBENT, _POSTERIOR, _AVERAGED = range(3)
+
+
+class _DeviceGrid(object):
+    """The steps of a GPU model with refine None or 'lbfgs': `dagnn_sgp_project` over the grid once, then per step one launch
+    of `dagnn_sgp_ei_step` and one 32-byte read; `_refine` runs on the host from the row as the kernels see it.  q = 0 (the
+    incumbent alone) projects the mean only."""
+
+    def __init__(self, model, D, grid, q: int, refine, lo, up):
+        M, d, dev = D.M, D.d, model.device
+        self.D, self.dev, self.refine, self.lo, self.up = D, dev, refine, lo, up
+        self.g32 = g32 = grid.to(dev, torch.float32).contiguous()
+        self.host = g32.double().cpu().numpy() if q > 0 and refine != "multistart" else None   # (else `_row` reads the one row)
+        if q < 1:   # (the argmin of the mean never looks at the variance)
+            self.mean = self.var0 = engine.sgp_project(g32, D.zt, D.inv_ls32, D.sf, None, 0, 0, D.a32)[0]
+            return
+        self.U = torch.empty(grid.shape[0], M + q, dtype=torch.float32, device=dev)
+        self.mean, self.var0, self.r = engine.sgp_project(g32, D.zt, D.inv_ls32, D.sf, D.Tt, 2 * M, M, D.a32, U=self.U, u_col0=M,
+                                                          want_var0=True, want_var1=True)
+        self.stage = torch.empty(q, d + M + q, dtype=torch.float32).pin_memory()   # (a row per step: p, then c)
+
+    def _row(self, i: int) -> np.ndarray:   # row i of the grid as the kernels see it, float64 on the host
+        return self.g32[i].double().cpu().numpy() if self.host is None else self.host[i]
+
+    def _send(self, fac, c):
+        """Stages what the step's kernels need of `fac`'s extension by its last point p: the fp32 row [p, c] on the device."""
+        Me = fac.Me - 1
+        return _stage(self.stage[Me + 1 - self.D.M], self.dev, fac.ze[Me], c)
+
+    def _step(self, kind, var, inc, update, fun, Me):
+        res, keys = engine.sgp_ei_step(_lib.SGP_ARGMIN_MEAN if kind == _INCUMBENT else _lib.SGP_ARGMIN_EI, self.mean, var, inc,
+                                       update=update, want_keys=self.refine == "multistart")
+        return self._point(res, keys, kind, inc, fun, Me)
+
+    def _point(self, res, keys, kind, inc, fun, Me):
+        i, nb, key = _decode(res.cpu().numpy())   # the step's one read
+        if kind == _INCUMBENT and not self.refine:
+            return i, nb, key, None, key, None    # (the row's mean is all that is asked for: the row stays where it is)
+        return (i, nb, key) + _from_row(self.refine, fun, self._row(i), key, self.lo, self.up)
+
+    def incumbent(self, fun):
+        return self._step(_INCUMBENT, self.var0, 0.0, None, fun, self.D.M)
+
+    def posterior(self, inc, fun):
+        return self._step(_POSTERIOR, self.var0, inc, None, fun, self.D.M)
+
+    def averaged(self, inc, fun, fac, c, delta):
+        D, d, Me = self.D, self.D.d, fac.Me - 1
+        pc = self._send(fac, c)
+        return self._step(_AVERAGED, self.r, inc, (self.g32, D.inv_ls32, D.sf, pc[:d], self.U, Me, pc[d:], 1.0 / delta), fun, fac.Me)
+
+
+class _DeviceMultistart(_DeviceGrid):
+    """The steps of a GPU model with refine='multistart': the grid step hands its keys on, csrc/sgp_refine.hip refines the `starts`
+    best rows in float64, and the step still reads the device once.  Kept in float64 on the device: ze [M + q, d] and its transpose
+    (the kernel columns read that one), W_e [M + q, M + q] (none for q = 0), the bounds and the workspace."""
+
+    def __init__(self, model, D, grid, q: int, lo, up, starts: int, max_evals: int):
+        super().__init__(model, D, grid, q, "multistart", lo, up)
+        model._derived64(D)
+        M, d, dev = D.M, D.d, self.dev
+        self.S, self.max_evals = starts, max_evals
+        self.lo_t, self.up_t = torch.from_numpy(lo.copy()).to(dev), torch.from_numpy(up.copy()).to(dev)
+        self.ze = torch.zeros(M + q, d, dtype=torch.float64, device=dev)
+        self.ze[:M] = D.z64
+        self.zet = torch.zeros(d, M + q, dtype=torch.float64, device=dev)
+        self.zet[:, :M] = D.z64.t()
+        self.We = None
+        if q > 0:
+            self.We = torch.zeros(M + q, M + q, dtype=torch.float64, device=dev)
+            self.We[:M, :M] = D.W64
+            self.stage64 = torch.empty(q, d + M + q, dtype=torch.float64).pin_memory()   # (p, then the new row of W_e)
+        self.inf = torch.full((), float("inf"), dtype=torch.float64, device=dev)
+        self.work = torch.empty(engine.sgp_refine_words(M, q, d, starts), dtype=torch.float64, device=dev)
+
+    def _send(self, fac, c):
+        pc = super()._send(fac, c)
+        Me, d = fac.Me - 1, self.D.d
+        pw = _stage(self.stage64[Me + 1 - self.D.M], self.dev, fac.ze[Me], fac.W[Me, :Me + 1])
+        self.ze[Me].copy_(pw[:d])
+        self.zet[:, Me].copy_(pw[:d])
+        self.We[Me, :Me + 1].copy_(pw[d:d + Me + 1])
+        return pc
+
+    def _point(self, res, keys, kind, inc, fun, Me):
+        """The starts (a stable sort), the refinement and the step's one read; without a live start the clipped grid row, f = NaN."""
+        D, S, d = self.D, self.S, self.D.d
+        mode, T = ((_lib.SGP_REFINE_MEAN, None), (_lib.SGP_REFINE_EI, D.G64), (_lib.SGP_REFINE_EI, self.We))[kind]
+        fin = torch.isfinite(keys)
+        rows = torch.sort(torch.where(fin, keys, self.inf), stable=True)[1][:S]
+        nstart = fin.sum().clamp(max=S).to(torch.int32).reshape(1)
+        X0 = torch.zeros(S, d, dtype=torch.float64, device=keys.device)
+        X0[:rows.numel()] = self.g32[rows].double()   # the rows as the kernels see them; the run clips them
+        out = engine.sgp_refine_run(mode, X0, self.lo_t, self.up_t, self.ze, D.inv_ls64, D.sf, D.a64, T, Me, kind == _AVERAGED, inc,
+                                    self.max_evals, nstart, self.work, zet=self.zet)
+        both = torch.cat([res, out.view(torch.int64)]).cpu().numpy()   # the step's one read
+        i, nb, key = _decode(both)
+        o = both[4:].view(np.float64)
+        best = int(o[0])
+        info = {"best": best, "status": [int(v) for v in o[2 + d:2 + d + S]], "evals": [int(v) for v in o[2 + d + S:2 + d + 2 * S]],
+                "f": o[2 + d + 2 * S:2 + d + 3 * S].copy()}
+        if best >= 0:
+            return i, nb, key, o[2:2 + d].copy(), float(o[1]), info
+        return i, nb, key, np.clip(self._row(i), self.lo, self.up), float("nan"), info
+
+
 def greedy_host(D, grid: np.ndarray, q: int, refine=None, lower=None, upper=None, starts: int = 16, max_evals: int = 64):
     """The numpy mirror of the device flow of `batched_greedy_ei` over `grid` [N, d], in float64: incumbent (argmin of the
     mean), first point (posterior log EI), q - 1 points by the averaged EI with the incrementally extended factor.  Returns
@@ -335,59 +532,7 @@ def greedy_host(D, grid: np.ndarray, q: int, refine=None, lower=None, upper=None
     [N] after the last step), info['bad'] (rows without a positive variance, per step).  refine='multistart' runs
     `refine_host` from the `starts` best rows of every step (the rows as given: float64) and adds info['starts'], the info of
     `refine_host` per step, the incumbent's first."""
-    grid = np.asarray(grid, dtype=np.float64)
-    multi = refine == "multistart"
-    if multi:
-        _check_refine(refine, lower, upper, starts, max_evals)
-        lower, upper = _bounds(lower, grid.shape[1], "lower"), _bounds(upper, grid.shape[1], "upper")
-        runs = []
-
-        def ms(fun, keys, i):
-            x, f, info = _multistart(fun, grid, keys, i, lower, upper, starts, max_evals)
-            runs.append(info)
-            return x, f
-    N = grid.shape[0]
-    K = kernel_host(D.lls, D.lsf, grid, D.z)
-    mean = K @ D.a
-    GK, U0 = K @ D.G.T, K @ D.W.T
-    var0 = D.sf - np.einsum("nm,nm->n", GK, GK)
-    r = D.sf - np.einsum("nm,nm->n", U0, U0)
-    i0 = int(np.argmin(mean))
-    inc = float(mean[i0])
-    if multi:
-        inc = ms(lambda x: _posterior_point(D, np.asarray(x, dtype=np.float64).reshape(-1))[0::2], mean, i0)[1]
-    elif refine:
-        inc = _refine(lambda x: _posterior_point(D, np.asarray(x, dtype=np.float64).reshape(-1))[0::2], grid[i0], lower, upper)[1]
-    keys = -log_ei_host(mean, var0, inc)
-    idx, bad = [int(np.argmin(keys))], [int((~(var0 > 0)).sum())]
-    p = grid[idx[0]]
-    if multi:
-        p = ms(_ei_objective(lambda x: _posterior_point(D, x), inc), keys, idx[0])[0]
-    elif refine:
-        p = _refine(_ei_objective(lambda x: _posterior_point(D, x), inc), p, lower, upper)[0]
-    points = [p]
-    fac = _Factor(D, q)
-    U = np.zeros((N, D.z.shape[0] + q))
-    U[:, :D.z.shape[0]] = U0
-    for _ in range(1, q):
-        Me = fac.Me
-        c, delta = fac.extend(p)
-        w = (kernel_host(D.lls, D.lsf, grid, p[None, :])[:, 0] - U[:, :Me] @ c) / delta
-        U[:, Me] = w
-        r = r - w * w
-        keys = -log_ei_host(mean, r, inc)
-        idx.append(int(np.argmin(keys)))
-        bad.append(int((~(r > 0)).sum()))
-        p = grid[idx[-1]]
-        if multi:
-            p = ms(_ei_objective(fac.point, inc), keys, idx[-1])[0]
-        elif refine:
-            p = _refine(_ei_objective(fac.point, inc), p, lower, upper)[0]
-        points.append(p)
-    info = {"incumbent": inc, "index": idx, "r": r, "bad": bad}
-    if multi:
-        info["starts"] = runs
-    return np.stack(points), info
+    return _greedy_flow(_HostGrid(D, grid, q, refine, lower, upper, starts, max_evals), D, q)
 
 
 # --------------------------------------------------------------------------------- the training step's host mirror (float64 torch)
@@ -817,38 +962,21 @@ class SparseGP(object):
     def get_incumbent(self, grid, lower=None, upper=None, refine="lbfgs", starts: int = 16, max_evals: int = 64) -> float:
         """`get_incumbent` (sparse_gp.py:272-283): the smallest predictive mean - over the grid, then refined from the best row
         by L-BFGS-B inside the bounds (refine=None: the best grid row's mean; refine='multistart': `refine_host`'s flow from the
-        `starts` best rows, on the device for a GPU model)."""
+        `starts` best rows, on the device for a GPU model): stage 0 of the flow of `batched_greedy_ei`."""
         _check_refine(refine, lower, upper, starts, max_evals)
         D = self.derived()
         grid = _as_rows(grid, self.d_input, "get_incumbent")
-        if refine == "multistart":
-            d = self.d_input
-            lo, up = _bounds(lower, d, "lower"), _bounds(upper, d, "upper")
-            if not self.on_gpu:
-                g64 = grid.detach().numpy().astype(np.float64)
-                mean = predict_host(D, g64)[0]
-                return _multistart(lambda x: _posterior_point(D, np.asarray(x, dtype=np.float64).reshape(-1))[0::2], g64, mean,
-                                   int(np.argmin(mean)), lo, up, starts, max_evals)[1]
-            g32 = grid.to(self.device, torch.float32).contiguous()
-            m, _, _ = engine.sgp_project(g32, D.zt, D.inv_ls32, D.sf, None, 0, 0, D.a32)
-            ctx = self._multistart_ctx(D, g32, 0, lo, up, int(starts), int(max_evals))
-            _, _, key, _, f, _ = self._multistart_step(ctx, _lib.SGP_ARGMIN_MEAN, m, m, 0.0, None, _lib.SGP_REFINE_MEAN, None, D.M, False)
-            return f if math.isfinite(f) else key
-        if self.on_gpu:
-            g32 = grid.to(self.device, torch.float32)
-            m, _, _ = engine.sgp_project(g32, D.zt, D.inv_ls32, D.sf, None, 0, 0, D.a32)
-            res = engine.sgp_ei_step(_lib.SGP_ARGMIN_MEAN, m, m)[0].cpu().numpy()
-            i0, inc = int(res[0]), float(res[2:3].view(np.float64)[0])
-            x0 = g32[i0].double().cpu().numpy() if refine else None
-        else:
-            mean = predict_host(D, grid.detach().numpy().astype(np.float64))[0]
-            i0 = int(np.argmin(mean))
-            inc, x0 = float(mean[i0]), grid[i0].detach().numpy().astype(np.float64)
         if refine:
-            d = self.d_input
-            inc = _refine(lambda x: _posterior_point(D, np.asarray(x, dtype=np.float64).reshape(-1))[0::2], x0,
-                          _bounds(lower, d, "lower"), _bounds(upper, d, "upper"))[1]
-        return inc
+            lower, upper = _bounds(lower, self.d_input, "lower"), _bounds(upper, self.d_input, "upper")
+        return _incumbent(self._steps(D, grid, 0, refine, lower, upper, starts, max_evals), D)[0]
+
+    def _steps(self, D, grid: torch.Tensor, q: int, refine, lo, up, starts, max_evals):
+        """The step provider of `_greedy_flow`: a CPU model's never touches `engine`, a GPU model's never the `*_host` grid."""
+        if not self.on_gpu:
+            return _HostGrid(D, grid.detach().numpy(), q, refine, lo, up, starts, max_evals)
+        if refine == "multistart":
+            return _DeviceMultistart(self, D, grid, q, lo, up, int(starts), int(max_evals))
+        return _DeviceGrid(self, D, grid, q, refine, lo, up)
 
     def batched_greedy_ei(self, q: int, lower, upper, mean=None, std=None, sample: str = "normal", grid=None,
                           grid_size: int = 10000, rng=None, refine="lbfgs", return_info: bool = False, starts: int = 16,
@@ -882,12 +1010,8 @@ class SparseGP(object):
         if grid.shape[0] < 1:
             raise ValueError("batched_greedy_ei: the grid has no row")
         D = self.derived()
-        if not self.on_gpu:
-            points, info = greedy_host(D, grid.detach().numpy(), q, refine, lo, up, starts, max_evals)
-            return (points, info) if return_info else points
-        if refine == "multistart":
-            return self._greedy_gpu_multistart(D, grid, q, lo, up, int(starts), int(max_evals), return_info)
-        return self._greedy_gpu(D, grid, q, refine, lo, up, return_info)
+        points, info = _greedy_flow(self._steps(D, grid, q, refine, lo, up, starts, max_evals), D, q)
+        return (points, info) if return_info else points
 
     # ----------------------------------------------------------------------------- refine="multistart" on the device
     def _derived64(self, D):
@@ -897,132 +1021,6 @@ class SparseGP(object):
             t = lambda v: torch.from_numpy(np.ascontiguousarray(v, dtype=np.float64)).to(self.device)   # noqa: E731
             D.z64, D.inv_ls64, D.a64, D.G64, D.W64 = t(D.z), t(D.inv_ls), t(D.a), t(D.G), t(D.W)
         return D
-
-    def _multistart_ctx(self, D, g32, q: int, lo, up, starts: int, max_evals: int):
-        """What the steps of one call share: the expanded operands ze [M + q, d] (and its transpose) and W_e [M + q, M + q], the bounds and the
-        workspace, float64 on the device."""
-        self._derived64(D)
-        M, d, dev = D.M, self.d_input, self.device
-        ze = torch.zeros(M + q, d, dtype=torch.float64, device=dev)
-        ze[:M] = D.z64
-        zet = torch.zeros(d, M + q, dtype=torch.float64, device=dev)   # the same rows transposed: the kernel columns read them
-        zet[:, :M] = D.z64.t()
-        We = None
-        if q > 0:
-            We = torch.zeros(M + q, M + q, dtype=torch.float64, device=dev)
-            We[:M, :M] = D.W64
-        return SimpleNamespace(D=D, g32=g32, lo=lo, up=up, lo_t=torch.from_numpy(lo.copy()).to(dev), up_t=torch.from_numpy(up.copy()).to(dev),
-                               ze=ze, zet=zet, We=We, S=starts, max_evals=max_evals, d=d,
-                               inf=torch.full((), float("inf"), dtype=torch.float64, device=dev),
-                               work=torch.empty(engine.sgp_refine_words(M, q, d, starts), dtype=torch.float64, device=dev))
-
-    def _multistart_step(self, ctx, grid_mode, mean, r, incumbent, update, mode, T, Me, tri):
-        """One greedy step: the grid step with its keys, the starts (a stable sort, nothing synchronises), the refinement, and
-        the step's one read.  Returns (grid row, rows without a positive variance, the row's key, x [d], f, info); without a
-        start of finite objective x is the clipped grid row and f is NaN."""
-        D, S, d = ctx.D, ctx.S, ctx.d
-        res, keys = engine.sgp_ei_step(grid_mode, mean, r, incumbent, update=update, want_keys=True)
-        fin = torch.isfinite(keys)
-        rows = torch.sort(torch.where(fin, keys, ctx.inf), stable=True)[1][:S]
-        nstart = fin.sum().clamp(max=S).to(torch.int32).reshape(1)
-        X0 = torch.zeros(S, d, dtype=torch.float64, device=keys.device)
-        X0[:rows.numel()] = ctx.g32[rows].double()   # the rows as the kernels see them; the run clips them
-        out = engine.sgp_refine_run(mode, X0, ctx.lo_t, ctx.up_t, ctx.ze, D.inv_ls64, D.sf, D.a64, T, Me, tri, incumbent, ctx.max_evals,
-                                    nstart, ctx.work, zet=ctx.zet)
-        both = torch.cat([res, out.view(torch.int64)]).cpu().numpy()   # the step's one read
-        i, nb, key = int(both[0]), int(both[1]), float(both[2:3].view(np.float64)[0])
-        o = both[4:].view(np.float64)
-        best = int(o[0])
-        info = {"best": best, "status": [int(v) for v in o[2 + d:2 + d + S]], "evals": [int(v) for v in o[2 + d + S:2 + d + 2 * S]],
-                "f": o[2 + d + 2 * S:2 + d + 3 * S].copy()}
-        if best >= 0:
-            return i, nb, key, o[2:2 + d].copy(), float(o[1]), info
-        return i, nb, key, np.clip(ctx.g32[i].double().cpu().numpy(), ctx.lo, ctx.up), float("nan"), info
-
-    def _greedy_gpu_multistart(self, D, grid, q, lo, up, starts, max_evals, return_info):
-        M, N, dev, d = D.M, grid.shape[0], self.device, self.d_input
-        g32 = grid.to(dev, torch.float32).contiguous()
-        ctx = self._multistart_ctx(D, g32, q, lo, up, starts, max_evals)
-        U = torch.empty(N, M + q, dtype=torch.float32, device=dev)
-        mean, var0, r = engine.sgp_project(g32, D.zt, D.inv_ls32, D.sf, D.Tt, 2 * M, M, D.a32, U=U, u_col0=M, want_var0=True,
-                                           want_var1=True)
-        runs = []
-        _, _, key, _, f, info = self._multistart_step(ctx, _lib.SGP_ARGMIN_MEAN, mean, var0, 0.0, None, _lib.SGP_REFINE_MEAN, None, M, False)
-        runs.append(info)
-        inc = f if math.isfinite(f) else key
-        i, nb, _, p, _, info = self._multistart_step(ctx, _lib.SGP_ARGMIN_EI, mean, var0, inc, None, _lib.SGP_REFINE_EI, D.G64, M, False)
-        runs.append(info)
-        idx, bad, points = [i], [nb], [p]
-        fac = _Factor(D, q)
-        stage = torch.empty(q, d + M + q, dtype=torch.float32).pin_memory()      # (a row per step: p, then c)
-        stage64 = torch.empty(q, d + M + q, dtype=torch.float64).pin_memory()    # (p, then the new row of W_e)
-        for j in range(1, q):
-            Me = fac.Me
-            c, delta = fac.extend(p)
-            row, row64 = stage[j], stage64[j]
-            row[:d] = torch.from_numpy(p)
-            row[d:d + Me] = torch.from_numpy(c)
-            row64[:d] = torch.from_numpy(p)
-            row64[d:d + Me + 1] = torch.from_numpy(fac.W[Me, :Me + 1])
-            pc, pw = row.to(dev, non_blocking=True), row64.to(dev, non_blocking=True)
-            ctx.ze[Me].copy_(pw[:d])
-            ctx.zet[:, Me].copy_(pw[:d])
-            ctx.We[Me, :Me + 1].copy_(pw[d:d + Me + 1])
-            i, nb, _, p, _, info = self._multistart_step(ctx, _lib.SGP_ARGMIN_EI, mean, r, inc,
-                                                         (g32, D.inv_ls32, D.sf, pc[:d], U, Me, pc[d:], 1.0 / delta),
-                                                         _lib.SGP_REFINE_EI, ctx.We, Me + 1, True)
-            runs.append(info)
-            idx.append(i)
-            bad.append(nb)
-            points.append(p)
-        points = np.stack(points)
-        if return_info:
-            return points, {"incumbent": inc, "index": idx, "r": r, "bad": bad, "starts": runs}
-        return points
-
-    def _greedy_gpu(self, D, grid, q, refine, lo, up, return_info):
-        M, N, dev = D.M, grid.shape[0], self.device
-        g32 = grid.to(dev, torch.float32).contiguous()
-        host = g32.double().cpu().numpy()   # the rows as the kernels see them
-        U = torch.empty(N, M + q, dtype=torch.float32, device=dev)
-        mean, var0, r = engine.sgp_project(g32, D.zt, D.inv_ls32, D.sf, D.Tt, 2 * M, M, D.a32, U=U, u_col0=M, want_var0=True,
-                                           want_var1=True)
-
-        def read(res):
-            res = res.cpu().numpy()   # the step's one read
-            return int(res[0]), int(res[1]), float(res[2:3].view(np.float64)[0])
-
-        i0, _, inc = read(engine.sgp_ei_step(_lib.SGP_ARGMIN_MEAN, mean, var0)[0])
-        if refine:
-            inc = _refine(lambda x: _posterior_point(D, np.asarray(x, dtype=np.float64).reshape(-1))[0::2], host[i0], lo, up)[1]
-        i, nb, _ = read(engine.sgp_ei_step(_lib.SGP_ARGMIN_EI, mean, var0, inc)[0])
-        idx, bad = [i], [nb]
-        p = host[i]
-        if refine:
-            p = _refine(_ei_objective(lambda x: _posterior_point(D, x), inc), p, lo, up)[0]
-        points = [p]
-        fac = _Factor(D, q)
-        stage = torch.empty(q, self.d_input + M + q, dtype=torch.float32).pin_memory()   # (a row per step: p, then c)
-        for j in range(1, q):
-            Me = fac.Me
-            c, delta = fac.extend(p)
-            row = stage[j]
-            row[:self.d_input] = torch.from_numpy(p)
-            row[self.d_input:self.d_input + Me] = torch.from_numpy(c)
-            pc = row.to(dev, non_blocking=True)
-            res = engine.sgp_ei_step(_lib.SGP_ARGMIN_EI, mean, r, inc,
-                                     update=(g32, D.inv_ls32, D.sf, pc[:self.d_input], U, Me, pc[self.d_input:], 1.0 / delta))[0]
-            i, nb, _ = read(res)
-            idx.append(i)
-            bad.append(nb)
-            p = host[i]
-            if refine:
-                p = _refine(_ei_objective(fac.point, inc), p, lo, up)[0]
-            points.append(p)
-        points = np.stack(points)
-        if return_info:
-            return points, {"incumbent": inc, "index": idx, "r": r, "bad": bad}
-        return points
 
 
 # --------------------------------------------------------------------------------- a BO round

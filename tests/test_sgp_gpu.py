@@ -283,6 +283,37 @@ def test_batched_greedy_ei_end_to_end(device):
         assert lei[idx[j]] >= lei[best] - (bound[idx[j]] + bound[best])
 
 
+def test_lbfgs_refinement_on_the_device_grid(device):
+    """refine='lbfgs', the default, on a GPU model - the device twin of test_sgp_cpu's
+    test_refinement_stays_inside_the_bounds_and_never_loses: in float64, every point is at least as good as the grid row it
+    started from (`_refine` never returns worse than its start, and both are judged by the same restatement, so the fp32 grid
+    does not enter); only the choice of the incumbent's start row is fp32, hence tol_m of the test above."""
+    pytest.importorskip("scipy.optimize")
+    d, M, N, q = 3, 7, 60, 4
+    g, P = model(d, M, device)
+    D = g.derived()
+    rng = np.random.RandomState(d + M)
+    lo, up = -1.5 * np.ones(d), 1.5 * np.ones(d)
+    grid = (lo + rng.rand(N, d) * (up - lo)).astype(np.float32).astype(np.float64)
+    pts, info = g.batched_greedy_ei(q, lo, up, grid=grid, refine="lbfgs", return_info=True)
+    assert pts.shape == (q, d) and (pts >= lo).all() and (pts <= up).all()
+    inc = info["incumbent"]
+    for j in range(q):
+        both = np.stack([pts[j], grid[info["index"][j]]])
+        mean, v0 = ref_predict(P, both)
+        v = v0 if j == 0 else ref_greedy_var(P, both, pts[:j])
+        lei = ref_log_ei(mean, v, inc)
+        print("step %d: log EI %.12g from row %d at %.12g" % (j, lei[0], info["index"][j], lei[1]))
+        assert lei[0] >= lei[1] - 1e-9 * max(1.0, abs(lei[1])), (j, lei)
+    m64 = ref_predict(P, grid)[0]
+    tm = torch_fp32(D, torch.from_numpy(grid).to(device, torch.float32))[0].double().cpu().numpy()
+    tol_m = max(4 * np.abs(tm - m64).max(), 4 * ULP32 * np.abs(m64).max())
+    print("incumbent %.12g, the grid's smallest float64 mean %.12g, tol_m %.3g" % (inc, m64.min(), tol_m))
+    assert inc <= m64.min() + tol_m
+    assert g.get_incumbent(grid, lo, up) == inc
+    np.testing.assert_array_equal(g.batched_greedy_ei(q, lo, up, grid=grid, refine="lbfgs"), pts)   # bitwise repeatable
+
+
 def test_bo_round_decodes_and_scores(device):
     model_bn = Hh.dvae_decoder_model("bn", max_n=10, nvt=10, hs=32, L=2, seed=3).to(device)
     nz = model_bn.nz

@@ -239,6 +239,38 @@ def test_the_other_modes_never_build_the_float64_operands(device):
     assert g.derived().z64.dtype == torch.float64 and g.derived().W64.is_cuda
 
 
+@pytest.mark.parametrize("refine", [None, "lbfgs", "multistart"])
+def test_reads_per_greedy_batch(device, monkeypatch, refine):
+    """How often a greedy batch waits for the device, counted as `Tensor.cpu` on device tensors: the grid's copy to the host,
+    the incumbent and q steps without refinement on the device; with it the incumbent and q steps alone, as long as every
+    step has a live start (no step then reads its grid row back)."""
+    if refine == "lbfgs":
+        pytest.importorskip("scipy.optimize")
+    d, M, N, q = 3, 7, 60, 3
+    g, P = model(d, M, device)
+    g._derived64(g.derived())            # (deriving the operands reads the device too: once per parameter version, not per batch)
+    rng = np.random.RandomState(d + M)
+    lo, up = -1.5 * np.ones(d), 1.5 * np.ones(d)
+    grid = (lo + rng.rand(N, d) * (up - lo)).astype(np.float32).astype(np.float64)
+    reads, to_host = [], torch.Tensor.cpu
+
+    def counting(t, *args, **kwargs):
+        if t.is_cuda:
+            reads.append(tuple(t.shape))
+        return to_host(t, *args, **kwargs)
+
+    monkeypatch.setattr(torch.Tensor, "cpu", counting)
+    pts, info = g.batched_greedy_ei(q, lo, up, grid=grid, refine=refine, return_info=True)
+    monkeypatch.undo()
+    print("refine=%r: %d reads, of shapes %s" % (refine, len(reads), reads))
+    assert pts.shape == (q, d)
+    if refine == "multistart":
+        assert all(r["best"] >= 0 for r in info["starts"])
+        assert len(reads) == q + 1
+    else:
+        assert len(reads) == q + 2
+
+
 def test_bo_round_with_multistart(device):
     model_bn = Hh.dvae_decoder_model("bn", max_n=10, nvt=10, hs=32, L=2, seed=3).to(device)
     nz = model_bn.nz
