@@ -3,6 +3,7 @@
 
     python bench.py --gpus 1 --steps 50 --warmup 5
     python bench.py --gpus 1 --steps 50 --warmup 5 --dump-outputs DIR   # + the last timed step's logits as DIR/head_<s>.npy
+    python bench.py --gpus 1 --steps 50 --warmup 5 --full               # + every further leg (below)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -15,10 +16,16 @@ values measure the system, not the depth spread of the synthetic shards (seeds 0
 topological layers; `--rank-seeds` draws batch `rank` on rank `rank` instead and the slowest shard
 then sets the time).  No data-path collective (graphs are independent).
 
+A plain run does what the headline figure needs and nothing else: set-up, warm-up, the timed steps, `--dump-outputs`, the
+line.  Everything that takes runs of its own - the instrumented second pass (`kernels_ms_per_step`, median / p90), the
+loader-side-plan, two-stream and separate-calls forwards, the N > 1 strong-scaling / rank-seeds legs and `multi_gpu`, the training
+step, BASELINE.json's other configurations and the CPU baseline - runs under `--full` only, where `--cpu-passes`, `--train-steps`
+and `--other-configs` size or disable single legs as before.
+
 Rank 0 prints ONE JSON line.  `roofline` is for the dominant kernel (the recurrence: one persistent dataflow
 launch per forward): duration from HIP events on the launching stream inside the timed region.  `cpu_baseline` is the
 oracle's op-for-op restatement of the reference (per-node edge scan, full [N,H] scatter) timed on
-this host - a reported baseline, never the thing measured.
+this host - a reported baseline, never the thing measured (`--full`).
 """
 from __future__ import annotations
 
@@ -435,7 +442,7 @@ def other_configs(device):
     return out
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=30)
@@ -444,15 +451,21 @@ def main():
     ap.add_argument("--hidden", type=int, default=256)
     ap.add_argument("--layers", type=int, default=2)
     ap.add_argument("--vocab", type=int, default=5002)
-    ap.add_argument("--cpu-passes", type=int, default=8, help="timed CPU forward passes (~1.4 s each); 0 disables the CPU baseline leg")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline measurement also run every further leg: the instrumented second pass, the "
+                         "loader-side-plan / two-stream / separate-calls forwards, the N > 1 scaling legs, the training step, "
+                         "the other configurations and the CPU baseline (about half a minute more); off by default - a plain "
+                         "run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--cpu-passes", type=int, default=8,
+                    help="with --full: timed CPU forward passes (~1.4 s each); 0 disables the CPU baseline leg")
     ap.add_argument("--no-kernel-timer", action="store_true")
     ap.add_argument("--rank-seeds", action="store_true",
                     help="rank r draws batch r (different depths per rank) instead of the headline batch everywhere")
     ap.add_argument("--other-configs", type=int, default=1,
-                    help="1: also time BASELINE.json's other configurations briefly (cfg 1 NA, cfg 4 BN, cfg 5 wide/deep) "
+                    help="with --full, 1: also time BASELINE.json's other configurations briefly (cfg 1 NA, cfg 4 BN, cfg 5 wide/deep) "
                          "and report them under `other_configs` (never as `value`); 0 disables")
     ap.add_argument("--train-steps", type=int, default=20,
-                    help="also time this many full training steps (fwd + bwd + optimizer) after the headline "
+                    help="with --full: also time this many full training steps (fwd + bwd + optimizer) after the headline "
                          "forward measurement and report them as `training_step`; 0 disables the leg")
     ap.add_argument("--schedule", choices=["lockstep", "pergraph"], default=None,
                     help="recurrence schedule (default: the library default, lock-step frontier launches)")
@@ -467,9 +480,14 @@ def main():
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write the logits the last timed step returned (rank 0) as DIR/head_<s>.npy, "
                          "float32, at most 64 MB in all (beyond that, a fixed seeded sample of the graphs' rows)")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    return args
+
+
+def main():
+    args = parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -547,9 +565,9 @@ def main():
         engine.TIMER = None
         # the last timed step's results, taken off the device before anything else runs (outside the timed region)
         dumped = [o.detach().cpu() for o in out] if args.dump_outputs and rank == 0 else None
-        # second pass (not the headline): every launch bracketed + one event per step boundary
+        # second pass (not the headline, --full): every launch bracketed + one event per step boundary
         detail, marks = None, None
-        if not args.no_kernel_timer and rank == 0 and streams is None:
+        if args.full and not args.no_kernel_timer and rank == 0 and streams is None:
             inputs2 = fresh_inputs(master, args.steps)
             detail = engine.KernelTimer()
             engine.TIMER = detail
@@ -575,14 +593,15 @@ def main():
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t.item())
+    # Everything from here to the result line is a leg of its own and runs under --full only.
     # the CPU baseline and the other configurations are single-process legs: rank 0 at N = 1 only (the other ranks would
     # sit in the final barrier for half a minute)
-    cpu_leg = rank == 0 and world == 1 and args.cpu_passes > 0
+    cpu_leg = args.full and rank == 0 and world == 1 and args.cpu_passes > 0
     cpu_sd = {k: v.detach().cpu() for k, v in model.state_dict().items()} if cpu_leg else None
     # the same forward with the plan built by the loader (dagnn_amd.collate_with_plan): no plan
     # kernels and no device->host read inside the step.  Reported next to the headline, never as `value`.
     planned_res = None
-    if args.streams == 1 and model.schedule == "lockstep":
+    if args.full and args.streams == 1 and model.schedule == "lockstep":
         from dagnn_amd import attach_plan
         groups = engine.dataflow_groups(device, 2, L, (H + 63) // 64 * 64, B)
         pm = attach_plan(batch_cpu.clone(), dataflow_groups=groups, cost_layer=engine.DF_COST_LAYER,
@@ -612,7 +631,7 @@ def main():
     # the host side of batch i + 1 run beside the recurrence of batch i; the all-resident recurrence launches themselves stay ordered
     # device-wide (engine.persistent_launch).  Reported next to the headline - `value` stays one batch strictly after the other.
     overlap_res = None
-    if args.streams == 1 and model.schedule == "lockstep" and rank == 0 and world == 1:
+    if args.full and args.streams == 1 and model.schedule == "lockstep" and rank == 0 and world == 1:
         two = [torch.cuda.Stream(device) for _ in range(2)]
         oin = fresh_inputs(master, args.warmup + args.steps)
         with torch.no_grad():
@@ -634,7 +653,7 @@ def main():
     # input GEMM of both directions - no fused pipeline, no tables folded through W_ih.  Reported next to the headline so that
     # what the folding and the fusion buy stays visible; never `value`.
     front_res = None
-    if args.streams == 1 and model.schedule == "lockstep" and rank == 0:
+    if args.full and args.streams == 1 and model.schedule == "lockstep" and rank == 0:
         saved = (engine.FOLD_INPUT, engine.PREPARE_FUSED, engine.PLAN_OVERLAP)
         engine.FOLD_INPUT, engine.PREPARE_FUSED, engine.PLAN_OVERLAP = 0, 0, 0
         fin = fresh_inputs(master, args.warmup + args.steps)
@@ -654,7 +673,7 @@ def main():
     # N > 1: the reference's own use of k devices - ONE global batch split by its Collater rule (tg/dataloader.py:17-27,
     # node-balanced contiguous shards) - next to the weak-scaling headline.  Bounded by the shard holding the deepest graph.
     strong_res = None
-    if world > 1 and args.streams == 1:
+    if args.full and world > 1 and args.streams == 1:
         from dagnn_amd import collate_sharded
         from dagnn_amd.synth import code2_graphs
         shards = collate_sharded(code2_graphs(0, B), world)
@@ -690,7 +709,7 @@ def main():
     # under the active communicator), the CUs a training pass leaves to the collective, and a second weak-scaling entry on
     # DIFFERENT batches per rank (seed = rank: other depths, the slowest rank binds) next to the same-batch headline
     multi_res = None
-    if world > 1 and args.streams == 1:
+    if args.full and world > 1 and args.streams == 1:
         from dagnn_amd import engine as _eng
         Hp_ = (H + 63) // 64 * 64
         mine_info = torch.tensor([_eng.dataflow_groups(device, 2, L, Hp_, B), _eng.dataflow_groups(device, 2, L, Hp_, B, training=True),
@@ -729,12 +748,12 @@ def main():
                 "ms_per_step": round(float(tr) / args.steps * 1e3, 4), "graphs_per_s": round(world * B * args.steps / float(tr), 1),
                 "nodes_layers_per_rank": [[int(v) for v in a.tolist()] for a in rall]}
     train_res = None
-    if args.train_steps > 0 and args.streams == 1 and model.schedule == "lockstep":
+    if args.full and args.train_steps > 0 and args.streams == 1 and model.schedule == "lockstep":
         tw = 5
         train_res = training_leg(model, fresh_inputs(master, tw + args.train_steps), B, S, V, args.train_steps, tw,
                                  world, device, barrier)
     other_res = None
-    if args.other_configs and rank == 0 and world == 1 and args.streams == 1:
+    if args.full and args.other_configs and rank == 0 and world == 1 and args.streams == 1:
         other_res = other_configs(device)
     ms_per_step = elapsed / args.steps * 1e3
     value = world * B * args.steps / elapsed

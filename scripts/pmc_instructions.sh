@@ -3,7 +3,7 @@
 # domains next to them), averaged per launch of dataflow_kernel<16> -> profiles/<name>.json
 name=${1:-r04_pmc_instructions}
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-CMD="python bench.py --steps 2 --warmup 1 --cpu-passes 0 --no-kernel-timer --train-steps 0 --other-configs 0"
+CMD="python bench.py --full --steps 2 --warmup 1 --cpu-passes 0 --no-kernel-timer --train-steps 0 --other-configs 0"
 i=0
 for set in "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_SMEM" "SQ_INSTS_MFMA SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAIT_INST_ANY" \
            "SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_ANY" "SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_BUSY_CYCLES SQ_INST_CYCLES_SALU"; do
@@ -22,7 +22,7 @@ for f in glob.glob("gpurun_out/%s_p*/**/*counter_collection.csv" % name, recursi
         k = r["Counter_Name"]
         tot[k] = tot.get(k, 0.0) + float(r["Counter_Value"])
         cnt[k] = cnt.get(k, 0) + 1
-out = {"note": "rocprofv3 --pmc passes (4 counters each, separate runs) over `python bench.py --steps 2 --warmup 1 --cpu-passes 0 "
+out = {"note": "rocprofv3 --pmc passes (4 counters each, separate runs) over `python bench.py --full --steps 2 --warmup 1 --cpu-passes 0 "
                "--no-kernel-timer --train-steps 0 --other-configs 0`; dataflow_kernel<16> only, average per launch. SQ cycle "
                "counters are in units of 4 clocks summed over waves.",
        "launches": {k: cnt[k] for k in sorted(cnt)},

@@ -12,7 +12,7 @@ run() {   # tag, command...
   timeout 600 rocprofv3 --pmc $C --output-format csv -d gpurun_out/${NAME}_$tag -o p -- "$@" > gpurun_out/${NAME}_$tag.log 2>&1
   echo "$tag rc=$?"
 }
-run headline python bench.py --steps 3 --warmup 1 --cpu-passes 0 --no-kernel-timer --train-steps 3 --other-configs 0
+run headline python bench.py --full --steps 3 --warmup 1 --cpu-passes 0 --no-kernel-timer --train-steps 3 --other-configs 0
 run h300 env HS=300 python scripts/h300_probe.py
 run cfg5 python bench.py --batch 256 --hidden 512 --layers 5 --steps 2 --warmup 1 --cpu-passes 0 --no-kernel-timer --train-steps 0 --other-configs 0
 run cfg5_tiles env DAGNN_AMD_TILES=2 python scripts/tiles_time.py

@@ -3,7 +3,7 @@
 # trace domains next to them), folded by scripts/pmc_summary.py into profiles/<name>.json
 name=${1:-r04_pmc_traffic}
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-CMD="python bench.py --steps 2 --warmup 1 --cpu-passes 0 --no-kernel-timer --train-steps 0 --other-configs 0"
+CMD="python bench.py --full --steps 2 --warmup 1 --cpu-passes 0 --no-kernel-timer --train-steps 0 --other-configs 0"
 rm -rf gpurun_out/${name}_fetch gpurun_out/${name}_write
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d gpurun_out/${name}_fetch -o f -- $CMD > gpurun_out/${name}_fetch.log 2>&1
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d gpurun_out/${name}_write -o w -- $CMD > gpurun_out/${name}_write.log 2>&1

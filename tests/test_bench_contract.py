@@ -114,16 +114,44 @@ def test_dump_outputs_keeps_the_cap_and_a_fixed_sample(tmp_path):
         rows = idx
 
 
+# what a plain run leaves to `--full`: every figure that takes runs of its own
+FULL_ONLY = ("kernels_ms_per_step", "ms_per_step_median", "ms_per_step_p90", "loader_side_plan", "separate_calls_no_folding",
+             "two_streams", "strong_scaling", "multi_gpu", "training_step", "other_configs", "cpu_baseline")
+
+
+def test_full_is_an_option_and_off_by_default():
+    import bench
+    assert bench.parse_args(["--gpus", "1", "--steps", "3", "--warmup", "1"]).full is False
+    a = bench.parse_args(["--gpus", "1", "--steps", "3", "--warmup", "1", "--full"])
+    assert a.full is True and (a.steps, a.warmup, a.cpu_passes, a.train_steps, a.other_configs) == (3, 1, 8, 20, 1)
+
+
 @pytest.mark.gpu
 def test_bench_single_gpu_line(tmp_path):
     import numpy as np
     j = _run_bench(["--gpus", "1", "--steps", "3", "--warmup", "1", "--cpu-passes", "0", "--train-steps", "0", "--other-configs", "0",
                     "--dump-outputs", str(tmp_path)])
     _check_line(j, 1, 3, 1, with_cpu=False)
+    assert not [k for k in FULL_ONLY if k in j]   # a plain run: the headline and nothing that takes runs of its own
     # the headline forward's five [128, 5002] logit matrices
     for s in range(5):
         a = np.load(tmp_path / ("head_%d.npy" % s))
         assert a.dtype == np.float32 and a.shape == (128, 5002) and np.isfinite(a).all()
+
+
+@pytest.mark.gpu
+def test_bench_full_adds_the_further_legs():
+    """`--full` with the long legs sized down (two training steps, no CPU baseline, no other configurations): the same
+    headline keys, plus the second pass, the three forward variants and the training step."""
+    j = _run_bench(["--gpus", "1", "--steps", "3", "--warmup", "1", "--full", "--cpu-passes", "0", "--train-steps", "2",
+                    "--other-configs", "0"])
+    _check_line(j, 1, 3, 1, with_cpu=False)
+    assert j["kernels_ms_per_step"]["prepare"] > 0 and j["ms_per_step_p90"] >= j["ms_per_step_median"] > 0
+    for k in ("loader_side_plan", "separate_calls_no_folding", "two_streams"):
+        assert j[k]["ms_per_step"] > 0 and j[k]["graphs_per_s"] > 0, k
+    t = j["training_step"]
+    assert t["steps"] == 2 and t["ms_per_step"] > 0 and t["kernels_ms_per_step"]["backward_run"] > 0
+    assert "cpu_baseline" not in j and "other_configs" not in j
 
 
 @pytest.mark.gpu
@@ -132,7 +160,8 @@ def test_bench_two_ranks_under_torchrun():
     here two ranks share the one visible GPU and rendezvous over gloo (RCCL refuses two ranks on one device)."""
     launcher = ["-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                 "--master-port", "29517"]
-    j = _run_bench(["--gpus", "2", "--steps", "3", "--warmup", "1", "--cpu-passes", "0", "--train-steps", "2", "--other-configs", "0"],
+    j = _run_bench(["--gpus", "2", "--steps", "3", "--warmup", "1", "--full", "--cpu-passes", "0", "--train-steps", "2",
+                    "--other-configs", "0"],
                    env_extra={"DAGNN_BENCH_BACKEND": "gloo"}, launcher=launcher)
     _check_line(j, 2, 3, 1, with_cpu=False)
     assert j["config"]["global_batch"] == 256   # weak scaling: 128 graphs per rank
