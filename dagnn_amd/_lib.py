@@ -332,6 +332,22 @@ class BnData(C.Structure):   # dagnn_bn_data
                 ("cards", C.c_int32 * BN_MAX_VARS)]
 
 
+TABLE_GRADS_MAX_TABLES, TABLE_GRADS_CHUNK = 3, 32   # DAGNN_TABLE_GRADS_MAX_TABLES / _CHUNK (the summation order's chunk length)
+
+
+class TableGradsTable(C.Structure):   # dagnn_table_grads_table
+    _fields_ = [("keys", C.c_void_p), ("key_stride", C.c_int64), ("R", C.c_int64), ("out", C.c_void_p), ("ld_out", C.c_int64)]
+
+
+class TableGradsArgs(C.Structure):   # dagnn_table_grads_args
+    _fields_ = [("g", C.c_void_p), ("ld_g", C.c_int64), ("N", C.c_int64), ("H", C.c_int32), ("num_tables", C.c_int32),
+                ("table", TableGradsTable * TABLE_GRADS_MAX_TABLES), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+                ("stages", C.c_int32), ("reserved", C.c_int32)]
+
+
+TABLE_GRADS_INDEX, TABLE_GRADS_SUM = 1, 2   # DAGNN_TABLE_GRADS_INDEX / _SUM (dagnn_table_grads_args.stages; 0 = both)
+
+
 SGP_MAX_M, SGP_MAX_D, SGP_MAX_Q = 512, 128, 128   # DAGNN_SGP_MAX_M / _MAX_D / _MAX_Q
 SGP_ARGMIN_MEAN, SGP_ARGMIN_EI = 0, 1             # DAGNN_SGP_ARGMIN_*
 SGP_REFINE_MAX_STARTS, SGP_REFINE_HISTORY = 32, 8    # DAGNN_SGP_REFINE_MAX_STARTS / _HISTORY
@@ -393,6 +409,8 @@ SYMBOLS = {
     "dagnn_wgrad_splits": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64]),
     "dagnn_wgrad_run": (C.c_int, [C.POINTER(WgradJob), C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                   C.c_size_t, C.c_void_p]),
+    "dagnn_table_grads_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.POINTER(C.c_int64), C.c_int]),
+    "dagnn_table_grads": (C.c_int, [C.POINTER(TableGradsArgs), C.c_void_p]),
     "dagnn_readout_max_backward": (C.c_int, [C.POINTER(Plan), C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                              C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "dagnn_pack_dataflow_batch": (C.c_int, [C.POINTER(DfPackJob), C.c_int, C.c_int, C.c_void_p]),

@@ -12,7 +12,7 @@ from __future__ import annotations
 
 import torch
 
-from . import engine
+from . import _lib, engine
 from .core import run_stack_lockstep
 
 
@@ -35,11 +35,61 @@ class EncodeAST(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         x = ctx.saved_tensors[0]
+        if engine.TABLE_GRADS:   # one fixed summation order (`table_grads_host` below), all tables in one call
+            grads = engine.table_grads(g, (x[:, 0], x[:, 1]) + tuple(ctx.saved_tensors[1:]), ctx.rows)
+            return (None, None, grads[0], grads[1], grads[2] if len(grads) > 2 else None, None)
         g = g.contiguous()
         grads = []
         for rows, idx in zip(ctx.rows, (x[:, 0], x[:, 1]) + tuple(ctx.saved_tensors[1:])):
             grads.append(torch.zeros(rows, g.shape[1], dtype=g.dtype, device=g.device).index_add_(0, idx, g))
         return (None, None, grads[0], grads[1], grads[2] if len(grads) > 2 else None, None)
+
+
+TABLE_GRADS_CHUNK = _lib.TABLE_GRADS_CHUNK   # DAGNN_TABLE_GRADS_CHUNK: members per chunk of a row's list
+
+
+def table_grads_host(g, keys, rows):
+    """Host mirror of `engine.table_grads` (`dagnn_table_grads`) in numpy fp32: the same bits, and the definition of the order.
+
+    For table t and row r, list the nodes v with keys[t][v] == r in ascending v and cut the list into chunks of
+    TABLE_GRADS_CHUNK consecutive members by position in the list (the last chunk may be short).  A chunk's partial is
+    ((g[v0] + g[v1]) + g[v2]) + ..., left to right from its first member; out[r] = ((+0.0 + p0) + p1) + ..., left to right
+    over the row's chunks; a row without members is +0.0.  Keys outside [0, rows[t]) contribute nothing.  Every add is
+    one IEEE fp32 add (numpy adds whole arrays of independent sums at a time: step j adds the j-th member of every chunk).
+
+    g [N, H] (tensor or array), keys: integer tensors / arrays of N entries (strided views allowed), rows: row counts.
+    Returns a list of float32 arrays [rows[t], H]."""
+    import numpy as np
+    as_np = lambda a: a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)   # noqa: E731
+    g = np.ascontiguousarray(as_np(g), dtype=np.float32)
+    C = TABLE_GRADS_CHUNK
+    outs = []
+    for k, R in zip(keys, rows):
+        k, R = as_np(k).astype(np.int64).reshape(-1), int(R)
+        assert k.shape[0] == g.shape[0], (k.shape, g.shape)
+        v = np.nonzero((k >= 0) & (k < R))[0]
+        members = v[np.argsort(k[v], kind="stable")]          # grouped by key, ascending v inside a group
+        row = k[members]
+        count = np.bincount(row, minlength=R)
+        off = np.concatenate([[0], np.cumsum(count)])
+        pos = np.arange(members.shape[0]) - off[row]          # position inside the row's list
+        chunks = (count + C - 1) // C
+        coff = np.concatenate([[0], np.cumsum(chunks)])
+        chunk = coff[row] + pos // C                          # chunk of each member; pos % C is its place in the chunk
+        partial = np.zeros((int(coff[-1]), g.shape[1]), dtype=np.float32)
+        for j in range(C):
+            sel = pos % C == j
+            if not sel.any():
+                break
+            partial[chunk[sel]] = g[members[sel]] if j == 0 else partial[chunk[sel]] + g[members[sel]]
+        out = np.zeros((R, g.shape[1]), dtype=np.float32)     # +0.0
+        chunk_row = np.repeat(np.arange(R), chunks)
+        chunk_at = np.arange(chunk_row.shape[0]) - coff[chunk_row]
+        for c in range(int(chunks.max()) if R > 0 else 0):
+            sel = chunk_at == c
+            out[chunk_row[sel]] = out[chunk_row[sel]] + partial[sel]
+        outs.append(out)
+    return outs
 
 
 def _wgrad(dg: torch.Tensor, u: torch.Tensor, splits: int = 32) -> torch.Tensor:

@@ -108,7 +108,8 @@ TILES_MAX_NODES = _env_int("DAGNN_AMD_TILES_MAX_NODES", 10000)  # measured on MI
                                                             # 0.75-0.82x the per-layer launches' time up to 8 k nodes, 0.95x at 15 k, 1.04-1.10x at 30 k
                                                             # (cfg 5); split at the thin tail 0.86x at 15 k and 0.88x at 30 k: larger batches are split
 BWD_DATAFLOW = _env_int("DAGNN_AMD_BWD_DATAFLOW", 1)        # 1: the reverse sweep as one persistent dataflow launch (H <= 256)
-DEBUG_WG = _env_int("DAGNN_AMD_DEBUG_WG", 0)                # workgroup whose blocks scripts/df_stamps.py stamps
+TABLE_GRADS = _env_int("DAGNN_AMD_TABLE_GRADS", 0)          # 1: the node encoder's embedding-table gradients in one fixed summation order (csrc/table_grads.hip: bitwise repeatable) instead of torch's atomic index_add_; read at call time
+DEBUG_WG = _env_int("DAGNN_AMD_DEBUG_WG", 0)               # workgroup whose blocks scripts/df_stamps.py stamps
 SPIN_LIMIT = _env_int("DAGNN_AMD_SPIN_LIMIT", 0)            # polls before a device-side wait gives up; 0 = library default
 DEBUG_TIMING: Optional[torch.Tensor] = None  # int64[8] device tensor: phase ticks of the deepest work item
 _NOSPAN = _NoSpan()
@@ -1525,6 +1526,44 @@ def colsums(jobs, N: int):
     nbytes = lib.dagnn_colsum_workspace_bytes(len(jobs), kmax)
     ws = _wgrad_ws("cs", jobs[0][0], nbytes)
     check(lib.dagnn_colsum_run(arr, len(jobs), N, ws.data_ptr(), ws.numel() * 4, _stream(jobs[0][0])), "dagnn_colsum_run")
+    return outs
+
+
+def table_grads(g: torch.Tensor, keys: Sequence[torch.Tensor], rows: Sequence[int], stages: int = 0,
+                workspace: Optional[torch.Tensor] = None) -> List[torch.Tensor]:
+    """Embedding-table gradients in the one summation order of `dagnn_table_grads` (include/dagnn_hip.h; the host mirror
+    is `autograd.table_grads_host`): out_t[r] = sum of g[v] over the nodes with keys[t][v] == r, bitwise repeatable, no float
+    atomics.  g [N, H] fp32 (row pitch kept), H % 4 == 0; keys: int64 [N] tensors, strided views allowed (the columns of one
+    [N, 2] tensor); rows: the tables' row counts.  Returns one [rows[t], H] tensor per table.
+    `stages` / `workspace` (at most three tables): the index launches (`_lib.TABLE_GRADS_INDEX`) or the sum launches
+    (`_lib.TABLE_GRADS_SUM`) alone, over a workspace the caller keeps between the two (scripts/bench_table_grads.py)."""
+    lib = _lib.load()
+    g = _rows(g, "g")
+    N, H = g.shape
+    outs = []
+    if (stages or workspace is not None) and len(keys) > _lib.TABLE_GRADS_MAX_TABLES:
+        raise DagnnHipError("table_grads: stages / workspace take at most %d tables" % _lib.TABLE_GRADS_MAX_TABLES)
+    with _span("table_grads", g):
+        for t0 in range(0, len(keys), _lib.TABLE_GRADS_MAX_TABLES):
+            ks, rs = list(keys[t0:t0 + _lib.TABLE_GRADS_MAX_TABLES]), [int(r) for r in rows[t0:t0 + _lib.TABLE_GRADS_MAX_TABLES]]
+            a = _lib.TableGradsArgs()
+            a.g, a.ld_g, a.N, a.H, a.num_tables = g.data_ptr(), g.stride(0) if N > 1 else max(g.stride(0), H), N, H, len(ks)
+            for t, (k, R) in enumerate(zip(ks, rs)):
+                if not isinstance(k, torch.Tensor) or not k.is_cuda or k.dim() != 1 or k.shape[0] != N:
+                    raise DagnnHipError("table_grads: keys[%d] must be a GPU tensor of %d entries (got %s)" % (
+                        t0 + t, N, getattr(k, "shape", type(k))))
+                if k.dtype != torch.int64 or (N > 1 and k.stride(0) < 0):
+                    k = k.to(torch.int64).contiguous()
+                    ks[t] = k   # (keeps the copy alive until the launches are queued: stream-ordered allocation does the rest)
+                out = torch.empty(R, H, dtype=torch.float32, device=g.device)
+                outs.append(out)
+                a.table[t] = _lib.TableGradsTable(k.data_ptr(), k.stride(0) if N > 1 else 1, R, out.data_ptr(), H)
+            nbytes = lib.dagnn_table_grads_workspace_bytes(N, H, (C.c_int64 * len(rs))(*rs), len(rs))
+            if nbytes == 0:
+                raise DagnnHipError("table_grads: shape out of range (N = %d, H = %d, rows = %s)" % (N, H, rs))
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=g.device) if workspace is None else workspace
+            a.workspace, a.workspace_bytes, a.stages = ws.data_ptr(), ws.numel() * ws.element_size(), stages
+            check(lib.dagnn_table_grads(C.byref(a), _stream(g)), "dagnn_table_grads")
     return outs
 
 

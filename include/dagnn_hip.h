@@ -659,6 +659,59 @@ int dagnn_wgrad_splits(int num_cus, int njob, int Hp, int max_in_dim, int64_t N)
 int dagnn_wgrad_run(const dagnn_wgrad_job* jobs /* host */, int njob, int64_t N, int Hp, int H, int splits, void* workspace,
                     size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Embedding-table gradients with ONE summation order (csrc/table_grads.hip): what autograd accumulates behind the three
+ * `nn.Embedding` lookups of ogbg-code/utils.py:26-28 (two for utils2.py:26-28), out_t[r] = sum of g[v] over the nodes v whose
+ * key in table t is r, without a floating-point atomic.
+ *
+ * The order.  For a row r, list the nodes with key r in ascending v and cut the list into chunks of
+ * DAGNN_TABLE_GRADS_CHUNK consecutive members BY POSITION IN THE LIST (the last chunk may be short):
+ *     chunk partial  p_c    = ((g[v0] + g[v1]) + g[v2]) + ...      left to right from the chunk's first member,
+ *     out[r]                = ((+0.0 + p_0) + p_1) + ...           left to right over the row's chunks,
+ * plain IEEE fp32 adds, never reassociated, independent of grid and device; a row without members is exactly +0.0.  Keys
+ * outside [0, R) contribute nothing and are never used as an index.  With n members and m = ceil(n / 32) chunks a term
+ * passes at most k = min(n, 32) - 1 + max(m - 1, 0) rounding adds: |out - exact| <= k u / (1 - k u) sum |g|, u = 2^-24.
+ * `autograd.table_grads_host` restates the order in numpy; the kernels' bits equal its bits.
+ *
+ *   g    [N, ld_g] fp32, ld_g >= H, 16-byte aligned rows (ld_g % 4 == 0); H % 4 == 0; 0 <= N < 2^24
+ *   per table (1..DAGNN_TABLE_GRADS_MAX_TABLES): keys[v * key_stride] int64 (the two columns of one [N, 2] tensor have
+ *        stride 2), 1 <= R < 2^24, out [R, ld_out] (ld_out >= H, ld_out % 4 == 0, 16-byte aligned).  `out` may arrive
+ *        uninitialised: all R rows of columns [0, H) are written (zero rows too, there is no fill), columns [H, ld_out)
+ *        are never touched.
+ *   workspace: dagnn_table_grads_workspace_bytes(N, H, rows, num_tables) bytes, 16-byte aligned, any contents.
+ * Six launches for all tables together: key counts per (node range, key) | their prefix over the ranges | segment
+ * offsets | stable placement of the member lists + chunk records | chunk partials (rows of one chunk go straight to
+ * `out`) | rows of several chunks and empty rows.  Integer atomics only.  N == 0: one launch that writes the zeros.
+ * DAGNN_EINVAL: a NULL pointer (g / keys / workspace only when N > 0), H % 4 != 0, a pitch below H or not a multiple of
+ * 4, a misaligned g / out, N >= 2^24, R < 1 or R >= 2^24, num_tables out of range; DAGNN_ENOSPC: workspace too small.
+ * Borrowed pointers, the caller's stream, no allocation, no synchronisation, no host read-back.
+ * ---------------------------------------------------------------------------------------- */
+#define DAGNN_TABLE_GRADS_MAX_TABLES 3
+#define DAGNN_TABLE_GRADS_CHUNK 32
+typedef struct dagnn_table_grads_table {
+    const int64_t* keys;     /* key of node v at keys[v * key_stride] */
+    int64_t key_stride;      /* in elements, >= 0 */
+    int64_t R;               /* rows of the table */
+    float* out;              /* [R, ld_out] */
+    int64_t ld_out;
+} dagnn_table_grads_table;
+typedef struct dagnn_table_grads_args {
+    const float* g;          /* [N, ld_g] */
+    int64_t ld_g, N;
+    int32_t H, num_tables;
+    dagnn_table_grads_table table[DAGNN_TABLE_GRADS_MAX_TABLES];
+    void* workspace;
+    size_t workspace_bytes;
+    int32_t stages;          /* 0: the whole call; DAGNN_TABLE_GRADS_INDEX: the four index launches only; DAGNN_TABLE_GRADS_SUM:
+                              * the two sum launches only, over the index an earlier call with the same N, H, keys and rows
+                              * left in `workspace` (what scripts/bench_table_grads.py times apart) */
+    int32_t reserved;        /* 0 */
+} dagnn_table_grads_args;
+#define DAGNN_TABLE_GRADS_INDEX 1
+#define DAGNN_TABLE_GRADS_SUM 2
+size_t dagnn_table_grads_workspace_bytes(int64_t N, int H, const int64_t* rows /* host */, int num_tables);   /* 0: out of range */
+int dagnn_table_grads(const dagnn_table_grads_args* args /* host */, void* stream);
+
 /* The small gradients of one cell's attention / edge encoder from the three column sums above, every cell in ONE launch
  * (replaces ~10 torch ops per cell behind `loss.backward()`, dagnn.py:362-373 under autograd):
  *   g_attn[j]      = 0 outside [dq, dq + kd);  g_attn[dq + k] = key_sum[k] + edge_w[k, :] . feat_sum + edge_b[k] * sigma_sum
