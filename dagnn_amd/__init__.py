@@ -8,6 +8,7 @@ Drop-in modules with the reference's constructor / state_dict / forward(G) contr
     from dagnn_amd import evaluate, SeqF1              # ogbg-code/main_pyg.py:91-124 (predicted tokens, the F1 evaluator)
     from dagnn_amd import ASTNodeEncoder2, lp          # ogbg-code/utils2.py, ogbg-code/main_pyg_lp.py (the LP task)
     from dagnn_amd import GraphStore                   # the loader side: the dataset on the device, a batch per launch
+    from dagnn_amd import EpochMeter, seq_ce_step      # ogbg-code/main_pyg.py:39-88 (train(): loss, tokens, train metric per launch)
     from dagnn_amd import DagStore                     # the same for D-VAE data sets (ENAS / BN rows), dvae/train.py's loops
     from dagnn_amd import attach_predictor             # dvae/train.py --predictor: the MLP on mu, its MSE and gradients
     from dagnn_amd import BnData, bn_scores            # bayesian_optimization/evaluate_BN.py: BIC scores of BN structures
@@ -22,11 +23,11 @@ from .data import (GraphBatch, GraphData, augment_edge2, collate_sharded, collat
 from .host_plan import attach_plan, build_plan_host  # noqa: F401
 from .dvae import DAGNN_BN, DAGNN_NA  # noqa: F401
 from .model import DAGNN, ASTNodeEncoder, ASTNodeEncoder2  # noqa: F401
-from .train import GradBucket  # noqa: F401
+from .train import EpochMeter, GradBucket, seq_ce_step  # noqa: F401
 from . import evaluate  # noqa: F401
 from .evaluate import SeqF1  # noqa: F401
 from . import lp  # noqa: F401
-from .lp import ClassAccuracy, class_cross_entropy, evaluate_lp, lp_batches, lp_targets  # noqa: F401
+from .lp import ClassAccuracy, class_ce_step, class_cross_entropy, evaluate_lp, lp_batches, lp_targets  # noqa: F401
 from .data_parallel import DataParallel  # noqa: F401
 from .store import GraphStore  # noqa: F401
 from .dvae_store import DagStore  # noqa: F401

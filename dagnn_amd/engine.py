@@ -2019,6 +2019,52 @@ def seq_f1_counts(tok: torch.Tensor, eos_id: int, ref_ids: torch.Tensor, ref_ext
     return out
 
 
+def seq_ce_step(base: torch.Tensor, y: torch.Tensor, S: int, V: int, need_grad: bool, eos_id: int,
+                ref_ids: Optional[torch.Tensor], ref_extra: Optional[torch.Tensor], counts: torch.Tensor, graph_offset: int,
+                epoch_sum: torch.Tensor, epoch_steps: torch.Tensor):
+    """`dagnn_seq_ce_step` (csrc/train_step.hip): (loss [1], d loss / d logits [B, S V] in rows pitched to a multiple of 4
+    floats or None, tok [B, S] int64) of fp32 GPU logits `base` [B, S V] and int64 targets `y` [B, S] - `dagnn_seq_ce`'s bits
+    - and in the same launch `epoch_sum` [1] float64 += loss, `epoch_steps` [1] int64 += 1 and, with `ref_ids` [B, R] int32
+    (`ref_extra` [B] int32), the F1 counts of the B graphs into rows `graph_offset` .. of `counts` [capacity, 4] int32.
+    Nothing synchronises."""
+    if not isinstance(base, torch.Tensor) or not base.is_cuda:
+        _dev(base, "logits")   # (raises: no CPU path)
+    if base.dim() != 2 or base.dtype != torch.float32:
+        raise DagnnHipError("seq_ce_step: fp32 logits [B, %d] needed (got %s %s)" % (S * V, base.dtype, tuple(base.shape)))
+    if base.stride(1) != 1 or (base.shape[0] > 1 and base.stride(0) < S * V):
+        base = base.contiguous()
+    y = _dev(y, "targets", torch.int64)
+    B = base.shape[0]
+    dev = base.device
+    if base.shape[1] != S * V or tuple(y.shape) != (B, S) or not y.is_contiguous() or y.device != dev:
+        raise DagnnHipError("seq_ce_step: logits [B, %d] and contiguous int64 targets [B, %d] on one device needed (got %s, %s)"
+                            % (S * V, S, tuple(base.shape), tuple(y.shape)))
+    counts, epoch_sum, epoch_steps = _dev(counts, "counts", torch.int32), _dev(epoch_sum, "epoch_sum", torch.float64), \
+        _dev(epoch_steps, "epoch_steps", torch.int64)
+    if counts.dim() != 2 or counts.shape[1] != 4 or not counts.is_contiguous() or {counts.device, epoch_sum.device, epoch_steps.device} != {dev}:
+        raise DagnnHipError("seq_ce_step: counts must be a contiguous int32 [capacity, 4] tensor, the epoch words on the logits' device")
+    R = 1
+    if ref_ids is not None:
+        ref_ids = _dev(ref_ids, "ref_ids", torch.int32)
+        if ref_ids.dim() != 2 or ref_ids.shape[0] != B or ref_ids.shape[1] < 1 or not ref_ids.is_contiguous() or ref_ids.device != dev:
+            raise DagnnHipError("seq_ce_step: contiguous int32 ref_ids [B, R >= 1] on the logits' device needed (got %s)" % (tuple(ref_ids.shape),))
+        R = ref_ids.shape[1]
+        if ref_extra is not None:
+            ref_extra = _dev(ref_extra, "ref_extra", torch.int32)
+            if ref_extra.numel() != B or not ref_extra.is_contiguous() or ref_extra.device != dev:
+                raise DagnnHipError("seq_ce_step: contiguous int32 ref_extra [B] on the logits' device needed")
+    dl = torch.empty(B, (S * V + 3) // 4 * 4, dtype=torch.float32, device=dev)[:, :S * V] if need_grad else None
+    row = torch.empty(B * S, dtype=torch.float32, device=dev)
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    tok = torch.empty(B, S, dtype=torch.int64, device=dev)
+    check(_lib.load().dagnn_seq_ce_step(base.data_ptr(), base.stride(0) if B > 1 else S * V, y.data_ptr(), B, S, V, _ptr(dl),
+                                        0 if dl is None else dl.stride(0), row.data_ptr(), loss.data_ptr(), tok.data_ptr(),
+                                        int(eos_id), _ptr(ref_ids), R, _ptr(ref_extra) if ref_ids is not None else None,
+                                        counts.data_ptr(), counts.shape[0], int(graph_offset), epoch_sum.data_ptr(),
+                                        epoch_steps.data_ptr(), _lp_counter(base).data_ptr(), _stream(base)), "dagnn_seq_ce_step")
+    return loss, dl, tok
+
+
 # ----------------------------------------------------------------------------- the LP task's tail (csrc/lp.hip)
 _LP_KINDS = {torch.int64: _lib.LP_INT64, torch.float32: _lib.LP_FLOAT32, torch.float64: _lib.LP_FLOAT64}
 _LP_WORDS = {}
@@ -2070,6 +2116,35 @@ def class_ce(pred: torch.Tensor, targ: torch.Tensor, need_grad: bool):
                                      0 if dl is None else dl.stride(0), row.data_ptr(), loss.data_ptr(),
                                      _lp_counter(pred).data_ptr(), _stream(pred)), "dagnn_class_ce")
     return loss, dl
+
+
+def class_ce_step(pred: torch.Tensor, targ: torch.Tensor, need_grad: bool, epoch_hits: torch.Tensor, epoch_sum: torch.Tensor,
+                  epoch_steps: torch.Tensor):
+    """`dagnn_class_ce_step` (csrc/train_step.hip): `class_ce`'s (loss [1], d loss / d logits) - its bits - plus tok [B] int64
+    (the row argmax) and, in the same launch, `epoch_hits` [2] int64 += (hits, labelled) by `dagnn_class_hits`' rules,
+    `epoch_sum` [1] float64 += loss, `epoch_steps` [1] int64 += 1.  Nothing synchronises."""
+    if not isinstance(pred, torch.Tensor) or not pred.is_cuda:
+        _dev(pred, "logits")   # (raises: no CPU path)
+    if pred.dim() != 2 or pred.dtype != torch.float32 or pred.shape[0] < 1 or pred.shape[1] < 1:
+        raise DagnnHipError("class_ce_step: fp32 logits [B >= 1, C >= 1] needed (got %s %s)" % (pred.dtype, tuple(pred.shape)))
+    if pred.stride(1) != 1 or (pred.shape[0] > 1 and pred.stride(0) < pred.shape[1]):
+        pred = pred.contiguous()
+    B, C = pred.shape
+    dev = pred.device
+    targ, kind = lp_target(targ, B, dev)
+    epoch_hits, epoch_sum, epoch_steps = _dev(epoch_hits, "epoch_hits", torch.int64), _dev(epoch_sum, "epoch_sum", torch.float64), \
+        _dev(epoch_steps, "epoch_steps", torch.int64)
+    if epoch_hits.numel() != 2 or {epoch_hits.device, epoch_sum.device, epoch_steps.device} != {dev}:
+        raise DagnnHipError("class_ce_step: epoch_hits [2] and the epoch words on the logits' device needed")
+    dl = torch.empty(B, (C + 3) // 4 * 4, dtype=torch.float32, device=dev)[:, :C] if need_grad else None
+    row = torch.empty(B, dtype=torch.float32, device=dev)
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    tok = torch.empty(B, dtype=torch.int64, device=dev)
+    check(_lib.load().dagnn_class_ce_step(pred.data_ptr(), pred.stride(0) if B > 1 else C, targ.data_ptr(), kind, B, C, _ptr(dl),
+                                          0 if dl is None else dl.stride(0), row.data_ptr(), loss.data_ptr(), tok.data_ptr(),
+                                          epoch_hits.data_ptr(), epoch_sum.data_ptr(), epoch_steps.data_ptr(),
+                                          _lp_counter(pred).data_ptr(), _stream(pred)), "dagnn_class_ce_step")
+    return loss, dl, tok
 
 
 def class_hits(pred: torch.Tensor, targ: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -22,8 +22,8 @@ import torch
 from . import engine
 from .core import num_graphs_of
 
-__all__ = ["lp_targets", "graph_depth_host", "class_cross_entropy", "class_hits_host", "ClassAccuracy", "lp_batches",
-           "evaluate_lp"]
+__all__ = ["lp_targets", "graph_depth_host", "class_cross_entropy", "class_ce_step", "class_ce_step_host", "class_hits_host",
+           "ClassAccuracy", "lp_batches", "evaluate_lp"]
 
 
 # ----------------------------------------------------------------------------- targets
@@ -88,6 +88,71 @@ def class_cross_entropy(pred: torch.Tensor, targ: torch.Tensor) -> torch.Tensor:
     if not fused:
         return torch.nn.functional.cross_entropy(pred, targ.reshape(-1).to(pred.device).to(torch.long))
     return _ClassCE.apply(pred, targ)
+
+
+class _ClassCEStep(torch.autograd.Function):
+    """`_ClassCE` through `dagnn_class_ce_step` (csrc/train_step.hip): the same loss and d logits, and in the same launch the
+    step's tokens, its (hits, labelled) pair and the epoch sums on `meter`."""
+
+    @staticmethod
+    def forward(ctx, pred, targ, meter):
+        loss, ctx.dl, meter.tok = engine.class_ce_step(pred, targ, pred.requires_grad, meter.hits, meter.loss_sum, meter.steps)
+        meter.graphs += pred.shape[0]
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        # exactly `_ClassCE.backward`: out of place, into rows of the same pitch
+        dl = ctx.dl
+        out = torch.empty(dl.shape[0], dl.stride(0), dtype=dl.dtype, device=dl.device)[:, :dl.shape[1]]
+        return torch.mul(dl, g, out=out), None, None
+
+
+def class_ce_step(pred: torch.Tensor, targ: torch.Tensor, meter) -> torch.Tensor:
+    """The loss of `class_cross_entropy(pred, targ)` - under autograd, the same bits - with the rest of the reference's LP
+    training step (main_pyg_lp.py:64-67) in the SAME launch: `loss_accum += loss.item()` as a float64 sum on the device, the
+    argmax (`meter.tok`, [B]) and the batch's (hits, labelled) pair of `Evaluator._eval_acc` added to the epoch's.  `meter`:
+    a `train.EpochMeter` made without `eos_id`.  Nothing synchronises; `meter.result()` is the epoch's one read.  The fused
+    launch (`dagnn_class_ce_step`) runs under the conditions of `class_cross_entropy` for a meter on the logits' device; anything
+    else composes `class_cross_entropy`, the argmax and `class_hits` / `class_hits_host` on the meter."""
+    if meter.eos_id is not None:
+        raise ValueError("class_ce_step: the meter was made with `eos_id` (a TOK meter)")
+    fused = isinstance(pred, torch.Tensor) and pred.is_cuda and pred.dtype == torch.float32 and pred.dim() == 2 and \
+        pred.shape[0] > 0 and pred.shape[1] > 0 and pred.stride(1) == 1 and (pred.shape[0] == 1 or pred.stride(0) >= pred.shape[1]) \
+        and targ.numel() == pred.shape[0] and meter.device == pred.device
+    if fused:
+        return _ClassCEStep.apply(pred, targ, meter)
+    loss = class_cross_entropy(pred, targ)
+    from .evaluate import rows_argmax
+    tok = rows_argmax(pred.detach()).reshape(-1)
+    if tok.is_cuda:
+        pair = engine.class_hits(tok, targ)
+    else:
+        pair = torch.from_numpy(class_hits_host(tok, targ))
+    meter.hits.add_(pair.to(meter.device))
+    meter.loss_sum.add_(loss.detach().to(torch.float32).to(meter.device, torch.float64))
+    meter.steps.add_(1)
+    meter.tok = tok
+    meter.graphs += pred.shape[0]
+    return loss
+
+
+def class_ce_step_host(logits, targ, epoch_hits=(0, 0), epoch_sum: float = 0.0) -> dict:
+    """The definition `dagnn_class_ce_step` implements, in numpy: `train.seq_ce_step_host` with one head - the target
+    truncated toward zero as `.to(torch.long)` does, a NaN target outside every class - with `hits` [2] int64 = the incoming
+    pair + `class_hits_host(tok, targ)` in place of the counts."""
+    from .train import seq_ce_step_host
+    t = _as_np(targ).reshape(-1)
+    if t.dtype.kind == "f":
+        with np.errstate(invalid="ignore"):
+            cls = np.where(np.isfinite(t), np.trunc(np.where(np.isfinite(t), t, 0.0)), -1).astype(np.int64)
+    else:
+        cls = t.astype(np.int64)
+    x = _as_np(logits)
+    out = seq_ce_step_host(x.reshape(x.shape[0], 1, -1), cls.reshape(-1, 1), 0, epoch_sum=epoch_sum)
+    tok = out["tok"].reshape(-1)
+    return {"row_loss": out["row_loss"], "loss": out["loss"], "tok": tok, "epoch_sum": out["epoch_sum"],
+            "hits": np.asarray(epoch_hits, dtype=np.int64) + class_hits_host(tok, t)}
 
 
 # ----------------------------------------------------------------------------- accuracy

@@ -323,3 +323,63 @@ class GraphStore(object):
             if was_training:
                 model.train()
         return metric.compute()
+
+    # ------------------------------------------------------------------------- the training epoch
+    def _train_epoch(self, what: str, model, optimizer, idx, batch_size: int, clip: float, seed: Optional[int], eos_id: Optional[int],
+                     step):
+        from .train import ClipAdam, EpochMeter
+        clip = float(clip or 0.0)
+        if clip > 0 and isinstance(optimizer, ClipAdam):
+            raise ValueError("GraphStore.%s: a ClipAdam optimizer clips through its own `max_norm`; pass clip=0" % what)
+        ids = self._ids(idx)
+        if int(batch_size) < 1:
+            raise ValueError("GraphStore.%s: batch_size must be positive" % what)
+        chunks = -(-ids.size // int(batch_size))   # every chunk of the loader, skipped ones included: the reference's `step + 1`
+        meter = EpochMeter(self.device, ids.size, eos_id)
+        model.train()
+        for batch in self.loader(ids, batch_size, shuffle=seed is not None, seed=0 if seed is None else int(seed), training=True):
+            loss = step(batch, meter)   # (forward, `optimizer.zero_grad()`, the fused loss: the reference's order)
+            loss.backward()
+            if clip > 0:
+                torch.nn.utils.clip_grad_norm_(model.parameters(), clip)
+            optimizer.step()
+        return meter.result(chunks)
+
+    def train_tok(self, model, optimizer, idx, batch_size: int, clip: float = 0.0, seed: Optional[int] = None):
+        """One epoch of the reference's `train()` for the TOK task (ogbg-code/main_pyg.py:39-88) over the graphs `idx`, fed by
+        the store -> (mean loss, {'precision', 'recall', 'F1', 'n'} of the training predictions).  `model.train()`; batches of
+        `self.loader(idx, batch_size, shuffle=seed is not None, seed=seed, training=True)`; per batch forward,
+        `optimizer.zero_grad()`, `train.seq_ce_step` on the batch's own `y_arr` / `ref_ids` / `ref_extra`, `backward()`,
+        `clip_grad_norm_(model.parameters(), clip)` when `clip` > 0, `optimizer.step()`.  The loss launch also leaves the step's
+        tokens, F1 counts and `loss_accum += loss.item()` on the device, so nothing synchronises inside the loop; the epoch
+        ends with one read.  The mean loss is the sum / the number of chunks of the loader, skipped one-graph and one-node
+        chunks included (the reference's `loss_accum / (step + 1)`).  With a `train.ClipAdam` optimizer clip through its
+        `max_norm`: `clip` > 0 then raises `ValueError`.  The model is left in training mode, as the reference leaves it."""
+        from .train import seq_ce_step
+        if "y_arr" not in self.arrays:
+            raise ValueError("GraphStore.train_tok: the store was packed without y_arr")
+        if "ref_ids" not in self.arrays or self.eos_id is None:
+            raise ValueError("GraphStore.train_tok: the store was packed without label words and vocab2idx")
+
+        def step(batch, meter):
+            y_arr, ref_ids, ref_extra = batch.y_arr, batch.ref_ids, batch.ref_extra   # (before the pass, which may rewrite the batch)
+            pred_list = model(batch)
+            optimizer.zero_grad()
+            return seq_ce_step(pred_list, y_arr, meter, ref_ids, ref_extra)
+
+        return self._train_epoch("train_tok", model, optimizer, idx, batch_size, clip, seed, self.eos_id, step)
+
+    def train_lp(self, model, optimizer, idx, batch_size: int, clip: float = 0.0, seed: Optional[int] = None):
+        """`train_tok` for the LP task (ogbg-code/main_pyg_lp.py:43-74) -> (mean loss, {'acc', 'n'}): the targets are the
+        batch's `len_longest_path`, the loss launch is `lp.class_ce_step`."""
+        from .lp import class_ce_step
+        if "y_arr" not in self.arrays:
+            raise ValueError("GraphStore.train_lp: the store was packed without y_arr")
+
+        def step(batch, meter):
+            targ = batch.len_longest_path   # (before the pass, which may rewrite the batch)
+            pred = model(batch)
+            optimizer.zero_grad()
+            return class_ce_step(pred, targ, meter)
+
+        return self._train_epoch("train_lp", model, optimizer, idx, batch_size, clip, seed, None, step)

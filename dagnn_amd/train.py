@@ -264,6 +264,171 @@ def seq_cross_entropy(pred_list, y_arr: torch.Tensor) -> torch.Tensor:
     return _SeqCE.apply(base, y_arr, S, V)
 
 
+# ----------------------------------------------------------------------------- an epoch of `train()` (main_pyg.py:39-88)
+class EpochMeter(object):
+    """The device state of one epoch of the reference's `train()` (ogbg-code/main_pyg.py:39-88, main_pyg_lp.py:43-74): the
+    float64 sum of the steps' losses (`loss_accum += loss.item()`), the step counter and what the training metric is made
+    of - for the TOK task (`eos_id` given: the id of `__EOS__`) the `[capacity_graphs, 4]` int32 F1 counts of every graph
+    seen, for the LP task (`eos_id` None) the (hits, labelled) int64 pair.  `seq_ce_step` / `lp.class_ce_step` update it
+    inside the loss launch; nothing synchronises until `result()`.  One buffer holds all of it, so the read is one copy.
+
+    `tok`: the predicted tokens of the last step ([B, S] / [B] int64).  `graphs`: graphs counted so far (host)."""
+
+    _HEAD = 8   # int32 words in front of the counts: sum (float64) | steps (int64) | hits, labelled (int64)
+
+    def __init__(self, device, capacity_graphs: int, eos_id: Optional[int] = None):
+        self.capacity = int(capacity_graphs)
+        if self.capacity < 0:
+            raise ValueError("EpochMeter: capacity_graphs must not be negative")
+        self.eos_id = None if eos_id is None else int(eos_id)
+        rows = self.capacity if self.eos_id is not None else 0
+        self._buf = torch.zeros(self._HEAD + 4 * rows, dtype=torch.int32, device=torch.device(device))
+        self.device = self._buf.device   # (with its index, as every tensor's: 'cuda' and 'cuda:0' name one device and compare unequal)
+        self.loss_sum = self._buf[0:2].view(torch.float64)
+        self.steps = self._buf[2:4].view(torch.int64)
+        self.hits = self._buf[4:8].view(torch.int64)
+        self.counts = self._buf[self._HEAD:].view(rows, 4)
+        self.graphs = 0
+        self.tok = None
+
+    def reset(self) -> None:
+        self._buf.zero_()
+        self.graphs = 0
+        self.tok = None
+
+    def room(self, B: int) -> int:
+        """The row of `counts` the next step's first graph goes to; `ValueError` when its B graphs do not fit."""
+        if self.eos_id is not None and self.graphs + B > self.capacity:
+            raise ValueError("EpochMeter: %d graphs counted, %d more do not fit capacity_graphs=%d" % (self.graphs, B, self.capacity))
+        return self.graphs
+
+    def result(self, num_batches: int):
+        """(`loss_sum / num_batches`, metric) after the epoch's ONE blocking read.  `num_batches` is the reference's
+        `step + 1`: every batch of its loader, skipped ones included.  TOK: `evaluate.f1_from_counts` on the rows written
+        -> {'precision', 'recall', 'F1', 'n'}; LP: {'acc', 'n'} as `ClassAccuracy.compute` gives it."""
+        from .evaluate import f1_from_counts
+        if int(num_batches) < 1:
+            raise ValueError("EpochMeter.result: num_batches must be positive")
+        rows = self.graphs if self.eos_id is not None else 0
+        host = self._buf[:self._HEAD + 4 * rows].cpu()
+        loss_sum = float(host[0:2].view(torch.float64)[0])
+        if self.eos_id is not None:
+            if rows == 0:
+                raise ValueError("EpochMeter.result: no graph was counted")
+            metric = f1_from_counts(host[self._HEAD:].view(rows, 4).numpy())
+        else:
+            hits, labelled = (int(v) for v in host[4:8].view(torch.int64))
+            if labelled == 0:
+                raise ValueError("EpochMeter.result: no labelled graph (the evaluator's division by zero)")
+            metric = {"acc": float(hits) / labelled, "n": labelled}
+        return loss_sum / int(num_batches), metric
+
+
+def seq_ce_step_host(logits, y, eos_id: int, ref_ids=None, ref_extra=None, epoch_sum: float = 0.0) -> dict:
+    """The definition `dagnn_seq_ce_step` implements, in numpy.  `logits` [B, S, V] (or [B, S V] with `y` [B, S]) fp32.
+    `row_loss` [B S] fp32: log-sum-exp minus the target's logit per (graph, head) row, NaN for a target outside [0, V);
+    `loss`: their fp32 sum in index order / (B S); `tok` [B, S] int64: lowest column among equals, a NaN beats every number,
+    -0 == +0; `counts` [B, 4] int32 = `evaluate.f1_counts_host` of `tok` (None without `ref_ids`); `epoch_sum`: the incoming
+    float64 + float64(loss), `loss_accum += loss.item()`."""
+    import numpy as np
+    from .evaluate import f1_counts_host
+    y = np.asarray(y.cpu() if isinstance(y, torch.Tensor) else y).astype(np.int64)
+    x = np.asarray(logits.detach().cpu() if isinstance(logits, torch.Tensor) else logits, dtype=np.float32)
+    B, S = y.shape
+    x = x.reshape(B, S, -1)
+    V = x.shape[2]
+    nan = np.isnan(x)
+    tok = np.where(nan.any(axis=2), nan.argmax(axis=2), np.where(nan, -np.inf, x).argmax(axis=2)).astype(np.int64)
+    x64 = x.astype(np.float64)
+    with np.errstate(invalid="ignore", over="ignore"):
+        m = x64.max(axis=2, keepdims=True)
+        lse = m[..., 0] + np.log(np.exp(x64 - m).sum(axis=2))
+    ok = (y >= 0) & (y < V)
+    picked = np.take_along_axis(x64, np.where(ok, y, 0)[..., None], axis=2)[..., 0]
+    row_loss = np.where(ok, lse - picked, np.nan).astype(np.float32).reshape(-1)
+    acc = np.float32(0.0)
+    for v in row_loss:
+        acc = np.float32(acc + v)
+    loss = np.float32(acc / np.float32(B * S))
+    counts = None if ref_ids is None else f1_counts_host(tok, eos_id, ref_ids, np.zeros(B, np.int32) if ref_extra is None else ref_extra)
+    return {"row_loss": row_loss, "loss": loss, "tok": tok, "counts": counts, "epoch_sum": float(epoch_sum) + float(loss)}
+
+
+class _SeqCEStep(torch.autograd.Function):
+    """`_SeqCE` through `dagnn_seq_ce_step` (csrc/train_step.hip): the same loss and d logits, and in the same launch the
+    step's tokens, its F1 counts and the epoch sums on `meter`."""
+
+    @staticmethod
+    def forward(ctx, base, y, S, V, meter, ref_ids, ref_extra):
+        from . import engine
+        B = base.shape[0]
+        off = meter.room(B) if ref_ids is not None else 0   # (a step without label sets counts no graph: nothing has to fit)
+        loss, ctx.dl, tok = engine.seq_ce_step(base, y, S, V, base.requires_grad, meter.eos_id, ref_ids, ref_extra, meter.counts,
+                                               off, meter.loss_sum, meter.steps)
+        meter.tok = tok
+        if ref_ids is not None:
+            meter.graphs = off + B
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        # exactly `_SeqCE.backward`: out of place, into rows of the same pitch
+        dl = ctx.dl
+        out = torch.empty(dl.shape[0], dl.stride(0), dtype=dl.dtype, device=dl.device)[:, :dl.shape[1]]
+        return torch.mul(dl, g, out=out), None, None, None, None, None, None
+
+
+def seq_ce_step(pred_list, y_arr: torch.Tensor, meter: EpochMeter, ref_ids: Optional[torch.Tensor] = None,
+                ref_extra: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The loss of `seq_cross_entropy(pred_list, y_arr)` - under autograd, the same bits - with the rest of the reference's
+    training step (main_pyg.py:67-83) in the SAME launch: `loss_accum += loss.item()` as a float64 sum on the device, the
+    argmax of every head (`meter.tok`, [B, S]) and, with the batch's label id sets `ref_ids` [B, R] / `ref_extra` [B] (int32:
+    `evaluate.encode_ref_sets`, or a `GraphStore` batch's own), the F1 counts of its graphs at their place in `meter.counts`.
+    Nothing synchronises; `meter.result()` is the epoch's one read.
+
+    The fused launch (`dagnn_seq_ce_step`) runs when `heads_base(pred_list)` is not None, under the conditions
+    `seq_cross_entropy` checks, for a TOK meter on the logits' device; any other list composes `seq_cross_entropy`,
+    `evaluate.rows_argmax` and the `SeqF1` arithmetic on the meter.  Without `ref_ids` the step counts no graph."""
+    from . import engine
+    from .evaluate import f1_counts_host, rows_argmax
+    if meter.eos_id is None:
+        raise ValueError("seq_ce_step: the meter was made without `eos_id` (an LP meter)")
+    if (ref_ids is None) != (ref_extra is None):
+        raise ValueError("seq_ce_step: `ref_ids` and `ref_extra` go together")
+    S = len(pred_list)
+    if S == 0:
+        raise ValueError("seq_ce_step: empty `pred_list`")
+    B = pred_list[0].shape[0]
+    if ref_ids is not None:
+        if ref_ids.dim() != 2 or ref_ids.shape[0] != B or ref_ids.shape[1] < 1 or ref_extra.numel() != B:
+            raise ValueError("seq_ce_step: ref_ids [B, R >= 1] and ref_extra [B] needed (got %s, %s)"
+                             % (tuple(ref_ids.shape), tuple(ref_extra.shape)))
+        dev = pred_list[0].device
+        # (host tensors go through pinned memory: the copies are queued behind the pass, the host does not wait)
+        ref_ids, ref_extra = ((t if t.device == dev else t.pin_memory().to(dev, non_blocking=True)) if dev.type == "cuda" else t
+                              for t in (ref_ids, ref_extra))
+        ref_ids, ref_extra = ref_ids.to(torch.int32).contiguous(), ref_extra.reshape(B).to(torch.int32).contiguous()
+    base = heads_base(pred_list)
+    fused = base is not None and y_arr.is_cuda and y_arr.dtype == torch.int64 and y_arr.dim() == 2 and y_arr.shape[1] == S \
+        and y_arr.is_contiguous() and y_arr.shape[0] == base.shape[0] and meter.device == base.device
+    if fused:
+        return _SeqCEStep.apply(base, y_arr, S, pred_list[0].shape[1], meter, ref_ids, ref_extra)
+    off = meter.room(B) if ref_ids is not None else 0
+    loss = seq_cross_entropy(pred_list, y_arr)
+    tok = rows_argmax([p.detach() for p in pred_list])
+    meter.loss_sum.add_(loss.detach().to(torch.float32).to(meter.device, torch.float64))
+    meter.steps.add_(1)
+    meter.tok = tok
+    if ref_ids is not None:
+        rows = meter.counts[off:off + B]
+        if tok.is_cuda and meter.device == tok.device:
+            engine.seq_f1_counts(tok, meter.eos_id, ref_ids, ref_extra, out=rows)
+        else:
+            rows.copy_(torch.from_numpy(f1_counts_host(tok, meter.eos_id, ref_ids, ref_extra)))
+        meter.graphs = off + B
+    return loss
+
+
 # ----------------------------------------------------------------------------- clip_grad_norm_ + Adam (main_pyg.py:63-65)
 class ClipAdam(torch.optim.Optimizer):
     """`torch.nn.utils.clip_grad_norm_(params, max_norm)` followed by `torch.optim.Adam(params, ...).step()` - the tail of the

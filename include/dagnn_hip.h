@@ -1298,6 +1298,36 @@ int dagnn_class_hits(const float* logits, int64_t ld, const int64_t* tok, int64_
                      void* work, size_t work_bytes, unsigned* counter, int64_t* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The loss launch of a training step with the epoch's bookkeeping in it (csrc/train_step.hip; `train()` of
+ * ogbg-code/main_pyg.py:39-88 and main_pyg_lp.py:43-74: `loss_accum += loss.item()`, the argmax of the training logits and
+ * the evaluator's counts, per step).
+ *
+ * dagnn_seq_ce_step: dagnn_seq_ce - same arguments up to `loss`, same sums in the same order, same counter protocol: loss
+ *   and dlogits are dagnn_seq_ce's bits - and in the same launch
+ *     tok [B, S] int64: each row's argmax in the order stated above dagnn_heads_argmax (lowest column among equals, a NaN
+ *       beats every number, -0 == +0): what dagnn_rows_argmax gives;
+ *     epoch_sum [1] float64 += (double)loss and epoch_steps [1] int64 += 1, by one thread of the workgroup that finishes
+ *       last: launches of one stream are ordered, so the sum is `loss_accum += loss.item()` in step order, bit for bit;
+ *     with ref_ids != NULL: counts [graph_offset + g, 4] int32 = dagnn_seq_f1_counts of the B graphs from tok, eos_id,
+ *       ref_ids [B, R >= 1] and ref_extra [B] (may be NULL), written by the last workgroup.  counts [counts_rows, 4] is
+ *       16-byte aligned; graph_offset + B > counts_rows returns DAGNN_ENOSPC before anything is launched.  ref_ids == NULL
+ *       skips the metric (R >= 1 and graph_offset >= 0 are still checked).
+ * dagnn_class_ce_step: dagnn_class_ce likewise (targets int64 / float32 / float64 by `targ_kind`), plus tok [B] int64 (the
+ *   row argmax), epoch_hits [2] int64 += (hits, labelled) by dagnn_class_hits' rules (a NaN target is unlabelled; target
+ *   and prediction are compared as values), epoch_sum and epoch_steps as above.
+ * The epoch words are the caller's: zero them to start an epoch, read them once at its end; 8-byte aligned.  counter [1]
+ * device word, zero before the first call (the kernel leaves it zero).  No allocation, no synchronisation, no float
+ * atomics: bitwise repeatable.
+ * ---------------------------------------------------------------------------------------- */
+int dagnn_seq_ce_step(const float* logits, int64_t ld, const int64_t* y, int B, int S, int V, float* dlogits, int64_t ld_dlogits,
+                      float* row_loss, float* loss, int64_t* tok, int64_t eos_id, const int32_t* ref_ids, int R,
+                      const int32_t* ref_extra, int32_t* counts, int64_t counts_rows, int64_t graph_offset, double* epoch_sum,
+                      int64_t* epoch_steps, unsigned* counter, void* stream);
+int dagnn_class_ce_step(const float* logits, int64_t ld, const void* targ, int targ_kind, int B, int C, float* dlogits,
+                        int64_t ld_dlogits, float* row_loss, float* loss, int64_t* tok, int64_t* epoch_hits, double* epoch_sum,
+                        int64_t* epoch_steps, unsigned* counter, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * The device-resident graph store (csrc/store.hip; dagnn_amd/store.py): a dataset of raw ogbg-code2 graphs packed once
  * into int32 arrays, and any batch of it - the collation of ogbg-code/tg/dataloader.py:13-35 over graphs that went through
  * `augment_edge2` (utils2.py:31-79) and `add_order_info_01` (src/utils_dag.py:39-52) - written by ONE launch.
