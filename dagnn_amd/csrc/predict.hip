@@ -9,6 +9,8 @@
 //                        loaders and main loops below are that file's, stage for stage) whose epilogue reduces every row of
 //                        the tile to (best, column, second) instead of storing C; column tiles never straddle two heads;
 //                        one 16-byte partial per (graph, head, tile), merged in ascending tile order by a second launch;
+//   dagnn_heads_score    the same two launches with a wider epilogue: the k best columns, the log-sum-exp and the row's
+//                        negative log-likelihood ("heads + score" below);
 //   dagnn_rows_argmax    the same answer from logits that exist (a training step needs them for the loss);
 //   dagnn_seq_f1_counts  per graph (true_positive, n_pred, n_ref, len) in integers.
 //
@@ -178,12 +180,9 @@ __device__ __forceinline__ void argmax_epilogue(const f32x16 (&acc)[2][2], float
     }
 }
 
+// the main loop of both generic kernels (argmax and score): the tile's 128 x 128 accumulators; `smem` = As[2] | Bs[2]
 template <bool VEC>
-__global__ void __launch_bounds__(256) heads_argmax_kernel(HeadsArgs a) {
-    __shared__ float smem[4 * BK * LDT];   // As[2] | Bs[2]; the epilogue's staging tiles afterwards (4 x 32 x SP floats)
-    __shared__ Part rowres[2 * BM];
-    static_assert(4 * 32 * SP <= 4 * BK * LDT, "staging tiles must fit the operand buffers");
-    const TileId t = tile_of(a);
+__device__ __forceinline__ void heads_mainloop(f32x16 (&acc)[2][2], float* __restrict__ smem, const HeadsArgs& a, const TileId& t) {
     const float* __restrict__ A = a.out;
     const float* __restrict__ W = a.wcat + (int64_t)t.head * a.V * a.ldw;
     const int K = a.D, n0 = t.tile * BN;
@@ -191,7 +190,6 @@ __global__ void __launch_bounds__(256) heads_argmax_kernel(HeadsArgs a) {
     const int wm = (wave >> 1) * 64, wn = (wave & 1) * 64;
     const int fr = lane & 31, fk = lane >> 5;
 
-    f32x16 acc[2][2];
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -234,16 +232,22 @@ __global__ void __launch_bounds__(256) heads_argmax_kernel(HeadsArgs a) {
         __syncthreads();
         cur ^= 1;
     }
+}
+
+template <bool VEC>
+__global__ void __launch_bounds__(256) heads_argmax_kernel(HeadsArgs a) {
+    __shared__ float smem[4 * BK * LDT];   // As[2] | Bs[2]; the epilogue's staging tiles afterwards (4 x 32 x SP floats)
+    __shared__ Part rowres[2 * BM];
+    static_assert(4 * 32 * SP <= 4 * BK * LDT, "staging tiles must fit the operand buffers");
+    const TileId t = tile_of(a);
+    f32x16 acc[2][2];
+    heads_mainloop<VEC>(acc, smem, a, t);
     argmax_epilogue(acc, smem, rowres, a, t);
 }
 
 // D a multiple of 32, 16-byte aligned rows (every model whose read-out width is: the headline's 1024): the 128-bit LDS
 // traffic of gemm_nt_bias_k32_kernel
-__global__ void __launch_bounds__(256, 2) heads_argmax_k32_kernel(HeadsArgs a) {
-    extern __shared__ __attribute__((aligned(16))) float gsm[];   // [2][A: 128 x GP | B: 128 x GP]
-    __shared__ Part rowres[2 * BM];
-    static_assert(4 * 32 * SP <= 2 * 2 * BM * GP, "staging tiles must fit the operand buffers");
-    const TileId t = tile_of(a);
+__device__ __forceinline__ void heads_mainloop_k32(f32x16 (&acc)[2][2], float* __restrict__ gsm, const HeadsArgs& a, const TileId& t) {
     const float* __restrict__ A = a.out;
     const float* __restrict__ W = a.wcat + (int64_t)t.head * a.V * a.ldw;
     const int K = a.D, n0 = t.tile * BN;
@@ -251,7 +255,6 @@ __global__ void __launch_bounds__(256, 2) heads_argmax_k32_kernel(HeadsArgs a) {
     const int wm = (wave >> 1) * 64, wn = (wave & 1) * 64;
     const int fr = lane & 31, fk = lane >> 5;
 
-    f32x16 acc[2][2];
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -298,6 +301,15 @@ __global__ void __launch_bounds__(256, 2) heads_argmax_k32_kernel(HeadsArgs a) {
         store_rows4(ns + BM * GP, tid, rb);
         __syncthreads();
     }
+}
+
+__global__ void __launch_bounds__(256, 2) heads_argmax_k32_kernel(HeadsArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float gsm[];   // [2][A: 128 x GP | B: 128 x GP]
+    __shared__ Part rowres[2 * BM];
+    static_assert(4 * 32 * SP <= 2 * 2 * BM * GP, "staging tiles must fit the operand buffers");
+    const TileId t = tile_of(a);
+    f32x16 acc[2][2];
+    heads_mainloop_k32(acc, gsm, a, t);
     argmax_epilogue(acc, gsm, rowres, a, t);
 }
 
@@ -315,6 +327,217 @@ __global__ void __launch_bounds__(256) heads_merge_kernel(const Part* __restrict
     if (top) {
         top[2 * r] = val_of((int)(p.best >> 32));
         top[2 * r + 1] = val_of(p.second);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------- heads + score
+// The same two launches with a wider epilogue: per (graph, head, tile) the KT best packed keys in descending order, the tile's
+// maximum m and sum of exp(x - m), and the logit at the target's column; the merge launch joins a row's tiles in ascending
+// tile order (keys: exact and order-free; softmax: the order fixes the rounding) into the k best columns, their logits, the
+// log-sum-exp and the row's negative log-likelihood.  KT in {1, 2, 4, 8}: every list lives in registers, insertion unrolled.
+//
+// A maximum of +-inf is replaced by 0 inside the exponentials, as torch.logsumexp does: a row with +inf sums to +inf, a row
+// of -inf alone to 0 (log: -inf), a NaN poisons its sum, and nothing ever forms inf - inf.
+template <int KT>
+struct __attribute__((aligned(8))) SPart {
+    long long top[KT];   // descending; LLONG_MIN (= pack_of(KEY_NONE, -1)) where the tile has no further live column
+    float m, s, xy;      // maximum, sum of exp(x - m) over the live columns; the target's logit if its column is in this tile
+    int pad;
+};
+
+struct ScoreArgs {
+    HeadsArgs h;
+    const long long* y;   // [B, S] targets or null
+    void* spart;          // SPart<KT> [B, S, tph]
+    unsigned* ticket;     // the merge launch's arrival counter, zeroed by the first launch
+};
+
+template <int KT>
+__device__ __forceinline__ void topk_insert(long long (&t)[KT], long long p) {
+    if (p <= t[KT - 1]) return;
+#pragma unroll
+    for (int j = 0; j < KT; ++j) {
+        const long long hi = t[j] < p ? p : t[j];
+        p = t[j] < p ? t[j] : p;
+        t[j] = hi;
+    }
+}
+
+__device__ __forceinline__ float finite_or_zero(float m) { return fabsf(m) == INFINITY ? 0.f : m; }
+
+// (m, s) <- (m, s) joined with (om, os), in this order
+__device__ __forceinline__ void soft_merge(float& m, float& s, float om, float os) {
+    const float M = fmaxf(m, om), Mf = finite_or_zero(M);
+    const float f0 = m == -INFINITY ? 1.f : __expf(finite_or_zero(m) - Mf);     // (a piece of -inf alone: s is 0 or NaN as it stands)
+    const float f1 = om == -INFINITY ? 1.f : __expf(finite_or_zero(om) - Mf);
+    s = s * f0 + os * f1;
+    m = M;
+}
+
+// The staging of argmax_epilogue; each of a row's two lanes keeps the KT best of its 32 columns, their maximum and - in a
+// second pass over the staged values - the sum of exponentials; lane pairs meet by shuffle, the wave of the upper 64 columns
+// hands its rows over in `rtop` / `rms`, the wave of the lower 64 writes the partial.  Columns ascend through every join.
+template <int KT>
+__device__ __forceinline__ void score_epilogue(const f32x16 (&acc)[2][2], float* __restrict__ stage, long long* __restrict__ rtop,
+                                               float2* __restrict__ rms, const ScoreArgs& sa, const TileId& t) {
+    const HeadsArgs& a = sa.h;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wm = (wave >> 1) * 64, wn = (wave & 1) * 64;
+    const int fr = lane & 31, fk = lane >> 5;
+    const int n0 = t.tile * BN;
+    float* __restrict__ st = stage + wave * (32 * SP);
+    SPart<KT>* __restrict__ part = reinterpret_cast<SPart<KT>*>(sa.spart);
+    float bv[2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int col = n0 + wn + j * 32 + fr;
+        bv[j] = col < a.V ? a.bcat[(int64_t)t.head * a.V + col] : 0.f;
+    }
+    const int row = lane >> 1, c0 = (lane & 1) * 32;
+    const int colbase = n0 + wn + c0;
+    const int ncol = min(32, a.V - colbase);   // live columns of this lane's half row (<= 0: none)
+    __syncthreads();   // (the main loop's last stage has been read by every wave)
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) st[((e & 3) + 8 * (e >> 2) + 4 * fk) * SP + j * 32 + fr] = acc[i][j][e] + bv[j];
+        __syncthreads();
+        const int lrow = wm + i * 32 + row;              // row of the tile
+        const int64_t grow = t.m0 + lrow;                // row of the batch
+        const float* __restrict__ x = st + row * SP + c0;
+        long long tk[KT];
+#pragma unroll
+        for (int j = 0; j < KT; ++j) tk[j] = LLONG_MIN;
+        float m = -INFINITY, s = 0.f;
+        for (int c = 0; c < ncol; ++c) {
+            const float v = x[c];
+            m = fmaxf(m, v);
+            topk_insert(tk, pack_of(key_of(v), colbase + c));
+        }
+        const float mf = finite_or_zero(m);
+        for (int c = 0; c < ncol; ++c) s += __expf(x[c] - mf);
+        if (sa.y && grow < a.M) {
+            const long long yc = sa.y[grow * a.S + t.head] - (long long)colbase;
+            if (yc >= 0 && yc < ncol) part[(grow * a.S + t.head) * a.tph + t.tile].xy = x[yc];
+        }
+        {   // the row's other 32 columns of this wave
+            const float om = __shfl_xor(m, 1, 64), os = __shfl_xor(s, 1, 64);
+            long long ot[KT];
+#pragma unroll
+            for (int j = 0; j < KT; ++j) ot[j] = __shfl_xor(tk[j], 1, 64);
+#pragma unroll
+            for (int j = 0; j < KT; ++j) topk_insert(tk, ot[j]);
+            soft_merge(m, s, om, os);   // (meaningful on the even lane: lower columns first)
+        }
+        if ((wave & 1) && (lane & 1) == 0) {
+#pragma unroll
+            for (int j = 0; j < KT; ++j) rtop[lrow * KT + j] = tk[j];
+            rms[lrow] = make_float2(m, s);
+        }
+        __syncthreads();
+        if (!(wave & 1) && (lane & 1) == 0 && grow < a.M) {
+#pragma unroll
+            for (int j = 0; j < KT; ++j) topk_insert(tk, rtop[lrow * KT + j]);
+            const float2 o = rms[lrow];
+            soft_merge(m, s, o.x, o.y);
+            SPart<KT>* __restrict__ dst = part + (grow * a.S + t.head) * a.tph + t.tile;
+#pragma unroll
+            for (int j = 0; j < KT; ++j) dst->top[j] = tk[j];
+            dst->m = m;
+            dst->s = s;
+        }
+    }
+}
+
+template <bool VEC, int KT>
+__global__ void __launch_bounds__(256) heads_score_kernel(ScoreArgs sa) {
+    __shared__ float smem[4 * BK * LDT];   // As[2] | Bs[2]; the epilogue's staging tiles afterwards (4 x 32 x SP floats)
+    __shared__ long long rtop[BM * KT];
+    __shared__ float2 rms[BM];
+    if (blockIdx.x == 0 && threadIdx.x == 0) *sa.ticket = 0u;
+    const TileId t = tile_of(sa.h);
+    f32x16 acc[2][2];
+    heads_mainloop<VEC>(acc, smem, sa.h, t);
+    score_epilogue<KT>(acc, smem, rtop, rms, sa, t);
+}
+
+// the row results live in the operand buffers behind the staging tiles: no static LDS, two blocks per CU as before
+template <int KT>
+__global__ void __launch_bounds__(256, 2) heads_score_k32_kernel(ScoreArgs sa) {
+    extern __shared__ __attribute__((aligned(16))) float gsm[];   // [2][A: 128 x GP | B: 128 x GP]
+    constexpr int ROWRES = 4 * 32 * SP;   // floats: 16-byte aligned offset
+    static_assert(ROWRES % 4 == 0 && (ROWRES + 2 * BM * KT + 2 * BM) <= 2 * 2 * BM * GP, "row results must fit the operand buffers");
+    if (blockIdx.x == 0 && threadIdx.x == 0) *sa.ticket = 0u;
+    const TileId t = tile_of(sa.h);
+    f32x16 acc[2][2];
+    heads_mainloop_k32(acc, gsm, sa.h, t);
+    long long* rtop = reinterpret_cast<long long*>(gsm + ROWRES);
+    score_epilogue<KT>(acc, gsm, rtop, reinterpret_cast<float2*>(rtop + BM * KT), sa, t);
+}
+
+// one thread per (graph, head): its tiles' partials in ascending tile order.  With `sums` the workgroup that arrives last adds
+// the batch's row losses to the float64 in row order (one thread, 256 rows at a time through LDS) and the row count to the
+// int64: no float atomics, bitwise repeatable.
+constexpr int MT = 64;
+template <int KT>
+__global__ void __launch_bounds__(MT) heads_score_merge_kernel(const SPart<KT>* __restrict__ part, int64_t rows, int tph, int V, int k,
+                                                               const long long* __restrict__ y, long long* __restrict__ tok,
+                                                               float* __restrict__ logit, float* __restrict__ lse, float* __restrict__ nll,
+                                                               double* __restrict__ sums, unsigned* __restrict__ ticket) {
+    __shared__ float chunk[4 * MT];
+    __shared__ unsigned last;
+    const int tid = threadIdx.x;
+    const int64_t r = (int64_t)blockIdx.x * MT + tid;
+    if (r < rows) {
+        const SPart<KT>* __restrict__ p = part + r * tph;
+        long long tk[KT];
+#pragma unroll
+        for (int j = 0; j < KT; ++j) tk[j] = p[0].top[j];
+        float m = p[0].m, s = p[0].s;
+        for (int q = 1; q < tph; ++q) {
+#pragma unroll
+            for (int j = 0; j < KT; ++j) topk_insert(tk, p[q].top[j]);
+            soft_merge(m, s, p[q].m, p[q].s);
+        }
+        const float L = finite_or_zero(m) + __logf(s);
+#pragma unroll
+        for (int j = 0; j < KT; ++j)
+            if (j < k) {
+                tok[r * k + j] = col_of(tk[j]);
+                logit[r * k + j] = val_of((int)(tk[j] >> 32));
+            }
+        lse[r] = L;
+        if (y) {
+            const long long t = y[r];
+            nll[r] = t >= 0 && t < V ? L - p[t / BN].xy : NAN;
+        }
+    }
+    if (!sums) return;   // (uniform)
+    __threadfence();
+    __syncthreads();
+    if (tid == 0) last = atomicAdd(ticket, 1u) == gridDim.x - 1 ? 1u : 0u;
+    __syncthreads();
+    if (!last) return;   // (uniform per workgroup)
+    __threadfence();
+    double acc = sums[0];
+    for (int64_t base = 0; base < rows; base += 4 * MT) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int64_t j = base + q * MT + tid;
+            chunk[q * MT + tid] = j < rows ? __hip_atomic_load(nll + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.f;
+        }
+        __syncthreads();
+        if (tid == 0) {
+            const int n = (int)min((int64_t)(4 * MT), rows - base);
+            for (int j = 0; j < n; ++j) acc += (double)chunk[j];
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        sums[0] = acc;
+        reinterpret_cast<long long*>(sums)[1] += rows;
     }
 }
 
@@ -448,6 +671,74 @@ extern "C" int dagnn_heads_argmax(const float* out, int64_t ld_out, const float*
                        reinterpret_cast<long long*>(tok), top);
     DAGNN_CHECK_LAUNCH();
     return DAGNN_OK;
+}
+
+namespace {
+
+constexpr size_t SCORE_HEAD_BYTES = 16;   // the merge launch's ticket, in front of the partials
+
+int score_kt(int k) { return k <= 1 ? 1 : k <= 2 ? 2 : k <= 4 ? 4 : 8; }
+
+template <int KT>
+int launch_score(const ScoreArgs& sa, bool vec, int64_t rows, int k, int64_t* tok, float* logit, float* lse, float* nll, double* sums,
+                 hipStream_t st) {
+    const HeadsArgs& a = sa.h;
+    const dim3 grid((unsigned)((int64_t)a.tiles_m * a.S * a.tph));
+    if (vec && a.D % GK == 0) {
+        constexpr size_t lds = (size_t)2 * 2 * BM * GP * sizeof(float);   // 72 KB: two blocks per CU
+        static std::atomic<unsigned long long> attr_done{0ull};
+        if (dagnn_lds_attr_once(attr_done, reinterpret_cast<const void*>(heads_score_k32_kernel<KT>), (int)lds) != hipSuccess)
+            return DAGNN_EHIP(hipGetLastError());
+        hipLaunchKernelGGL(heads_score_k32_kernel<KT>, grid, dim3(256), lds, st, sa);
+    } else if (vec)
+        hipLaunchKernelGGL((heads_score_kernel<true, KT>), grid, dim3(256), 0, st, sa);
+    else
+        hipLaunchKernelGGL((heads_score_kernel<false, KT>), grid, dim3(256), 0, st, sa);
+    DAGNN_CHECK_LAUNCH();
+    hipLaunchKernelGGL(heads_score_merge_kernel<KT>, dim3((unsigned)((rows + MT - 1) / MT)), dim3(MT), 0, st,
+                       reinterpret_cast<const SPart<KT>*>(sa.spart), rows, a.tph, a.V, k, sa.y, reinterpret_cast<long long*>(tok), logit,
+                       lse, nll, sums, sa.ticket);
+    DAGNN_CHECK_LAUNCH();
+    return DAGNN_OK;
+}
+
+}  // namespace
+
+extern "C" size_t dagnn_heads_score_bytes(int64_t B, int S, int V, int k) {
+    if (!heads_shape_ok(B, S, V) || k < 1 || k > 8) return 0;
+    const int64_t tph = (V + BN - 1) / BN;
+    return SCORE_HEAD_BYTES + (size_t)(B > 0 ? B : 1) * S * tph * (8 * (size_t)score_kt(k) + 16);
+}
+
+extern "C" int dagnn_heads_score(const float* out, int64_t ld_out, const float* wcat, int64_t ldw, const float* bcat, int64_t B,
+                                 int D, int S, int V, const int64_t* y, int k, int64_t* tok, float* logit, float* lse, float* nll,
+                                 void* sums, void* work, size_t work_bytes, void* stream) {
+    if (!heads_shape_ok(B, S, V) || D <= 0 || ld_out < D || ldw < D || k < 1 || k > 8) return DAGNN_EINVAL;
+    if ((y != nullptr) != (nll != nullptr) || (sums && !y)) return DAGNN_EINVAL;
+    if (B == 0) return DAGNN_OK;
+    if (!out || !wcat || !bcat || !tok || !logit || !lse || !work || ((uintptr_t)work & 15) || ((uintptr_t)sums & 7))
+        return DAGNN_EINVAL;
+    if (work_bytes < dagnn_heads_score_bytes(B, S, V, k)) return DAGNN_ENOSPC;
+    ScoreArgs sa;
+    HeadsArgs& a = sa.h;
+    a.out = out; a.wcat = wcat; a.bcat = bcat; a.part = nullptr;
+    a.M = B; a.ld_out = ld_out; a.ldw = ldw; a.D = D; a.S = S; a.V = V;
+    a.tph = (V + BN - 1) / BN;
+    const int64_t tiles_m = (B + BM - 1) / BM;
+    if (tiles_m * S * a.tph >= (int64_t(1) << 31)) return DAGNN_EINVAL;
+    a.tiles_m = (int)tiles_m;
+    sa.y = reinterpret_cast<const long long*>(y);
+    sa.ticket = reinterpret_cast<unsigned*>(work);
+    sa.spart = reinterpret_cast<char*>(work) + SCORE_HEAD_BYTES;
+    hipStream_t st = (hipStream_t)stream;
+    const bool vec = ld_out % 4 == 0 && ldw % 4 == 0 && ((uintptr_t)out & 15) == 0 && ((uintptr_t)wcat & 15) == 0;
+    double* sm = reinterpret_cast<double*>(sums);
+    switch (score_kt(k)) {
+        case 1: return launch_score<1>(sa, vec, B * S, k, tok, logit, lse, nll, sm, st);
+        case 2: return launch_score<2>(sa, vec, B * S, k, tok, logit, lse, nll, sm, st);
+        case 4: return launch_score<4>(sa, vec, B * S, k, tok, logit, lse, nll, sm, st);
+        default: return launch_score<8>(sa, vec, B * S, k, tok, logit, lse, nll, sm, st);
+    }
 }
 
 extern "C" int dagnn_rows_argmax(const float* logits, int64_t ld, int64_t B, int S, int V, int64_t* tok, void* stream) {

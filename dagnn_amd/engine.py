@@ -1984,6 +1984,49 @@ def heads_argmax(out: torch.Tensor, wcat: torch.Tensor, bcat: torch.Tensor, S: i
     return tok, top
 
 
+def heads_score(out: torch.Tensor, wcat: torch.Tensor, bcat: torch.Tensor, S: int, V: int, y: Optional[torch.Tensor] = None,
+                k: int = 1, sums: Optional[torch.Tensor] = None, arena: Optional[GranuleArena] = None):
+    """`dagnn_heads_score`: (tok [B, S, k] int64, logit [B, S, k], lse [B, S], nll [B, S] or None) of the S heads kept as one
+    matrix `wcat` [S V, D] / `bcat` [S V] on the pooled vectors `out` [B, D], without the logits: the k best columns of every
+    (graph, head) with their logits, the log-sum-exp, and with targets `y` [B, S] int64 the row losses.  `sums`: an
+    `evaluate.SeqLoss`'s 16 device bytes (a float64 tensor of 2 elements: the running sum of row losses, and the row count as
+    int64 bits), added to in place.  The per-tile partials live in `arena`'s scratch (a fresh tensor without one).  Nothing
+    synchronises."""
+    out = _rows(out, "pooled graph vectors")
+    wcat, bcat = _rows(wcat, "head weights"), _dev(bcat, "head biases", torch.float32)
+    B, D = out.shape
+    k = int(k)
+    if tuple(wcat.shape) != (S * V, D) or bcat.numel() != S * V or wcat.device != out.device or bcat.device != out.device:
+        raise DagnnHipError("heads_score: heads of shape [%d, %d] / [%d] on the device of `out` needed (got %s / %s)"
+                            % (S * V, D, S * V, tuple(wcat.shape), tuple(bcat.shape)))
+    if not 1 <= k <= 8:
+        raise DagnnHipError("heads_score: k must lie in 1..8 (got %d)" % k)
+    if y is not None:
+        y = _dev(y, "targets", torch.int64)
+        if y.numel() != B * S or y.device != out.device:
+            raise DagnnHipError("heads_score: targets [%d, %d] on the device of `out` needed (got %s)" % (B, S, tuple(y.shape)))
+        y = y.reshape(B, S).contiguous()
+    if sums is not None:
+        if y is None:
+            raise DagnnHipError("heads_score: `sums` accumulates row losses: targets needed")
+        if sums.dtype != torch.float64 or sums.numel() != 2 or not sums.is_contiguous() or sums.device != out.device:
+            raise DagnnHipError("heads_score: `sums` must be 2 contiguous float64 elements on the device of `out`")
+    lib = _lib.load()
+    tok = torch.empty(B, S, k, dtype=torch.int64, device=out.device)
+    logit = torch.empty(B, S, k, dtype=torch.float32, device=out.device)
+    lse = torch.empty(B, S, dtype=torch.float32, device=out.device)
+    nll = torch.empty(B, S, dtype=torch.float32, device=out.device) if y is not None else None
+    nbytes = lib.dagnn_heads_score_bytes(B, S, V, k)
+    if nbytes == 0:
+        raise DagnnHipError("heads_score: unsupported shape (B=%d, S=%d, V=%d)" % (B, S, V))
+    work = arena.scratch(nbytes, out.device) if arena is not None else torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=out.device)
+    with _span("heads_score", out):
+        check(lib.dagnn_heads_score(out.data_ptr(), out.stride(0), wcat.data_ptr(), wcat.stride(0), bcat.data_ptr(), B, D, S, V,
+                                    _ptr(y), k, tok.data_ptr(), logit.data_ptr(), lse.data_ptr(), _ptr(nll), _ptr(sums),
+                                    work.data_ptr(), work.numel() * work.element_size(), _stream(out)), "dagnn_heads_score")
+    return tok, logit, lse, nll
+
+
 def rows_argmax(logits: torch.Tensor, S: int, V: int) -> torch.Tensor:
     """`dagnn_rows_argmax`: tok [B, S] int64 of `logits` [B, S V] (fp32, unit column stride, any row pitch), one launch."""
     if not isinstance(logits, torch.Tensor) or not logits.is_cuda:

@@ -228,19 +228,37 @@ def lp_batches(batches: Iterable, training: bool) -> Iterator:
         yield b
 
 
-def evaluate_lp(model, batches: Iterable) -> dict:
+def evaluate_lp(model, batches: Iterable, loss: bool = False) -> dict:
     """The evaluation loop of main_pyg_lp.py:77-107: `predict`, `lp_targets`, `ClassAccuracy.update` per batch and one
     `compute()` - the loop's only synchronisation besides what the passes themselves need - at the end -> {'acc', 'n'}.
-    Filtering (`lp_batches`) stays with the caller; the model's mode is restored."""
+    Filtering (`lp_batches`) stays with the caller; the model's mode is restored.  `loss=True`: the passes are
+    `score(batch, targets)` - the targets cast as `class_cross_entropy` casts them, `.to(torch.long)` - and the dict gains
+    'loss', the float64 sum of every graph's `CrossEntropyLoss` term divided by the number of graphs."""
+    from .evaluate import SeqLoss, _with_loss
     was_training = model.training
     model.eval()
     metric = ClassAccuracy()
+    acc = None
     try:
         for batch in batches:
             B = num_graphs_of(batch)
             targ = lp_targets(batch, B)   # (before the pass: `forward` may replace `batch.batch`)
-            metric.update(model.predict(batch), targ)
+            if loss:
+                if acc is None:
+                    acc = SeqLoss(targ.device)
+                metric.update(model.score(batch, _class_targets(targ), sums=acc).tok.reshape(-1), targ)
+            else:
+                metric.update(model.predict(batch), targ)
     finally:
         if was_training:
             model.train()
-    return metric.compute()
+    return _with_loss(metric, acc)
+
+
+def _class_targets(targ: torch.Tensor) -> torch.Tensor:
+    """Targets as classes, [B] int64: truncated toward zero as `.to(torch.long)` does; a NaN or infinite target lies outside
+    every class (-1), as `dagnn_class_ce` decides."""
+    targ = targ.reshape(-1)
+    if targ.dtype.is_floating_point:
+        return torch.where(torch.isfinite(targ), targ, torch.full_like(targ, -1.0)).to(torch.long)
+    return targ.to(torch.long)

@@ -543,8 +543,55 @@ class DAGNN(HipModule):
             tok, top = self._pass(G, self._heads_argmax)
         return (tok, top) if return_top else tok
 
+    def score(self, G, y_arr=None, topk: int = 1, sums=None):
+        """An evaluation pass that says more than `predict` and still never writes the [B, S V] logits (`dagnn_heads_score`,
+        csrc/predict.hip): an `evaluate.Score` with `tok` / `logit` [B, S, topk] - the `topk` (1..8) best columns of every
+        (graph, head) and their logits, best first in `predict`'s order, so `tok[:, :, 0]` IS `predict(G)` - `lse` [B, S], and
+        with targets `y_arr` [B, S] (`num_class` models: [B] or [B, 1]) `nll` [B, S], the row terms of the reference's
+        criterion `CrossEntropyLoss` (ogbg-code/main_pyg.py:37,55-60): `.loss` is `train.seq_cross_entropy(model(G), y_arr)` by
+        definition, `.logprob` the log-probabilities of the candidates.  A target outside [0, V) makes its row's `nll` NaN.
+        `sums`: an `evaluate.SeqLoss` the pass adds its row losses to, inside its own launch.  `forward`'s side effects on
+        `G`; evaluation mode only, under `torch.no_grad()` (a training step has its logits and `train.seq_ce_step`)."""
+        from .evaluate import Score
+        if self.training:
+            raise RuntimeError("DAGNN.score is an evaluation pass: call model.eval() first (a training step has its logits: "
+                               "dagnn_amd.train.seq_ce_step)")
+        topk = int(topk)
+        if not 1 <= topk <= 8:
+            raise ValueError("DAGNN.score: topk must lie in 1..8 (got %d)" % topk)
+        if sums is not None and y_arr is None:
+            raise ValueError("DAGNN.score: `sums` accumulates row losses: targets needed")
+        with torch.no_grad():
+            return Score(*self._pass(G, lambda out: self._heads_score(out, y_arr, topk, sums)))
+
+    def _heads_score(self, out, y_arr, topk, sums):
+        """(tok, logit, lse, nll) of the heads on the pooled graph vectors: the head step of `score`, routed as
+        `_heads_argmax` routes `predict`'s."""
+        single = self.num_class > 0
+        heads = [self.graph_pred_linear] if single else list(self.graph_pred_linear_list)
+        S = len(heads)
+        if y_arr is not None:
+            if y_arr.numel() != out.shape[0] * S:
+                raise ValueError("DAGNN.score: targets [%d, %d] needed (got %s)" % (out.shape[0], S, tuple(y_arr.shape)))
+            y_arr = y_arr.reshape(out.shape[0], S).to(out.device)
+            if y_arr.dtype != torch.int64:
+                y_arr = y_arr.to(torch.int64)
+        if out.is_cuda and out.dtype == torch.float32 and all(
+                isinstance(hd, nn.Linear) and hd.bias is not None and hd.weight.dtype == torch.float32 and hd.weight.is_cuda
+                for hd in heads):
+            wcat, bcat = (heads[0].weight, heads[0].bias) if single else self._head_storage()
+            return engine.heads_score(out, wcat.detach(), bcat.detach(), S, heads[0].weight.shape[0], y=y_arr, k=topk,
+                                      sums=None if sums is None else sums.sums, arena=self._arena_for(out))
+        from .evaluate import rows_score
+        pred = self._heads(out)
+        res = rows_score([pred] if single else pred, y_arr, topk)
+        if sums is not None:
+            sums.update(res[3])
+        return res
+
     def _pass(self, G, head):
-        """`forward` up to the pooled graph vectors, then `head` on them (`_heads`: the logits; `_heads_argmax`: `predict`)."""
+        """`forward` up to the pooled graph vectors, then `head` on them (`_heads`: the logits; `_heads_argmax`: `predict`;
+        `_heads_score`: `score`)."""
         L, H, dirs = self.num_layers, self.hidden_dim, self.dirs
         if not self._hip_supported():
             # constructor strings outside every BASELINE configuration (SURVEY §8 a12): same contract, torch-ROCm ops

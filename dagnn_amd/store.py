@@ -306,23 +306,32 @@ class GraphStore(object):
                 continue
             yield self.batch(chunk)
 
-    def evaluate_tok(self, model, idx, batch_size: int) -> dict:
+    def evaluate_tok(self, model, idx, batch_size: int, loss: bool = False) -> dict:
         """The loop of `evaluate.evaluate` (ogbg-code/main_pyg.py:91-124) over the graphs `idx`, fed by the store: `predict`
         and `SeqF1.update` on the batch's own `ref_ids` / `ref_extra` - no host string work and no copy of reference sets
-        per batch - and one synchronisation, in `compute()`.  One-node batches are skipped as the reference skips them."""
+        per batch - and one synchronisation, in `compute()`.  One-node batches are skipped as the reference skips them.
+        `loss=True`: the passes are `score(batch, batch.y_arr)` and the dict gains 'loss', the float64 sum of all row losses
+        divided by (graphs * S), as in `evaluate.evaluate`."""
         if "ref_ids" not in self.arrays or self.eos_id is None:
             raise ValueError("GraphStore.evaluate_tok: the store was packed without label words and vocab2idx")
+        if loss and "y_arr" not in self.arrays:
+            raise ValueError("GraphStore.evaluate_tok: the store was packed without y_arr")
+        from .evaluate import SeqLoss, _with_loss
         was_training = model.training
         model.eval()
         metric = SeqF1(self.eos_id)
+        acc = SeqLoss(self.device) if loss else None
         try:
             for batch in self.loader(idx, batch_size):
                 ref_ids, ref_extra = batch.ref_ids, batch.ref_extra   # (before the pass, which may rewrite the batch)
-                metric.update(model.predict(batch), ref_ids, ref_extra)
+                if loss:
+                    metric.update(model.score(batch, batch.y_arr, sums=acc).tok[:, :, 0], ref_ids, ref_extra)
+                else:
+                    metric.update(model.predict(batch), ref_ids, ref_extra)
         finally:
             if was_training:
                 model.train()
-        return metric.compute()
+        return _with_loss(metric, acc)
 
     # ------------------------------------------------------------------------- the training epoch
     def _train_epoch(self, what: str, model, optimizer, idx, batch_size: int, clip: float, seed: Optional[int], eos_id: Optional[int],

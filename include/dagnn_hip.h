@@ -1256,10 +1256,26 @@ int dagnn_seq_ce(const float* logits, int64_t ld, const int64_t* y, int B, int S
  *   ids in ref_ids[b] ([B, R] int32, padded with -1: the graph's in-vocabulary label words) + ref_extra[b] (its distinct
  *   label words outside the vocabulary, which no prediction can match), true_positive = size of the intersection.
  *   false_positive = n_pred - tp, false_negative = n_ref - tp.  A thread per graph.
- * No allocation, no synchronisation, no float atomics: bitwise repeatable.  The size query returns 0 for arguments the
+ * dagnn_heads_score: the same pass with a wider epilogue, for what an evaluation wants beyond the arg-max - still without
+ *   the logits.  Per (graph, head): tok [B, S, k] int64 / logit [B, S, k] = the k best columns (1 <= k <= 8) and their
+ *   logits, descending in the order above (tok[.., 0] and logit[.., 0] are dagnn_heads_argmax's tok and top[.., 0], bit for
+ *   bit; ranks beyond V hold column -1 and -inf); lse [B, S] = log sum_c exp(logit_c) as torch.logsumexp defines it (any NaN:
+ *   NaN; else any +inf: +inf; all -inf: -inf); with targets y [B, S] int64 (NULL: none), nll [B, S] = lse - logit at
+ *   y[b, s] - CrossEntropyLoss per row; a target outside [0, V) makes that row's nll NaN and nothing else, as dagnn_seq_ce
+ *   decides.  y and nll come together or not at all.  sums (NULL, or 16 device bytes {float64, int64}; needs y): the
+ *   batch's B S row losses are added to the float64 one by one in row order by a single thread, B S to the int64, so an
+ *   evaluation's mean loss is sums[0] / sums[1] after one read.  `work` >= dagnn_heads_score_bytes(B, S, V, k) bytes,
+ *   16-byte aligned: per (graph, head, 128-column tile) the tile's best columns (k rounded up to 1, 2, 4 or 8), its maximum,
+ *   its sum of exponentials and the target's logit, merged in ascending tile order by the second launch
+ *   (M = max(m1, m2), s = s1 exp(m1 - M) + s2 exp(m2 - M), fast-math exp / log as dagnn_seq_ce).  B = 0 returns at once.
+ * No allocation, no synchronisation, no float atomics: bitwise repeatable.  The size queries return 0 for arguments the
  * entry point refuses with DAGNN_EINVAL.
  * ---------------------------------------------------------------------------------------- */
 size_t dagnn_heads_argmax_bytes(int64_t B, int S, int V);
+size_t dagnn_heads_score_bytes(int64_t B, int S, int V, int k);
+int dagnn_heads_score(const float* out, int64_t ld_out, const float* wcat, int64_t ldw, const float* bcat, int64_t B, int D,
+                      int S, int V, const int64_t* y, int k, int64_t* tok, float* logit, float* lse, float* nll, void* sums,
+                      void* work, size_t work_bytes, void* stream);
 int dagnn_heads_argmax(const float* out, int64_t ld_out, const float* wcat, int64_t ldw, const float* bcat, int64_t B, int D,
                        int S, int V, int64_t* tok, float* top, void* work, size_t work_bytes, void* stream);
 int dagnn_rows_argmax(const float* logits, int64_t ld, int64_t B, int S, int V, int64_t* tok, void* stream);
