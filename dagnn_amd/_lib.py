@@ -42,6 +42,16 @@ class ReadoutBwdJob(C.Structure):
                 ("dir", C.c_int32), ("col_off", C.c_int32)]
 
 
+class PoolJob(C.Structure):   # dagnn_pool_job
+    _fields_ = [("h", C.c_void_p), ("ld_h", C.c_int32), ("width", C.c_int32), ("scope", C.c_int32), ("mode", C.c_int32),
+                ("col_off", C.c_int32)]
+
+
+class PoolBwdJob(C.Structure):   # dagnn_pool_bwd_job
+    _fields_ = [("h", C.c_void_p), ("grad_h", C.c_void_p), ("ld_h", C.c_int32), ("ld_g", C.c_int32), ("width", C.c_int32),
+                ("scope", C.c_int32), ("mode", C.c_int32), ("col_off", C.c_int32)]
+
+
 class AttnGradJob(C.Structure):
     _fields_ = [("key_sum", C.c_void_p), ("feat_sum", C.c_void_p), ("sigma_sum", C.c_void_p), ("edge_w", C.c_void_p),
                 ("edge_b", C.c_void_p), ("attn_w", C.c_void_p), ("g_attn", C.c_void_p), ("g_edge_w", C.c_void_p),
@@ -417,6 +427,9 @@ SYMBOLS = {
     "dagnn_attn_grads_run": (C.c_int, [C.POINTER(AttnGradJob), C.c_int, C.c_void_p]),
     "dagnn_readout_max_backward_batch": (C.c_int, [C.POINTER(Plan), C.POINTER(ReadoutBwdJob), C.c_int, C.c_void_p, C.c_int,
                                                    C.c_void_p]),
+    "dagnn_readout_pool_batch": (C.c_int, [C.POINTER(Plan), C.POINTER(PoolJob), C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "dagnn_readout_pool_backward_batch": (C.c_int, [C.POINTER(Plan), C.POINTER(PoolBwdJob), C.c_int, C.c_void_p, C.c_int,
+                                                    C.c_void_p]),
     "dagnn_topo_layers": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p]),
     "dagnn_variant_aggregate": (C.c_int, [C.POINTER(Plan), C.POINTER(VariantAggregator), C.c_int, C.c_int32, C.c_int32,

@@ -11,6 +11,7 @@ ordinary torch autograd, as in the reference.
 from __future__ import annotations
 
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import _lib, engine
 from .core import run_stack_lockstep
@@ -107,6 +108,36 @@ def _wgrad(dg: torch.Tensor, u: torch.Tensor, splits: int = 32) -> torch.Tensor:
     return out
 
 
+class PoolNodes(torch.autograd.Function):
+    """`(plan, h [N, W], scope, how) -> [B, W]`: max / add / mean pool of the rows of an ordinary autograd tensor over the
+    output nodes of direction 0 / 1 (scope 0 / 1) or over all nodes of every graph (scope 2) - `global_{max,add,mean}_pool`
+    of dagnn.py:194-202 and dvae/dagnn.py:163-172 - in HIP, forward (`dagnn_readout_pool_batch`) and backward
+    (`dagnn_readout_pool_backward_batch` into a zero-filled [N, W]): no mask index, no scatter, no atomics.  The mean
+    divides by the number of nodes in scope.  `h` may be a row-pitched view (`engine._rows`); once differentiable.  The
+    recurrence states of a `Recurrence` pass do not come here: their read-out seeds the reverse sweep directly."""
+
+    @staticmethod
+    def forward(ctx, plan, h, scope, how):
+        h = engine._rows(h, "pooled rows")
+        out = torch.empty(plan.B, h.shape[1], dtype=torch.float32, device=h.device)   # (every element is written)
+        if h.shape[1] > 0:
+            engine.readout_pool_batch(plan, [(h, scope, how, 0)], out)
+        ctx.plan, ctx.scope, ctx.how, ctx.shape = plan, int(scope), how, tuple(h.shape)
+        ctx.save_for_backward(*([h] if how == "max" else []))   # (only the arg-max needs the values again)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        if g is None or not ctx.needs_input_grad[1]:
+            return None, None, None, None
+        gh = torch.zeros(ctx.shape, dtype=torch.float32, device=g.device)
+        if ctx.shape[1] > 0:
+            h = ctx.saved_tensors[0] if ctx.how == "max" else None
+            engine.readout_pool_backward_batch(ctx.plan, [(h, ctx.scope, ctx.how, 0, gh)], g.contiguous().float())
+        return None, gh, None, None
+
+
 class Recurrence(torch.autograd.Function):
     """Plan + node inputs -> graph read-out, differentiable (dagnn.py:144-193; dvae/dagnn.py:99-175).
 
@@ -121,7 +152,8 @@ class Recurrence(torch.autograd.Function):
     def forward(ctx, mod, plan, B, fused, x, *params):
         """fused: returns (read-out [B, .], states...) with the read-out done by the module's HIP hooks and the states
         not differentiable; otherwise returns the states h[d][i] ([N, H] each, d over `dirs`, i over layers) as
-        differentiable outputs - any torch read-out can follow (other pools, all nodes, unidirectional)."""
+        differentiable outputs - what follows is ordinary autograd (the D-VAE encoders' all-node read-out projects every node
+        first, dvae/dagnn.py:163-172, and pools the projection through `PoolNodes`)."""
         L, H, dirs = mod.num_layers, mod.hidden_dim, mod.dirs
         ctx.set_materialize_grads(False)   # (outputs nobody differentiates arrive as None in backward, not as [N, H] zero fills)
         cells = mod._cells(fresh=True)   # a differentiable pass: the optimizer changes the parameters every step
@@ -154,7 +186,7 @@ class Recurrence(torch.autograd.Function):
         if ctx.fused:
             if gouts[0] is not None:
                 mod._readout_backward(plan, x, h, gouts[0].contiguous().float(), g_ext, dx)
-        else:   # gradients of the states themselves, from whatever torch read-out followed
+        else:   # gradients of the states themselves, from whatever autograd ops followed
             for q, d in enumerate(dirs):
                 for i in range(L):
                     if gouts[q * L + i] is not None:

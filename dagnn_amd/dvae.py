@@ -843,7 +843,8 @@ class _DvaeDagnn(_DvaeBase):
 
     def _pool_all(self, G, plan, x, flat, B):
         """Pool over ALL nodes (dvae/dagnn.py:163-172) of the flat states: per-node projection, then HIP pooling over the
-        nodes of every graph (`plan` given, no gradient wanted) or torch pooling."""
+        nodes of every graph (`plan` given: `dagnn_readout_pool`, or `autograd.PoolNodes` where a gradient is wanted - every
+        graph has `num_nodes` nodes, so the kernel's mean factor is the reference's) or torch pooling."""
         G.h = torch.cat(([x] if self.out_wx else []) + list(flat), dim=-1)
         if self.bidirectional:
             G.h = self.hg_unify(G.h)
@@ -853,6 +854,9 @@ class _DvaeDagnn(_DvaeBase):
             out = torch.empty(B, G.h.shape[1], dtype=torch.float32, device=G.h.device)
             engine.readout_pool(plan, G.h, 2, self.out_pool, out, 0)
             return out
+        if plan is not None and G.h.is_cuda and G.h.dtype == torch.float32:
+            from .autograd import PoolNodes
+            return PoolNodes.apply(plan, G.h, 2, self.out_pool)
         idx = G.batch.view(-1, 1).expand_as(G.h)
         out = G.h.new_zeros(B, G.h.shape[1])
         if self.out_pool == K.P_MAX:
@@ -942,7 +946,7 @@ class _DvaeDagnn(_DvaeBase):
             h = self._gated_sum_states(G, x) if gated else variants.run(view, G, x)
         N = x.shape[0]
         if self.output_all:
-            return self._pool_all(G, None, x, [h[d][i] for d in self.dirs for i in range(L)], B)
+            return self._pool_all(G, plan, x, [h[d][i] for d in self.dirs for i in range(L)], B)
         first = torch.arange(0, N, nn_, device=x.device)
         last = first + (nn_ - 1)
         parts = [h[0][i][last] for i in range(L)]

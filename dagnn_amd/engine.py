@@ -1168,6 +1168,54 @@ def readout_max_backward_batch(plan: PlanHandle, jobs, grad_out: torch.Tensor) -
                                                    _stream(grad_out)), "dagnn_readout_max_backward_batch")
 
 
+_POOL_MODES = {"max": _lib.POOL_MAX, "add": _lib.POOL_ADD, "sum": _lib.POOL_ADD, "mean": _lib.POOL_MEAN}
+
+
+def readout_pool_batch(plan: PlanHandle, jobs, out: torch.Tensor) -> None:
+    """`readout_pool` for several (h, scope, how, col_off) jobs in ONE launch (`dagnn_readout_pool_batch`): job by job the
+    same bits.  Longer job lists go in chunks of `MAX_READOUT_JOBS`."""
+    if not jobs:
+        return
+    lib = _lib.load()
+    for k0 in range(0, len(jobs), _lib.MAX_READOUT_JOBS):
+        part = jobs[k0:k0 + _lib.MAX_READOUT_JOBS]
+        arr = (_lib.PoolJob * len(part))()
+        keep = []
+        for q, (h, scope, how, col) in enumerate(part):
+            h = _rows(h, "hidden states")
+            keep.append(h)
+            arr[q] = _lib.PoolJob(h.data_ptr(), h.stride(0), h.shape[1], int(scope), _POOL_MODES[how], int(col))
+        check(lib.dagnn_readout_pool_batch(C.byref(plan.desc), arr, len(part), out.data_ptr(), out.stride(0), _stream(out)),
+              "dagnn_readout_pool_batch")
+
+
+def readout_pool_backward_batch(plan: PlanHandle, jobs, grad_out: torch.Tensor) -> None:
+    """The backward of `readout_pool_batch`: (h, scope, how, col_off, grad_h) jobs, `grad_h[v] +=` node v's share of
+    `grad_out[:, col_off : col_off + width]`, ONE launch per `MAX_READOUT_JOBS` jobs (distinct `grad_h` each; `grad_h`
+    [N, >= width] is initialised by the caller and may be row-pitched).  `h` is read for 'max' only: None otherwise is fine,
+    the width is `h`'s or, without it, `grad_h`'s."""
+    if not jobs:
+        return
+    grad_out = _dev(grad_out, "grad_out", torch.float32)
+    lib = _lib.load()
+    for k0 in range(0, len(jobs), _lib.MAX_READOUT_JOBS):
+        part = jobs[k0:k0 + _lib.MAX_READOUT_JOBS]
+        arr = (_lib.PoolBwdJob * len(part))()
+        keep = []
+        for q, (h, scope, how, col, gh) in enumerate(part):
+            mode = _POOL_MODES[how]
+            if mode == _lib.POOL_MAX:
+                h = _rows(h, "h")
+                keep.append(h)
+            width = h.shape[1] if h is not None else gh.shape[1]
+            if gh.dtype != torch.float32 or gh.stride(1) != 1 or gh.shape[1] < width:
+                raise DagnnHipError("readout_pool_backward_batch: grad_h must be fp32 rows of at least the pooled width")
+            arr[q] = _lib.PoolBwdJob(h.data_ptr() if mode == _lib.POOL_MAX else None, gh.data_ptr(),
+                                     h.stride(0) if mode == _lib.POOL_MAX else 0, gh.stride(0), width, int(scope), mode, int(col))
+        check(lib.dagnn_readout_pool_backward_batch(C.byref(plan.desc), arr, len(part), grad_out.data_ptr(), grad_out.stride(0),
+                                                    _stream(grad_out)), "dagnn_readout_pool_backward_batch")
+
+
 def attn_grads(jobs):
     """Gradients of attn_lin.weight / edge_encoder.{weight, bias} of every cell from the epilogue's column sums, ONE launch
     (`dagnn_attn_grads_run`).  `jobs`: list of dicts {key_sum [kd], feat_sum [R] | None, sigma_sum [1] | None, edge_w [kd, R] |

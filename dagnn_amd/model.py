@@ -394,9 +394,9 @@ class DAGNN(HipModule):
         return plan, gi0
 
     def _training_pass(self) -> bool:
-        """True when this call must be differentiable.  The HIP backward (csrc/backward.hip) covers what the
-        reference's training scripts run (scripts/ogb_tok.sh: attn_h, bidirectional, max-pool over the output
-        nodes); other combinations raise instead of silently detaching."""
+        """True when this call must be differentiable.  The HIP backward (csrc/backward.hip) covers the additive-attention
+        aggregators with GRU cells on the lock-step schedule, with every read-out the constructor offers (`_readout`);
+        other combinations raise instead of silently detaching."""
         if not (torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())):
             return False
         ok = self._hip_supported() and self.schedule == "lockstep" and self.emb_dim % 4 == 0
@@ -418,9 +418,43 @@ class DAGNN(HipModule):
             return None
         return {k: torch.mv(x.detach(), c.key_raw) for k, c in cells.items()}
 
+    def _pool_how(self) -> str:
+        """The pool the kernels run.  P_ATTN (dagnn.py:114-117) is a softmax over a size-1 dimension: weights of exactly 1,
+        i.e. add-pooling - and the exact derivative with respect to `self_attn_linear_out.{weight, bias}` is zero: a
+        training step through the HIP read-out leaves their `.grad` at None (`train.ClipAdam`, like `torch.optim.Adam`,
+        skips a parameter without a gradient)."""
+        return K.P_ADD if self.out_pool in (K.P_ATTN, K.P_SUM) else self.out_pool
+
+    def _max_over_outputs(self) -> bool:
+        """The read-out the reference trains (scripts/ogb_tok.sh): max over the output nodes of both directions."""
+        return bool(self.bidirectional and not self.output_all and self.out_pool == K.P_MAX)
+
+    def _readout_jobs(self, x, h):
+        """The column blocks of the pooled vector, left to right, as (matrix, (d, i) - None for `x` -, scope, column):
+        [d][x?, layer 0 .. L-1] over the output nodes of direction d (dagnn.py:184-193), or [x?, [d][layer 0 .. L-1]]
+        over all nodes / over the output nodes of direction 0 (dagnn.py:194-202) - there `x` appears once."""
+        L = self.num_layers
+        xs = [(x, None)] if self.out_wx else []
+        if self.bidirectional and not self.output_all:
+            blocks = [(d, xs + [(h[d][i], (d, i)) for i in range(L)]) for d in (0, 1)]
+        else:
+            blocks = [(2 if self.output_all else 0, xs + [(h[d][i], (d, i)) for d in self.dirs for i in range(L)])]
+        jobs, col = [], 0
+        for scope, ts in blocks:
+            for t, key in ts:
+                jobs.append((t, key, scope, col))
+                col += t.shape[1]
+        return jobs
+
     def _readout(self, plan, B, x, h):
-        """Max-pool over the output nodes of both directions (dagnn.py:184-193), columns [d][x?, layer 0.. L-1]."""
+        """The read-out of a training step, for every (bidirectional, out_pool_all, out_pool, out_wx): the pooled graph
+        vectors [B, out_hidden_dim] from the states in ONE launch (`_readout_jobs`; P_ATTN pools as add: `_pool_how`).
+        Max over the output nodes of both directions (dagnn.py:184-193) keeps its own kernel."""
         out = torch.empty(B, self.out_hidden_dim, dtype=torch.float32, device=x.device)
+        if not self._max_over_outputs():
+            how = self._pool_how()
+            engine.readout_pool_batch(plan, [(t, scope, how, col) for t, _, scope, col in self._readout_jobs(x, h)], out)
+            return out
         col, jobs = 0, []
         for d in (0, 1):
             for t in ([x] if self.out_wx else []) + [h[d][i] for i in range(self.num_layers)]:
@@ -434,6 +468,18 @@ class DAGNN(HipModule):
         return out
 
     def _readout_backward(self, plan, x, h, gout, g_ext, dx):
+        """`gout` [B, out_hidden_dim] straight into the reverse sweep's seeds `g_ext[d][i]` and into `dx`: no [N, H]
+        gradient tensors in between.  Jobs of one launch add into distinct buffers, so the second `x` block of the
+        bidirectional output-node read-out with `out_wx` goes in a launch of its own."""
+        if not self._max_over_outputs():
+            how = self._pool_how()
+            first, second = [], []
+            for t, key, scope, col in self._readout_jobs(x, h):
+                job = (t, scope, how, col, dx if key is None else g_ext[key[0]][key[1]])
+                (second if key is None and any(j[4] is dx for j in first) else first).append(job)
+            engine.readout_pool_backward_batch(plan, first, gout)
+            engine.readout_pool_backward_batch(plan, second, gout)
+            return
         col, jobs = 0, []
         for d in (0, 1):  # to the arg-max output node of every (graph, column)
             if self.out_wx:   # (both directions add into dx: one after the other, not in one launch)
@@ -443,6 +489,20 @@ class DAGNN(HipModule):
                 jobs.append((h[d][i], d, col, g_ext[d][i]))
                 col += self.hidden_dim
         engine.readout_max_backward_batch(plan, jobs, gout)   # one launch for all (direction, stacked layer) state buffers
+
+    def _state_side_effects(self, G, x, h):
+        """Side effect 4 (dagnn.py:141-142,182) and those of the read-out branch (dagnn.py:124-126,194-202) after a training
+        step whose read-out ran in HIP: `G.h` - and `G.batch` - as `_finish` leaves them, from the non-differentiable states.
+        Unidirectional without `out_pool_all` narrows both to the output nodes, which needs a row count: that one mask
+        index (a host synchronisation, as the evaluation path has it) stays; the pooling itself does not use it."""
+        L, dirs = self.num_layers, self.dirs
+        if self.bidirectional and not self.output_all:
+            G.h = [[h[d][i] for i in range(L)] for d in dirs]
+            return
+        G.h = torch.cat(([x.detach()] if self.out_wx else []) + [h[d][i] for d in dirs for i in range(L)], dim=-1)
+        if not self.output_all:
+            idx = G.bi_layer_index[1][1][G.bi_layer_index[1][0] == 0]  # dagnn.py:124-126
+            G.h, G.batch = G.h[idx], G.batch[idx]
 
     def _pool(self, h, batch, B):
         """`global_{max,mean,add}_pool` / P_ATTN read-outs on torch (variants outside BASELINE)."""
@@ -610,7 +670,7 @@ class DAGNN(HipModule):
                     plan = self._plan_of(G, B)
                     flat_params = [p for d in self.dirs for i in range(L) for _, p in variants._cell_params(self, d, i)]
                     flat = variants.VariantRecurrence.apply(self, G, plan, G.x, *flat_params)
-                    return self._finish(G, None, G.x, self._unflatten(flat), B, head)
+                    return self._finish(G, plan, G.x, self._unflatten(flat), B, head)   # (the plan: HIP read-out, `PoolNodes`)
                 if self.variant_backend != "torch":   # (an explicit 'torch' backend is a choice, not a cliff)
                     variants.warn_torch_path(self, G)
                 return self._finish(G, None, G.x, variants.run(self, G, G.x), B, head)   # training: differentiable torch ops
@@ -639,17 +699,14 @@ class DAGNN(HipModule):
         x_idx, depth = G.x, G.node_depth.view(-1, )
         G.x = self.encoder(x_idx, depth)
         x = G.x
-        fused_readout = self.bidirectional and not self.output_all and self.out_pool == K.P_MAX
         if train:
-            # differentiable call: HIP read-out + its backward for the configuration the reference trains
-            # (scripts/ogb_tok.sh), otherwise differentiable states and the torch read-outs below
+            # differentiable call: the read-out and its backward in HIP for every (bidirectional, out_pool_all, out_pool,
+            # out_wx) (`_readout` / `_readout_backward`: hooks of autograd.Recurrence); the states come back non-differentiable
             from .autograd import Recurrence
-            res = Recurrence.apply(self, plan, B, fused_readout, x, *self._train_params())
-            h = self._unflatten(res[1:] if fused_readout else res)
-            if fused_readout:
-                G.h = [[h[d][i] for i in range(L)] for d in dirs]
-                return head(self.dropout(res[0]))
-            return self._finish(G, plan, x, h, B, head)
+            res = Recurrence.apply(self, plan, B, True, x, *self._train_params())
+            self._state_side_effects(G, x, self._unflatten(res[1:]))
+            self.__dict__["readout_hip_passes"] = self.__dict__.get("readout_hip_passes", 0) + 1   # (tests assert the path a pass took)
+            return head(self.dropout(res[0]))
         cells = self._cells()
         sscore = self._static_scores(x, cells)
         h = run_stack(plan, x, cells, dirs, L, H, schedule=self.schedule, static_score=sscore,
@@ -723,15 +780,24 @@ class DAGNN(HipModule):
         return tok, top
 
     def _finish(self, G, plan, x, h, B, head=None):
-        """Read-out + `head` (default `_heads`: dagnn.py:184-215) on the states h[d][i]."""
+        """Read-out + `head` (default `_heads`: dagnn.py:184-215) on the states h[d][i]: of an evaluation pass, and of the
+        constructor-string variants' training passes (the additive-attention path trains through `_readout`).  With a plan the
+        pooling is HIP - `autograd.PoolNodes` where a gradient is wanted -, without one (`variant_backend = "torch"`, the
+        variants' torch fall-back) torch ops."""
         L, dirs = self.num_layers, self.dirs
         G.h = [[h[d][i] for i in range(L)] for d in dirs]  # side effect 4 (dagnn.py:141-142,182)
 
         differentiable = torch.is_grad_enabled() and (x.requires_grad or any(h[d][i].requires_grad
                                                                              for d in dirs for i in range(L)))
         hip_pool = plan is not None and not differentiable
-        # P_ATTN (dagnn.py:114-117) is a softmax over a size-1 dimension: weights of exactly 1, i.e. add-pooling
-        how = K.P_ADD if self.out_pool in (K.P_ATTN, K.P_SUM) else self.out_pool
+        # a differentiable read-out of ordinary autograd tensors (the constructor-string variants' HIP training branch): HIP
+        # pool and HIP backward as one autograd node per matrix (`autograd.PoolNodes`) - no mask index, no scatter
+        node_pool = plan is not None and differentiable and all(
+            t.is_cuda and t.dtype == torch.float32 for t in [x] + [h[d][i] for d in dirs for i in range(L)])
+        if node_pool:
+            from .autograd import PoolNodes
+            self.__dict__["readout_hip_passes"] = self.__dict__.get("readout_hip_passes", 0) + 1   # (tests assert the path a pass took)
+        how = self._pool_how()   # (P_ATTN pools as add)
         if self.bidirectional and not self.output_all:
             if hip_pool and how == K.P_MAX:
                 out = self._readout(plan, B, x, h)   # HIP max-pool over the output nodes
@@ -742,6 +808,9 @@ class DAGNN(HipModule):
                     for t in ([x] if self.out_wx else []) + [h[d][i] for i in range(L)]:
                         engine.readout_pool(plan, t, d, how, out, col)
                         col += t.shape[1]
+            elif node_pool:
+                out = torch.cat([PoolNodes.apply(plan, t, d, how) for d in (0, 1)
+                                 for t in ([x] if self.out_wx else []) + [h[d][i] for i in range(L)]], dim=-1)
             else:
                 outs = []
                 for d in (0, 1):
@@ -754,10 +823,12 @@ class DAGNN(HipModule):
             if hip_pool:   # over all nodes, or over the output nodes of direction 0 (dagnn.py:124-126,194-202)
                 out = torch.empty(B, G.h.shape[1], dtype=torch.float32, device=x.device)
                 engine.readout_pool(plan, G.h, 2 if self.output_all else 0, how, out, 0)
+            elif node_pool:
+                out = PoolNodes.apply(plan, G.h, 2 if self.output_all else 0, how)
             if not self.output_all:
                 idx = G.bi_layer_index[1][1][G.bi_layer_index[1][0] == 0]  # dagnn.py:124-126
                 G.h, G.batch = G.h[idx], G.batch[idx]
-            if not hip_pool:
+            if not (hip_pool or node_pool):
                 out = self._pool(G.h, G.batch, B)
 
         return (head or self._heads)(self.dropout(out))

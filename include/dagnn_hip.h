@@ -746,6 +746,31 @@ typedef struct dagnn_readout_bwd_job {
 int dagnn_readout_max_backward_batch(const dagnn_plan* plan /* host */, const dagnn_readout_bwd_job* jobs /* host */, int n,
                                      const float* grad_out, int ld_out, void* stream);
 
+/* The generic read-out (dagnn_readout_pool) for several matrices in ONE launch, grid (graph, job), and its backward: the
+ * read-out of a TRAINING step for every (bidirectional, out_pool_all, out_pool, out_wx).  jobs: host arrays,
+ * n <= DAGNN_MAX_READOUT_JOBS (n == 0: nothing to do, returns 0).
+ *   forward:  job by job the bits of dagnn_readout_pool (the same nodes in the same order, the same mean factor).
+ *   backward: grad_h[v, j] += grad_out[g, col_off + j] for every node v of graph g in scope (ADD); the same addend times
+ *             the forward's factor 1.f / (float)max(count, 1), rounded once and applied with one multiply (MEAN); the
+ *             addend at the FIRST node in visiting order that attains the maximum of column j (MAX: scope 0 / 1 visit the
+ *             plan's output-node range as dagnn_readout_max_backward does, scope 2 visits ascending node ids).  h is read
+ *             for DAGNN_POOL_MAX only and may be NULL otherwise.  grad_h is initialised by the caller; a graph with
+ *             nothing in scope writes nothing.  Jobs of one launch have distinct grad_h (equal pointers: DAGNN_EINVAL).
+ * One thread owns a (graph, column) pair and every node belongs to one graph: no atomics, two runs agree bit for bit. */
+typedef struct dagnn_pool_job {
+    const float* h;      /* [N, ld_h] */
+    int32_t ld_h, width, scope, mode, col_off;
+} dagnn_pool_job;
+typedef struct dagnn_pool_bwd_job {
+    const float* h;      /* [N, ld_h]; DAGNN_POOL_MAX only */
+    float* grad_h;       /* [N, ld_g] */
+    int32_t ld_h, ld_g, width, scope, mode, col_off;
+} dagnn_pool_bwd_job;
+int dagnn_readout_pool_batch(const dagnn_plan* plan /* host */, const dagnn_pool_job* jobs /* host */, int n, float* out,
+                             int ld_out, void* stream);
+int dagnn_readout_pool_backward_batch(const dagnn_plan* plan /* host */, const dagnn_pool_bwd_job* jobs /* host */, int n,
+                                      const float* grad_out, int ld_out, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Constructor-string variants of the same loop (no BASELINE configuration selects
  * them): the aggregators `MultAttnConv` (dagnn.py:379-409), `GatedSumConv` (:254-276), `AggConv` add / max
