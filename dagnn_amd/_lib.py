@@ -24,10 +24,6 @@ class DagnnHipError(RuntimeError):
     pass
 
 
-class ReadoutJob(C.Structure):
-    _fields_ = [("h", C.c_void_p), ("ld_h", C.c_int), ("width", C.c_int), ("dir", C.c_int), ("col_off", C.c_int)]
-
-
 class OptTensor(C.Structure):
     _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p), ("numel", C.c_int64)]
 
@@ -35,11 +31,6 @@ class OptTensor(C.Structure):
 class DfPackJob(C.Structure):
     _fields_ = [("w", C.c_void_p), ("out", C.c_void_p), ("aux", C.c_void_p), ("transposed", C.c_int32), ("rows", C.c_int32),
                 ("cols", C.c_int32)]
-
-
-class ReadoutBwdJob(C.Structure):
-    _fields_ = [("h", C.c_void_p), ("grad_h", C.c_void_p), ("ld_h", C.c_int32), ("ld_g", C.c_int32), ("width", C.c_int32),
-                ("dir", C.c_int32), ("col_off", C.c_int32)]
 
 
 class PoolJob(C.Structure):   # dagnn_pool_job
@@ -399,11 +390,6 @@ SYMBOLS = {
     "dagnn_pack_dataflow": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "dagnn_pack_dataflow_transposed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "dagnn_score_parts": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
-    "dagnn_readout_max": (C.c_int, [C.POINTER(Plan), C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
-                                    C.c_int, C.c_void_p]),
-    "dagnn_readout_max_batch": (C.c_int, [C.POINTER(Plan), C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
-    "dagnn_readout_pool": (C.c_int, [C.POINTER(Plan), C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
-                                     C.c_int, C.c_int, C.c_void_p]),
     "dagnn_backward_prepare": (C.c_int, [C.POINTER(Plan), C.POINTER(BackwardArgs), C.c_void_p]),
     "dagnn_backward_run": (C.c_int, [C.POINTER(Plan), C.POINTER(BackwardArgs), C.POINTER(C.POINTER(C.c_int32)),
                                      C.POINTER(C.c_int32), C.c_void_p]),
@@ -421,12 +407,8 @@ SYMBOLS = {
                                   C.c_size_t, C.c_void_p]),
     "dagnn_table_grads_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.POINTER(C.c_int64), C.c_int]),
     "dagnn_table_grads": (C.c_int, [C.POINTER(TableGradsArgs), C.c_void_p]),
-    "dagnn_readout_max_backward": (C.c_int, [C.POINTER(Plan), C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
-                                             C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "dagnn_pack_dataflow_batch": (C.c_int, [C.POINTER(DfPackJob), C.c_int, C.c_int, C.c_void_p]),
     "dagnn_attn_grads_run": (C.c_int, [C.POINTER(AttnGradJob), C.c_int, C.c_void_p]),
-    "dagnn_readout_max_backward_batch": (C.c_int, [C.POINTER(Plan), C.POINTER(ReadoutBwdJob), C.c_int, C.c_void_p, C.c_int,
-                                                   C.c_void_p]),
     "dagnn_readout_pool_batch": (C.c_int, [C.POINTER(Plan), C.POINTER(PoolJob), C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "dagnn_readout_pool_backward_batch": (C.c_int, [C.POINTER(Plan), C.POINTER(PoolBwdJob), C.c_int, C.c_void_p, C.c_int,
                                                     C.c_void_p]),

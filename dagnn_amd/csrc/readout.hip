@@ -1,6 +1,6 @@
-// readout.hip - the generic read-out (dagnn.py:194-202: max / add / mean over the output nodes of a direction or over all
-// nodes of a graph) for several matrices in ONE launch, and its backward: what a TRAINING step needs of every
-// (bidirectional, out_pool_all, out_pool, out_wx).  Grid (graph, job) as `readout_max_batch_kernel`; a thread owns a
+// readout.hip - the read-out (dagnn.py:119-126,184-202: max / add / mean over the output nodes of a direction or over
+// all nodes of a graph) for several matrices in ONE launch, and its backward: all the read-out code there is, for every
+// (bidirectional, out_pool_all, out_pool, out_wx), training and evaluation.  Grid (graph, job); a thread owns a
 // (graph, column) pair and every node belongs to one graph, so nothing here is atomic and two runs agree bit for bit.
 #include "common.h"
 
@@ -26,7 +26,8 @@ __device__ inline void scope_range(const int32_t* __restrict__ plan, const PlanL
     }
 }
 
-// Job by job the bits of `readout_pool_kernel` (csrc/misc.hip): the same nodes in the same order, the same `inv`.
+// out[g, col_off + j] = the pool of h[v, j] over the nodes v in scope, visited in range order; `inv` is exactly 1 for max
+// and add, and multiplying by it changes no float.
 __global__ void __launch_bounds__(256) readout_pool_batch_kernel(const int32_t* __restrict__ plan, PlanLayout L, PoolJobs J,
                                                                   float* __restrict__ out, int ld_out) {
     const dagnn_pool_job& K = J.j[blockIdx.y];
@@ -49,8 +50,8 @@ __global__ void __launch_bounds__(256) readout_pool_batch_kernel(const int32_t* 
 }
 
 // grad_h[v, j] += the share of grad_out[g, col_off + j] node v has in the pool (ADD: all of it; MEAN: it times the
-// forward's own factor, rounded once; MAX: all of it at the first node in visiting order that attains the maximum, as
-// `readout_max_bwd_batch_kernel` decides).  A graph with nothing in scope writes nothing.
+// forward's own factor, rounded once; MAX: all of it at the first node in visiting order that attains the maximum: a
+// later node wins only if strictly greater, scatter-max's single winner).  A graph with nothing in scope writes nothing.
 __global__ void __launch_bounds__(256) readout_pool_bwd_batch_kernel(const int32_t* __restrict__ plan, PlanLayout L, PoolBwdJobs J,
                                                                       const float* __restrict__ gout, int ld_out) {
     const dagnn_pool_bwd_job& K = J.j[blockIdx.y];

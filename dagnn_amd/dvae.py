@@ -843,7 +843,7 @@ class _DvaeDagnn(_DvaeBase):
 
     def _pool_all(self, G, plan, x, flat, B):
         """Pool over ALL nodes (dvae/dagnn.py:163-172) of the flat states: per-node projection, then HIP pooling over the
-        nodes of every graph (`plan` given: `dagnn_readout_pool`, or `autograd.PoolNodes` where a gradient is wanted - every
+        nodes of every graph (`plan` given: `dagnn_readout_pool_batch`, or `autograd.PoolNodes` where a gradient is wanted - every
         graph has `num_nodes` nodes, so the kernel's mean factor is the reference's) or torch pooling."""
         G.h = torch.cat(([x] if self.out_wx else []) + list(flat), dim=-1)
         if self.bidirectional:
@@ -852,7 +852,7 @@ class _DvaeDagnn(_DvaeBase):
             G.h = self.out_linear(G.h)
         if plan is not None and not (torch.is_grad_enabled() and G.h.requires_grad):
             out = torch.empty(B, G.h.shape[1], dtype=torch.float32, device=G.h.device)
-            engine.readout_pool(plan, G.h, 2, self.out_pool, out, 0)
+            engine.readout_pool_batch(plan, [(G.h, 2, self.out_pool, 0)], out)
             return out
         if plan is not None and G.h.is_cuda and G.h.dtype == torch.float32:
             from .autograd import PoolNodes

@@ -1115,65 +1115,13 @@ def recurrence_layer(plan: PlanHandle, dirs: Sequence[int], H: int, gi, w_hh_t, 
     return h
 
 
-def readout_max(plan: PlanHandle, h: torch.Tensor, direction: int, out: torch.Tensor, col_off: int) -> None:
-    h = _rows(h, "h")
-    check(_lib.load().dagnn_readout_max(C.byref(plan.desc), h.data_ptr(), h.stride(0), h.shape[1], direction,
-                                        out.data_ptr(), out.shape[1], col_off, _stream(h)), "dagnn_readout_max")
-
-
-def readout_max_batch(plan: PlanHandle, jobs, out: torch.Tensor) -> None:
-    """`readout_max` for several (h, direction, col_off) in one launch."""
-    arr = (_lib.ReadoutJob * len(jobs))()
-    keep = []
-    for k, (h, direction, col_off) in enumerate(jobs):
-        h = _rows(h, "h")
-        keep.append(h)
-        arr[k].h, arr[k].ld_h, arr[k].width, arr[k].dir, arr[k].col_off = h.data_ptr(), h.stride(0), h.shape[1], int(direction), int(col_off)
-    check(_lib.load().dagnn_readout_max_batch(C.byref(plan.desc), arr, len(jobs), out.data_ptr(), out.shape[1], _stream(out)),
-          "dagnn_readout_max_batch")
-
-
-def readout_pool(plan: PlanHandle, h: torch.Tensor, scope: int, how: str, out: torch.Tensor, col_off: int) -> None:
-    """out[:, col_off : col_off + width] = max / add / mean pool of h over scope 0 / 1 (output nodes of that direction)
-    or 2 (all nodes of the graph)."""
-    h = _rows(h, "hidden states")
-    mode = {"max": _lib.POOL_MAX, "add": _lib.POOL_ADD, "sum": _lib.POOL_ADD, "mean": _lib.POOL_MEAN}[how]
-    check(_lib.load().dagnn_readout_pool(C.byref(plan.desc), h.data_ptr(), h.stride(0), h.shape[1], int(scope), mode,
-                                         out.data_ptr(), out.stride(0), int(col_off), _stream(h)), "dagnn_readout_pool")
-
-
-def readout_max_backward(plan: PlanHandle, h: torch.Tensor, direction: int, grad_out: torch.Tensor, col_off: int,
-                         grad_h: torch.Tensor) -> None:
-    """grad_h[v, :] += grad_out[g, col_off : col_off + width] at the arg-max output node of every graph/column."""
-    h = _rows(h, "h")
-    grad_out = _dev(grad_out, "grad_out", torch.float32)
-    check(_lib.load().dagnn_readout_max_backward(C.byref(plan.desc), h.data_ptr(), h.stride(0), h.shape[1], direction,
-                                                 grad_out.data_ptr(), grad_out.shape[1], col_off, grad_h.data_ptr(),
-                                                 grad_h.stride(0), _stream(h)), "dagnn_readout_max_backward")
-
-
-def readout_max_backward_batch(plan: PlanHandle, jobs, grad_out: torch.Tensor) -> None:
-    """`readout_max_backward` for several (h, direction, col_off, grad_h) jobs in ONE launch (distinct `grad_h` each)."""
-    if not jobs:
-        return
-    grad_out = _dev(grad_out, "grad_out", torch.float32)
-    lib = _lib.load()
-    for k0 in range(0, len(jobs), _lib.MAX_READOUT_JOBS):
-        part = jobs[k0:k0 + _lib.MAX_READOUT_JOBS]
-        arr = (_lib.ReadoutBwdJob * len(part))()
-        for q, (h, d, col, gh) in enumerate(part):
-            h = _rows(h, "h")
-            arr[q] = _lib.ReadoutBwdJob(h.data_ptr(), gh.data_ptr(), h.stride(0), gh.stride(0), h.shape[1], int(d), int(col))
-        check(lib.dagnn_readout_max_backward_batch(C.byref(plan.desc), arr, len(part), grad_out.data_ptr(), grad_out.shape[1],
-                                                   _stream(grad_out)), "dagnn_readout_max_backward_batch")
-
-
 _POOL_MODES = {"max": _lib.POOL_MAX, "add": _lib.POOL_ADD, "sum": _lib.POOL_ADD, "mean": _lib.POOL_MEAN}
 
 
 def readout_pool_batch(plan: PlanHandle, jobs, out: torch.Tensor) -> None:
-    """`readout_pool` for several (h, scope, how, col_off) jobs in ONE launch (`dagnn_readout_pool_batch`): job by job the
-    same bits.  Longer job lists go in chunks of `MAX_READOUT_JOBS`."""
+    """(h, scope, how, col_off) jobs in ONE launch (`dagnn_readout_pool_batch`): out[:, col_off : col_off + width] = max /
+    add / mean pool of h over scope 0 / 1 (output nodes of that direction) or 2 (all nodes of the graph).  Longer job
+    lists go in chunks of `MAX_READOUT_JOBS`."""
     if not jobs:
         return
     lib = _lib.load()

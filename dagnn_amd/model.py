@@ -425,10 +425,6 @@ class DAGNN(HipModule):
         skips a parameter without a gradient)."""
         return K.P_ADD if self.out_pool in (K.P_ATTN, K.P_SUM) else self.out_pool
 
-    def _max_over_outputs(self) -> bool:
-        """The read-out the reference trains (scripts/ogb_tok.sh): max over the output nodes of both directions."""
-        return bool(self.bidirectional and not self.output_all and self.out_pool == K.P_MAX)
-
     def _readout_jobs(self, x, h):
         """The column blocks of the pooled vector, left to right, as (matrix, (d, i) - None for `x` -, scope, column):
         [d][x?, layer 0 .. L-1] over the output nodes of direction d (dagnn.py:184-193), or [x?, [d][layer 0 .. L-1]]
@@ -447,48 +443,26 @@ class DAGNN(HipModule):
         return jobs
 
     def _readout(self, plan, B, x, h):
-        """The read-out of a training step, for every (bidirectional, out_pool_all, out_pool, out_wx): the pooled graph
-        vectors [B, out_hidden_dim] from the states in ONE launch (`_readout_jobs`; P_ATTN pools as add: `_pool_how`).
-        Max over the output nodes of both directions (dagnn.py:184-193) keeps its own kernel."""
-        out = torch.empty(B, self.out_hidden_dim, dtype=torch.float32, device=x.device)
-        if not self._max_over_outputs():
-            how = self._pool_how()
-            engine.readout_pool_batch(plan, [(t, scope, how, col) for t, _, scope, col in self._readout_jobs(x, h)], out)
-            return out
-        col, jobs = 0, []
-        for d in (0, 1):
-            for t in ([x] if self.out_wx else []) + [h[d][i] for i in range(self.num_layers)]:
-                jobs.append((t, d, col))
-                col += t.shape[1]
-        if len(jobs) <= 16:
-            engine.readout_max_batch(plan, jobs, out)   # one launch for all (direction, stacked layer) columns
-        else:
-            for t, d, c in jobs:
-                engine.readout_max(plan, t, d, out, c)
+        """The read-out, for every (bidirectional, out_pool_all, out_pool, out_wx): the pooled graph vectors
+        [B, out_hidden_dim] from the states in ONE launch (`_readout_jobs`; P_ATTN pools as add: `_pool_how`)."""
+        how = self._pool_how()
+        jobs = [(t, scope, how, col) for t, _, scope, col in self._readout_jobs(x, h)]
+        out = torch.empty(B, jobs[-1][3] + jobs[-1][0].shape[1], dtype=torch.float32, device=x.device)   # (the blocks tile it)
+        engine.readout_pool_batch(plan, jobs, out)
         return out
 
     def _readout_backward(self, plan, x, h, gout, g_ext, dx):
         """`gout` [B, out_hidden_dim] straight into the reverse sweep's seeds `g_ext[d][i]` and into `dx`: no [N, H]
         gradient tensors in between.  Jobs of one launch add into distinct buffers, so the second `x` block of the
-        bidirectional output-node read-out with `out_wx` goes in a launch of its own."""
-        if not self._max_over_outputs():
-            how = self._pool_how()
-            first, second = [], []
-            for t, key, scope, col in self._readout_jobs(x, h):
-                job = (t, scope, how, col, dx if key is None else g_ext[key[0]][key[1]])
-                (second if key is None and any(j[4] is dx for j in first) else first).append(job)
-            engine.readout_pool_backward_batch(plan, first, gout)
-            engine.readout_pool_backward_batch(plan, second, gout)
-            return
-        col, jobs = 0, []
-        for d in (0, 1):  # to the arg-max output node of every (graph, column)
-            if self.out_wx:   # (both directions add into dx: one after the other, not in one launch)
-                engine.readout_max_backward(plan, x, d, gout, col, dx)
-                col += x.shape[1]
-            for i in range(self.num_layers):
-                jobs.append((h[d][i], d, col, g_ext[d][i]))
-                col += self.hidden_dim
-        engine.readout_max_backward_batch(plan, jobs, gout)   # one launch for all (direction, stacked layer) state buffers
+        bidirectional output-node read-out with `out_wx` goes in a launch of its own: `dx` takes direction 0's share in
+        the first launch and direction 1's in the second, always in that order, which fixes its bits."""
+        how = self._pool_how()
+        first, second = [], []
+        for t, key, scope, col in self._readout_jobs(x, h):
+            job = (t, scope, how, col, dx if key is None else g_ext[key[0]][key[1]])
+            (second if key is None and any(j[4] is dx for j in first) else first).append(job)
+        engine.readout_pool_backward_batch(plan, first, gout)
+        engine.readout_pool_backward_batch(plan, second, gout)
 
     def _state_side_effects(self, G, x, h):
         """Side effect 4 (dagnn.py:141-142,182) and those of the read-out branch (dagnn.py:124-126,194-202) after a training
@@ -799,15 +773,8 @@ class DAGNN(HipModule):
             self.__dict__["readout_hip_passes"] = self.__dict__.get("readout_hip_passes", 0) + 1   # (tests assert the path a pass took)
         how = self._pool_how()   # (P_ATTN pools as add)
         if self.bidirectional and not self.output_all:
-            if hip_pool and how == K.P_MAX:
-                out = self._readout(plan, B, x, h)   # HIP max-pool over the output nodes
-            elif hip_pool:
-                out = torch.empty(B, self.out_hidden_dim, dtype=torch.float32, device=x.device)
-                col = 0
-                for d in (0, 1):
-                    for t in ([x] if self.out_wx else []) + [h[d][i] for i in range(L)]:
-                        engine.readout_pool(plan, t, d, how, out, col)
-                        col += t.shape[1]
+            if hip_pool:
+                out = self._readout(plan, B, x, h)   # one launch for all (direction, stacked layer) columns
             elif node_pool:
                 out = torch.cat([PoolNodes.apply(plan, t, d, how) for d in (0, 1)
                                  for t in ([x] if self.out_wx else []) + [h[d][i] for i in range(L)]], dim=-1)
@@ -821,8 +788,7 @@ class DAGNN(HipModule):
         else:
             G.h = torch.cat(([x] if self.out_wx else []) + [h[d][i] for d in dirs for i in range(L)], dim=-1)
             if hip_pool:   # over all nodes, or over the output nodes of direction 0 (dagnn.py:124-126,194-202)
-                out = torch.empty(B, G.h.shape[1], dtype=torch.float32, device=x.device)
-                engine.readout_pool(plan, G.h, 2 if self.output_all else 0, how, out, 0)
+                out = self._readout(plan, B, x, h)
             elif node_pool:
                 out = PoolNodes.apply(plan, G.h, 2 if self.output_all else 0, how)
             if not self.output_all:

@@ -468,33 +468,6 @@ int dagnn_tiles_launches(int num_cus, int num_dirs, int num_stacked, int H, int 
 int dagnn_tiles_run(const dagnn_plan* plan /* host */, const dagnn_tiles_args* args /* host */, void* stream);
 
 /* ------------------------------------------------------------------------------------------
- * Read-out over output nodes (dagnn.py:119-126,184-193 with out_pool='max', out_pool_all=0):
- *   out[g, col_off[d] + j] = max over { v in graph g : layer_{1-d}(v) == 0 } of h[d][v, j]
- * d = 0 pools the sinks, d = 1 the sources.  h[d] is [N,ld_h]; `width` columns are pooled
- * (pass a [N, L*H] concatenation or call once per layer with a column offset).
- * ---------------------------------------------------------------------------------------- */
-int dagnn_readout_max(const dagnn_plan* plan /* host */, const float* h, int ld_h, int width, int dir,
-                      float* out, int ld_out, int col_off, void* stream);
-
-/* The same for several state buffers in ONE launch (the bidirectional L-layer read-out of dagnn.py:184-193 is 2 L calls
- * of the above: launch-bound).  jobs: host array, n <= 16. */
-typedef struct dagnn_readout_job {
-    const float* h;   /* [N, ld_h] */
-    int ld_h, width, dir, col_off;
-} dagnn_readout_job;
-int dagnn_readout_max_batch(const dagnn_plan* plan /* host */, const dagnn_readout_job* jobs /* host */, int n,
-                            float* out, int ld_out, void* stream);
-
-/* The other read-outs of dagnn.py:194-202 (`global_max_pool` / `global_mean_pool` / `global_add_pool`; `P_ATTN`,
- * dagnn.py:114-117, is a softmax over a size-1 dimension and therefore add-pooling): pool `width` columns of
- * h [N,ld_h] per graph over scope 0 / 1 = the output nodes of direction 0 / 1 (as dagnn_readout_max) or scope 2 = all
- * nodes of the graph (`out_pool_all=1`).  Nodes are visited in id order (a fixed summation order); a graph without
- * nodes in scope reads 0, the mean divides by max(count, 1). */
-enum { DAGNN_POOL_MAX = 0, DAGNN_POOL_ADD = 1, DAGNN_POOL_MEAN = 2 };
-int dagnn_readout_pool(const dagnn_plan* plan /* host */, const float* h, int ld_h, int width, int scope, int mode,
-                       float* out, int ld_out, int col_off, void* stream);
-
-/* ------------------------------------------------------------------------------------------
  * Backward pass of the recurrence (training: what `loss.backward()`, ogbg-code/main_pyg.py:62, does to
  * dagnn.py:144-182).  Additive attention with keys from the hidden states (`attn_h`), GRU cells.
  * The forward pass keeps only the lock-step state buffers h[d][i] ([N,ld_h], scores behind the rows).
@@ -502,7 +475,7 @@ int dagnn_readout_pool(const dagnn_plan* plan /* host */, const float* h, int ld
  *   1. dagnn_backward_prepare: a[c] [N,H] (attention aggregates) and alpha[c] [E] (attention weights,
  *      indexed by ORIGINAL edge id) of every cell, one parallel launch;
  *   2. caller: gh[c] = a[c] W_hh^T + b_hh and gi[c] = u W_ih^T + b_ih (dagnn_gemm_nt_bias), g_ext[c] [N,H]
- *      = gradient reaching h[c] from outside the recurrence (read-out; dagnn_readout_max_backward);
+ *      = gradient reaching h[c] from outside the recurrence (read-out; dagnn_readout_pool_backward_batch);
  *   3. dagnn_backward_run: T + L - 1 reverse lock-step launches.  Adds W_ih^T dgi of stacked layer i into
  *      g_ext of layer i-1 and writes, per cell: da [N,H], dgi, dgh [N,3H] (gradients of the GRU
  *      pre-activations, gate blocks r,z,n), sigma [N] (sum over a node's out-edges of the attention-logit
@@ -731,32 +704,30 @@ typedef struct dagnn_attn_grad_job {
 } dagnn_attn_grad_job;
 int dagnn_attn_grads_run(const dagnn_attn_grad_job* jobs /* host */, int njob, void* stream);
 
-/* grad_h[v, j] += grad_out[g, col_off + j] for the first output node v of graph g attaining the maximum
- * of column j (the single winner of scatter-max); grad_h must be initialised by the caller. */
-int dagnn_readout_max_backward(const dagnn_plan* plan /* host */, const float* h, int ld_h, int width, int dir,
-                               const float* grad_out, int ld_out, int col_off, float* grad_h, int ld_g, void* stream);
-
-/* ... for several state buffers in one launch (distinct grad_h per job) */
-#define DAGNN_MAX_READOUT_JOBS 24
-typedef struct dagnn_readout_bwd_job {
-    const float* h;      /* [N, ld_h] */
-    float* grad_h;       /* [N, ld_g] */
-    int32_t ld_h, ld_g, width, dir, col_off;
-} dagnn_readout_bwd_job;
-int dagnn_readout_max_backward_batch(const dagnn_plan* plan /* host */, const dagnn_readout_bwd_job* jobs /* host */, int n,
-                                     const float* grad_out, int ld_out, void* stream);
-
-/* The generic read-out (dagnn_readout_pool) for several matrices in ONE launch, grid (graph, job), and its backward: the
- * read-out of a TRAINING step for every (bidirectional, out_pool_all, out_pool, out_wx).  jobs: host arrays,
- * n <= DAGNN_MAX_READOUT_JOBS (n == 0: nothing to do, returns 0).
- *   forward:  job by job the bits of dagnn_readout_pool (the same nodes in the same order, the same mean factor).
+/* ------------------------------------------------------------------------------------------
+ * Read-out (dagnn.py:119-126,184-202: `global_max_pool` / `global_add_pool` / `global_mean_pool`; `P_ATTN`,
+ * dagnn.py:114-117, is a softmax over a size-1 dimension and therefore add-pooling) and its backward, for several
+ * matrices in ONE launch, grid (graph, job).  jobs: host arrays, n <= DAGNN_MAX_READOUT_JOBS (n == 0: nothing to do,
+ * returns 0).  A job pools `width` columns of h [N,ld_h] per graph g into out[g, col_off .. col_off + width).
+ *   scope:    0 / 1 = the output nodes of direction 0 / 1 (0: the sinks, 1: the sources): the layer-0 frontier of the
+ *             OPPOSITE direction, { v in g : layer_{1-scope}(v) == 0 }, which the plan holds as a contiguous range of
+ *             order[1 - scope];  2 = every node of the graph (`out_pool_all=1`).
+ *   order:    scope 0 / 1 visit that range of order[1 - scope] front to back, scope 2 visits ascending node ids.  Sums
+ *             are taken in this order, one fp32 addition per node from 0.f (the first node's value, but for -0); the
+ *             maximum starts from the first node's value.
+ *   empty:    a graph with nothing in scope reads 0 in the forward; the backward writes nothing for it.
+ *   forward:  MAX: the maximum (fmaxf) in visiting order; ADD: the sum; MEAN: the sum times 1.f / (float)count, i.e.
+ *             two roundings after the sum: one of the reciprocal, one of the product.
  *   backward: grad_h[v, j] += grad_out[g, col_off + j] for every node v of graph g in scope (ADD); the same addend times
- *             the forward's factor 1.f / (float)max(count, 1), rounded once and applied with one multiply (MEAN); the
- *             addend at the FIRST node in visiting order that attains the maximum of column j (MAX: scope 0 / 1 visit the
- *             plan's output-node range as dagnn_readout_max_backward does, scope 2 visits ascending node ids).  h is read
- *             for DAGNN_POOL_MAX only and may be NULL otherwise.  grad_h is initialised by the caller; a graph with
- *             nothing in scope writes nothing.  Jobs of one launch have distinct grad_h (equal pointers: DAGNN_EINVAL).
- * One thread owns a (graph, column) pair and every node belongs to one graph: no atomics, two runs agree bit for bit. */
+ *             the forward's factor 1.f / (float)count, rounded once and applied with one multiply of its own (MEAN); the
+ *             addend at the FIRST node in visiting order that attains the maximum of column j (MAX: a later node wins
+ *             only if strictly greater, the single winner of scatter-max).  h is read for DAGNN_POOL_MAX only and may
+ *             be NULL otherwise.  grad_h is initialised by the caller.  Jobs of one launch have distinct grad_h (equal
+ *             pointers: DAGNN_EINVAL).
+ * One thread owns a (graph, column) pair and every node belongs to one graph: no atomics, two runs agree bit for bit.
+ * ---------------------------------------------------------------------------------------- */
+#define DAGNN_MAX_READOUT_JOBS 24
+enum { DAGNN_POOL_MAX = 0, DAGNN_POOL_ADD = 1, DAGNN_POOL_MEAN = 2 };
 typedef struct dagnn_pool_job {
     const float* h;      /* [N, ld_h] */
     int32_t ld_h, width, scope, mode, col_off;

@@ -45,14 +45,15 @@ def test_host_only_entry_points_without_gpu():
     assert lib.dagnn_pack_whh(None, None, 8, None) == -22
     assert lib.dagnn_encode_ast(None, None, None, None, None, 20, None, 6, 5, 6, None) == -22  # H % 4 != 0
     assert lib.dagnn_gather_rows(None, 4, 4, 1, 8, 9, None, 4, 0, None) == -22
-    assert lib.dagnn_readout_pool(None, None, 4, 4, 0, 0, None, 4, 0, None) == -22
     assert lib.dagnn_pack_batch(None, 1, None) == -22
-    assert lib.dagnn_readout_max_batch(None, None, 1, None, 4, None) == -22
-    rj = (_lib.ReadoutJob * 1)()
-    rj[0].h, rj[0].ld_h, rj[0].width, rj[0].dir, rj[0].col_off = 64, 4, 8, 0, 0   # pitch < width
+    assert lib.dagnn_readout_pool_batch(None, None, 1, None, 4, None) == -22   # null plan
+    rj = (_lib.PoolJob * 25)()
+    for q in rj:
+        q.h, q.ld_h, q.width, q.scope, q.mode, q.col_off = 64, 8, 8, 0, _lib.POOL_MAX, 0
+    rj[0].ld_h = 4   # pitch < width
     plan0 = _lib.Plan(64, 0, 4, 3, 1, 0)
-    assert lib.dagnn_readout_max_batch(ctypes.byref(plan0), rj, 1, 64, 8, None) == -22
-    assert lib.dagnn_readout_max_batch(ctypes.byref(plan0), rj, 17, 64, 8, None) == -22 and lib.dagnn_readout_max_batch(ctypes.byref(plan0), rj, 0, 64, 8, None) == 0
+    assert lib.dagnn_readout_pool_batch(ctypes.byref(plan0), rj, 1, 64, 8, None) == -22
+    assert lib.dagnn_readout_pool_batch(ctypes.byref(plan0), rj, 25, 64, 8, None) == -22 and lib.dagnn_readout_pool_batch(ctypes.byref(plan0), rj, 0, 64, 8, None) == 0
     job = (_lib.PackJob * 1)()
     job[0].w, job[0].H, job[0].K = 64, 48, 64   # H % 32 != 0
     assert lib.dagnn_pack_batch(job, 1, None) == -22 and lib.dagnn_pack_batch(job, 0, None) == 0

@@ -1271,8 +1271,8 @@ def test_device_side_failures_raise(device, monkeypatch):
 
 def test_data_parallel_shim_runs_the_first_batch_on_the_gpu(device):
     """`dagnn_amd.DataParallel(model)(list_of_batches)` on one device = `model(list[0].to(device))`
-    (`tg/data_parallel.py:48-50`), batches handed over on the host as the reference's loader does; and the batched
-    max read-out equals one launch per column block."""
+    (`tg/data_parallel.py:48-50`), batches handed over on the host as the reference's loader does; and one launch of
+    the k max read-out jobs equals k launches of one job (the job index picks the right matrix, scope and columns)."""
     from dagnn_amd import DataParallel, collate_sharded
     model = _headline_model(H=64, L=2, V=16, seed=5).to(device)
     graphs = synth.code2_graphs(9, 10, 40)
@@ -1290,9 +1290,9 @@ def test_data_parallel_shim_runs_the_first_batch_on_the_gpu(device):
     hs = [G.h[d][i] for d in range(2) for i in range(2)]
     one = torch.zeros(shards[0].num_graphs, 4 * 64, device=device)
     many = torch.zeros_like(one)
-    engine.readout_max_batch(plan, [(h, k // 2, 64 * k) for k, h in enumerate(hs)], one)
+    engine.readout_pool_batch(plan, [(h, k // 2, "max", 64 * k) for k, h in enumerate(hs)], one)
     for k, h in enumerate(hs):
-        engine.readout_max(plan, h, k // 2, many, 64 * k)
+        engine.readout_pool_batch(plan, [(h, k // 2, "max", 64 * k)], many)
     assert torch.equal(one, many)
 
 

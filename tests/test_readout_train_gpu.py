@@ -2,7 +2,8 @@
 (csrc/readout.hip) at kernel level on one hand-made batch, then `DAGNN`, the constructor-string variants and the D-VAE
 encoders through them for one training step each against float64 autograd through the oracle.
 
-Bounds.  The forward batch is the single-job kernel's arithmetic: bit for bit.  Backward, ADD and MAX from a zero `grad_h`:
+Bounds.  The forward is a float32 host replay's arithmetic (`_replay`: the first node's value, then `np.maximum` or one
+fp32 `+` per node in the plan's visiting order, then one fp32 multiply by 1 / count for mean): bit for bit.  Backward, ADD and MAX from a zero `grad_h`:
 every element receives ONE addend, an fp32 number of `grad_out` itself, so the float64 reference cast to fp32 is hit
 exactly.  MEAN: the factor 1.f / count and its product with `grad_out` are two fp32 roundings, (1 + 2^-24)^2 - 1 < 2.4e-7
 relative.  Accumulation into a pre-filled `grad_h` is one fp32 addition of that addend: bit for bit.  Model level:
@@ -60,6 +61,19 @@ def hand(device):
     return b, plan, masks
 
 
+@pytest.fixture(scope="module")
+def visits(hand):
+    """`_visits` of the hand batch; the SET of nodes per (scope, graph) is the one the layer ids describe - only the order
+    is the plan's."""
+    b, plan, masks = hand
+    visit = _visits(plan, b)
+    for scope in range(3):
+        for g in range(b.num_graphs):
+            want = torch.nonzero(masks[scope] & (b.batch == g)).view(-1).tolist()
+            assert sorted(visit[scope][g].tolist()) == want and len(set(visit[scope][g].tolist())) == len(want), (scope, g)
+    return visit
+
+
 def _pitched(N, W, gen, device, ints=False):
     """[N, W] view of a [N, W + 3] buffer (ld = W + 3: rows that are neither contiguous nor aligned)."""
     buf = (torch.randint(0, 3, (N, W + 3), generator=gen).float() if ints else torch.randn(N, W + 3, generator=gen)).to(device)
@@ -77,6 +91,54 @@ def _pool64(h, mask, batch, B, how):
     if how == "mean":
         out = out / torch.bincount(seg, minlength=B).clamp(min=1).to(h.dtype).view(-1, 1)
     return out
+
+
+def _visits(plan, b):
+    """visit[scope][g]: the node ids the kernels read for graph g, in their visiting order - scope 0 / 1 from the plan's
+    own words (`depth`, `lstart`, `order` of direction 1 - scope, ONE copy of `plan.ws`), scope 2 ascending node ids."""
+    lay, ws, B = plan.layout(), plan.ws.cpu().numpy(), b.num_graphs
+    node_ptr = ws[lay["node_ptr"]:lay["node_ptr"] + B + 1]
+    visit = []
+    for scope in (0, 1):
+        od = 1 - scope
+        per = []
+        for g in range(B):
+            ls = ws[lay["lstart%d" % od] + node_ptr[g] + g:][:2]
+            p0, p1 = (int(ls[0]), int(ls[1])) if ws[lay["depth%d" % od] + g] > 0 else (0, 0)
+            per.append(ws[lay["order%d" % od] + p0:lay["order%d" % od] + p1].copy())
+        visit.append(per)
+    visit.append([np.arange(node_ptr[g], node_ptr[g + 1]) for g in range(B)])
+    return visit
+
+
+def _replay(h, nodes_of, how):
+    """The forward on the host in numpy float32.  h [N, W] float32; nodes_of[g]: graph g's nodes in visiting order."""
+    out = np.zeros((len(nodes_of), h.shape[1]), dtype=np.float32)
+    for g, nodes in enumerate(nodes_of):
+        if len(nodes) == 0:
+            continue   # nothing in scope: 0
+        m = h[nodes[0]].copy()
+        for v in nodes[1:]:
+            m = np.maximum(m, h[v]) if how == "max" else m + h[v]
+        out[g] = m * (np.float32(1) / np.float32(len(nodes))) if how == "mean" else m
+    assert out.dtype == np.float32
+    return out
+
+
+def _replay_backward(h, go, nodes_of, how):
+    """The backward from a zero `grad_h` on the host: go [B, W] float32 -> [N, W] float32 (one addend per element; max: to
+    the first node in visiting order attaining the column maximum)."""
+    gh = np.zeros_like(h)
+    cols = np.arange(h.shape[1])
+    for g, nodes in enumerate(nodes_of):
+        if len(nodes) == 0:
+            continue
+        if how == "max":
+            rows = h[nodes]
+            gh[np.asarray(nodes)[np.argmax(rows, axis=0)], cols] = go[g]   # (numpy: the FIRST of equal maxima, in `nodes` order)
+        else:
+            gh[nodes] = go[g] * (np.float32(1) / np.float32(len(nodes))) if how == "mean" else go[g]
+    return gh
 
 
 def _forward_jobs(views):
@@ -129,21 +191,22 @@ def kernel_runs(hand, device):
 
 # ============================================================================= kernel level
 @pytest.mark.parametrize("W", WIDTHS)
-def test_forward_batch_is_the_single_job_kernel_bit_for_bit(hand, kernel_runs, device, W):
+def test_forward_batch_is_the_single_job_kernel_bit_for_bit(hand, visits, kernel_runs, device, W):
+    """Nine (scope, mode) jobs in one launch against `_replay`, which shares no source with the kernel."""
     b, plan, masks = hand
     r = kernel_runs[W]
-    single = torch.full_like(r["out"], -7.0)
+    host = np.full((b.num_graphs, r["ld_out"]), -7.0, dtype=np.float32)
     for k, ((scope, how), h) in enumerate(zip(CASES, r["views"])):
-        rc = _lib.load().dagnn_readout_pool(C.byref(plan.desc), h.data_ptr(), h.stride(0), W, scope, MODES[how], single.data_ptr(),
-                                            r["ld_out"], COL0 + k * W, engine._stream(h))
-        assert rc == 0
-    assert torch.equal(bits(r["out"]), bits(single))     # (the columns no job owns still hold the sentinel in both)
+        host[:, COL0 + k * W:COL0 + (k + 1) * W] = _replay(h.cpu().numpy(), visits[scope], how)
+    assert np.array_equal(r["out"].cpu().numpy().view(np.int32), host.view(np.int32))   # (the columns no job owns still hold the sentinel)
     assert bool((r["out"][:, :COL0] == -7.0).all()) and bool((r["out"][:, COL0 + len(CASES) * W:] == -7.0).all())
     for k, ((scope, how), h) in enumerate(zip(CASES, r["views"])):   # ... and it is the pool the layer ids describe
         ref = _pool64(h.double().cpu(), masks[scope], b.batch, b.num_graphs, how)
-        got = r["out"][:, COL0 + k * W:COL0 + (k + 1) * W].double().cpu()
         # (at most 7 nodes: 6 fp32 additions, each within 2^-24 of a partial sum <= sum |v|, + the mean's two roundings)
-        assert bool(((got - ref).abs() <= 9 * 2.0 ** -24 * _pool64(h.double().cpu().abs(), masks[scope], b.batch, b.num_graphs, "add")).all()), (scope, how)
+        bound = 9 * 2.0 ** -24 * _pool64(h.double().cpu().abs(), masks[scope], b.batch, b.num_graphs, "add")
+        for got in (r["out"][:, COL0 + k * W:COL0 + (k + 1) * W].double().cpu(),
+                    torch.from_numpy(host[:, COL0 + k * W:COL0 + (k + 1) * W]).double()):   # (the kernel's, the replay's on its own)
+            assert bool(((got - ref).abs() <= bound).all()), (scope, how)
 
 
 @pytest.mark.parametrize("W", WIDTHS)
@@ -175,8 +238,9 @@ def test_backward_adds_into_a_prefilled_grad_h_and_repeats_bit_for_bit(kernel_ru
         assert torch.equal(bits(r["zero2"][k]), bits(addend)), (scope, how)  # a second run (h given where it is not read)
 
 
-def test_max_ties(hand, device):
-    """Rows with equal entries: scope 0 / 1 decide as `dagnn_readout_max_backward_batch`, scope 2 gives the lowest node id."""
+def test_max_ties(hand, visits, device):
+    """Rows with equal entries: scope 0 / 1 give the first node in the plan's visiting order that attains the maximum,
+    scope 2 the lowest node id."""
     b, plan, masks = hand
     N, B, W = b.batch.shape[0], b.num_graphs, 257
     gen = torch.Generator().manual_seed(9)
@@ -187,22 +251,55 @@ def test_max_ties(hand, device):
     arr = (_lib.PoolBwdJob * 3)(*[_lib.PoolBwdJob(h.data_ptr(), new[s].data_ptr(), h.stride(0), W, W, s, _lib.POOL_MAX, COL0)
                                   for s in range(3)])
     assert lib.dagnn_readout_pool_backward_batch(C.byref(plan.desc), arr, 3, gout.data_ptr(), gout.stride(0), engine._stream(h)) == 0
-    old = [torch.zeros(N, W, device=device) for _ in range(2)]
-    arr_old = (_lib.ReadoutBwdJob * 2)(*[_lib.ReadoutBwdJob(h.data_ptr(), old[d].data_ptr(), h.stride(0), W, W, d, COL0)
-                                         for d in range(2)])
-    assert lib.dagnn_readout_max_backward_batch(C.byref(plan.desc), arr_old, 2, gout.data_ptr(), gout.stride(0),
-                                                engine._stream(h)) == 0
     torch.cuda.synchronize()
-    for d in range(2):
-        assert torch.equal(bits(new[d]), bits(old[d])), d
-        assert int((new[d] != 0).sum()) > 0
     hc, gc = h.cpu().numpy(), gout.cpu().numpy()
+    for d in range(2):
+        want = _replay_backward(hc, gc[:, COL0:COL0 + W], visits[d], "max")
+        assert np.array_equal(new[d].cpu().numpy().view(np.int32), want.view(np.int32)), d
+        assert int((new[d] != 0).sum()) > 0
     want = np.zeros((N, W), dtype=np.float32)
     ptr = b.ptr.tolist()
     for g in range(B):
         first = ptr[g] + np.argmax(hc[ptr[g]:ptr[g + 1]], axis=0)     # (numpy: the FIRST of equal maxima)
         want[first, np.arange(W)] = gc[g, COL0:COL0 + W]
     assert np.array_equal(new[2].cpu().numpy().view(np.int32), want.view(np.int32))
+
+
+@pytest.mark.parametrize("n_jobs", [17, 24, 25])
+def test_job_count_edges_against_the_host_replay(hand, visits, device, n_jobs):
+    """17 jobs (more than 16), 24 (a full `MAX_READOUT_JOBS` launch) in one library call; 25 through the engine wrapper,
+    which takes two chunks: forward and backward from zero, every job against the host replay bit for bit."""
+    b, plan, masks = hand
+    N, B, W = b.batch.shape[0], b.num_graphs, 4
+    assert _lib.MAX_READOUT_JOBS == 24
+    gen = torch.Generator().manual_seed(200 + n_jobs)
+    cases = [CASES[k % len(CASES)] for k in range(n_jobs)]
+    views = [_pitched(N, W, gen, device)[1] for _ in cases]
+    ld_out = COL0 + n_jobs * W + 2
+    out = torch.full((B, ld_out), -7.0, device=device)
+    gout = torch.randn(B, ld_out, generator=gen).to(device)
+    grads = [torch.zeros(N, W + 1, device=device) for _ in cases]
+    if n_jobs > _lib.MAX_READOUT_JOBS:
+        engine.readout_pool_batch(plan, [(h, scope, how, COL0 + k * W) for k, ((scope, how), h) in enumerate(zip(cases, views))], out)
+        engine.readout_pool_backward_batch(plan, [(h, scope, how, COL0 + k * W, gh[:, :W])
+                                                  for k, ((scope, how), h, gh) in enumerate(zip(cases, views, grads))], gout)
+    else:
+        fwd, bwd = (_lib.PoolJob * n_jobs)(), (_lib.PoolBwdJob * n_jobs)()
+        for k, ((scope, how), h, gh) in enumerate(zip(cases, views, grads)):
+            fwd[k] = _lib.PoolJob(h.data_ptr(), h.stride(0), W, scope, MODES[how], COL0 + k * W)
+            bwd[k] = _lib.PoolBwdJob(h.data_ptr(), gh.data_ptr(), h.stride(0), gh.stride(0), W, scope, MODES[how], COL0 + k * W)
+        lib = _lib.load()
+        assert lib.dagnn_readout_pool_batch(C.byref(plan.desc), fwd, n_jobs, out.data_ptr(), ld_out, engine._stream(out)) == 0
+        assert lib.dagnn_readout_pool_backward_batch(C.byref(plan.desc), bwd, n_jobs, gout.data_ptr(), ld_out, engine._stream(out)) == 0
+    torch.cuda.synchronize()
+    host, gc = np.full((B, ld_out), -7.0, dtype=np.float32), gout.cpu().numpy()
+    for k, ((scope, how), h, gh) in enumerate(zip(cases, views, grads)):
+        cols = slice(COL0 + k * W, COL0 + (k + 1) * W)
+        host[:, cols] = _replay(h.cpu().numpy(), visits[scope], how)
+        want = _replay_backward(h.cpu().numpy(), gc[:, cols], visits[scope], how)
+        assert np.array_equal(gh[:, :W].cpu().numpy().view(np.int32), want.view(np.int32)), (k, scope, how)
+        assert bool((gh[:, W:] == 0).all())
+    assert np.array_equal(out.cpu().numpy().view(np.int32), host.view(np.int32))
 
 
 def test_equal_grad_h_in_two_jobs_is_refused(hand, device):
