@@ -281,7 +281,7 @@ class VariantBwdCell(C.Structure):
         [(k, C.c_void_p) for k in ("h", "a", "gi", "gh", "node0", "node1", "alpha", "edge_mat0", "edge_vec0", "edge_mat1",
                                    "edge_vec1", "w_node", "w_query", "w_hh", "w_ih", "g", "g_in", "da", "dgi", "dgh",
                                    "dnode0", "dnode1", "dlogit", "esum", "w_node2")] + \
-        [("w_ld", C.c_int32), ("ld_in", C.c_int32)]
+        [("w_ld", C.c_int32), ("ld_in", C.c_int32), ("ties", C.c_void_p)]
 
 
 class VariantBwdArgs(C.Structure):
@@ -420,6 +420,8 @@ SYMBOLS = {
                                     C.POINTER(C.c_int32), C.c_void_p]),
     "dagnn_variant_mattn_prepare": (C.c_int, [C.POINTER(Plan), C.POINTER(VariantBwdCell), C.c_int, C.c_int, C.c_int32,
                                               C.c_int32, C.c_void_p]),
+    "dagnn_variant_max_prepare": (C.c_int, [C.POINTER(Plan), C.POINTER(VariantBwdCell), C.c_int, C.c_int, C.c_int, C.c_int32,
+                                            C.c_int32, C.c_void_p]),
     "dagnn_variant_aggregator_backward": (C.c_int, [C.POINTER(Plan), C.POINTER(VariantBwdCell), C.c_int, C.c_int, C.c_int32,
                                                     C.c_int32, C.c_void_p]),
     "dagnn_variant_backward_run": (C.c_int, [C.POINTER(Plan), C.POINTER(VariantBwdArgs), C.POINTER(C.POINTER(C.c_int32)),

@@ -12,9 +12,16 @@
 //                gamma_e / mu_e = the edge-encoder terms (the [dim, R] products of variants.py):
 //                dP_v = sum_e da_w (.) m_e (.) g_e (1 - g_e),  dM_v = sum_e da_w (.) g_e,  g_v += [dP_v ; dM_v] [W_g ; W_m]
 //     mattn      logit_e = Ql_w . (Kr_v + rho_e),  alpha = segment softmax over the in-edges of w,  a_w = sum alpha_e h_v:
-//                g_v += sum_e alpha_e da_w + (sum_e dlogit_e Ql_w) W_r,   dlogit_e = alpha_e (da_w . h_v - da_w . a_w)
-//                (dlogit_e was stored by edge id when w was processed - a later step of the forward is an earlier one here)
-//     add        g_v += sum_e da_w            max: only where v's message attained the maximum a_w[k]
+//                g_v += sum_e alpha_e da_w + (sum_e dlogit_e Ql_w) W_r,   dlogit_e = alpha_e (t_e - sum_e' alpha_e' t_e'),
+//                t_e = da_w . h_v  (dlogit_e was stored by edge id when w was processed - a later step of the forward is an
+//                earlier one here; the additive attentions take their ds_e from the same target-side kernel)
+//     add        g_v += sum_e da_w
+//     max        only where v's message attained the maximum a_w[k].  TIES SPLIT EVENLY: when c messages of (w, k) equal the
+//                maximum, each receives da_w[k] / c (what torch's `amax` reduction does; together they receive da_w[k], not c
+//                times it).  The pull for v cannot count the in-edges of w, so the caller provides `ties` [N, ld] = c per
+//                (w, k) (`dagnn_variant_max_prepare`, one pass over the in-edges of every row before the sweep; no atomics,
+//                integer counts: the same bits on every run).  c = 1 divides nothing: results without ties are unchanged.
+//                The edge-encoder shares in `esum` take the same divided gradient.
 //   `recurr=0` (the Linear cell h = W [u ; a] + b, dagnn.py:83-85): no gate algebra, da_v = g_v W[:, in:], du_v = g_v W[:, :in]
 //   GRU backward (gates recomputed from gi, gh):  dgi, dgh,  da_v = z (.) g_v + dgh_v W_hh,  du_v = dgi_v W_ih -> gradient
 //            of the cell's input (the state one stacked layer down, or the node input x)
@@ -35,6 +42,12 @@ namespace {
 constexpr int VBC = 8;   // cells per launch (the step table travels as a kernel argument: 8 x ~270 bytes)
 
 __device__ __forceinline__ float vb_sigm(float x) { return 1.0f / (1.0f + expf(-x)); }
+
+__device__ __forceinline__ double vb_wave_sum_d(double v) {   // the same value in every lane
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
 
 __device__ __forceinline__ float vb_edge_term(const float* __restrict__ m, const float* __restrict__ v, int k, int R,
                                               const float* __restrict__ attr) {
@@ -100,8 +113,14 @@ __global__ void __launch_bounds__(256) vb_pull_kernel(const int32_t* __restrict_
                 float dw = C.da[(int64_t)col[e] * ld + k];
                 // max: the gradient of a_w[k] goes to the message that attained it - recomputed with the forward's own
                 // operations (variants.hip: vals + edge term), so the comparison with the stored maximum is exact
-                if (is_max && hv + vb_edge_term(C.edge_mat0, C.edge_vec0, k, R, ea + (int64_t)e * R) != C.a[(int64_t)col[e] * ld + k])
-                    dw = 0.f;
+                if (is_max) {
+                    if (hv + vb_edge_term(C.edge_mat0, C.edge_vec0, k, R, ea + (int64_t)e * R) != C.a[(int64_t)col[e] * ld + k]) {
+                        dw = 0.f;
+                    } else {   // c tied messages share the gradient evenly (c = 1: untouched)
+                        const float c = C.ties[(int64_t)col[e] * ld + k];
+                        if (c > 1.0f) dw /= c;
+                    }
+                }
                 acc += dw;
                 if (es)
                     for (int r = 0; r < R; ++r) eg[r] = fmaf(dw, ea[(int64_t)e * R + r], eg[r]);
@@ -116,8 +135,8 @@ __global__ void __launch_bounds__(256) vb_pull_kernel(const int32_t* __restrict_
     } else if (C.mode == DAGNN_AGG_ATTN) {
         // additive attention (AttnConv / SelfAttnConv, dagnn.py:279-313,347-376): logit_e = w_k . key_v + gain . attr_e (+ terms
         // constant inside a soft-max segment), a_w = sum alpha_e h_v.  g_v += sum_e alpha_e da_w + sigma_v w_k (keys = states),
-        // sigma_v = sum_e ds_e, ds_e = alpha_e (da_w . h_v - da_w . a_w); outputs sigma_v and sum_e ds_e attr_e
-        const float* __restrict__ hv = C.h + (int64_t)v * H;
+        // sigma_v = sum_e ds_e, ds_e = dlogit_e = alpha_e (da_w . h_v - sum_e' alpha_e' da_w . h_v'); outputs sigma_v and sum_e ds_e attr_e
+        // (ds_e was stored by edge id when w was processed: `vb_mattn_target_kernel`, which forms it from the in-edges of w)
         float sig = 0.f, m[2] = {0.f, 0.f};
         float acc[4] = {0.f, 0.f, 0.f, 0.f};   // H <= 256 per lane chunk; wider rows loop below
         const bool narrow = H <= 256;
@@ -125,15 +144,12 @@ __global__ void __launch_bounds__(256) vb_pull_kernel(const int32_t* __restrict_
             const int w = col[e];
             const float al = C.alpha[eidx[e]];
             const float* __restrict__ daw = C.da + (int64_t)w * H;
-            const float* __restrict__ aw = C.a + (int64_t)w * H;
-            float dot = 0.f;
             for (int k = lane, c = 0; k < H; k += 64, ++c) {
                 const float dv = daw[k];
-                dot = fmaf(dv, hv[k] - aw[k], dot);
                 if (narrow) acc[c] = fmaf(al, dv, acc[c]);
                 else g[k] = fmaf(al, dv, g[k]);
             }
-            const float ds = al * wave_sum(dot);
+            const float ds = C.dlogit[eidx[e]];
             sig += ds;
             for (int r = 0; r < R && r < 2; ++r) m[r] = fmaf(ds, ea[(int64_t)e * R + r], m[r]);
         }
@@ -260,11 +276,16 @@ __global__ void __launch_bounds__(256) vb_map_kernel(const int32_t* __restrict__
     }
 }
 
-// ---- mattn, target side: one wave per frontier row v: dlogit of its in-edges (by edge id), dQl_v
+// ---- mattn and additive attention, target side: one wave per frontier row v: dlogit of its in-edges (by edge id); mattn: dQl_v.
+// dlogit_e = alpha_e (t_e - q) with t_e = da_v . h_j and q = sum_e alpha_e t_e - the soft-max Jacobian on the t_e themselves (two
+// passes over the in-edges, t_e recomputed with the same operations: the same bits).  q = da_v . a_v is the same number in exact
+// arithmetic, but carries the rounding of a_v (eps |da| |a|, NOT scaled by the attention weights): with a sharp soft-max, where
+// the true dlogit is alpha_1 alpha_2 (t_1 - t_2) and tiny, that noise was the whole result
 __global__ void __launch_bounds__(256) vb_mattn_target_kernel(const int32_t* __restrict__ plan, PlanLayout L, VbStep S) {
     const int ci = blockIdx.y;
     const dagnn_variant_bwd_cell& C = S.c[ci];
-    if (C.mode != DAGNN_AGG_MATTN) return;
+    const bool mattn = C.mode == DAGNN_AGG_MATTN;
+    if (!mattn && C.mode != DAGNN_AGG_ATTN) return;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int slot = S.r0[ci] + blockIdx.x * 4 + wave;
     if (slot >= S.r1[ci]) return;
@@ -275,20 +296,24 @@ __global__ void __launch_bounds__(256) vb_mattn_target_kernel(const int32_t* __r
     const int32_t* __restrict__ eidx = plan + L.eidx[d];
     const float* __restrict__ ea = reinterpret_cast<const float*>(plan + L.eattr[d]);
     const float* __restrict__ dav = C.da + (int64_t)v * H;
-    const float* __restrict__ av = C.a + (int64_t)v * H;
-    float* __restrict__ dql = C.dnode1 + (int64_t)v * P;
-    float q = 0.f;   // da_v . a_v
-    for (int k = lane; k < H; k += 64) q = fmaf(dav[k], av[k], q);
-    q = wave_sum(q);
-    for (int k = lane; k < P; k += 64) dql[k] = 0.f;
+    // t_e, q and their difference in double: t_e - q cancels to alpha_2 (t_1 - t_2) under a sharp soft-max, and a float
+    // difference keeps eps |t| of noise whatever the attention weights are (H fmas per edge: nothing next to the pull)
+    auto dot_h = [&](int e) {   // da_v . h_j, the same value in every lane
+        const float* hj = C.h + (int64_t)col[e] * H;
+        double t = 0.0;
+        for (int k = lane; k < H; k += 64) t = fma((double)dav[k], (double)hj[k], t);
+        return vb_wave_sum_d(t);
+    };
+    double q = 0.0;
+    for (int e = eb; e < ee; ++e) q = fma((double)C.alpha[eidx[e]], dot_h(e), q);
+    float* __restrict__ dql = mattn ? C.dnode1 + (int64_t)v * P : nullptr;
+    if (mattn)
+        for (int k = lane; k < P; k += 64) dql[k] = 0.f;
     for (int e = eb; e < ee; ++e) {
         const int j = col[e];
-        const float* hj = C.h + (int64_t)j * H;
-        float t = 0.f;
-        for (int k = lane; k < H; k += 64) t = fmaf(dav[k], hj[k], t);
-        t = wave_sum(t);
-        const float dl = C.alpha[eidx[e]] * (t - q);
+        const float dl = (float)((double)C.alpha[eidx[e]] * (dot_h(e) - q));
         if (lane == 0) C.dlogit[eidx[e]] = dl;
+        if (!mattn) continue;
         const float* attr = ea + (int64_t)e * R;
         for (int k = lane; k < P; k += 64)
             dql[k] = fmaf(dl, C.node0[(int64_t)j * P + k] + vb_edge_term(C.edge_mat0, C.edge_vec0, k, R, attr), dql[k]);
@@ -296,6 +321,9 @@ __global__ void __launch_bounds__(256) vb_mattn_target_kernel(const int32_t* __r
 }
 
 // ---- mattn, preparation: alpha of every edge (by edge id) and the aggregates a, all rows of one direction in one launch
+// Logits, their maximum, the exponentials and the quotient in double: what a float chain leaves in a large logit becomes the
+// same RELATIVE error of every alpha that is not the dominant one - and those are what the gradients of the attention
+// projections are made of (they cancel to a small fraction of their terms)
 __global__ void __launch_bounds__(256) vb_mattn_prepare_kernel(const int32_t* __restrict__ plan, PlanLayout L,
                                                                 dagnn_variant_bwd_cell C, int dir, int r0, int r1, int R, int H) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -313,19 +341,19 @@ __global__ void __launch_bounds__(256) vb_mattn_prepare_kernel(const int32_t* __
     auto logit = [&](int e) {
         const int j = col[e];
         const float* attr = ea + (int64_t)e * R;
-        float t = 0.f;
+        double t = 0.0;
         for (int k = lane; k < P; k += 64)
-            t = fmaf(ql[k], C.node0[(int64_t)j * P + k] + vb_edge_term(C.edge_mat0, C.edge_vec0, k, R, attr), t);
-        return wave_sum(t);
+            t = fma((double)ql[k], (double)(C.node0[(int64_t)j * P + k] + vb_edge_term(C.edge_mat0, C.edge_vec0, k, R, attr)), t);
+        return vb_wave_sum_d(t);
     };
-    float mx = -INFINITY;
-    for (int e = eb; e < ee; ++e) mx = fmaxf(mx, logit(e));
-    float sum = 0.f;
-    for (int e = eb; e < ee; ++e) sum += expf(logit(e) - mx);
-    const float den = sum + 1e-16f;   // PyG softmax
+    double mx = -INFINITY;
+    for (int e = eb; e < ee; ++e) mx = fmax(mx, logit(e));
+    double sum = 0.0;
+    for (int e = eb; e < ee; ++e) sum += exp(logit(e) - mx);
+    const double den = sum + 1e-16;   // PyG softmax
     for (int k = lane; k < H; k += 64) aout[k] = 0.f;
     for (int e = eb; e < ee; ++e) {
-        const float al = expf(logit(e) - mx) / den;
+        const float al = (float)(exp(logit(e) - mx) / den);
         if (lane == 0) alpha[eidx[e]] = al;
         const float* hj = C.h + (int64_t)col[e] * H;
         for (int k = lane; k < H; k += 64) aout[k] = fmaf(al, hj[k], aout[k]);
@@ -333,6 +361,7 @@ __global__ void __launch_bounds__(256) vb_mattn_prepare_kernel(const int32_t* __
 }
 
 // ---- additive attention, preparation: alpha of every edge (by edge id) and the aggregates a
+// (logits and soft-max in double, as above)
 __global__ void __launch_bounds__(256) vb_attn_prepare_kernel(const int32_t* __restrict__ plan, PlanLayout L,
                                                                dagnn_variant_bwd_cell C, int dir, int r0, int r1, int R, int H) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -348,24 +377,47 @@ __global__ void __launch_bounds__(256) vb_attn_prepare_kernel(const int32_t* __r
     float* __restrict__ aout = const_cast<float*>(C.a) + (int64_t)v * H;
     auto logit = [&](int e) {
         const float* key = C.node0 + (int64_t)col[e] * kd;
-        float t = 0.f;
-        for (int k = lane; k < kd; k += 64) t = fmaf(C.w_node[k], key[k], t);
-        t = wave_sum(t);
+        double t = 0.0;
+        for (int k = lane; k < kd; k += 64) t = fma((double)C.w_node[k], (double)key[k], t);
+        t = vb_wave_sum_d(t);
         if (C.edge_mat0)
-            for (int r = 0; r < R; ++r) t = fmaf(C.edge_mat0[r], ea[(int64_t)e * R + r], t);
+            for (int r = 0; r < R; ++r) t = fma((double)C.edge_mat0[r], (double)ea[(int64_t)e * R + r], t);
         return t;
     };
-    float mx = -INFINITY;
-    for (int e = eb; e < ee; ++e) mx = fmaxf(mx, logit(e));
-    float sum = 0.f;
-    for (int e = eb; e < ee; ++e) sum += expf(logit(e) - mx);
-    const float den = sum + 1e-16f;
+    double mx = -INFINITY;
+    for (int e = eb; e < ee; ++e) mx = fmax(mx, logit(e));
+    double sum = 0.0;
+    for (int e = eb; e < ee; ++e) sum += exp(logit(e) - mx);
+    const double den = sum + 1e-16;
     for (int k = lane; k < H; k += 64) aout[k] = 0.f;
     for (int e = eb; e < ee; ++e) {
-        const float al = expf(logit(e) - mx) / den;
+        const float al = (float)(exp(logit(e) - mx) / den);
         if (lane == 0) alpha[eidx[e]] = al;
         const float* hj = C.h + (int64_t)col[e] * H;
         for (int k = lane; k < H; k += 64) aout[k] = fmaf(al, hj[k], aout[k]);
+    }
+}
+
+// ---- max, preparation: ties[w, k] = how many messages of the in-edges of w equal the stored maximum a_w[k] - each recomputed
+// with the operations of the forward and of the pull (vals + edge term), so the comparisons agree with the pull's.  One wave
+// per row, lane k: plain stores of whole numbers
+__global__ void __launch_bounds__(256) vb_max_prepare_kernel(const int32_t* __restrict__ plan, PlanLayout L,
+                                                              dagnn_variant_bwd_cell C, int dir, int r0, int r1, int R, int H, int ld) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int slot = r0 + blockIdx.x * 4 + wave;
+    if (slot >= r1) return;
+    const int32_t* __restrict__ rec = plan + L.rowrec[dir] + 16 * (int64_t)slot;
+    const int w = rec[0], eb = rec[1], ee = rec[2];
+    const int32_t* __restrict__ col = plan + L.col[dir];
+    const float* __restrict__ ea = reinterpret_cast<const float*>(plan + L.eattr[dir]);
+    const float* __restrict__ aw = C.a + (int64_t)w * ld;
+    float* __restrict__ out = C.ties + (int64_t)w * ld;
+    for (int k = lane; k < H; k += 64) {
+        const float top = aw[k];
+        int c = 0;
+        for (int e = eb; e < ee; ++e)
+            c += C.h[(int64_t)col[e] * ld + k] + vb_edge_term(C.edge_mat0, C.edge_vec0, k, R, ea + (int64_t)e * R) == top;
+        out[k] = (float)c;
     }
 }
 
@@ -434,6 +486,18 @@ extern "C" int dagnn_variant_mattn_prepare(const dagnn_plan* pl, const dagnn_var
     return DAGNN_OK;
 }
 
+extern "C" int dagnn_variant_max_prepare(const dagnn_plan* pl, const dagnn_variant_bwd_cell* c, int dir, int H, int ld,
+                                         int32_t row_begin, int32_t row_end, void* stream) {
+    if (!pl || !pl->data || !c || (dir != 0 && dir != 1) || H <= 0 || ld < H || row_begin < 0 || row_end > pl->N) return DAGNN_EINVAL;
+    if (c->mode != DAGNN_AGG_MAX || !c->h || !c->a || !c->ties) return DAGNN_EINVAL;
+    if (row_end <= row_begin) return DAGNN_OK;
+    const PlanLayout L = dagnn_plan_layout_words(pl->N, pl->E, pl->B, pl->num_edge_feats);
+    hipLaunchKernelGGL(vb_max_prepare_kernel, dim3((unsigned)((row_end - row_begin + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
+                       (const int32_t*)pl->data, L, *c, dir, row_begin, row_end, pl->num_edge_feats, H, ld);
+    DAGNN_CHECK_LAUNCH();
+    return DAGNN_OK;
+}
+
 extern "C" int dagnn_variant_backward_run(const dagnn_plan* pl, const dagnn_variant_bwd_args* a, const int32_t* const* layer_ptr,
                                           const int32_t* num_layers, void* stream) {
     if (!pl || !a || !layer_ptr || !num_layers) return DAGNN_EINVAL;
@@ -454,10 +518,11 @@ extern "C" int dagnn_variant_backward_run(const dagnn_plan* pl, const dagnn_vari
                 return DAGNN_EINVAL;
             if ((c.mode == DAGNN_AGG_ATTN || c.mode == DAGNN_AGG_MATTN) && ld != H) return DAGNN_EINVAL;   // (their kernels know one stride)
             if (c.ld_in < 0 || (c.ld_in && c.ld_in < c.in_dim) || c.w_ld < 0 || (c.w_ld && c.w_ld < H)) return DAGNN_EINVAL;
-            if (c.mode == DAGNN_AGG_ATTN && (!c.alpha || !c.dnode0 || !c.w_node)) return DAGNN_EINVAL;
+            if (c.mode == DAGNN_AGG_ATTN && (!c.alpha || !c.dnode0 || !c.w_node || !c.dlogit)) return DAGNN_EINVAL;
             if (!c.h || !c.a || !c.w_hh || !c.w_ih || !c.g || !c.g_in || !c.da || c.in_dim <= 0) return DAGNN_EINVAL;
             if (c.recurrent && (!c.gi || !c.gh || !c.dgi || !c.dgh)) return DAGNN_EINVAL;
             if (c.mode == DAGNN_AGG_GATED && (!c.node0 || !c.dnode0 || !c.w_node)) return DAGNN_EINVAL;
+            if (c.mode == DAGNN_AGG_MAX && c.lands && !c.ties) return DAGNN_EINVAL;
             if (c.mode == DAGNN_AGG_MATTN && (!c.node0 || !c.node1 || !c.dnode0 || !c.dnode1 || !c.w_node || !c.w_query ||
                                               !c.alpha || !c.dlogit || c.proj_dim <= 0))
                 return DAGNN_EINVAL;
@@ -470,7 +535,7 @@ extern "C" int dagnn_variant_backward_run(const dagnn_plan* pl, const dagnn_vari
         VbStep S;
         S.n = 0; S.R = R; S.H = H; S.ld = ld;
         int rows = 0;
-        bool any_mattn = false;
+        bool any_mattn = false;   // (or additive attention: both store dlogit of a row's in-edges for the predecessors' pull)
         for (int d = 0; d < DAGNN_MAX_DIRS; ++d) {
             if (!(a->dir_mask >> d & 1)) continue;
             for (int i = 0; i < Ls; ++i) {
@@ -482,7 +547,7 @@ extern "C" int dagnn_variant_backward_run(const dagnn_plan* pl, const dagnn_vari
                 S.c[S.n] = a->cell[d][i];
                 S.dir[S.n] = d; S.r0[S.n] = r0; S.r1[S.n] = r1;
                 rows = r1 - r0 > rows ? r1 - r0 : rows;
-                any_mattn = any_mattn || a->cell[d][i].mode == DAGNN_AGG_MATTN;
+                any_mattn = any_mattn || a->cell[d][i].mode == DAGNN_AGG_MATTN || a->cell[d][i].mode == DAGNN_AGG_ATTN;
                 ++S.n;
             }
         }
@@ -541,7 +606,8 @@ extern "C" int dagnn_variant_aggregator_backward(const dagnn_plan* pl, const dag
     if (c->mode == DAGNN_AGG_MATTN && (!c->node0 || !c->node1 || !c->dnode0 || !c->dnode1 || !c->w_node || !c->w_query || !c->alpha ||
                                        !c->dlogit || c->proj_dim <= 0))
         return DAGNN_EINVAL;
-    if (c->mode == DAGNN_AGG_ATTN && (!c->alpha || !c->dnode0 || !c->w_node || !c->node0)) return DAGNN_EINVAL;
+    if (c->mode == DAGNN_AGG_ATTN && (!c->alpha || !c->dnode0 || !c->w_node || !c->node0 || !c->dlogit)) return DAGNN_EINVAL;
+    if (c->mode == DAGNN_AGG_MAX && c->lands && !c->ties) return DAGNN_EINVAL;
     if (row_end <= row_begin) return DAGNN_OK;
     const PlanLayout L = dagnn_plan_layout_words(pl->N, pl->E, pl->B, pl->num_edge_feats);
     const int32_t* plan = (const int32_t*)pl->data;
@@ -550,7 +616,7 @@ extern "C" int dagnn_variant_aggregator_backward(const dagnn_plan* pl, const dag
     S.n = 1; S.R = pl->num_edge_feats; S.H = width; S.ld = width;
     S.c[0] = *c; S.dir[0] = dir; S.r0[0] = row_begin; S.r1[0] = row_end;
     const dim3 wgrid((unsigned)((row_end - row_begin + 3) / 4), 1);
-    if (c->mode == DAGNN_AGG_MATTN) {   // dlogit of every edge first: the pull below reads it for the out-edges
+    if (c->mode == DAGNN_AGG_MATTN || c->mode == DAGNN_AGG_ATTN) {   // dlogit of every edge first: the pull below reads it for the out-edges
         hipLaunchKernelGGL(vb_mattn_target_kernel, wgrid, dim3(256), 0, st, plan, L, S);
         DAGNN_CHECK_LAUNCH();
     }

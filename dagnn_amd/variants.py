@@ -541,15 +541,26 @@ def _setup_aggregator(mod, plan, bc, o, p, cp, mode, lands, d, i, vals, query, W
         if has_enc and R > 0 and lands:
             o["esum"] = torch.zeros(N, (R + 1) * W, **f32)
         aggregate(mode)
+        if mode == _lib.AGG_MAX and lands:
+            # tied messages share the gradient of their maximum evenly: the count per (node, column), at the pitch of `vals`
+            if a_out.stride(0) != Wp:
+                raise engine.DagnnHipError("max: values (pitch %d) and aggregates (pitch %d) differ in row pitch" % (Wp, a_out.stride(0)))
+            o["ties"] = torch.zeros(N, Wp, **f32)
+            bc.ties = o["ties"].data_ptr()
+            if rows[1] > rows[0]:
+                engine.check(lib.dagnn_variant_max_prepare(C.byref(plan.desc), C.byref(bc), d, W, Wp, rows[0], rows[1], stream),
+                             "dagnn_variant_max_prepare")
     elif mode == _lib.AGG_ATTN:
         keys = x if (mod.agg_attn_x or mod.agg_x) else vals
         off, kd = _attn_slice(mod, i)
-        o.update(node0=keys, dnode0=torch.zeros(N, **f32), alpha=torch.zeros(max(plan.E, 1), **f32))
+        o.update(node0=keys, dnode0=torch.zeros(N, **f32), alpha=torch.zeros(max(plan.E, 1), **f32),
+                 dlogit=torch.zeros(max(plan.E, 1), **f32))
         if has_enc and R > 0:
             o["esum"] = torch.zeros(N, R, **f32)
         bc.proj_dim = kd
         bc.reserved = 1 if (mod.agg_x or not mod.agg_attn_x) else 0   # the keys are the aggregated values themselves
         bc.node0, bc.dnode0, bc.alpha = keys.data_ptr(), o["dnode0"].data_ptr(), o["alpha"].data_ptr()
+        bc.dlogit = o["dlogit"].data_ptr()
         bc.w_node = p["edge_vec0"].data_ptr()
         if rows[1] > rows[0]:
             engine.check(lib.dagnn_variant_mattn_prepare(C.byref(plan.desc), C.byref(bc), d, W, rows[0], rows[1], stream),

@@ -854,7 +854,8 @@ typedef struct dagnn_variant_bwd_cell {
                               * dgh are unused, w_ih = W[:, :in_dim] and w_hh = W[:, in_dim:] as contiguous [H, .] copies */
     int32_t reserved;        /* additive attention (DAGNN_AGG_ATTN): 1 = the keys are this cell's states (their gradient gets
                               * sigma w_k), 0 = the keys are the node inputs; node0 = keys [N, proj_dim], w_node = w_k [proj_dim],
-                              * edge_mat0 = the folded edge gains [R]; outputs dnode0 = sigma [N], esum = sum_e ds_e attr_e [N, R] */
+                              * edge_mat0 = the folded edge gains [R]; outputs dnode0 = sigma [N], esum = sum_e ds_e attr_e [N, R];
+                              * dlogit [E] (work space by edge id, as for mattn) is required */
     const float* h;  const float* a;  const float* gi;  const float* gh;
     const float* node0;  const float* node1;  const float* alpha;
     const float* edge_mat0;  const float* edge_vec0;  const float* edge_mat1;  const float* edge_vec1;
@@ -868,6 +869,8 @@ typedef struct dagnn_variant_bwd_cell {
     int32_t w_ld;            /* gated: row stride of w_node / w_node2, of which the first H columns are read (D-VAE NA: H +
                               * num_nodes - the rest are the one-hot vertex-id columns); 0: H */
     int32_t ld_in;           /* row pitch of g_in; 0: in_dim */
+    float* ties;             /* max: [N, ld] - how many messages of (w, k) equal the maximum a_w[k]; they share da_w[k] evenly.
+                              * Written by dagnn_variant_max_prepare, read by the sweep; required when `lands` */
 } dagnn_variant_bwd_cell;
 
 typedef struct dagnn_variant_bwd_args {
@@ -879,6 +882,10 @@ typedef struct dagnn_variant_bwd_args {
 /* (also the additive-attention aggregators: mode DAGNN_AGG_ATTN) */
 int dagnn_variant_mattn_prepare(const dagnn_plan* plan /* host */, const dagnn_variant_bwd_cell* cell /* host */, int dir, int H,
                                 int32_t row_begin, int32_t row_end, void* stream);
+/* max: fills cell->ties [N, ld] for the rows [row_begin, row_end) of direction `dir` from h (the aggregated values, [N, ld]), a
+ * (the stored maxima, [N, ld]) and the edge terms - one pass over the in-edges of every row, whole numbers, no atomics. */
+int dagnn_variant_max_prepare(const dagnn_plan* plan /* host */, const dagnn_variant_bwd_cell* cell /* host */, int dir, int H,
+                              int ld, int32_t row_begin, int32_t row_end, void* stream);
 int dagnn_variant_backward_run(const dagnn_plan* plan /* host */, const dagnn_variant_bwd_args* args /* host */,
                                const int32_t* const* layer_ptr /* host */, const int32_t* num_layers /* host [2] */, void* stream);
 /* `agg_x` (dagnn.py:159-169: the aggregator reads the node inputs only): the cells' sweep runs with mode DAGNN_AGG_GIVEN

@@ -337,3 +337,38 @@ def dvae_decoder64(key, model, types, preds, mu, logvar, graphs=None, diag=None)
     if key is not None:
         _REF64[key] = val
     return val
+
+
+# ------------------------------------------------------------------ shared by the GPU gradient tests
+def _degenerate_batch(extra=()):
+    """Single-node graphs, a chain, stars with a 200-way fan-in / fan-out, a graph with no edges, a duplicate edge
+    (`extra`: more graphs behind them)."""
+    from dagnn_amd import GraphData
+    from dagnn_amd.dag_utils import add_order_info_01
+
+    def g(n, edges, attr=None):
+        ei = torch.tensor(edges, dtype=torch.long).t().reshape(2, -1)
+        ea = torch.zeros(ei.shape[1], 2) if attr is None else torch.tensor(attr, dtype=torch.float32)
+        d = GraphData(x=torch.stack([torch.arange(n) % 98, torch.arange(n) % 300], 1),
+                      node_depth=(torch.arange(n) % 30).view(-1, 1), edge_index=ei, edge_attr=ea)
+        add_order_info_01(d)
+        return d
+
+    graphs = [g(1, []), g(5, []), g(40, [(i, i + 1) for i in range(39)]),
+              g(201, [(i, 200) for i in range(200)], [[i % 2, 0] for i in range(200)]),
+              g(201, [(0, i) for i in range(1, 201)]), g(2, [(0, 1), (0, 1)])]
+    from dagnn_amd import synth
+    return synth.GraphBatch.from_data_list(graphs + list(extra))
+
+
+def _train_step(model, G, y, fused_loss=False):
+    model.train()
+    model.zero_grad(set_to_none=True)
+    pred = model(G)
+    if fused_loss:   # the same loss through the library's one-launch entry (train.seq_cross_entropy, csrc/loss.hip)
+        from dagnn_amd.train import seq_cross_entropy
+        loss = seq_cross_entropy(pred, y)
+    else:
+        loss = sum(torch.nn.functional.cross_entropy(p, y[:, s]) for s, p in enumerate(pred)) / len(pred)  # main_pyg.py:55-60
+    loss.backward()
+    return loss.detach(), {k: (torch.zeros_like(p) if p.grad is None else p.grad) for k, p in model.named_parameters()}

@@ -13,6 +13,7 @@ from dagnn_amd._lib import DagnnHipError
 from oracle import dagnn_oracle as O
 from oracle.seeding import seeded_fill
 from tests import helpers as Hh
+from tests.helpers import _degenerate_batch, _train_step
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-4  # BASELINE.json north_star: "within 1e-4 fp32"
@@ -854,26 +855,6 @@ def test_static_rows_from_the_forward_launch_feed_the_reverse_sweep(device, monk
         assert Hh.maxdiff(g, ref) <= 2e-5 * max(float(ref.abs().max()), 1e-3), k
 
 
-def _degenerate_batch(extra=()):
-    """Single-node graphs, a chain, stars with a 200-way fan-in / fan-out, a graph with no edges, a duplicate edge
-    (`extra`: more graphs behind them)."""
-    from dagnn_amd import GraphData
-    from dagnn_amd.dag_utils import add_order_info_01
-
-    def g(n, edges, attr=None):
-        ei = torch.tensor(edges, dtype=torch.long).t().reshape(2, -1)
-        ea = torch.zeros(ei.shape[1], 2) if attr is None else torch.tensor(attr, dtype=torch.float32)
-        d = GraphData(x=torch.stack([torch.arange(n) % 98, torch.arange(n) % 300], 1),
-                      node_depth=(torch.arange(n) % 30).view(-1, 1), edge_index=ei, edge_attr=ea)
-        add_order_info_01(d)
-        return d
-
-    graphs = [g(1, []), g(5, []), g(40, [(i, i + 1) for i in range(39)]),
-              g(201, [(i, 200) for i in range(200)], [[i % 2, 0] for i in range(200)]),
-              g(201, [(0, i) for i in range(1, 201)]), g(2, [(0, 1), (0, 1)])]
-    return synth.GraphBatch.from_data_list(graphs + list(extra))
-
-
 def test_edge_cases(device, schedule):
     """Single-node graphs, a chain, a star with a 200-way fan-in, and a graph with no edges."""
     b = _degenerate_batch()
@@ -922,19 +903,6 @@ def test_smoke_entry(device):
 
 
 # ----------------------------------------------------------------------------- training step
-def _train_step(model, G, y, fused_loss=False):
-    model.train()
-    model.zero_grad(set_to_none=True)
-    pred = model(G)
-    if fused_loss:   # the same loss through the library's one-launch entry (train.seq_cross_entropy, csrc/loss.hip)
-        from dagnn_amd.train import seq_cross_entropy
-        loss = seq_cross_entropy(pred, y)
-    else:
-        loss = sum(torch.nn.functional.cross_entropy(p, y[:, s]) for s, p in enumerate(pred)) / len(pred)  # main_pyg.py:55-60
-    loss.backward()
-    return loss.detach(), {k: (torch.zeros_like(p) if p.grad is None else p.grad) for k, p in model.named_parameters()}
-
-
 @pytest.mark.parametrize("fused_loss", [False, True])
 @pytest.mark.parametrize("name", Hh.GRAD)
 def test_training_step_gradients_match_reference_golden(device, name, fused_loss):
@@ -1736,9 +1704,10 @@ def test_variant_training_step_matches_oracle_autograd(device, name):
     kw = meta["ctor"]
     model = Hh.code2_model(meta)
     y = torch.from_numpy(np.random.default_rng(2).integers(0, meta["V"], size=(int(arr["batch"].max()) + 1, meta["S"])))
-    loss_ref, ref = O.code2_grads(model.state_dict(), Hh.code2_batch(arr), y, num_layers=kw["num_layers"],
-                                  bidirectional=True, out_wx=kw["out_wx"], max_seq_len=meta["S"], agg=kw["agg"],
-                                  agg_x=kw.get("agg_x", False), recurr=kw.get("recurr", 1))
+    # the reference is the float64 oracle: the bound below measures fp32 against exact arithmetic, not against another fp32 sum
+    loss_ref, ref = Hh.code2_grads64(None, model, Hh.code2_batch(arr), y, num_layers=kw["num_layers"],
+                                     bidirectional=True, out_wx=kw["out_wx"], max_seq_len=meta["S"], agg=kw["agg"],
+                                     agg_x=kw.get("agg_x", False), recurr=kw.get("recurr", 1))
     model = model.to(device)
     loss, grads = _train_step(model, Hh.code2_batch(arr, device), y.to(device))
     assert abs(float(loss) - float(loss_ref)) < 1e-5
