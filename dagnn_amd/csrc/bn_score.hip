@@ -47,12 +47,6 @@ __device__ __forceinline__ int bn_family_cells(const BnCards& cards, int i, uint
     return (int)cells;
 }
 
-__device__ __forceinline__ double bn_wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 template <bool STAGED>
 __global__ void __launch_bounds__(BN_T) bn_score_kernel(const uint8_t* __restrict__ cols, int64_t ld, int64_t S, int n_var,
                                                         BnCards cards, const uint32_t* __restrict__ parents,
@@ -158,7 +152,7 @@ __global__ void __launch_bounds__(BN_T) bn_score_kernel(const uint8_t* __restric
                 }
                 for (int k = 0; k < r; ++k) cj[k] = 0;
             }
-            acc = bn_wave_sum(acc);
+            acc = wave_sum(acc);
             if (lane == 0) fam[i * BN_WAVES + wave] = acc;
             __syncthreads();   // the table is all zero again
         }

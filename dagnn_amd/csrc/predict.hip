@@ -14,36 +14,22 @@
 //   dagnn_rows_argmax    the same answer from logits that exist (a training step needs them for the loss);
 //   dagnn_seq_f1_counts  per graph (true_positive, n_pred, n_ref, len) in integers.
 //
-// The order of logits: every value maps to a 32-bit integer key that is monotone in the value, with -0 and +0 on the same
-// key and every NaN on INT_MAX (torch.argmax: NaN beats everything, the first one wins); (key, ~column) packed into one
-// int64 makes "greatest value, lowest column" a single integer maximum, so the merges are exact, associative and
-// independent of the order they run in.
-#include <limits.h>
-
-#include "common.h"
+// The order of logits (rows_dev.h: logit_key / logit_pack / logit_col) makes "greatest value, lowest column" a single integer
+// maximum, so the merges are exact, associative and independent of the order they run in.
+#include "rows_dev.h"
 
 namespace {
 
-constexpr int KEY_NAN = INT_MAX, KEY_NONE = INT_MIN;
+constexpr int KEY_NONE = INT_MIN;
 constexpr int KEY_NEG_INF = -0x7f800000;
 
-__device__ __forceinline__ int key_of(float v) {
-    if (v != v) return KEY_NAN;
-    const int b = __float_as_int(v);
-    return b >= 0 ? b : (int)(0x80000000u - (unsigned)b);
-}
 __device__ __forceinline__ float val_of(int k) {
     if (k == KEY_NAN) return __int_as_float(0x7fc00000);
     if (k < KEY_NEG_INF) return -INFINITY;   // (no such column: the runner-up of a one-column head)
     return __int_as_float(k >= 0 ? k : (int)(0x80000000u - (unsigned)k));
 }
-__device__ __forceinline__ long long pack_of(int key, int col) {
-    return (long long)(((unsigned long long)(unsigned)key << 32) | (unsigned long long)(0xffffffffu - (unsigned)col));
-}
-__device__ __forceinline__ int col_of(long long p) { return (int)(0xffffffffu - (unsigned)(unsigned long long)p); }
-
 struct __attribute__((aligned(16))) Part {
-    long long best;   // pack_of(key, column) of the winner; pack_of(KEY_NONE, ..) = nothing seen
+    long long best;   // logit_pack(key, column) of the winner; logit_pack(KEY_NONE, ..) = nothing seen
     int second;       // key of the runner-up
     int pad;
 };
@@ -165,7 +151,7 @@ __device__ __forceinline__ void argmax_epilogue(const f32x16 (&acc)[2][2], float
         __syncthreads();
         Part p = part_none();
         const int ncol = min(32, a.V - (n0 + wn + c0));   // live columns of this lane's half row (<= 0: none)
-        for (int c = 0; c < ncol; ++c) part_merge(p, pack_of(key_of(st[row * SP + c0 + c]), n0 + wn + c0 + c), KEY_NONE);
+        for (int c = 0; c < ncol; ++c) part_merge(p, logit_pack(logit_key(st[row * SP + c0 + c]), n0 + wn + c0 + c), KEY_NONE);
         const long long ob = __shfl_xor(p.best, 1, 64);
         const int os = __shfl_xor(p.second, 1, 64);
         part_merge(p, ob, os);
@@ -323,7 +309,7 @@ __global__ void __launch_bounds__(256) heads_merge_kernel(const Part* __restrict
         const Part o = part[r * tph + k];
         part_merge(p, o.best, o.second);
     }
-    tok[r] = col_of(p.best);
+    tok[r] = logit_col(p.best);
     if (top) {
         top[2 * r] = val_of((int)(p.best >> 32));
         top[2 * r + 1] = val_of(p.second);
@@ -340,7 +326,7 @@ __global__ void __launch_bounds__(256) heads_merge_kernel(const Part* __restrict
 // of -inf alone to 0 (log: -inf), a NaN poisons its sum, and nothing ever forms inf - inf.
 template <int KT>
 struct __attribute__((aligned(8))) SPart {
-    long long top[KT];   // descending; LLONG_MIN (= pack_of(KEY_NONE, -1)) where the tile has no further live column
+    long long top[KT];   // descending; LLONG_MIN (= logit_pack(KEY_NONE, -1)) where the tile has no further live column
     float m, s, xy;      // maximum, sum of exp(x - m) over the live columns; the target's logit if its column is in this tile
     int pad;
 };
@@ -414,7 +400,7 @@ __device__ __forceinline__ void score_epilogue(const f32x16 (&acc)[2][2], float*
         for (int c = 0; c < ncol; ++c) {
             const float v = x[c];
             m = fmaxf(m, v);
-            topk_insert(tk, pack_of(key_of(v), colbase + c));
+            topk_insert(tk, logit_pack(logit_key(v), colbase + c));
         }
         const float mf = finite_or_zero(m);
         for (int c = 0; c < ncol; ++c) s += __expf(x[c] - mf);
@@ -505,7 +491,7 @@ __global__ void __launch_bounds__(MT) heads_score_merge_kernel(const SPart<KT>* 
 #pragma unroll
         for (int j = 0; j < KT; ++j)
             if (j < k) {
-                tok[r * k + j] = col_of(tk[j]);
+                tok[r * k + j] = logit_col(tk[j]);
                 logit[r * k + j] = val_of((int)(tk[j] >> 32));
             }
         lse[r] = L;
@@ -542,15 +528,6 @@ __global__ void __launch_bounds__(MT) heads_score_merge_kernel(const SPart<KT>* 
 }
 
 // ---------------------------------------------------------------------------------------------- argmax of existing logits
-__device__ __forceinline__ long long wave_max_ll(long long v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const long long w = __shfl_xor(v, o, 64);
-        v = w > v ? w : v;
-    }
-    return v;
-}
-
 // a workgroup per (graph, head): scalar reads up to the first 16-byte boundary of the head's V floats (V = 5002 puts the
 // heads at every alignment), float4 reads behind it
 __global__ void __launch_bounds__(256) rows_argmax_kernel(const float* __restrict__ logits, int64_t ld, int S, int V,
@@ -564,67 +541,44 @@ __global__ void __launch_bounds__(256) rows_argmax_kernel(const float* __restric
     const int pre = min(V, (int)((4 - (((uintptr_t)x >> 2) & 3)) & 3));
     const int nvec = (V - pre) >> 2;
     long long best = LLONG_MIN;
-    if (tid < pre) best = pack_of(key_of(x[tid]), tid);
+    if (tid < pre) best = logit_pack(logit_key(x[tid]), tid);
     const float4* __restrict__ xv = reinterpret_cast<const float4*>(x + pre);
     for (int q = tid; q < nvec; q += 256) {
         const float4 v = xv[q];
         const int c = pre + 4 * q;
-        long long p = pack_of(key_of(v.x), c);
+        long long p = logit_pack(logit_key(v.x), c);
         best = p > best ? p : best;
-        p = pack_of(key_of(v.y), c + 1);
+        p = logit_pack(logit_key(v.y), c + 1);
         best = p > best ? p : best;
-        p = pack_of(key_of(v.z), c + 2);
+        p = logit_pack(logit_key(v.z), c + 2);
         best = p > best ? p : best;
-        p = pack_of(key_of(v.w), c + 3);
+        p = logit_pack(logit_key(v.w), c + 3);
         best = p > best ? p : best;
     }
     const int tail0 = pre + 4 * nvec;
     if (tail0 + tid < V) {   // (at most 3 columns)
-        const long long p = pack_of(key_of(x[tail0 + tid]), tail0 + tid);
+        const long long p = logit_pack(logit_key(x[tail0 + tid]), tail0 + tid);
         best = p > best ? p : best;
     }
-    best = wave_max_ll(best);
+    best = wave_max(best);
     if ((tid & 63) == 0) red[tid >> 6] = best;
     __syncthreads();
     if (tid == 0) {
         for (int w = 1; w < 4; ++w) best = red[w] > best ? red[w] : best;
-        tok[r] = col_of(best);
+        tok[r] = logit_col(best);
     }
 }
 
 // ---------------------------------------------------------------------------------------------- the evaluator's counts
-// a thread per graph; S and R are a handful (max_seq_len = 5, label lengths of method names), so the set arithmetic is
-// plain quadratic loops over the graph's own rows
+// a thread per graph (rows_dev.h: f1_counts_of_graph)
 __global__ void __launch_bounds__(128) seq_f1_counts_kernel(const long long* __restrict__ tok, int64_t B, int S, long long eos,
                                                             const int* __restrict__ ref_ids, int R, const int* __restrict__ ref_extra,
                                                             int* __restrict__ counts) {
     const int64_t b = (int64_t)blockIdx.x * 128 + threadIdx.x;
     if (b >= B) return;
     const long long* __restrict__ t = tok + b * S;
-    const int* __restrict__ ref = ref_ids + b * R;
-    int len = S;
-    for (int i = S - 1; i >= 0; --i)
-        if (t[i] == eos) len = i;
-    int n_ref = 0;
-    for (int i = 0; i < R; ++i) {
-        const int v = ref[i];
-        bool fresh = v >= 0;
-        for (int j = 0; j < i && fresh; ++j) fresh = ref[j] != v;
-        n_ref += fresh;
-    }
-    int n_pred = 0, tp = 0;
-    for (int i = 0; i < len; ++i) {
-        const long long v = t[i];
-        bool fresh = true;
-        for (int j = 0; j < i && fresh; ++j) fresh = t[j] != v;
-        if (!fresh) continue;
-        ++n_pred;
-        bool hit = false;
-        for (int j = 0; j < R && !hit; ++j) hit = ref[j] >= 0 && (long long)ref[j] == v;
-        tp += hit;
-    }
-    const int extra = ref_extra ? ref_extra[b] : 0;
-    reinterpret_cast<int4*>(counts)[b] = make_int4(tp, n_pred, n_ref + extra, len);
+    reinterpret_cast<int4*>(counts)[b] =
+        f1_counts_of_graph([t](int i) { return t[i]; }, S, eos, ref_ids + b * R, R, ref_extra ? ref_extra[b] : 0);
 }
 
 bool heads_shape_ok(int64_t B, int S, int V) {

@@ -240,12 +240,6 @@ __global__ void __launch_bounds__(PR_THREADS) predictor_forward_kernel(const flo
 }
 
 // ---------------------------------------------------------------------------------------------- fit sums
-__device__ __forceinline__ double fit_wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // out [6] = sum p, sum y, sum p^2, sum y^2, sum p y, sum (p - y)^2 with p = (-pred - mean) / std, all in float64: a thread
 // adds the elements tid + 256 (block + blocks c) in order, the wave butterfly, the four waves in order, the workgroups' partials
 // in order by the last one in.
@@ -264,7 +258,7 @@ __global__ void __launch_bounds__(256) fit_sums_kernel(const float* __restrict__
     }
 #pragma unroll
     for (int q = 0; q < 6; ++q) {
-        const double v = fit_wave_sum(s[q]);
+        const double v = wave_sum(s[q]);
         if (lane == 0) red[wave][q] = v;
     }
     __syncthreads();

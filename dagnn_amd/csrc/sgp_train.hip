@@ -312,12 +312,6 @@ __global__ void __launch_bounds__(256) st_gemm_kernel(GemmArgs g) {
 // y = alpha op(A) x for the matrix blockIdx.y (A + z a_zs, y + z y_zs), A(i, k) = A[i rs + k ks].  ks == 1 (rows contiguous): a wave
 // per row, lane l adds k = l, l + 64, ..., then the butterfly; otherwise (rs == 1) a lane per row, the four waves split k
 // (k = w, w + 4, ...) and are added as ((0 + 1) + 2) + 3.
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 __global__ void __launch_bounds__(256) st_gemv_kernel(const double* __restrict__ A, int64_t rs, int64_t ks, int64_t a_zs,
                                                       const double* __restrict__ x, double* __restrict__ y, int64_t y_zs, int m, int k,
                                                       double alpha) {
@@ -331,7 +325,7 @@ __global__ void __launch_bounds__(256) st_gemv_kernel(const double* __restrict__
         const double* __restrict__ row = A + (int64_t)i * rs;
         double s = 0.0;
         for (int q = lane; q < k; q += 64) s = fma(row[q], x[q], s);
-        s = wave_sum_f64(s);
+        s = wave_sum(s);
         if (lane == 0) y[i] = alpha * s;
     } else {
         const int i = blockIdx.x * 64 + lane;
@@ -482,17 +476,17 @@ __global__ void __launch_bounds__(256) st_final_kernel(int M, int d, int64_t b, 
         const double* __restrict__ v = ab + wave * Mv;
         double s = 0.0;
         for (int m = lane; m < M; m += 64) s = fma(t[m], v[m], s);
-        s = wave_sum_f64(s);
+        s = wave_sum(s);
         if (lane == 0) sh[wave] = s;
     } else if (wave == 2) {  // sum ll, sum d_out, sum d_v
         double s0 = 0.0, s1 = 0.0, s2 = 0.0;
         for (int64_t q = lane; q < nparts; q += 64) { s0 += part[q * 4]; s1 += part[q * 4 + 1]; s2 += part[q * 4 + 2]; }
-        s0 = wave_sum_f64(s0); s1 = wave_sum_f64(s1); s2 = wave_sum_f64(s2);
+        s0 = wave_sum(s0); s1 = wave_sum(s1); s2 = wave_sum(s2);
         if (lane == 0) { sh[2] = s0; sh[3] = s1; sh[4] = s2; }
     } else {
         double s = 0.0;
         for (int m = lane; m < M; m += 64) s += Plsf[m];
-        s = wave_sum_f64(s);
+        s = wave_sum(s);
         if (lane == 0) sh[5] = s;
     }
     __syncthreads();

@@ -43,12 +43,6 @@ constexpr int VBC = 8;   // cells per launch (the step table travels as a kernel
 
 __device__ __forceinline__ float vb_sigm(float x) { return 1.0f / (1.0f + expf(-x)); }
 
-__device__ __forceinline__ double vb_wave_sum_d(double v) {   // the same value in every lane
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 __device__ __forceinline__ float vb_edge_term(const float* __restrict__ m, const float* __restrict__ v, int k, int R,
                                               const float* __restrict__ attr) {
     float e = v ? v[k] : 0.f;
@@ -302,7 +296,7 @@ __global__ void __launch_bounds__(256) vb_mattn_target_kernel(const int32_t* __r
         const float* hj = C.h + (int64_t)col[e] * H;
         double t = 0.0;
         for (int k = lane; k < H; k += 64) t = fma((double)dav[k], (double)hj[k], t);
-        return vb_wave_sum_d(t);
+        return wave_sum(t);
     };
     double q = 0.0;
     for (int e = eb; e < ee; ++e) q = fma((double)C.alpha[eidx[e]], dot_h(e), q);
@@ -344,7 +338,7 @@ __global__ void __launch_bounds__(256) vb_mattn_prepare_kernel(const int32_t* __
         double t = 0.0;
         for (int k = lane; k < P; k += 64)
             t = fma((double)ql[k], (double)(C.node0[(int64_t)j * P + k] + vb_edge_term(C.edge_mat0, C.edge_vec0, k, R, attr)), t);
-        return vb_wave_sum_d(t);
+        return wave_sum(t);
     };
     double mx = -INFINITY;
     for (int e = eb; e < ee; ++e) mx = fmax(mx, logit(e));
@@ -379,7 +373,7 @@ __global__ void __launch_bounds__(256) vb_attn_prepare_kernel(const int32_t* __r
         const float* key = C.node0 + (int64_t)col[e] * kd;
         double t = 0.0;
         for (int k = lane; k < kd; k += 64) t = fma((double)C.w_node[k], (double)key[k], t);
-        t = vb_wave_sum_d(t);
+        t = wave_sum(t);
         if (C.edge_mat0)
             for (int r = 0; r < R; ++r) t = fma((double)C.edge_mat0[r], (double)ea[(int64_t)e * R + r], t);
         return t;

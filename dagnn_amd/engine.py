@@ -2058,12 +2058,39 @@ def seq_f1_counts(tok: torch.Tensor, eos_id: int, ref_ids: torch.Tensor, ref_ext
     return out
 
 
+def _ce_buffers(B: int, S: int, V: int, need_grad: bool, dev):
+    """(d logits [B, S V] in rows pitched to a multiple of 4 floats - what the heads' weight-gradient product reads 16 bytes
+    at a time - or None, row losses [B S], loss [1]) of one cross-entropy launch."""
+    dl = torch.empty(B, (S * V + 3) // 4 * 4, dtype=torch.float32, device=dev)[:, :S * V] if need_grad else None
+    return dl, torch.empty(B * S, dtype=torch.float32, device=dev), torch.empty(1, dtype=torch.float32, device=dev)
+
+
+def _scale_rows(dl: torch.Tensor, g: torch.Tensor) -> torch.Tensor:
+    """`dl * g`, the backward of the four cross-entropy functions: out of place (`backward(retain_graph=True)` may run it
+    again on the same `dl`), into rows of the same pitch."""
+    out = torch.empty(dl.shape[0], dl.stride(0), dtype=dl.dtype, device=dl.device)[:, :dl.shape[1]]
+    return torch.mul(dl, g, out=out)
+
+
+def seq_ce(base: torch.Tensor, y: torch.Tensor, S: int, V: int, need_grad: bool):
+    """`dagnn_seq_ce` (csrc/loss.hip): (loss [1], d loss / d logits [B, S V] in rows pitched to a multiple of 4 floats, or
+    None) of fp32 GPU logits `base` [B, S V] with unit column stride and contiguous int64 targets `y` [B, S] on its device.
+    One launch, nothing synchronises."""
+    B = base.shape[0]
+    dl, row, loss = _ce_buffers(B, S, V, need_grad, base.device)
+    check(_lib.load().dagnn_seq_ce(base.data_ptr(), base.stride(0), y.data_ptr(), B, S, V, _ptr(dl),
+                                   0 if dl is None else dl.stride(0), row.data_ptr(), loss.data_ptr(),
+                                   _lp_counter(base).data_ptr(), _stream(base)), "dagnn_seq_ce")
+    return loss, dl
+
+
 def seq_ce_step(base: torch.Tensor, y: torch.Tensor, S: int, V: int, need_grad: bool, eos_id: int,
                 ref_ids: Optional[torch.Tensor], ref_extra: Optional[torch.Tensor], counts: torch.Tensor, graph_offset: int,
                 epoch_sum: torch.Tensor, epoch_steps: torch.Tensor):
-    """`dagnn_seq_ce_step` (csrc/train_step.hip): (loss [1], d loss / d logits [B, S V] in rows pitched to a multiple of 4
-    floats or None, tok [B, S] int64) of fp32 GPU logits `base` [B, S V] and int64 targets `y` [B, S] - `dagnn_seq_ce`'s bits
-    - and in the same launch `epoch_sum` [1] float64 += loss, `epoch_steps` [1] int64 += 1 and, with `ref_ids` [B, R] int32
+    """`dagnn_seq_ce_step` (csrc/loss.hip): (loss [1], d loss / d logits [B, S V] in rows pitched to a multiple of 4
+    floats or None, tok [B, S] int64) of fp32 GPU logits `base` [B, S V] and int64 targets `y` [B, S] - `seq_ce`'s bits, the
+    same kernel - and in the same launch `epoch_sum` [1] float64 += loss, `epoch_steps` [1] int64 += 1 and, with `ref_ids`
+    [B, R] int32
     (`ref_extra` [B] int32), the F1 counts of the B graphs into rows `graph_offset` .. of `counts` [capacity, 4] int32.
     Nothing synchronises."""
     if not isinstance(base, torch.Tensor) or not base.is_cuda:
@@ -2092,9 +2119,7 @@ def seq_ce_step(base: torch.Tensor, y: torch.Tensor, S: int, V: int, need_grad: 
             ref_extra = _dev(ref_extra, "ref_extra", torch.int32)
             if ref_extra.numel() != B or not ref_extra.is_contiguous() or ref_extra.device != dev:
                 raise DagnnHipError("seq_ce_step: contiguous int32 ref_extra [B] on the logits' device needed")
-    dl = torch.empty(B, (S * V + 3) // 4 * 4, dtype=torch.float32, device=dev)[:, :S * V] if need_grad else None
-    row = torch.empty(B * S, dtype=torch.float32, device=dev)
-    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    dl, row, loss = _ce_buffers(B, S, V, need_grad, dev)
     tok = torch.empty(B, S, dtype=torch.int64, device=dev)
     check(_lib.load().dagnn_seq_ce_step(base.data_ptr(), base.stride(0) if B > 1 else S * V, y.data_ptr(), B, S, V, _ptr(dl),
                                         0 if dl is None else dl.stride(0), row.data_ptr(), loss.data_ptr(), tok.data_ptr(),
@@ -2122,7 +2147,8 @@ def lp_target(targ: torch.Tensor, B: int, device) -> Tuple[torch.Tensor, int]:
 
 
 def _lp_counter(t: torch.Tensor) -> torch.Tensor:
-    """The zeroed device word the last-workgroup-in kernels of csrc/lp.hip count on (they leave it zero), one per stream."""
+    """The zeroed device word the last-workgroup-in kernels (csrc/loss.hip, lp.hip, predictor.hip) count on, one per (device,
+    stream): launches on a stream are ordered and every kernel leaves the word zero, so one is enough for all of them."""
     key = (t.device.index, _stream(t))
     cnt = _LP_WORDS.get(key)
     if cnt is None:
@@ -2143,14 +2169,13 @@ def graph_depth(layer: torch.Tensor, batch: torch.Tensor, num_graphs: int) -> to
 
 
 def class_ce(pred: torch.Tensor, targ: torch.Tensor, need_grad: bool):
-    """`dagnn_class_ce`: (loss [1], d loss / d logits [B, C] in rows pitched to a multiple of 4 floats, or None) for fp32 GPU
-    logits `pred` [B, C] with unit column stride.  One launch, nothing synchronises."""
+    """`dagnn_class_ce` (csrc/loss.hip, the S = 1 instance of `seq_ce`'s kernel): (loss [1], d loss / d logits [B, C] in rows
+    pitched to a multiple of 4 floats, or None) for fp32 GPU logits `pred` [B, C] with unit column stride.  One launch,
+    nothing synchronises."""
     B, C = pred.shape
     dev = pred.device
     targ, kind = lp_target(targ, B, dev)
-    dl = torch.empty(B, (C + 3) // 4 * 4, dtype=torch.float32, device=dev)[:, :C] if need_grad else None
-    row = torch.empty(B, dtype=torch.float32, device=dev)
-    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    dl, row, loss = _ce_buffers(B, 1, C, need_grad, dev)
     check(_lib.load().dagnn_class_ce(pred.data_ptr(), pred.stride(0) if B > 1 else C, targ.data_ptr(), kind, B, C, _ptr(dl),
                                      0 if dl is None else dl.stride(0), row.data_ptr(), loss.data_ptr(),
                                      _lp_counter(pred).data_ptr(), _stream(pred)), "dagnn_class_ce")
@@ -2159,7 +2184,8 @@ def class_ce(pred: torch.Tensor, targ: torch.Tensor, need_grad: bool):
 
 def class_ce_step(pred: torch.Tensor, targ: torch.Tensor, need_grad: bool, epoch_hits: torch.Tensor, epoch_sum: torch.Tensor,
                   epoch_steps: torch.Tensor):
-    """`dagnn_class_ce_step` (csrc/train_step.hip): `class_ce`'s (loss [1], d loss / d logits) - its bits - plus tok [B] int64
+    """`dagnn_class_ce_step` (csrc/loss.hip): `class_ce`'s (loss [1], d loss / d logits) - its bits, the same kernel - plus
+    tok [B] int64
     (the row argmax) and, in the same launch, `epoch_hits` [2] int64 += (hits, labelled) by `dagnn_class_hits`' rules,
     `epoch_sum` [1] float64 += loss, `epoch_steps` [1] int64 += 1.  Nothing synchronises."""
     if not isinstance(pred, torch.Tensor) or not pred.is_cuda:
@@ -2175,9 +2201,7 @@ def class_ce_step(pred: torch.Tensor, targ: torch.Tensor, need_grad: bool, epoch
         _dev(epoch_steps, "epoch_steps", torch.int64)
     if epoch_hits.numel() != 2 or {epoch_hits.device, epoch_sum.device, epoch_steps.device} != {dev}:
         raise DagnnHipError("class_ce_step: epoch_hits [2] and the epoch words on the logits' device needed")
-    dl = torch.empty(B, (C + 3) // 4 * 4, dtype=torch.float32, device=dev)[:, :C] if need_grad else None
-    row = torch.empty(B, dtype=torch.float32, device=dev)
-    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    dl, row, loss = _ce_buffers(B, 1, C, need_grad, dev)
     tok = torch.empty(B, dtype=torch.int64, device=dev)
     check(_lib.load().dagnn_class_ce_step(pred.data_ptr(), pred.stride(0) if B > 1 else C, targ.data_ptr(), kind, B, C, _ptr(dl),
                                           0 if dl is None else dl.stride(0), row.data_ptr(), loss.data_ptr(), tok.data_ptr(),

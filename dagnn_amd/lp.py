@@ -6,7 +6,7 @@ ogb/graphproppred/evaluate.py:221-229 - on the argmax and the targets of every b
 (main_pyg_lp.py:66-74, 93-107).  Here: `lp_targets` (the attribute, or the per-graph maximum of `_bi_layer_idx0` in one
 launch when the dataset is a stock one), `class_cross_entropy` (loss and d logits in one launch), `ClassAccuracy` (one
 launch per batch, one copy to the host at the end), with the model built as `DAGNN(..., encoder=ASTNodeEncoder2(...),
-num_class=275)`.  Kernels: csrc/lp.hip.
+num_class=275)`.  Kernels: csrc/lp.hip; the loss is the one-head instance of csrc/loss.hip's kernel.
 
     for batch in lp_batches(loader, training=True):
         loss = class_cross_entropy(model(batch), lp_targets(batch)); loss.backward(); optimizer.step()
@@ -59,8 +59,8 @@ def lp_targets(batch, num_graphs: Optional[int] = None) -> torch.Tensor:
 
 # ----------------------------------------------------------------------------- loss
 class _ClassCE(torch.autograd.Function):
-    """Mean cross-entropy of one [B, C] head, loss and gradient in one HIP launch (`dagnn_class_ce`, csrc/lp.hip); the backward
-    is one multiplication by the incoming scalar, into rows of the pitch `_HeadsLinear.backward` reads."""
+    """Mean cross-entropy of one [B, C] head, loss and gradient in one HIP launch (`dagnn_class_ce`, csrc/loss.hip); the
+    backward is one multiplication by the incoming scalar, into rows of the pitch `_HeadsLinear.backward` reads."""
 
     @staticmethod
     def forward(ctx, pred, targ):
@@ -69,10 +69,15 @@ class _ClassCE(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        # out of place (`backward(retain_graph=True)` may run this again on the same `ctx.dl`), into rows of the same pitch
-        dl = ctx.dl
-        out = torch.empty(dl.shape[0], dl.stride(0), dtype=dl.dtype, device=dl.device)[:, :dl.shape[1]]
-        return torch.mul(dl, g, out=out), None
+        return engine._scale_rows(ctx.dl, g), None
+
+
+def _fused_ok(pred, targ: torch.Tensor) -> bool:
+    """Whether the one-launch loss can take `pred` and `targ` - fp32 GPU logits [B >= 1, C >= 1] with unit column stride,
+    one target per row: the predicate of `class_cross_entropy` and `class_ce_step`."""
+    return isinstance(pred, torch.Tensor) and pred.is_cuda and pred.dtype == torch.float32 and pred.dim() == 2 and \
+        pred.shape[0] > 0 and pred.shape[1] > 0 and pred.stride(1) == 1 and (pred.shape[0] == 1 or pred.stride(0) >= pred.shape[1]) \
+        and targ.numel() == pred.shape[0]
 
 
 def class_cross_entropy(pred: torch.Tensor, targ: torch.Tensor) -> torch.Tensor:
@@ -82,17 +87,14 @@ def class_cross_entropy(pred: torch.Tensor, targ: torch.Tensor) -> torch.Tensor:
     truncates toward zero as `.to(torch.long)` does.  A target outside [0, C) - a NaN included - makes the loss NaN (the
     contract of `dagnn_seq_ce`; there is no `ignore_index`), where torch raises.  Anything else (CPU, other dtypes, strided
     columns) takes `F.cross_entropy`."""
-    fused = isinstance(pred, torch.Tensor) and pred.is_cuda and pred.dtype == torch.float32 and pred.dim() == 2 and \
-        pred.shape[0] > 0 and pred.shape[1] > 0 and pred.stride(1) == 1 and (pred.shape[0] == 1 or pred.stride(0) >= pred.shape[1]) \
-        and targ.numel() == pred.shape[0]
-    if not fused:
+    if not _fused_ok(pred, targ):
         return torch.nn.functional.cross_entropy(pred, targ.reshape(-1).to(pred.device).to(torch.long))
     return _ClassCE.apply(pred, targ)
 
 
 class _ClassCEStep(torch.autograd.Function):
-    """`_ClassCE` through `dagnn_class_ce_step` (csrc/train_step.hip): the same loss and d logits, and in the same launch the
-    step's tokens, its (hits, labelled) pair and the epoch sums on `meter`."""
+    """`_ClassCE` through `dagnn_class_ce_step` (the STEP instance of the same kernel, csrc/loss.hip): the same loss and d
+    logits, and in the same launch the step's tokens, its (hits, labelled) pair and the epoch sums on `meter`."""
 
     @staticmethod
     def forward(ctx, pred, targ, meter):
@@ -102,10 +104,7 @@ class _ClassCEStep(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        # exactly `_ClassCE.backward`: out of place, into rows of the same pitch
-        dl = ctx.dl
-        out = torch.empty(dl.shape[0], dl.stride(0), dtype=dl.dtype, device=dl.device)[:, :dl.shape[1]]
-        return torch.mul(dl, g, out=out), None, None
+        return engine._scale_rows(ctx.dl, g), None, None
 
 
 def class_ce_step(pred: torch.Tensor, targ: torch.Tensor, meter) -> torch.Tensor:
@@ -117,10 +116,7 @@ def class_ce_step(pred: torch.Tensor, targ: torch.Tensor, meter) -> torch.Tensor
     else composes `class_cross_entropy`, the argmax and `class_hits` / `class_hits_host` on the meter."""
     if meter.eos_id is not None:
         raise ValueError("class_ce_step: the meter was made with `eos_id` (a TOK meter)")
-    fused = isinstance(pred, torch.Tensor) and pred.is_cuda and pred.dtype == torch.float32 and pred.dim() == 2 and \
-        pred.shape[0] > 0 and pred.shape[1] > 0 and pred.stride(1) == 1 and (pred.shape[0] == 1 or pred.stride(0) >= pred.shape[1]) \
-        and targ.numel() == pred.shape[0] and meter.device == pred.device
-    if fused:
+    if _fused_ok(pred, targ) and meter.device == pred.device:
         return _ClassCEStep.apply(pred, targ, meter)
     loss = class_cross_entropy(pred, targ)
     from .evaluate import rows_argmax

@@ -192,40 +192,20 @@ class OverlappedGradReducer(object):
 
 
 # ----------------------------------------------------------------------------- the TOK task's loss (main_pyg.py:55-60)
-_CE_COUNTERS = {}
-
-
 class _SeqCE(torch.autograd.Function):
     """Mean cross-entropy over the S heads' logits laid side by side in ONE [B, S * V] tensor, loss and gradient in one HIP
-    launch (`dagnn_seq_ce`, csrc/loss.hip); the backward is one multiplication by the incoming scalar."""
+    launch (`engine.seq_ce`: `dagnn_seq_ce`, csrc/loss.hip); the backward is one multiplication by the incoming scalar."""
 
     @staticmethod
     def forward(ctx, base, y, S, V):
         from . import engine
-        lib = engine._lib.load()
-        B = base.shape[0]
-        dev = base.device
-        need_grad = base.requires_grad
-        # (d logits with rows pitched to a multiple of 4 floats: what the heads' weight-gradient product reads 16 bytes at a time)
-        dl = torch.empty(B, (S * V + 3) // 4 * 4, dtype=torch.float32, device=dev)[:, :S * V] if need_grad else None
-        row = torch.empty(B * S, dtype=torch.float32, device=dev)
-        loss = torch.empty(1, dtype=torch.float32, device=dev)
-        key = (dev.index, engine._stream(base))
-        cnt = _CE_COUNTERS.get(key)
-        if cnt is None:
-            cnt = _CE_COUNTERS[key] = torch.zeros(1, dtype=torch.int32, device=dev)
-        engine.check(lib.dagnn_seq_ce(base.data_ptr(), base.stride(0), y.data_ptr(), B, S, V, None if dl is None else dl.data_ptr(),
-                                      0 if dl is None else dl.stride(0), row.data_ptr(), loss.data_ptr(), cnt.data_ptr(),
-                                      engine._stream(base)), "dagnn_seq_ce")
-        ctx.dl = dl
+        loss, ctx.dl = engine.seq_ce(base, y, S, V, base.requires_grad)
         return loss[0]
 
     @staticmethod
     def backward(ctx, g):
-        # out of place (`backward(retain_graph=True)` may run this again on the same `ctx.dl`), into rows of the same pitch
-        dl = ctx.dl
-        out = torch.empty(dl.shape[0], dl.stride(0), dtype=dl.dtype, device=dl.device)[:, :dl.shape[1]]
-        return torch.mul(dl, g, out=out), None, None, None
+        from . import engine
+        return engine._scale_rows(ctx.dl, g), None, None, None
 
 
 def heads_base(pred_list):
@@ -246,16 +226,23 @@ def heads_base(pred_list):
     return base if base.shape[1] == S * V else None
 
 
+def _fused_ok(pred_list, y_arr: torch.Tensor):
+    """`heads_base(pred_list)` when the one-launch loss can take it with the targets `y_arr` - contiguous int64 [B, S] on a
+    GPU - else None: the predicate of `seq_cross_entropy` and `seq_ce_step`."""
+    base = heads_base(pred_list)
+    ok = base is not None and y_arr.is_cuda and y_arr.dtype == torch.int64 and y_arr.dim() == 2 \
+        and y_arr.shape[1] == len(pred_list) and y_arr.is_contiguous() and y_arr.shape[0] == base.shape[0]
+    return base if ok else None
+
+
 def seq_cross_entropy(pred_list, y_arr: torch.Tensor) -> torch.Tensor:
     """`sum_i CrossEntropyLoss()(pred_list[i], y_arr[:, i]) / len(pred_list)` - the loss of the reference's training loop
     (ogbg-code/main_pyg.py:55-60).  When the list is what `DAGNN.forward` returns on a GPU - views of one [B, S * V] tensor, the
     heads' outputs side by side - loss and gradient are ONE launch (`dagnn_seq_ce`) and the backward pass meets the heads as
     one matrix; any other list takes the plain loop.  Targets must lie in [0, V) (no `ignore_index`)."""
     S = len(pred_list)
-    base = heads_base(pred_list)
-    fused = base is not None and y_arr.is_cuda and y_arr.dtype == torch.int64 and y_arr.dim() == 2 and y_arr.shape[1] == S \
-        and y_arr.is_contiguous() and y_arr.shape[0] == base.shape[0]
-    if not fused:
+    base = _fused_ok(pred_list, y_arr)
+    if base is None:
         loss = 0
         for i in range(S):
             loss = loss + torch.nn.functional.cross_entropy(pred_list[i].to(torch.float32), y_arr[:, i])
@@ -355,8 +342,8 @@ def seq_ce_step_host(logits, y, eos_id: int, ref_ids=None, ref_extra=None, epoch
 
 
 class _SeqCEStep(torch.autograd.Function):
-    """`_SeqCE` through `dagnn_seq_ce_step` (csrc/train_step.hip): the same loss and d logits, and in the same launch the
-    step's tokens, its F1 counts and the epoch sums on `meter`."""
+    """`_SeqCE` through `dagnn_seq_ce_step` (the STEP instance of the same kernel, csrc/loss.hip): the same loss and d logits,
+    and in the same launch the step's tokens, its F1 counts and the epoch sums on `meter`."""
 
     @staticmethod
     def forward(ctx, base, y, S, V, meter, ref_ids, ref_extra):
@@ -372,10 +359,8 @@ class _SeqCEStep(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        # exactly `_SeqCE.backward`: out of place, into rows of the same pitch
-        dl = ctx.dl
-        out = torch.empty(dl.shape[0], dl.stride(0), dtype=dl.dtype, device=dl.device)[:, :dl.shape[1]]
-        return torch.mul(dl, g, out=out), None, None, None, None, None, None
+        from . import engine
+        return engine._scale_rows(ctx.dl, g), None, None, None, None, None, None
 
 
 def seq_ce_step(pred_list, y_arr: torch.Tensor, meter: EpochMeter, ref_ids: Optional[torch.Tensor] = None,
@@ -408,10 +393,8 @@ def seq_ce_step(pred_list, y_arr: torch.Tensor, meter: EpochMeter, ref_ids: Opti
         ref_ids, ref_extra = ((t if t.device == dev else t.pin_memory().to(dev, non_blocking=True)) if dev.type == "cuda" else t
                               for t in (ref_ids, ref_extra))
         ref_ids, ref_extra = ref_ids.to(torch.int32).contiguous(), ref_extra.reshape(B).to(torch.int32).contiguous()
-    base = heads_base(pred_list)
-    fused = base is not None and y_arr.is_cuda and y_arr.dtype == torch.int64 and y_arr.dim() == 2 and y_arr.shape[1] == S \
-        and y_arr.is_contiguous() and y_arr.shape[0] == base.shape[0] and meter.device == base.device
-    if fused:
+    base = _fused_ok(pred_list, y_arr)
+    if base is not None and meter.device == base.device:
         return _SeqCEStep.apply(base, y_arr, S, pred_list[0].shape[1], meter, ref_ids, ref_extra)
     off = meter.room(B) if ref_ids is not None else 0
     loss = seq_cross_entropy(pred_list, y_arr)

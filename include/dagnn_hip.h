@@ -1294,8 +1294,9 @@ int dagnn_seq_f1_counts(const int64_t* tok, int64_t B, int S, int64_t eos_id, co
  *   wave per graph, no atomics.  B = 0 returns at once.
  * Targets below are int64, float32 or float64 [B] (`targ_kind`): what the reference concatenates and hands to
  *   `.to(torch.long)` / to the evaluator.
- * dagnn_class_ce: `CrossEntropyLoss()(pred, targ.to(torch.long))` (main_pyg_lp.py:56-58) = dagnn_seq_ce with S = 1 - same
- *   arguments, same sums in the same order, same counter protocol - with the target truncated toward zero in the kernel.
+ * dagnn_class_ce: `CrossEntropyLoss()(pred, targ.to(torch.long))` (main_pyg_lp.py:56-58) = dagnn_seq_ce with S = 1 - the
+ *   same kernel (csrc/loss.hip), so the same arguments, sums and counter protocol; with int64 targets the same bits - with
+ *   the target truncated toward zero in the kernel.
  *   dlogits = (softmax - onehot) / B.  A target outside [0, C) (a NaN included) makes the loss NaN.
  * dagnn_class_hits: out [2] int64 = (hits, labelled) of `Evaluator._eval_acc` (ogb/graphproppred/evaluate.py:221-229) over
  *   one batch.  Predictions are EITHER logits [B, ld >= C] - argmax in the order stated above dagnn_heads_argmax: lowest
@@ -1317,12 +1318,12 @@ int dagnn_class_hits(const float* logits, int64_t ld, const int64_t* tok, int64_
                      void* work, size_t work_bytes, unsigned* counter, int64_t* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
- * The loss launch of a training step with the epoch's bookkeeping in it (csrc/train_step.hip; `train()` of
+ * The loss launch of a training step with the epoch's bookkeeping in it (csrc/loss.hip; `train()` of
  * ogbg-code/main_pyg.py:39-88 and main_pyg_lp.py:43-74: `loss_accum += loss.item()`, the argmax of the training logits and
  * the evaluator's counts, per step).
  *
- * dagnn_seq_ce_step: dagnn_seq_ce - same arguments up to `loss`, same sums in the same order, same counter protocol: loss
- *   and dlogits are dagnn_seq_ce's bits - and in the same launch
+ * dagnn_seq_ce_step: dagnn_seq_ce - same arguments up to `loss`, the same kernel and row stage (csrc/rows_dev.h), same
+ *   counter protocol: loss and dlogits are dagnn_seq_ce's bits - and in the same launch
  *     tok [B, S] int64: each row's argmax in the order stated above dagnn_heads_argmax (lowest column among equals, a NaN
  *       beats every number, -0 == +0): what dagnn_rows_argmax gives;
  *     epoch_sum [1] float64 += (double)loss and epoch_steps [1] int64 += 1, by one thread of the workgroup that finishes

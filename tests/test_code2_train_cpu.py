@@ -1,4 +1,4 @@
-"""The ogbg-code2 training epoch, CPU tier (-m "not gpu"): the numpy mirrors of the csrc/train_step.hip kernels, `EpochMeter`,
+"""The ogbg-code2 training epoch, CPU tier (-m "not gpu"): the numpy mirrors of the STEP kernels of csrc/loss.hip, `EpochMeter`,
 the host route of `seq_ce_step` / `class_ce_step`, `GraphStore.train_tok` / `train_lp` on a CPU store with a small torch model,
 against torch's own operations and against fixtures generated from the reference's `train()` loop bodies
 (tests/golden/make_golden_code2_train.py).  Integer results and the float64 epoch sum are compared exactly."""

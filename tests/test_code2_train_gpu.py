@@ -1,4 +1,4 @@
-"""The ogbg-code2 training epoch on the GPU (-m gpu): the two kernels of csrc/train_step.hip against the entry points they
+"""The ogbg-code2 training epoch on the GPU (-m gpu): the two STEP instances of csrc/loss.hip's kernel against the entry points they
 fuse - bit for bit, no tolerance -, the epoch accumulators, `GraphStore.train_tok` / `train_lp` against the loop written out on
 the pieces, against the fixtures of the reference's own `train()` loop bodies (tests/golden/make_golden_code2_train.py),
 and that nothing synchronises inside the loop.
@@ -188,6 +188,47 @@ def test_class_step_kernel_is_bitwise_the_pieces(device, C, B, kind):
             assert np.isnan(float(esum)) == np.isnan(float(loss))
     if B > 2 and C > 1:                                # (the last variant: one NaN target among the float kinds)
         assert int(pair[0]) > 0 and int(pair[1]) == (B if kind == "int64" else B - 1)
+
+
+@pytest.mark.parametrize("B,C", [(1, 1), (3, 255), (3, 257), (65, 300), (5, 5002)])
+def test_class_ce_is_bitwise_seq_ce_with_one_head(device, B, C):
+    """`dagnn_class_ce` with int64 targets and `dagnn_seq_ce` with S = 1 are two instances of one kernel around one row stage
+    (csrc/loss.hip, csrc/rows_dev.h): on the same logits `loss`, `row_loss` and `dlogits` are the same bits, NaN where NaN.
+    Rows from the back (`special_rows`): a two-way tie, a NaN, one finite value among -inf; with every target in range, then
+    with the target of row 0 out of range."""
+    lib = L.load()
+    g = torch.Generator().manual_seed(7000 * B + C)
+    x = torch.randn(B, C, generator=g)
+    cases = special_rows(x, C)
+    assert C < 2 or "tie" in cases and (B < 2 or "nan" in cases)
+    ld, ld_d = C + 3, (C + 3) // 4 * 4
+    logits = torch.full((B, ld), NAN, device=device)
+    logits[:, :C] = x.to(device)
+    st = engine._stream(logits)
+    targ = torch.randint(0, C, (B,), generator=g)
+    for out_of_range in (False, True):
+        if out_of_range:
+            targ[0] = C
+        t_dev = targ.to(device)
+        got = []
+        for entry in ("class", "seq"):
+            dl = torch.full((B, ld_d), NAN, device=device)
+            row, loss = torch.full((B,), SENT, dtype=torch.float32, device=device), torch.full((1,), SENT, dtype=torch.float32, device=device)
+            ticket = torch.zeros(1, dtype=torch.int32, device=device)
+            if entry == "class":
+                rc = lib.dagnn_class_ce(logits.data_ptr(), ld, t_dev.data_ptr(), L.LP_INT64, B, C, dl.data_ptr(), ld_d,
+                                        row.data_ptr(), loss.data_ptr(), ticket.data_ptr(), st)
+            else:
+                rc = lib.dagnn_seq_ce(logits.data_ptr(), ld, t_dev.data_ptr(), B, 1, C, dl.data_ptr(), ld_d, row.data_ptr(),
+                                      loss.data_ptr(), ticket.data_ptr(), st)
+            assert rc == 0 and int(ticket) == 0
+            got.append((loss, row, dl))
+        (loss_c, row_c, dl_c), (loss_s, row_s, dl_s) = got
+        assert same(loss_c, loss_s) and same(row_c, row_s) and same(dl_c, dl_s)   # (the pitch's padding columns: both left NaN)
+        nan_rows = torch.isnan(row_c).nonzero().view(-1).tolist()
+        want = sorted(({0} if out_of_range else set()) | ({cases["nan"]} if "nan" in cases else set()))
+        assert nan_rows == want and bool(torch.isnan(loss_c)) == bool(want)
+        assert torch.isnan(dl_c[:, :C]).any(dim=1).nonzero().view(-1).tolist() == ([cases["nan"]] if "nan" in cases else [])
 
 
 # ============================================================================= 3. the accumulators
