@@ -160,7 +160,7 @@ class Recurrence(torch.autograd.Function):
         keep = {}
         sscore = mod._static_scores(x, cells)   # keys from the inputs (`*_x` aggregators): one score per node and cell
         h = run_stack_lockstep(plan, x, cells, dirs, L, H, vid_nodes=mod._vid_nodes, arena=mod._arena_for(x), keep=keep,
-                               static_score=sscore)
+                               static_score=sscore, route=plan.route)
         ctx.mod, ctx.plan, ctx.cells, ctx.keep, ctx.h, ctx.fused = mod, plan, cells, keep, h, bool(fused)
         ctx.sscore = sscore
         ctx.save_for_backward(x, *[p for p in params if p is not None])
@@ -191,10 +191,8 @@ class Recurrence(torch.autograd.Function):
                 for i in range(L):
                     if gouts[q * L + i] is not None:
                         g_ext[d][i][:, :H] = gouts[q * L + i]
-        groups = keep.get("groups", 0)
-        if groups > 0 and engine.bwd_dataflow_groups(dev, len(dirs), L, Hp, plan.B) == groups and \
-                engine.bwd_dataflow_fits(dev, N, len(dirs) * L):
-            res = engine.bwd_dataflow_sweep(plan, dirs, L, Hp, cells, keep["h_buf"], keep["gi0"], g_ext, groups,
+        if keep["route"].reverse == "dataflow":   # (decided with the forward's path: it runs on the forward's schedule)
+            res = engine.bwd_dataflow_sweep(plan, dirs, L, Hp, cells, keep["h_buf"], keep["gi0"], g_ext, keep["route"].groups,
                                             arena=mod._arena_for(x, "backward"), vid_mod=mod._vid_nodes,
                                             static_score=ctx.sscore, preact=keep.get("preact"))
         else:

@@ -19,6 +19,7 @@ import torch
 import torch.nn as nn
 
 from . import engine
+from . import route as routing
 from ._lib import DagnnHipError
 
 
@@ -326,8 +327,10 @@ def derive_cell(w_ih, w_hh, b_ih, b_hh, attn_w, H: int, dq: int, in_is_hidden: b
     `stacked` is the number of stacked cells of the model: it only picks the padded width (`engine.state_width`).
     """
     lock = schedule == "lockstep"
-    wide_ok = edge_w is not None and not vid_nodes and (key_dim is None or key_dim == H)   # what dagnn_dataflow_run_wide takes
-    Hp = engine.state_width(H, stacked, 0 if edge_w is None else int(edge_w.shape[1]), wide_ok=wide_ok) if lock else round_up4(H)
+    # the dataflow kernel's layout instead of the launches' (packed below) where `routing.width` says the kernel serves the cell
+    # - a 320-wide cell it does not serve would otherwise be packed twice on every training step
+    Hp, use_df = routing.width(H, stacked, 0 if edge_w is None else int(edge_w.shape[1]), key_dim is None or key_dim == H,
+                             vid_nodes, edge_w is not None) if lock else (round_up4(H), False)
     c = CellParams()
     c.Hp = Hp
     c.fold = None   # (model._folded_tables: the encoder's tables folded through this cell's W_ih, stacked layer 0 only)
@@ -343,11 +346,6 @@ def derive_cell(w_ih, w_hh, b_ih, b_hh, attn_w, H: int, dq: int, in_is_hidden: b
     c.w_hh_pk = c.w_ih_pk = None
     c.w_hh_df = c.w_ih_df = None
     c.w_hh_bt = c.w_ih_bt = None   # reverse sweep: packed gate-wise transposes (engine.bwd_dataflow_sweep)
-    # the dataflow kernel's layout instead (packed below); a 320-wide cell only where `dagnn_dataflow_run_wide` applies (two
-    # edge features, hidden-state keys, no vertex-id biases) - other 320-wide shapes run on the per-layer launches and
-    # would otherwise be packed twice on every training step
-    use_df = bool(engine.DATAFLOW and engine.dataflow_width(Hp) and
-                  (Hp <= 256 or (wide_ok and edge_w is not None and int(edge_w.shape[1]) == 2)))
     c.df_ok = use_df
     if lock and pack and not use_df:   # pack=False: the caller batches the packing of all its cells (pack_lockstep)
         c.w_hh_pk = {js: engine.pack_slices(whh, Hp, js) for js in (16, 32)}
@@ -378,28 +376,22 @@ def derive_cell(w_ih, w_hh, b_ih, b_hh, attn_w, H: int, dq: int, in_is_hidden: b
 _OFF_DATAFLOW_SEEN = set()
 
 
-def _warn_off_dataflow(dev, ndirs: int, L: int, Hp: int) -> None:
+def _warn_off_dataflow(dev, ndirs: int, L: int, r: routing.Route) -> None:
     """Say ONCE per model shape that it runs on the per-layer launches instead of the persistent dataflow kernel (which
-    is 1.5-2x faster where it applies): the applicability limits are otherwise a silent cliff."""
+    is 1.5-2x faster where it applies): the applicability limits are otherwise a silent cliff.  The reason is the route's
+    own (`r.why`); only a 0 that came back from the library is explained here."""
+    Hp, why = r.Hp, r.why
     key = (str(dev), ndirs, L, Hp)
-    if key in _OFF_DATAFLOW_SEEN:
+    if why in routing.QUIET or key in _OFF_DATAFLOW_SEEN:
         return
     _OFF_DATAFLOW_SEEN.add(key)
     import warnings
     cells = ndirs * (2 * L - 1)
     cus = torch.cuda.get_device_properties(dev).multi_processor_count
-    if Hp == 320 and not engine.DF_WIDE:
-        why = "DAGNN_AMD_DF_WIDE=0 keeps hidden sizes 257..320 off the dataflow kernel's 320-wide shape"
-    elif Hp == 320:
-        why = "hidden size 320 runs on the dataflow kernel only with exactly two edge features, hidden-state keys and no vertex-id key biases"
-    elif Hp > 256:
-        why = "hidden size %d > 256 (a 32-unit slice of the [3H, H] matrices no longer fits the register file)" % Hp
-    elif cells > 24:
+    if why == routing.LIB and cells > 24:
         why = "%d kernel cells (directions x (2 x stacked layers - 1)) > 24" % cells
-    elif cells * (Hp // 32) > cus:
+    elif why == routing.LIB and cells * (Hp // 32) > cus:
         why = "%d kernel cells x %d slices need more than the %d CUs of this device" % (cells, Hp // 32, cus)
-    else:
-        why = "the kernel does not apply to this shape"
     warnings.warn("dagnn_amd: this model (hidden %d, %d stacked layers, %d direction(s)) runs on the per-layer launch path, "
                   "not the persistent dataflow kernel: %s" % (Hp, L, ndirs, why), RuntimeWarning, stacklevel=3)
 
@@ -407,12 +399,16 @@ def _warn_off_dataflow(dev, ndirs: int, L: int, Hp: int) -> None:
 def run_stack_lockstep(plan: engine.PlanHandle, x: torch.Tensor, cells: Dict[Tuple[int, int], CellParams],
                        dirs: Sequence[int], L: int, H: int, vid_nodes: int = 0,
                        arena: Optional[engine.GranuleArena] = None, static_score=None,
-                       keep: Optional[dict] = None, gi0: Optional[Sequence[torch.Tensor]] = None) -> List[List[torch.Tensor]]:
-    """Lock-step schedule (default): one batched input GEMM for stacked layer 0 of every direction,
-    then T + L - 1 frontier launches covering all cells (csrc/frontier.hip).  `keep` (training) receives
-    what the backward pass needs: the raw state buffers (`h_buf`) and `gi0`.  `gi0` (one [N, 3Hp] per direction): the
-    input-side pre-activations of stacked layer 0 when the caller already has them (model._folded_gi0)."""
-    Hp = cells[(dirs[0], 0)].Hp
+                       keep: Optional[dict] = None, gi0: Optional[Sequence[torch.Tensor]] = None,
+                       route: Optional[routing.Route] = None) -> List[List[torch.Tensor]]:
+    """Lock-step schedule (default): one batched input GEMM for stacked layer 0 of every direction, then the recurrence
+    on the path `routing.with_plan` names: the persistent dataflow kernel, the tile kernel, or T + L - 1 frontier launches
+    covering all cells (csrc/frontier.hip), with or without the tile kernel on the thin tail.  `keep` (training) receives
+    what the backward pass needs: the raw state buffers (`h_buf`), `gi0` and the route.  `gi0` (one [N, 3Hp] per
+    direction): the input-side pre-activations of stacked layer 0 when the caller already has them (model._folded_gi0).
+    `route`: what `routing.before_plan` told the caller that built the plan; it counts if it is for these cells' width."""
+    c0 = cells[(dirs[0], 0)]
+    Hp, keys_hidden = c0.Hp, c0.w_key is not None and static_score is None   # (keys: the hidden states, or one static score per node)
     N, dev = x.shape[0], x.device
     if gi0 is None:
         gi0 = engine.gemm_nt_bias([x] * len(dirs), [cells[(d, 0)].w_ih for d in dirs], [cells[(d, 0)].b_ih for d in dirs])
@@ -423,58 +419,47 @@ def run_stack_lockstep(plan: engine.PlanHandle, x: torch.Tensor, cells: Dict[Tup
     h = [[torch.empty(N, ld, dtype=torch.float32, device=dev) if d in dirs else None for _ in range(L)]
          for d in range(2)]
     plan.wait_ready()   # a plan built on the side stream (model._plan_of) meets the caller's stream here
-    groups = engine.dataflow_groups(dev, len(dirs), L, Hp, plan.B, training=keep is not None) if (arena is not None and N > 0) else 0
-    if N * 3 * Hp >= (1 << 31):   # the dataflow kernels address their granule buffers with 32-bit row offsets
-        groups = 0
-    if Hp > 256 and (plan.R != 2 or static_score is not None or vid_nodes or any(c.edge_gain is None or c.w_key is None for c in cells.values())):
-        groups = 0   # the H = 320 shape has the lean loaders only (dagnn_dataflow_run_wide)
+    active, train = arena is not None and N > 0, keep is not None
+    if route is None or route.Hp != Hp:
+        route = routing.before_plan(dev, H, L, len(dirs), plan.R, plan.B, keys_hidden, vid_nodes, c0.edge_gain is not None, train,
+                                    Hp=Hp, active=active)
+    route = routing.with_plan(route, dev, plan, dirs, L, N, keys_hidden, active, train)
     if arena is not None:
         arena.poll()   # a failure an earlier pass reported (no synchronisation); either path below is watched
-    tiles = 0
-    if groups == 0 and arena is not None and N > 0 and static_score is None and \
-            N * ld * 4 < (1 << 31) - 16 and all(cells[(d, 0)].w_key is not None for d in dirs):
-        tiles = engine.tiles_launches(dev, len(dirs), L, Hp, plan.R, N)   # wide states (H = 512): csrc/tiles.hip
-        if tiles > 0 and engine.tiles_batch_too_flat(plan, dirs):
-            tiles = 0   # few wide layers: the launches' 32-row tiles win (no thin tail either: the split below says None)
-    if groups == 0 and tiles == 0 and arena is not None and N > 0 and engine.DATAFLOW and not (engine.TILES == 1 and L >= 2 and Hp == 512):
-        _warn_off_dataflow(dev, len(dirs), L, Hp)
-    split = None
-    if tiles == 0 and groups == 0 and engine.TILES == 1 and L >= 2 and arena is not None and N > 0 and static_score is None and \
-            N * ld * 4 < (1 << 31) - 16 and all(cells[(d, 0)].w_key is not None for d in dirs) and \
-            engine._lib.load().dagnn_tiles_launches(engine._num_cus(dev), len(dirs), L, Hp, plan.R) > 0:
-        split = engine.tiles_tail_split(plan, dirs)   # a batch too large for the tile kernel alone: it takes the thin tail
-    if tiles > 0:
+    if route.kind == "tiles":
         engine.tiles_run(plan, dirs, L, Hp, cells, gi, h, arena, vid_mod=vid_nodes)
-    elif split is not None:
+    elif route.kind == "launches+tiles":
         pack_lockstep(cells.values(), force=True)
-        engine.frontier_run(plan, dirs, L, Hp, cells, gi, h, vid_mod=vid_nodes, arena=None, static_score=static_score, stop_layer=split,
-                            chains=arena)
-        engine.tiles_run(plan, dirs, L, Hp, cells, gi, h, arena, first_layer=split, vid_mod=vid_nodes)
-    elif groups > 0:
-        pack_dataflow(cells.values(), transposed_too=keep is not None and bool(engine.BWD_DATAFLOW))
-        preact = {} if (keep is not None and engine.BWD_DATAFLOW) else None
-        if preact is not None and engine.stat_rows_ok(dev, N, Hp, len(dirs), L, plan.B, groups):
+        engine.frontier_run(plan, dirs, L, Hp, cells, gi, h, vid_mod=vid_nodes, arena=None, static_score=static_score,
+                            stop_layer=route.split, chains=arena)
+        engine.tiles_run(plan, dirs, L, Hp, cells, gi, h, arena, first_layer=route.split, vid_mod=vid_nodes)
+    elif route.kind == "dataflow":
+        pack_dataflow(cells.values(), transposed_too=train and bool(engine.BWD_DATAFLOW))
+        preact = {} if (train and engine.BWD_DATAFLOW) else None
+        if route.stat_rows:
             preact["stat_rows"] = True
-        engine.dataflow_run(plan, dirs, L, Hp, cells, gi, h, groups, vid_mod=vid_nodes, arena=arena,
-                            static_score=static_score, score_parts=keep is not None, preact=preact, training=keep is not None)
-        if keep is not None:
+        engine.dataflow_run(plan, dirs, L, Hp, cells, gi, h, route.groups, vid_mod=vid_nodes, arena=arena,
+                            static_score=static_score, score_parts=train, preact=preact, training=train)
+        if train:
             keep["preact"] = preact
     else:
+        _warn_off_dataflow(dev, len(dirs), L, route)
         pack_lockstep(cells.values(), force=True)
         engine.frontier_run(plan, dirs, L, Hp, cells, gi, h, vid_mod=vid_nodes, arena=arena, static_score=static_score, chains=arena)
-    if keep is not None:
-        keep["h_buf"], keep["gi0"], keep["Hp"], keep["groups"] = h, gi, Hp, groups
+    if train:
+        keep["h_buf"], keep["gi0"], keep["Hp"], keep["route"] = h, gi, Hp, route
     return [[h[d][i][:, :H] if h[d][i] is not None else None for i in range(L)] for d in range(2)]
 
 
 def run_stack(plan: engine.PlanHandle, x: torch.Tensor, cells: Dict[Tuple[int, int], CellParams],
               dirs: Sequence[int], L: int, H: int, vid_nodes: int = 0,
               schedule: str = "pergraph", arena: Optional[engine.GranuleArena] = None,
-              static_score=None, gi0: Optional[Sequence[torch.Tensor]] = None) -> List[List[torch.Tensor]]:
+              static_score=None, gi0: Optional[Sequence[torch.Tensor]] = None,
+              route: Optional[routing.Route] = None) -> List[List[torch.Tensor]]:
     """Hidden states h[d][i] ([N, H] each) of all stacked layers and directions.  `static_score[(d, i)]`
     ([N]) replaces the hidden-state attention scores for the aggregators whose keys are the inputs."""
     if schedule == "lockstep":
-        return run_stack_lockstep(plan, x, cells, dirs, L, H, vid_nodes, arena, static_score, gi0=gi0)
+        return run_stack_lockstep(plan, x, cells, dirs, L, H, vid_nodes, arena, static_score, gi0=gi0, route=route)
     Hp = round_up4(H)
     N = x.shape[0]
     dev = x.device

@@ -28,6 +28,7 @@ from . import constants as K
 from . import engine
 from .core import HipModule, default_schedule, derive_cell, pack_lockstep, run_stack
 from .data import GraphBatch
+from .route import dataflow_only
 
 ENCODE_FUSED = int(__import__("os").environ.get("DAGNN_AMD_ENCODE_FUSED", "1"))   # 1: evaluation passes of the encoders as ONE library call (csrc/encode.hip)
 OWN_LINEAR_MAX = 1 << 22   # multiply-adds up to which the final Linear of an evaluation pass runs on dagnn_gemm_nt_bias (see forward)
@@ -970,9 +971,7 @@ class _DvaeDagnn(_DvaeBase):
         cells = self._cells()
         Hp = cells[(dirs[0], 0)].Hp
         N, dev = x.shape[0], x.device
-        if N == 0 or not engine.dataflow_width(Hp) or Hp > 256 or N * 3 * Hp >= (1 << 31):
-            return None
-        groups = engine.dataflow_groups(dev, len(dirs), L, Hp, B)
+        groups = dataflow_only(dev, len(dirs), L, Hp, B, N)
         if groups <= 0:
             return None
         lib = _lib.load()

@@ -264,6 +264,8 @@ def _status_words(device) -> torch.Tensor:
 class PlanHandle(object):
     """Device workspace holding the layer-sorted per-graph CSR of one batch (both directions)."""
 
+    route = None   # what `route.before_plan` said (width, dataflow groups) where the plan's builder asked, for the pass to go on from
+
     def __init__(self, N: int, E: int, B: int, R: int, device):
         lib = _lib.load()
         self.N, self.E, self.B, self.R = int(N), int(E), int(B), int(R)
@@ -628,7 +630,7 @@ def effective_cus(device, training: bool = False) -> int:
 def dataflow_groups(device, num_dirs: int, num_stacked: int, H: int, B: int, training: bool = False) -> int:
     """Groups the dataflow kernel runs on this device for this model shape; 0 = not applicable.  `training`: a pass
     whose reverse sweep may overlap a gradient collective (`reserved_cus`)."""
-    if not DATAFLOW or not dataflow_width(int(H)):
+    if not DATAFLOW or not (H <= 256 or (H == 320 and DF_WIDE)):   # (320: `dagnn_dataflow_run_wide`, for the models `route.width` names)
         return 0
     cus = effective_cus(device, training)
     g = _lib.load().dagnn_dataflow_groups(cus, int(num_dirs), int(num_stacked), int(H), int(B))
@@ -663,13 +665,6 @@ def lib_static_floats(N: int, H: int) -> int:
 
 
 STAT_FWD = _env_int("DAGNN_AMD_STAT_FWD", 1)   # 1: a training pass's forward launch writes the reverse sweep's static rows itself
-
-
-def stat_rows_ok(device, N: int, H: int, num_dirs: int, L: int, B: int, groups: int) -> bool:
-    """Whether the forward dataflow launch of a training pass should write the reverse sweep's static rows (`stat_rows`):
-    the reverse pass will be `bwd_dataflow_sweep` on the same schedule, and a node's record is addressable with 32 bits."""
-    return bool(STAT_FWD) and groups > 0 and N > 0 and bwd_dataflow_groups(device, num_dirs, L, H, B) == groups and \
-        bwd_dataflow_fits(device, N, num_dirs * L) and lib_static_floats(N, H) * 4 < (1 << 32)
 
 
 def dataflow_args(plan: PlanHandle, dirs: Sequence[int], L: int, H: int, cells, gi0, h, groups: int, vid_mod: int = 0,
@@ -735,12 +730,6 @@ def dataflow_args(plan: PlanHandle, dirs: Sequence[int], L: int, H: int, cells, 
 
 
 DF_WIDE = _env_int("DAGNN_AMD_DF_WIDE", 1)   # 1: hidden sizes 257..320 run 320 wide on the dataflow kernel (csrc/dataflow_w.hip)
-
-
-def dataflow_width(Hp: int) -> bool:
-    """Padded widths the forward dataflow kernel exists for: multiples of 64 up to 256, and 320 (`dagnn_dataflow_run_wide`:
-    two edge features, hidden-state keys, no vertex-id key biases - `state_width` only picks 320 for such models)."""
-    return Hp <= 256 or (Hp == 320 and bool(DF_WIDE))
 
 
 def state_width(H: int, num_stacked: int = 1, num_edge_feats: int = 0, wide_ok: bool = False) -> int:
@@ -1299,14 +1288,6 @@ def pack_dataflow_transposed(w: torch.Tensor, H: int) -> torch.Tensor:
     check(_lib.load().dagnn_pack_dataflow_transposed(w.data_ptr(), out.data_ptr(), H, _stream(w)),
           "dagnn_pack_dataflow_transposed")
     return out
-
-
-def bwd_dataflow_groups(device, num_dirs: int, num_stacked: int, H: int, B: int) -> int:
-    """Groups the reverse dataflow launch runs with (same cell count and workgroup shape as the forward kernel, so the
-    forward pass's schedule workspace serves both); 0 = not applicable."""
-    if not BWD_DATAFLOW or not dataflow_width(int(H)):
-        return 0
-    return dataflow_groups(device, num_dirs, num_stacked, H, B, training=True)
 
 
 # cap on what the reverse dataflow sweep may keep: unset (-1) = a third of the device's memory (96 GB on an MI355X); a value is

@@ -23,7 +23,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import constants as K
-from . import engine
+from . import engine, route
 from .core import HipModule, built_marker, default_schedule, derive_cell, meet_built, num_graphs_of, pack_lockstep, run_stack
 
 
@@ -372,26 +372,30 @@ class DAGNN(HipModule):
         enc = self.encoder
         if not (self._rows_ok(x_idx, depth) and tabs[0].shape[1] % 4 == 0 and G.edge_index.is_cuda):
             return None
-        has_edge_enc = getattr(self.node_aggr_0[0], "wea", False)
-        ea = G.edge_attr if has_edge_enc else None
         dev, N = x_idx.device, x_idx.shape[0]
-        R = 0 if ea is None else int(ea.numel() // max(1, G.edge_index.shape[1]))
-        wide_ok = has_edge_enc and not (self.agg_x or self.agg_attn_x)
-        Hp = engine.state_width(self.hidden_dim, self.num_layers, R, wide_ok=wide_ok)
-        groups = engine.dataflow_groups(dev, len(self.dirs), self.num_layers, Hp, B, training=False)
+        ea, r = self._route0(G, B, training=False)
         tables = [(*tabs, torch.empty(N, tabs[0].shape[1], dtype=torch.float32, device=dev))]
         folded = self._folded_tables(cells)
         gi0 = None
         if folded is not None:
             gi0 = [torch.empty(N, t.shape[1], dtype=torch.float32, device=dev) for (t, _, _) in folded]
             tables += [(t, a, dp, o) for (t, a, dp), o in zip(folded, gi0)]
-        srcs = [G._bi_layer_idx0, G._bi_layer_index0, G._bi_layer_idx1, G._bi_layer_index1]
         lidx = torch.empty(4, N, dtype=torch.int64, device=dev)
         plan = engine.build_plan(G.edge_index, G._bi_layer_idx0, G._bi_layer_idx1, G.batch, B, ea, launch=False)
-        plan.launch_prepare(groups, enc=(x_idx, depth, enc.max_depth, tables), stack=(srcs, lidx))
+        plan.route = r
+        plan.launch_prepare(r.groups, enc=(x_idx, depth, enc.max_depth, tables), stack=(self._layer_index_srcs(G), lidx))
         G.bi_layer_index = lidx.view(2, 2, -1)   # side effect 1 (dagnn.py:130-133)
         G.x = tables[0][3]                       # side effects 2 + 3 (dagnn.py:139, utils.py:27)
         return plan, gi0
+
+    def _route0(self, G, B, training: bool):
+        """(the edge features the batch's plan carries, `route.before_plan` of this model on this batch): the padded width
+        and the dataflow kernel's group count, which the plan's schedule is built for and the recurrence goes on from."""
+        has_edge_enc = getattr(self.node_aggr_0[0], "wea", False)
+        ea = G.edge_attr if has_edge_enc else None
+        R = 0 if ea is None else int(ea.numel() // max(1, G.edge_index.shape[1]))
+        return ea, route.before_plan(G.edge_index.device, self.hidden_dim, self.num_layers, len(self.dirs), R, B,
+                                     keys_hidden=not (self.agg_x or self.agg_attn_x), edge_enc=has_edge_enc, training=training)
 
     def _training_pass(self) -> bool:
         """True when this call must be differentiable.  The HIP backward (csrc/backward.hip) covers the additive-attention
@@ -505,24 +509,20 @@ class DAGNN(HipModule):
                 return engine.PlanHandle.from_words(G._dagnn_plan, G._dagnn_plan_meta, getattr(G, "_dagnn_df", None))
             # the loader packed edge features this model has no encoder for (w_edge_attr=False): the kernels would
             # want an edge gain per feature - build the plan without them here instead
-        ea = G.edge_attr if has_edge_enc else None
         if not (overlap and G.edge_index.is_cuda and self.schedule == "lockstep"):
             if overlap:
                 self._set_layer_index(G)
-            return engine.build_plan(G.edge_index, G._bi_layer_idx0, G._bi_layer_idx1, G.batch, B, ea)
+            return engine.build_plan(G.edge_index, G._bi_layer_idx0, G._bi_layer_idx1, G.batch, B, G.edge_attr if has_edge_enc else None)
         dev = G.edge_index.device
-        # the same (width, group count) key `run_stack_lockstep` will ask for: hidden sizes 257..320 run 320 wide on the
-        # dataflow kernel (`wide_ok`), a training pass under an active communicator reserves CUs for the collective
-        R = 0 if ea is None else int(ea.numel() // max(1, G.edge_index.shape[1]))
-        wide_ok = has_edge_enc and not (self.agg_x or self.agg_attn_x)
-        Hp = engine.state_width(self.hidden_dim, self.num_layers, R, wide_ok=wide_ok)
-        groups = engine.dataflow_groups(dev, len(self.dirs), self.num_layers, Hp, B, training=self._training_pass())
+        ea, r = self._route0(G, B, self._training_pass())   # (`plan.route`: the recurrence goes on from it)
+        groups = r.groups
         # every buffer comes from the CALLER's pool (no `record_stream`, no foreign-pool blocks that cannot be reused: a forward
         # that allocated under a side stream cost seven hipMalloc calls per batch); only the launches may go to a side stream
         plan = engine.build_plan(G.edge_index, G._bi_layer_idx0, G._bi_layer_idx1, G.batch, B, ea, launch=False)
+        plan.route = r
         if groups > 0:
             plan.dataflow_schedule(groups, launch=False)
-        srcs = [G._bi_layer_idx0, G._bi_layer_index0, G._bi_layer_idx1, G._bi_layer_index1]
+        srcs = self._layer_index_srcs(G)
         stack = None
         if engine.PREPARE_FUSED and all(t.is_cuda and t.dtype == torch.int64 and t.is_contiguous() for t in srcs):
             stack = (srcs, torch.empty(4, srcs[0].shape[0], dtype=torch.int64, device=dev))
@@ -554,10 +554,13 @@ class DAGNN(HipModule):
         return plan
 
     @staticmethod
-    def _set_layer_index(G, out=None):
+    def _layer_index_srcs(G):
+        return [G._bi_layer_idx0, G._bi_layer_index0, G._bi_layer_idx1, G._bi_layer_index1]
+
+    @classmethod
+    def _set_layer_index(cls, G):
         """side effect 1 (dagnn.py:130-133): `G.bi_layer_index` [2, 2, N] (one copy kernel instead of three)"""
-        srcs = [G._bi_layer_idx0, G._bi_layer_index0, G._bi_layer_idx1, G._bi_layer_index1]
-        G.bi_layer_index = (torch.stack(srcs, dim=0) if out is None else torch.stack(srcs, dim=0, out=out)).view(2, 2, -1)
+        G.bi_layer_index = torch.stack(cls._layer_index_srcs(G), dim=0).view(2, 2, -1)
 
     # ------------------------------------------------------------------------------ forward
     def forward(self, G):
@@ -632,8 +635,7 @@ class DAGNN(HipModule):
             if not G.x.is_cuda:
                 raise engine.DagnnHipError("DAGNN.forward needs its batch on a ROCm GPU (there is no CPU path)")
             from . import variants
-            G.bi_layer_index = torch.stack([G._bi_layer_idx0, G._bi_layer_index0, G._bi_layer_idx1, G._bi_layer_index1],
-                                        dim=0).view(2, 2, -1)   # (one copy kernel instead of three)
+            self._set_layer_index(G)
             B = num_graphs_of(G)
             G.x = self.encoder(G.x, G.node_depth.view(-1, ))
             if self.variant_backend == "torch" or (torch.is_grad_enabled()
@@ -663,7 +665,7 @@ class DAGNN(HipModule):
                 x = G.x
                 sscore = self._static_scores(x, cells)
                 h = run_stack(plan, x, cells, dirs, L, H, schedule=self.schedule, static_score=sscore,
-                              arena=self._arena_for(x), gi0=gi0)
+                              arena=self._arena_for(x), gi0=gi0, route=plan.route)
                 self._guard_params(x)
                 return self._finish(G, plan, x, h, B, head)
         # side effect 1 (dagnn.py:130-133) + the plan: on a side stream next to the encoder and the input GEMM, which do not
@@ -684,7 +686,7 @@ class DAGNN(HipModule):
         cells = self._cells()
         sscore = self._static_scores(x, cells)
         h = run_stack(plan, x, cells, dirs, L, H, schedule=self.schedule, static_score=sscore,
-                      arena=self._arena_for(x), gi0=self._folded_gi0(x_idx, depth, cells))
+                      arena=self._arena_for(x), gi0=self._folded_gi0(x_idx, depth, cells), route=plan.route)
         self._guard_params(x)
         return self._finish(G, plan, x, h, B, head)
 

@@ -33,6 +33,7 @@ from typing import List, Optional
 import torch
 
 from . import _lib, engine
+from .route import dataflow_only
 
 
 def _segment_softmax(logit: torch.Tensor, seg: torch.Tensor, num_seg: int) -> torch.Tensor:
@@ -263,7 +264,7 @@ def run_plain_dataflow(mod, x: torch.Tensor, plan) -> Optional[List[List[Optiona
                     zkey = torch.zeros(1, H, dtype=torch.float32, device=dev)   # (no keys: derive_cell's attention slots stay unused)
                 c = derive_cell(cell.weight_ih, cell.weight_hh, cell.bias_ih, cell.bias_hh, zkey, H, 0, i > 0, None, 0,
                                 schedule="lockstep", pack=False, stacked=L)
-                if c.Hp > 256 or not c.df_ok:
+                if not c.df_ok:   # (`route.width`: wider than 256)
                     return None
                 c.agg = 3 if (shared_flow and d == 1) else (1 if mod.agg == "add" else 2)
                 c.agg_w = c.agg_b = None
@@ -281,8 +282,8 @@ def run_plain_dataflow(mod, x: torch.Tensor, plan) -> Optional[List[List[Optiona
     if cells is None:
         return None
     Hp = cells[(dirs[0], 0)].Hp
-    groups = engine.dataflow_groups(dev, len(dirs), L, Hp, plan.B)
-    if groups <= 0 or N * 3 * Hp >= (1 << 31):
+    groups = dataflow_only(dev, len(dirs), L, Hp, plan.B, N)
+    if groups <= 0:
         return None
     arena = mod._arena_for(x)
     arena.poll()

@@ -823,7 +823,7 @@ def test_reserved_cus_change_the_schedule_not_the_gradients(device, monkeypatch)
 
 @pytest.mark.parametrize("H,L", [(256, 2), (128, 1), (320, 1)])
 def test_static_rows_from_the_forward_launch_feed_the_reverse_sweep(device, monkeypatch, H, L):
-    """`DAGNN_AMD_STAT_FWD` (engine.stat_rows_ok): the forward launch of a training pass writes the reverse sweep's static
+    """`DAGNN_AMD_STAT_FWD` (`Route.stat_rows`): the forward launch of a training pass writes the reverse sweep's static
     record rows - state and gate coefficients (csrc/dataflow.hip, the AUX == 2 epilogue) - and `dagnn_bwd_dataflow_prepare`
     only adds the external-gradient row.  The same loss; gradients within fp32 rounding of the ones from the records
     `bd_stat_kernel` builds out of the kept pre-activations (it re-evaluates the gates with expf / tanhf, the forward
@@ -853,6 +853,68 @@ def test_static_rows_from_the_forward_launch_feed_the_reverse_sweep(device, monk
     for k, g in got[1][1].items():
         ref = got[0][1][k]
         assert Hh.maxdiff(g, ref) <= 2e-5 * max(float(ref.abs().max()), 1e-3), k
+
+
+def test_a_pass_runs_the_route_it_computed_once(device, monkeypatch):
+    """Seven passes on 3-graph batches of at most 40 nodes, one per path: the launch functions that ran are exactly those of
+    the route the pass computed (`route.with_plan`, asked once), a dataflow schedule was built at most once and for
+    `route.groups`, and the reverse function that ran is `route.reverse`."""
+    from dagnn_amd import DAGNN, ASTNodeEncoder, route
+    runs = {"dataflow": ["dataflow_run"], "tiles": ["tiles_run"], "launches+tiles": ["frontier_run", "tiles_run"], "launches": ["frontier_run"]}
+    reverse = {"dataflow": ["bwd_dataflow_sweep"], "lockstep": ["backward_sweep"], None: []}
+    ran, routes, asked, built = [], [], [], []
+
+    def spy(owner, name, log, note=None):
+        orig = getattr(owner, name)
+
+        def wrapper(*a, **k):
+            out = orig(*a, **k)
+            log.append(name if note is None else note(out))
+            return out
+        monkeypatch.setattr(owner, name, wrapper)
+    for name in ("dataflow_run", "tiles_run", "frontier_run", "bwd_dataflow_sweep", "backward_sweep"):
+        spy(engine, name, ran)
+    spy(route, "with_plan", routes, lambda r: r)
+    spy(route, "before_plan", asked)
+    for name in ("dataflow_schedule", "launch_prepare"):   # a schedule is built by the call that leaves it in the plan's cache
+        orig = getattr(engine.PlanHandle, name)
+
+        def builder(self, groups=0, *a, _orig=orig, **k):
+            had = set(self.__dict__.get("_df", {}))
+            out = _orig(self, groups, *a, **k)
+            built.extend(key[0] for key in set(self.__dict__.get("_df", {})) - had)
+            return out
+        monkeypatch.setattr(engine.PlanHandle, name, builder)
+
+    cases = [(64, 1, True, {}, False, (64, "dataflow", None)), (300, 2, True, {}, False, (320, "dataflow", None)),
+             (300, 1, False, {}, False, (320, "launches", None)), (512, 2, True, {}, False, (512, "tiles", None)),
+             (64, 2, True, {"DATAFLOW": 0}, False, (64, "launches", None)), (64, 2, True, {}, True, (64, "dataflow", "dataflow")),
+             (64, 2, True, {"BWD_DF_MAX_BYTES": 0}, True, (64, "dataflow", "lockstep"))]
+    for k, (H, L, wea, flags, train, expect) in enumerate(cases):
+        with monkeypatch.context() as m:
+            for name, v in flags.items():
+                m.setattr(engine, name, v)
+            model = DAGNN(num_vocab=8, max_seq_len=5, emb_dim=H, hidden_dim=H, out_dim=None, encoder=ASTNodeEncoder(H, 98, 10030, 20),
+                          w_edge_attr=wea, num_layers=L, bidirectional=True, agg="attn_h", out_wx=False, out_pool_all=False,
+                          out_pool="max", dropout=0.0)
+            seeded_fill(model, 70 + k)
+            model = model.to(device)
+            b = synth.code2_batch(20 + k, 3, 20, 40).to(device)
+            del ran[:], routes[:], asked[:], built[:]
+            with warnings.catch_warnings():
+                warnings.simplefilter("ignore", RuntimeWarning)   # (the per-layer launches say once that they are not the dataflow kernel)
+                if train:
+                    y = torch.randint(0, 8, (3, 5), generator=torch.Generator().manual_seed(k)).to(device)
+                    _train_step(model, b, y)
+                else:
+                    with torch.no_grad():
+                        model.eval()(b)
+            model.check()
+            assert len(routes) == 1 and len(asked) == 1, (H, L, routes, asked)
+            r = routes[0]
+            assert (r.Hp, r.kind, r.reverse) == expect, r
+            assert ran == runs[r.kind] + reverse[r.reverse], (r, ran)
+            assert built == ([r.groups] if r.groups > 0 else []) and (r.groups > 0) == (r.kind == "dataflow"), (r, built)
 
 
 def test_edge_cases(device, schedule):
