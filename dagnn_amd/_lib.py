@@ -151,7 +151,15 @@ class BwdDataflowArgs(C.Structure):
                 ("H", C.c_int), ("ld_h", C.c_int), ("ld_g", C.c_int), ("gld", C.c_int), ("groups", C.c_int),
                 ("epoch", C.c_uint), ("spin_limit", C.c_uint), ("schedule", C.c_void_p), ("records", C.c_void_p),
                 ("err", C.c_void_p), ("plan_status", C.c_void_p), ("num_cus", C.c_int), ("xcc_table", C.c_void_p), ("xcd_first", C.c_int),
-                ("stat_rows_written", C.c_int)]
+                ("stat_rows_written", C.c_int), ("pull_rows", C.c_int)]
+
+
+PULL_ROW = 256   # DAGNN_PULL_ROW: floats per edge of the per-unit pull weights (`agg = max` on the reverse dataflow sweep)
+
+
+class PlainPull(C.Structure):   # dagnn_plain_pull
+    _fields_ = [(k, C.c_void_p) for k in ("h", "a", "edge_mat", "edge_vec", "weights", "da_granules", "esum")] + \
+        [("ld_h", C.c_int), ("ld_a", C.c_int), ("gld", C.c_int)]
 
 
 class GatherJob0(C.Structure):   # (dagnn_gather_job inside dagnn_encode_args; `GatherJob` below has the same layout)
@@ -422,6 +430,8 @@ SYMBOLS = {
                                               C.c_int32, C.c_void_p]),
     "dagnn_variant_max_prepare": (C.c_int, [C.POINTER(Plan), C.POINTER(VariantBwdCell), C.c_int, C.c_int, C.c_int, C.c_int32,
                                             C.c_int32, C.c_void_p]),
+    "dagnn_plain_max_weights": (C.c_int, [C.POINTER(Plan), C.POINTER(PlainPull), C.c_int, C.c_int, C.c_int32, C.c_int32, C.c_void_p]),
+    "dagnn_plain_edge_grads": (C.c_int, [C.POINTER(Plan), C.POINTER(PlainPull), C.c_int, C.c_int, C.c_int32, C.c_int32, C.c_void_p]),
     "dagnn_variant_aggregator_backward": (C.c_int, [C.POINTER(Plan), C.POINTER(VariantBwdCell), C.c_int, C.c_int, C.c_int32,
                                                     C.c_int32, C.c_void_p]),
     "dagnn_variant_backward_run": (C.c_int, [C.POINTER(Plan), C.POINTER(VariantBwdArgs), C.POINTER(C.POINTER(C.c_int32)),

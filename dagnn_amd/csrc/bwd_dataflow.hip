@@ -68,7 +68,7 @@ enum { ST_GEXT = DF_ST_GEXT, ST_H = DF_ST_H, ST_CR = DF_ST_CR, ST_CZ = DF_ST_CZ,
 struct BdCell {            // (104 bytes: 30 kernel cells - 8 stacked layers, both directions - fit the kernel-argument segment)
     const float4* w;       // packed slices (dagnn_pack_dataflow of the gate-wise transposed matrix)
     const float* wkey;     // da: [H] key weights (zeros when the scores are static)
-    const float* alpha;    // da: [E] attention weights by original edge id
+    const float* alpha;    // da: [E] attention weights by original edge id (PULLW: [E, BD_SP] per-unit weight rows)
     const float* stat;     // da: [N, 8 * 256] static rows
     const gran_t* du_in;   // da: [N, gld] du arriving from stacked layer i + 1, or null (top layer)
     gran_t* out_g;         // da: [N, gld] granules of da (also read by this cell's own loaders); du: [N, gld] granules of du
@@ -435,7 +435,11 @@ struct BdSweep {
         break;
 #define BD_CASES(n_) BD_CASE(n_, 0) BD_CASE(n_, 1)
 
-template <int KPT, bool HAS_DU>
+// PULLW (agg = max of the constructor-string variants, dagnn_bwd_dataflow_args.pull_rows): the pull of row v weighs successor
+// w's da row per unit - C.alpha is [E, BD_SP], a row of static weights per original edge id in this loader's lane order
+// (dagnn_plain_max_weights), read with one plain 16-byte load per successor in front of the chunk's first trip.  Same polls,
+// granules, hand-offs and flags; no scores, so sigma_v and the edge-feature sums are zeros.
+template <int KPT, bool HAS_DU, bool PULLW = false>
 __device__ __forceinline__ void bd_loader_da(const int32_t* __restrict__ plan, const BdArgs& S, const BdCell& C, int sl,
                                              int group, const BdLds& lds, int w, int set) {
     constexpr int H = 16 * KPT;
@@ -543,6 +547,8 @@ __device__ __forceinline__ void bd_loader_da(const int32_t* __restrict__ plan, c
 #define BD_W(i) __builtin_amdgcn_readlane(cur, i)
         const int v = BD_W(0), eb = BD_W(1), ee = BD_W(2);
         const int s4[4] = {BD_W(4), BD_W(5), BD_W(6), BD_W(7)};
+        int e4[4] = {0, 0, 0, 0};   // (PULLW) the original edge ids of those four
+        if constexpr (PULLW) { e4[0] = BD_W(8); e4[1] = BD_W(9); e4[2] = BD_W(10); e4[3] = BD_W(11); }
         // the first four edges' features and attention weights ride in the record (bd_records_kernel): no loads in front of the trip
         const float rf0[4] = {__int_as_float(BD_W(16)), __int_as_float(BD_W(17)), __int_as_float(BD_W(18)), __int_as_float(BD_W(19))};
         const float rf1[4] = {__int_as_float(BD_W(20)), __int_as_float(BD_W(21)), __int_as_float(BD_W(22)), __int_as_float(BD_W(23))};
@@ -582,9 +588,16 @@ __device__ __forceinline__ void bd_loader_da(const int32_t* __restrict__ plan, c
                 constexpr int DU = (FIRST && HAS_DU) ? 1 : 0;
                 int pj[4] = {0, 0, 0, 0};
                 float al[4] = {0.f, 0.f, 0.f, 0.f}, f0[4] = {0.f, 0.f, 0.f, 0.f}, f1[4] = {0.f, 0.f, 0.f, 0.f};
+                bf4 mw[4];   // (PULLW) the successors' weight rows
+                (void)mw;
 #pragma unroll
                 for (int e = 0; e < NN; ++e) {
-                    if (FIRST) { pj[e] = s4[e]; al[e] = ral[e]; f0[e] = rf0[e]; f1[e] = rf1[e]; }
+                    if constexpr (PULLW) {
+                        static_assert(!PULLW || NC == 4, "a weight row is one float4 per lane");
+                        pj[e] = FIRST ? s4[e] : col[eb + c0 + e];
+                        const int eid = FIRST ? e4[e] : eidx[eb + c0 + e];
+                        mw[e] = *reinterpret_cast<const bf4*>(alpha + ((int64_t)eid * BD_SP + 4 * lane));
+                    } else if (FIRST) { pj[e] = s4[e]; al[e] = ral[e]; f0[e] = rf0[e]; f1[e] = rf1[e]; }
                     else {
                         pj[e] = col[eb + c0 + e];
                         al[e] = alpha[eidx[eb + c0 + e]];
@@ -646,6 +659,11 @@ __device__ __forceinline__ void bd_loader_da(const int32_t* __restrict__ plan, c
 #pragma unroll
                 for (int e = 0; e < NN; ++e) {
 #define BD_X(q) __uint_as_float((unsigned)A.x[e][q])
+                    if constexpr (PULLW) {
+#pragma unroll
+                        for (int q = 0; q < NC; ++q) acc[q] = fmaf(mw[e][q & 3], BD_X(q), acc[q]);
+                        continue;
+                    }
                     float dot = BD_X(0) * ST[ST_H].x;
                     if (NQ4 > 1) dot = fmaf(BD_X(1), ST[ST_H].y, dot);
                     if (NQ4 > 2) dot = fmaf(BD_X(2), ST[ST_H].z, dot);
@@ -1085,7 +1103,8 @@ __device__ __forceinline__ void bd_compute(const BdArgs& S, const BdCell& C, int
     else run(std::false_type(), std::false_type());
 }
 
-template <int KPT>
+// (PULLW: per-unit pull weights, see bd_loader_da - instantiated for H <= 256 only, where dagnn_bwd_dataflow_run asks for it)
+template <int KPT, bool PULLW = false>
 __global__ void __launch_bounds__(BD_THREADS, BD_THREADS / 256) bwd_dataflow_kernel(const int32_t* __restrict__ plan, BdArgs S) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     typedef BdSlot<KPT> Slot;
@@ -1166,8 +1185,8 @@ __global__ void __launch_bounds__(BD_THREADS, BD_THREADS / 256) bwd_dataflow_ker
         const int grp = bd_stream_group(pair, set, S.groups);
         if (grp >= 0) {
             if (C.kind == BD_DU) bd_loader_du<KPT>(S, C, grp, lds, w, set);
-            else if (C.du_in) bd_loader_da<KPT, true>(plan, S, C, sl, grp, lds, w, set);
-            else bd_loader_da<KPT, false>(plan, S, C, sl, grp, lds, w, set);
+            else if (C.du_in) bd_loader_da<KPT, true, PULLW>(plan, S, C, sl, grp, lds, w, set);
+            else bd_loader_da<KPT, false, PULLW>(plan, S, C, sl, grp, lds, w, set);
         }
     }
 }
@@ -1207,7 +1226,7 @@ extern "C" int dagnn_bwd_dataflow_prepare(const dagnn_plan* pl, const dagnn_bwd_
     if (!pl || !pl->data || !a || !a->schedule || !a->records) return DAGNN_EINVAL;
     const int H = a->H, Ls = a->num_stacked, dir_mask = a->dir_mask & 3, G = a->groups;
     if (H <= 0 || (H % 64) || H > 320 || Ls <= 0 || Ls > DAGNN_MAX_STACKED || !dir_mask || G < 1 || G > DF_MAX_GROUPS ||
-        a->ld_h < H || a->ld_g < H)
+        a->ld_h < H || a->ld_g < H || (a->pull_rows && H > 256))
         return DAGNN_EINVAL;
     if (pl->B == 0 || pl->N == 0) return DAGNN_OK;
     hipStream_t st = (hipStream_t)stream;
@@ -1220,6 +1239,7 @@ extern "C" int dagnn_bwd_dataflow_prepare(const dagnn_plan* pl, const dagnn_bwd_
         for (int i = 0; i < Ls; ++i) {
             AL.alpha[d][i] = ((dir_mask >> d) & 1) ? a->cell[d][i].alpha : nullptr;
             if (((dir_mask >> d) & 1) && !AL.alpha[d][i]) return DAGNN_EINVAL;
+            if (a->pull_rows) AL.alpha[d][i] = nullptr;   // (weight rows, not scalars: the records carry zeros)
         }
     hipLaunchKernelGGL(bd_records_kernel, dim3((unsigned)((nrec + 255) / 256), 2), dim3(256), 0, st, (const int32_t*)pl->data, L,
                        (const int32_t*)a->schedule, SL, (int32_t*)a->records, nrec, G, (const int32_t*)a->plan_status, AL);
@@ -1249,7 +1269,7 @@ extern "C" int dagnn_bwd_dataflow_prepare(const dagnn_plan* pl, const dagnn_bwd_
 #ifdef BD_WIDE_TU
 extern "C" int dagnn_bwd_dataflow_run_wide(const dagnn_plan* pl, const dagnn_bwd_dataflow_args* a, void* stream) {
     if (!pl || !pl->data || !a || !a->schedule || !a->records) return DAGNN_EINVAL;
-    if (a->H <= 256) return DAGNN_EINVAL;
+    if (a->H <= 256 || a->pull_rows) return DAGNN_EINVAL;
 #else
 extern "C" int dagnn_bwd_dataflow_run(const dagnn_plan* pl, const dagnn_bwd_dataflow_args* a, void* stream) {
     if (!pl || !pl->data || !a || !a->schedule || !a->records) return DAGNN_EINVAL;
@@ -1340,22 +1360,30 @@ extern "C" int dagnn_bwd_dataflow_run(const dagnn_plan* pl, const dagnn_bwd_data
     S.dbg = g_bd_dbg; S.dbg_role = g_bd_dbg_role;
 #endif
     const int32_t* plan = (const int32_t*)pl->data;
-#define BD_LAUNCH(KPT)                                                                                                   \
+#define BD_LAUNCH(KPT, PW)                                                                                               \
     do {                                                                                                                 \
-        const void* fn = reinterpret_cast<const void*>(bwd_dataflow_kernel<KPT>);                                        \
+        const void* fn = reinterpret_cast<const void*>(bwd_dataflow_kernel<KPT, PW>);                                    \
         const hipError_t ea = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bd_lds_bytes<KPT>()); \
         if (ea != hipSuccess) return DAGNN_EHIP(ea);                                                                     \
-        hipLaunchKernelGGL((bwd_dataflow_kernel<KPT>), dim3(grid), dim3(BD_THREADS), bd_lds_bytes<KPT>(), st, plan, S);  \
+        hipLaunchKernelGGL((bwd_dataflow_kernel<KPT, PW>), dim3(grid), dim3(BD_THREADS), bd_lds_bytes<KPT>(), st, plan, S); \
     } while (0)
 #ifdef BD_WIDE_TU
-    BD_LAUNCH(20);
+    BD_LAUNCH(20, false);
 #else
-    switch (H / 16) {
-        case 4: BD_LAUNCH(4); break;
-        case 8: BD_LAUNCH(8); break;
-        case 12: BD_LAUNCH(12); break;
-        default: BD_LAUNCH(16); break;
-    }
+    if (a->pull_rows)
+        switch (H / 16) {
+            case 4: BD_LAUNCH(4, true); break;
+            case 8: BD_LAUNCH(8, true); break;
+            case 12: BD_LAUNCH(12, true); break;
+            default: BD_LAUNCH(16, true); break;
+        }
+    else
+        switch (H / 16) {
+            case 4: BD_LAUNCH(4, false); break;
+            case 8: BD_LAUNCH(8, false); break;
+            case 12: BD_LAUNCH(12, false); break;
+            default: BD_LAUNCH(16, false); break;
+        }
 #endif
 #undef BD_LAUNCH
     DAGNN_CHECK_LAUNCH();

@@ -415,6 +415,61 @@ __global__ void __launch_bounds__(256) vb_max_prepare_kernel(const int32_t* __re
     }
 }
 
+// ---- max on the reverse dataflow sweep (csrc/bwd_dataflow.hip, per-unit pull): the twin of vb_max_prepare_kernel that
+// turns its counts into the pull's weights.  weights[e, k] (e = ORIGINAL edge id, the index the sweep's loaders know an edge
+// by; a row is 256 floats in the loaders' lane order, column k at 4 (k % 64) + k / 64) = 0 where the message of e did not
+// attain a_w[k], else 1 / c with c the count of the kernel above (c = 1: exactly 1) - the same comparison, the same even split
+__global__ void __launch_bounds__(256) vb_max_weights_kernel(const int32_t* __restrict__ plan, PlanLayout L, dagnn_plain_pull C,
+                                                              int dir, int r0, int r1, int R, int H) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int slot = r0 + blockIdx.x * 4 + wave;
+    if (slot >= r1) return;
+    const int32_t* __restrict__ rec = plan + L.rowrec[dir] + 16 * (int64_t)slot;
+    const int w = rec[0], eb = rec[1], ee = rec[2];
+    const int32_t* __restrict__ col = plan + L.col[dir];
+    const int32_t* __restrict__ eidx = plan + L.eidx[dir];
+    const float* __restrict__ ea = reinterpret_cast<const float*>(plan + L.eattr[dir]);
+    const float* __restrict__ aw = C.a + (int64_t)w * C.ld_a;
+    for (int k = lane; k < H; k += 64) {
+        const float top = aw[k];
+        int c = 0;
+        for (int e = eb; e < ee; ++e)
+            c += C.h[(int64_t)col[e] * C.ld_h + k] + vb_edge_term(C.edge_mat, C.edge_vec, k, R, ea + (int64_t)e * R) == top;
+        const float share = c > 1 ? 1.0f / (float)c : 1.0f;
+        for (int e = eb; e < ee; ++e) {
+            const bool hit = C.h[(int64_t)col[e] * C.ld_h + k] + vb_edge_term(C.edge_mat, C.edge_vec, k, R, ea + (int64_t)e * R) == top;
+            C.weights[(int64_t)eidx[e] * DAGNN_PULL_ROW + 4 * (k & 63) + (k >> 6)] = hit ? share : 0.f;
+        }
+    }
+}
+
+// ---- add / max on the reverse dataflow sweep: the edge encoder's share of row w, esum[w, r, k] = sum over the in-edges e of w,
+// in CSR order, of weight_e[k] da_w[k] f_e[r] (r < R) and esum[w, R, k] = sum_e weight_e[k] da_w[k]; weight = 1 for add.  da_w
+// is read from the sweep's hand-off granules (the low word of a granule is the value).  One wave per row, lane k: no atomics
+__global__ void __launch_bounds__(256) vb_plain_edge_grads_kernel(const int32_t* __restrict__ plan, PlanLayout L, dagnn_plain_pull C,
+                                                                   int dir, int r0, int r1, int R, int H) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int slot = r0 + blockIdx.x * 4 + wave;
+    if (slot >= r1) return;
+    const int32_t* __restrict__ rec = plan + L.rowrec[dir] + 16 * (int64_t)slot;
+    const int w = rec[0], eb = rec[1], ee = rec[2];
+    const int32_t* __restrict__ eidx = plan + L.eidx[dir];
+    const float* __restrict__ ea = reinterpret_cast<const float*>(plan + L.eattr[dir]);
+    const unsigned long long* __restrict__ dg = reinterpret_cast<const unsigned long long*>(C.da_granules) + (int64_t)w * C.gld;
+    float* __restrict__ o = C.esum + (int64_t)w * (R + 1) * H;
+    for (int k = lane; k < H; k += 64) {
+        const float dav = __uint_as_float((unsigned)dg[k]);
+        float eg[2] = {0.f, 0.f}, eb_sum = 0.f;
+        for (int e = eb; e < ee; ++e) {
+            const float g = C.weights ? C.weights[(int64_t)eidx[e] * DAGNN_PULL_ROW + 4 * (k & 63) + (k >> 6)] * dav : dav;
+            for (int r = 0; r < R; ++r) eg[r] = fmaf(g, ea[(int64_t)e * R + r], eg[r]);
+            eb_sum += g;
+        }
+        for (int r = 0; r < R; ++r) o[r * H + k] = eg[r];
+        o[R * H + k] = eb_sum;
+    }
+}
+
 int vb_launch_maps(const int32_t* plan, const PlanLayout& L, VbMaps& M, hipStream_t st) {
     if (M.n == 0) return DAGNN_OK;
     int rows = 0, J = 0, K = 0;
@@ -488,6 +543,35 @@ extern "C" int dagnn_variant_max_prepare(const dagnn_plan* pl, const dagnn_varia
     const PlanLayout L = dagnn_plan_layout_words(pl->N, pl->E, pl->B, pl->num_edge_feats);
     hipLaunchKernelGGL(vb_max_prepare_kernel, dim3((unsigned)((row_end - row_begin + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
                        (const int32_t*)pl->data, L, *c, dir, row_begin, row_end, pl->num_edge_feats, H, ld);
+    DAGNN_CHECK_LAUNCH();
+    return DAGNN_OK;
+}
+
+static bool vb_plain_pull_ok(const dagnn_plan* pl, const dagnn_plain_pull* c, int dir, int H, int32_t row_begin, int32_t row_end) {
+    if (!pl || !pl->data || !c || (dir != 0 && dir != 1) || H <= 0 || H > DAGNN_PULL_ROW || row_begin < 0 || row_end > pl->N) return false;
+    return pl->num_edge_feats >= 0 && pl->num_edge_feats <= 2 && (!c->edge_mat || c->edge_vec);
+}
+
+extern "C" int dagnn_plain_max_weights(const dagnn_plan* pl, const dagnn_plain_pull* c, int dir, int H, int32_t row_begin,
+                                       int32_t row_end, void* stream) {
+    if (!vb_plain_pull_ok(pl, c, dir, H, row_begin, row_end)) return DAGNN_EINVAL;
+    if (!c->h || !c->a || !c->weights || c->ld_h < H || c->ld_a < H) return DAGNN_EINVAL;
+    if (row_end <= row_begin) return DAGNN_OK;
+    const PlanLayout L = dagnn_plan_layout_words(pl->N, pl->E, pl->B, pl->num_edge_feats);
+    hipLaunchKernelGGL(vb_max_weights_kernel, dim3((unsigned)((row_end - row_begin + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
+                       (const int32_t*)pl->data, L, *c, dir, row_begin, row_end, pl->num_edge_feats, H);
+    DAGNN_CHECK_LAUNCH();
+    return DAGNN_OK;
+}
+
+extern "C" int dagnn_plain_edge_grads(const dagnn_plan* pl, const dagnn_plain_pull* c, int dir, int H, int32_t row_begin,
+                                      int32_t row_end, void* stream) {
+    if (!vb_plain_pull_ok(pl, c, dir, H, row_begin, row_end)) return DAGNN_EINVAL;
+    if (!c->da_granules || !c->esum || c->gld < H) return DAGNN_EINVAL;
+    if (row_end <= row_begin) return DAGNN_OK;
+    const PlanLayout L = dagnn_plan_layout_words(pl->N, pl->E, pl->B, pl->num_edge_feats);
+    hipLaunchKernelGGL(vb_plain_edge_grads_kernel, dim3((unsigned)((row_end - row_begin + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
+                       (const int32_t*)pl->data, L, *c, dir, row_begin, row_end, pl->num_edge_feats, H);
     DAGNN_CHECK_LAUNCH();
     return DAGNN_OK;
 }

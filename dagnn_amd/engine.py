@@ -1322,9 +1322,14 @@ def bwd_dataflow_fits(device, N: int, cells: int) -> bool:
 
 
 def bwd_dataflow_sweep(plan: PlanHandle, dirs: Sequence[int], L: int, H: int, cells, h, gi0, g_ext, groups: int,
-                       arena: "GranuleArena", vid_mod: int = 0, static_score=None, preact: Optional[dict] = None):
+                       arena: "GranuleArena", vid_mod: int = 0, static_score=None, preact: Optional[dict] = None,
+                       plain: Optional[dict] = None):
     """Reverse pass of the recurrence as ONE persistent dataflow launch (csrc/bwd_dataflow.hip).  Same operands and
-    the same result dictionary as `backward_sweep`; `groups` must be the group count of the forward pass's schedule."""
+    the same result dictionary as `backward_sweep`; `groups` must be the group count of the forward pass's schedule.
+    `plain` (agg = add / max, `variants.PlainRecurrence`): {(d, i): (a [N, H] contiguous, pull)} - the aggregates and the
+    pull weights the caller prepared instead of `dagnn_backward_prepare`'s: `pull` is [E] (add: ones, or zeros for a cell
+    that aggregates nothing), or with `plain["pull_rows"]` (max) [E, _lib.PULL_ROW] per-unit weight rows; the keys are
+    zeros, and every cell's result also carries its `da_granules` [N, H] (the edge encoder's gradient reads them)."""
     dev = plan.ws.device
     N, E, R = plan.N, plan.E, plan.R
     lib = _lib.load()
@@ -1337,10 +1342,15 @@ def bwd_dataflow_sweep(plan: PlanHandle, dirs: Sequence[int], L: int, H: int, ce
         mask |= 1 << d
         for i in range(L):
             c, bc = cells[(d, i)], pargs.cell[d][i]
-            o = dict(a=torch.empty(N, H, **f32), alpha=torch.empty(max(E, 1), **f32),
+            o = dict(a=plain[(d, i)][0] if plain else torch.empty(N, H, **f32),
+                     alpha=plain[(d, i)][1] if plain else torch.empty(max(E, 1), **f32),
                      dgi=torch.empty(N, 3 * H, **f32), dgh=torch.empty(N, 3 * H, **f32), sigma=torch.empty(N, **f32),
                      edge_feat_grad=torch.empty(N, R, **f32) if R > 0 else None)
             out[(d, i)] = o
+            if plain:
+                o["_wkey"] = torch.zeros(H, **f32)
+                keep.append(o["_wkey"])
+                continue
             if static_score is not None:
                 zero_key = torch.zeros(H, **f32)
                 keep.append(zero_key)
@@ -1355,7 +1365,8 @@ def bwd_dataflow_sweep(plan: PlanHandle, dirs: Sequence[int], L: int, H: int, ce
     pargs.num_stacked, pargs.dir_mask, pargs.H, pargs.ld_h = L, mask, H, h[dirs[0]][0].shape[1]
     pargs.vid_mod = int(vid_mod)
     with _span("backward_prepare", plan.ws):
-        check(lib.dagnn_backward_prepare(C.byref(plan.desc), C.byref(pargs), _stream(plan.ws)), "dagnn_backward_prepare")
+        if not plain:
+            check(lib.dagnn_backward_prepare(C.byref(plan.desc), C.byref(pargs), _stream(plan.ws)), "dagnn_backward_prepare")
         keys = [(d, i) for d in dirs for i in range(L)]
         gh = {}
         gi = {(d, 0): gi0[d] for d in dirs}
@@ -1404,6 +1415,7 @@ def bwd_dataflow_sweep(plan: PlanHandle, dirs: Sequence[int], L: int, H: int, ce
         args.ld_h, args.ld_g, args.gld, args.groups = h[dirs[0]][0].shape[1], g_ext[dirs[0]][0].shape[1], H, int(groups)
         args.epoch, args.spin_limit = epoch, SPIN_LIMIT
         args.stat_rows_written = 1 if stat_fwd else 0
+        args.pull_rows = 1 if (plain and plain.get("pull_rows")) else 0
         sched = plan.dataflow_schedule(groups)
         recs = torch.empty(lib.dagnn_bwd_dataflow_record_bytes(N) // 4, dtype=torch.int32, device=dev)
         keep.append(recs)
@@ -1417,8 +1429,10 @@ def bwd_dataflow_sweep(plan: PlanHandle, dirs: Sequence[int], L: int, H: int, ce
     with persistent_launch(plan.ws), _span("backward_run", plan.ws):
         check(lib.dagnn_bwd_dataflow_run(C.byref(plan.desc), C.byref(args), _stream(plan.ws)), "dagnn_bwd_dataflow_run")
     arena.watch(plan, folded=True)
-    for o in out.values():
+    for k, o in out.items():
         o.pop("_wkey", None)
+        if plain:
+            o["da_granules"] = gran[("da",) + k]
     out["_keep"] = keep   # buffers the launch reads: alive until the caller drops the result
     return out
 

@@ -269,6 +269,10 @@ class DAGNN(HipModule):
         self.variant_backend = "hip"       # constructor-string variants (a12): 'hip' = csrc/variants.hip forward and
                                             # csrc/variants_bwd.hip reverse sweep; 'torch' = always the differentiable
                                             # torch-ROCm ops (the checker of the HIP sweep in the GPU tests)
+                                            # 'dataflow' = as 'hip', but training passes of add / max run on the two
+                                            # persistent dataflow kernels where `route.plain` allows (else exactly 'hip')
+        self.last_variant_path = None      # what the last differentiable variant pass ran on: 'dataflow' | 'lockstep' | 'torch'
+        self.last_variant_route = None     # ... and its `route.plain` (`.why`: the reason it stayed off the dataflow kernels)
 
     # ------------------------------------------------------------------------------ helpers
     # additive-attention aggregators: the logit is w . [query ; key (+ edge)] (+ b); query and bias cancel
@@ -645,10 +649,18 @@ class DAGNN(HipModule):
                     # gated_sum / mattn_h / add with GRU cells: forward AND reverse sweep in HIP (csrc/variants_bwd.hip)
                     plan = self._plan_of(G, B)
                     flat_params = [p for d in self.dirs for i in range(L) for _, p in variants._cell_params(self, d, i)]
-                    flat = variants.VariantRecurrence.apply(self, G, plan, G.x, *flat_params)
+                    # add / max under variant_backend = 'dataflow': both persistent kernels where `route.plain` says so
+                    r = self.last_variant_route = variants.plain_route(self, plan, G.x.shape[0], G.x.device, training=True)
+                    if r.kind == "dataflow":
+                        self.last_variant_path = "dataflow"
+                        flat = variants.PlainRecurrence.apply(self, plan, r, G.x, *flat_params)
+                    else:
+                        self.last_variant_path = "lockstep"
+                        flat = variants.VariantRecurrence.apply(self, G, plan, G.x, *flat_params)
                     return self._finish(G, plan, G.x, self._unflatten(flat), B, head)   # (the plan: HIP read-out, `PoolNodes`)
                 if self.variant_backend != "torch":   # (an explicit 'torch' backend is a choice, not a cliff)
                     variants.warn_torch_path(self, G)
+                self.last_variant_path = "torch"
                 return self._finish(G, None, G.x, variants.run(self, G, G.x), B, head)   # training: differentiable torch ops
             plan = self._plan_of(G, B)
             h = variants.run_hip(self, G, G.x, plan)

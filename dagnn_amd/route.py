@@ -3,8 +3,9 @@
 `before_plan` gives what the plan and schedule builders need - the padded width `Hp` and the dataflow kernel's group
 count - from the model's shape alone; `with_plan` completes the `Route` once the batch's plan exists.  A forward pass
 evaluates each once and hands the result on: `core.run_stack_lockstep` dispatches on `kind`, the backward pass reads
-`reverse`.  `dataflow_only` is the question of the callers that can run on nothing else (`dvae._encode_fused`,
-`variants.run_plain_dataflow`).  The primitives stay in `engine`; every flag is read there when the function runs."""
+`reverse`.  `dataflow_only` is the question of the caller that can run on nothing else (`dvae._encode_fused`); `plain` is
+the whole route of the `add` / `max` passes (`variants.run_plain_dataflow`, `variants.PlainRecurrence`).  The primitives
+stay in `engine`; every flag is read there when the function runs."""
 from typing import NamedTuple, Optional, Sequence
 
 from . import engine
@@ -60,6 +61,63 @@ def dataflow_only(device, ndirs: int, L: int, Hp: int, B: int, N: int) -> int:
     if N == 0 or Hp > 256 or not _rows32(N, Hp):
         return 0
     return engine.dataflow_groups(device, ndirs, L, Hp, B)
+
+
+PLAIN_OFF = "DAGNN_AMD_VARIANT_DATAFLOW=0"
+PLAIN_BACKEND = "variant_backend = 'hip': training passes of add / max take the lock-step sweep unless 'dataflow' is asked for"
+
+
+def plain(device, backend: str, training: bool, agg: str, recurr: bool, agg_x: bool, schedule: str, wea: bool, R: int,
+          H: int, L: int, ndirs: int, B: int, N: int, ok: bool = True, groups: Optional[int] = None,
+          fits: Optional[bool] = None) -> Route:
+    """The route of a pass of `agg` = `add` / `max` (AggConv, `variants.run_plain_dataflow` and its training twin): `kind`
+    "dataflow" - the persistent kernel with a plain fold in its loaders - or "launches", the per-layer variant launches; a
+    training pass that takes the kernel also takes the reverse dataflow sweep (`reverse`), or neither.  An evaluation pass
+    takes the kernel under either HIP backend; a training pass only under `backend` "dataflow".  `wea`: the aggregator has an
+    edge encoder, `R`: edge features of the batch's plan, `ok`: the model class shares one AggConv the way the kernel
+    assumes.  `groups` / `fits`: what `dataflow_only` / `engine.bwd_dataflow_fits` answer for this device (asked here when
+    None, and only once everything else holds).  `why`: None on the kernel, else the first condition that failed."""
+    Hp = width(H, L, 0, True, 0, False)[0]
+    stat_rows = False
+
+    def off(why):
+        return Route(Hp, 0, "launches", 0, None, False, "lockstep" if training else None, why)
+
+    if not engine.DATAFLOW:
+        return off(OFF)
+    if not engine.VARIANT_DATAFLOW:
+        return off(PLAIN_OFF)
+    if training and backend != "dataflow":
+        return off(PLAIN_BACKEND)
+    if agg not in ("add", "max") or not ok:
+        return off("aggregator %r is not a plain fold of one shared AggConv" % (agg,))
+    if not recurr:
+        return off("recurr=0: the kernel's cells are GRU cells")
+    if agg_x:
+        return off("agg_x: the aggregator reads the inputs, nothing couples the layers")
+    if schedule != "lockstep":
+        return off("schedule %r: the kernel runs on the lock-step schedule" % (schedule,))
+    if R > 2 or (wea and R == 0):
+        return off("the loaders fold at most two edge features (and an edge encoder needs the batch's)")
+    if Hp > 256:
+        return off("hidden size %d > 256: the plain loaders exist up to 256 wide" % Hp)
+    if N == 0:
+        return off(IDLE)
+    if not _rows32(N, Hp):
+        return off(LIB)
+    if training:
+        if not engine.BWD_DATAFLOW:
+            return off("DAGNN_AMD_BWD_DATAFLOW=0")
+        if fits is None:
+            fits = engine.bwd_dataflow_fits(device, N, ndirs * L)
+        if not fits:
+            return off("the reverse dataflow sweep's records do not fit this device's memory budget")
+        stat_rows = bool(engine.STAT_FWD and engine.lib_static_floats(N, Hp) * 4 < (1 << 32))   # a record: 32-bit offsets
+    if groups is None:
+        groups = engine.dataflow_groups(device, ndirs, L, Hp, B, training=training)
+    if groups <= 0:
+        return off(LIB)
+    return Route(Hp, groups, "dataflow", 0, None, stat_rows, "dataflow" if training else None, None)
 
 
 def with_plan(r: Route, device, plan, dirs: Sequence[int], L: int, N: int, keys_hidden: bool = True, active: bool = True,

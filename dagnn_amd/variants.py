@@ -2,7 +2,7 @@
 
 `agg` in {`mattn_h`, `gated_sum`, `add`, `max`}, `agg_x=True`, `recurr=0` of `ogbg-code/model/dagnn.py`: the module
 keeps the reference's constructor and `state_dict` for them, and `forward` lands here instead of in the tuned HIP
-recurrence.  Two paths, same values:
+recurrence.  Three paths, same values:
 
 * `run_hip` (evaluation / inference, i.e. whenever no gradient is requested): one lock-step pass of the generic HIP
   kernels of `csrc/variants.hip` (`dagnn_variant_run`, `dagnn_variant_aggregate`): an aggregate launch, a cell launch
@@ -11,8 +11,10 @@ recurrence.  Two paths, same values:
   per parameter version) and marshals pointers.
 * `run` (training): the reference's loop nest (`dagnn.py:144-182`) on differentiable torch-ROCm ops, with its
   O(F*E) per-node edge scan replaced by one stable sort of the edges by the layer of the node they feed.
+* `PlainRecurrence` (training of `add` / `max` under `variant_backend = "dataflow"`, where `route.plain` allows): the
+  persistent dataflow kernels forward and reverse instead of the per-layer launches.
 
-Neither runs anything on the CPU.
+None of them runs anything on the CPU.
 
 Conv semantics restated from `dagnn.py:232-313,347-409` and PyG-1.6 `propagate` (messages flow j -> i; the result of a
 conv is a full [N, .] tensor that is zero where no edge lands, of which the caller reads the frontier rows):
@@ -32,8 +34,7 @@ from typing import List, Optional
 
 import torch
 
-from . import _lib, engine
-from .route import dataflow_only
+from . import _lib, engine, route as routing
 
 
 def _segment_softmax(logit: torch.Tensor, seg: torch.Tensor, num_seg: int) -> torch.Tensor:
@@ -233,24 +234,22 @@ def _ptr(t):
     return None if t is None else t.data_ptr()
 
 
-def run_plain_dataflow(mod, x: torch.Tensor, plan) -> Optional[List[List[Optional[torch.Tensor]]]]:
-    """`agg` = `add` / `max` with GRU cells on the persistent dataflow kernel (csrc/dataflow.hip: the generic loader folds the
-    messages h_j + edge_encoder(edge_attr_j) by sum or maximum instead of the attention soft-max; the GRU side is the
-    kernel's own).  The reference builds ONE AggConv for both directions (dagnn.py:74-75): in the reverse direction its
-    messages land on the successors, the frontier rows read zeros - those cells run with an empty aggregate and poll nothing.
-    Returns None where the kernel does not apply (the caller keeps the per-layer variant launches)."""
+def plain_route(mod, plan, N: int, device, training: bool) -> "routing.Route":
+    """`route.plain` of this module on this batch: whether a pass of `add` / `max` runs on the persistent dataflow kernel(s)."""
+    wea = bool(getattr(mod.node_aggr_0[0], "wea", False))
+    return routing.plain(device, getattr(mod, "variant_backend", "hip"), training, mod.agg, bool(mod.recurr), bool(mod.agg_x), mod.schedule, wea,
+                         plan.R, mod.hidden_dim, mod.num_layers, len(mod.dirs), plan.B, N,
+                         ok=bool(getattr(mod, "_plain_dataflow_ok", False)))
+
+
+def _plain_cells(mod, R: int, dev):
+    """The dataflow kernel's cells of `add` / `max` (cached per parameter version): GRU weights in the kernel's layout, the
+    fold of each cell (`agg` 1 add, 2 max, 3 nothing lands) and the edge encoder zero-padded to the kernel's width."""
     from .core import derive_cell, pack_dataflow
     H, L = mod.hidden_dim, mod.num_layers
     dirs = list(mod.dirs)
-    N, dev = x.shape[0], x.device
-    if not getattr(mod, "_plain_dataflow_ok", False) or not engine.VARIANT_DATAFLOW or not engine.DATAFLOW \
-            or mod.agg not in ("add", "max") or not mod.recurr or mod.agg_x \
-            or N == 0 or plan.R > 2 or mod.schedule != "lockstep":
-        return None
     conv = mod.node_aggr_0[0]
     wea = bool(getattr(conv, "wea", False))
-    if wea and plan.R == 0:
-        return None
     shared_flow = getattr(mod, "shared_agg_flow", True)
     srcs = [p for d in dirs for cell in getattr(mod, "cells_%d" % d) for p in cell.parameters()] + \
         ([conv.edge_encoder.weight, conv.edge_encoder.bias] if wea else [])
@@ -269,7 +268,7 @@ def run_plain_dataflow(mod, x: torch.Tensor, plan) -> Optional[List[List[Optiona
                 c.agg = 3 if (shared_flow and d == 1) else (1 if mod.agg == "add" else 2)
                 c.agg_w = c.agg_b = None
                 if wea and c.agg != 3:
-                    w = torch.zeros(c.Hp, plan.R, dtype=torch.float32, device=dev)
+                    w = torch.zeros(c.Hp, R, dtype=torch.float32, device=dev)
                     w[:H] = conv.edge_encoder.weight.detach().float()
                     b = torch.zeros(c.Hp, dtype=torch.float32, device=dev)
                     b[:H] = conv.edge_encoder.bias.detach().float()
@@ -278,23 +277,40 @@ def run_plain_dataflow(mod, x: torch.Tensor, plan) -> Optional[List[List[Optiona
         pack_dataflow(out.values())
         return out
 
-    cells = mod._cache("plain_df").get(srcs, make, fresh=mod.training)
-    if cells is None:
-        return None
-    Hp = cells[(dirs[0], 0)].Hp
-    groups = dataflow_only(dev, len(dirs), L, Hp, plan.B, N)
-    if groups <= 0:
-        return None
+    return mod._cache("plain_df").get(srcs, make, fresh=mod.training)
+
+
+def _plain_forward(mod, x: torch.Tensor, plan, r, cells, preact: Optional[dict] = None):
+    """One launch of the dataflow kernel over the plain cells on route `r`: (raw state buffers h[d][i] [N, ld], gi0 per direction)."""
+    L, dirs = mod.num_layers, list(mod.dirs)
+    N, dev = x.shape[0], x.device
     arena = mod._arena_for(x)
     arena.poll()
     gi0 = engine.gemm_nt_bias([x] * len(dirs), [cells[(d, 0)].w_ih for d in dirs], [cells[(d, 0)].b_ih for d in dirs])
     gi = [None, None]
     for q, d in enumerate(dirs):
         gi[d] = gi0[q]
-    ld = engine.frontier_ld(Hp)
+    ld = engine.frontier_ld(r.Hp)
     h = [[torch.empty(N, ld, dtype=torch.float32, device=dev) if d in dirs else None for _ in range(L)] for d in range(2)]
     plan.wait_ready()
-    engine.dataflow_run(plan, dirs, L, Hp, cells, gi, h, groups, arena=arena)
+    engine.dataflow_run(plan, dirs, L, r.Hp, cells, gi, h, r.groups, arena=arena, preact=preact, training=preact is not None)
+    return h, gi
+
+
+def run_plain_dataflow(mod, x: torch.Tensor, plan) -> Optional[List[List[Optional[torch.Tensor]]]]:
+    """`agg` = `add` / `max` with GRU cells on the persistent dataflow kernel (csrc/dataflow.hip: the generic loader folds the
+    messages h_j + edge_encoder(edge_attr_j) by sum or maximum instead of the attention soft-max; the GRU side is the
+    kernel's own).  The reference builds ONE AggConv for both directions (dagnn.py:74-75): in the reverse direction its
+    messages land on the successors, the frontier rows read zeros - those cells run with an empty aggregate and poll nothing.
+    Returns None where the kernel does not apply (`route.plain`; the caller keeps the per-layer variant launches)."""
+    H, L = mod.hidden_dim, mod.num_layers
+    r = plain_route(mod, plan, x.shape[0], x.device, training=False)
+    if r.kind != "dataflow":
+        return None
+    cells = _plain_cells(mod, plan.R, x.device)
+    if cells is None:
+        return None
+    h, _ = _plain_forward(mod, x, plan, r, cells)
     return [[h[d][i][:, :H] if h[d][i] is not None else None for i in range(L)] for d in range(2)]
 
 
@@ -854,4 +870,167 @@ class VariantRecurrence(torch.autograd.Function):
             dx = None
             if ctx.needs_input_grad[3]:
                 dx = sum(dxd[d] for d in mod.dirs)
+        return (None, None, None, dx) + tuple(grads[n] for n in names)
+
+
+def plain_pull_host(h, a, edge_w, edge_b, src, dst, edge_attr):
+    """Host mirror (numpy fp32) of the pull weights of `agg = max` on the reverse dataflow sweep (`dagnn_plain_max_weights`):
+    weight[e, k] = 0 where the message h[src[e], k] + (edge_b[k] + sum_r edge_w[k, r] edge_attr[e, r]) is not the maximum
+    a[dst[e], k], else 1 / c with c the number of in-edges of dst[e] whose message is (ties split evenly - the rule of
+    `dagnn_variant_max_prepare`).  `edge_w` None: no edge encoder; `a` None: the maxima of the messages as formed
+    here.  Returns [E, H] float32."""
+    import numpy as np
+    h, a = np.asarray(h, dtype=np.float32), None if a is None else np.asarray(a, dtype=np.float32)
+    src, dst = np.asarray(src, dtype=np.int64), np.asarray(dst, dtype=np.int64)
+    msg = h[src]
+    if edge_w is not None:
+        term = np.broadcast_to(np.asarray(edge_b, dtype=np.float32), msg.shape).copy()
+        ea = np.asarray(edge_attr, dtype=np.float32).reshape(src.shape[0], -1)
+        for r in range(ea.shape[1]):   # (the kernels' order: the bias, then one feature after the other)
+            term = term + np.asarray(edge_w, dtype=np.float32)[None, :, r] * ea[:, r:r + 1]
+        msg = msg + term
+    if a is None:   # the maxima of these very messages (rows without an in-edge: zero, which no message is compared with)
+        a = np.full(h.shape, -np.inf, dtype=np.float32)
+        np.maximum.at(a, dst, msg)
+        a[np.isinf(a)] = 0
+    hit = msg == a[dst]
+    count = np.zeros_like(a)
+    np.add.at(count, dst, hit.astype(np.float32))
+    c = count[dst]
+    share = np.where(c > 1, np.float32(1) / np.maximum(c, 1), np.float32(1)).astype(np.float32)
+    return np.where(hit, share, np.float32(0)).astype(np.float32)
+
+
+def plain_edge_grads_host(weight, da, dst, edge_attr):
+    """Host mirror of `dagnn_plain_edge_grads` + its column sums in float64: (d edge_encoder.weight [H, R], d edge_encoder.bias
+    [H]) = (sum_e weight_e (.) da[dst[e]] f_e[r], sum_e weight_e (.) da[dst[e]]); `weight` None: `add` (all ones)."""
+    import numpy as np
+    da, dst = np.asarray(da, dtype=np.float64), np.asarray(dst, dtype=np.int64)
+    g = da[dst] if weight is None else np.asarray(weight, dtype=np.float64) * da[dst]
+    ea = np.asarray(edge_attr, dtype=np.float64).reshape(dst.shape[0], -1)
+    return g.T @ ea, g.sum(0)
+
+
+class PlainRecurrence(torch.autograd.Function):
+    """States h[d][i] of `agg` = `add` / `max` (GRU cells), differentiable, on the two persistent kernels: forward = the plain
+    loaders of csrc/dataflow.hip (one launch, which also leaves the reverse sweep's static rows or pre-activations), backward =
+    the reverse dataflow sweep of csrc/bwd_dataflow.hip with a plain pull - `add`: alpha = 1 on every edge, `max`: per-unit
+    weight rows (`dagnn_plain_max_weights`) -, then the edge encoder's gradient from the sweep's `da` granules
+    (`dagnn_plain_edge_grads` + `engine.colsums`) and the GRU weight gradients of `engine.wgrad`.  `r`: the `route.plain` that
+    chose this path.  Inputs after `x`: the parameters in `_cell_params` order, as for `VariantRecurrence`."""
+
+    @staticmethod
+    def forward(ctx, mod, plan, r, x, *params):
+        mod._cache("plain_df").invalidate()   # (a training pass never reads weights derived from earlier parameters: `VariantRecurrence`)
+        xd = engine._dev(x.detach(), "node inputs", torch.float32)
+        cells = _plain_cells(mod, plan.R, xd.device)
+        if cells is None or cells[(mod.dirs[0], 0)].Hp != r.Hp:
+            raise engine.DagnnHipError("plain dataflow pass: the cells' width does not match the route's (%d)" % r.Hp)
+        preact = {"stat_rows": True} if r.stat_rows else {}
+        hbuf, gi = _plain_forward(mod, xd, plan, r, cells, preact=preact)
+        H, L = mod.hidden_dim, mod.num_layers
+        ctx.mod, ctx.plan, ctx.route, ctx.cells, ctx.hbuf, ctx.gi, ctx.preact = mod, plan, r, cells, hbuf, gi, preact
+        ctx.save_for_backward(x, *params)
+        ctx.set_materialize_grads(False)
+        return tuple(hbuf[d][i][:, :H] for d in mod.dirs for i in range(L))
+
+    @staticmethod
+    def backward(ctx, *gouts):
+        mod, plan, r, cells, hb = ctx.mod, ctx.plan, ctx.route, ctx.cells, ctx.hbuf
+        saved = list(ctx.saved_tensors)
+        x, params = saved[0].detach(), [p.detach() for p in saved[1:]]
+        N, H, L, Hp, R, E = x.shape[0], mod.hidden_dim, mod.num_layers, r.Hp, plan.R, plan.E
+        dirs = list(mod.dirs)
+        f32 = dict(dtype=torch.float32, device=x.device)
+        lib = _lib.load()
+        stream = engine._stream(x)
+        is_max = mod.agg == "max"
+        shared_flow = getattr(mod, "shared_agg_flow", True)
+        names, cellp, k = [], {}, 0
+        for d in dirs:
+            for i in range(L):
+                spec = _cell_params(mod, d, i)
+                cellp[(d, i)] = {n: params[k + q] for q, (n, _) in enumerate(spec)}
+                names += [(d, i, n) for n, _ in spec]
+                k += len(spec)
+        with torch.no_grad():
+            g_all = torch.zeros(len(dirs) * L, N, Hp, **f32)
+            g_ext = [[g_all[dirs.index(d) * L + i] if d in dirs else None for i in range(L)] for d in range(2)]
+            for q, d in enumerate(dirs):
+                for i in range(L):
+                    if gouts[q * L + i] is not None:
+                        g_ext[d][i][:, :H] = gouts[q * L + i]
+            # per cell: the aggregate a (the W_hh gradient's operand; for max also what a message is compared with) and the pull
+            plain, pulls, nothing = {"pull_rows": is_max}, {}, None
+            ones = None
+            for d in dirs:
+                lands = not (shared_flow and d == 1)
+                for i in range(L):
+                    cp = cellp[(d, i)]
+                    a = torch.zeros(N, Hp, **f32)
+                    pp = _lib.PlainPull()
+                    pp.h, pp.ld_h, pp.a, pp.ld_a = hb[d][i].data_ptr(), hb[d][i].stride(0), a.data_ptr(), Hp
+                    if "we" in cp:
+                        cp["we"], cp["be"] = cp["we"].contiguous(), cp["be"].contiguous()   # (held by `cellp` until the last launch)
+                        pp.edge_mat, pp.edge_vec = cp["we"].data_ptr(), cp["be"].data_ptr()
+                    pulls[(d, i)] = pp
+                    if not lands:
+                        if nothing is None:
+                            nothing = torch.zeros(max(E, 1), _lib.PULL_ROW if is_max else 1, **f32)
+                        plain[(d, i)] = (a, nothing)
+                        continue
+                    ag = _lib.VariantAggregator()
+                    ag.mode, ag.lands, ag.val_dim, ag.out_dim = _MODES[mod.agg], 1, H, H
+                    ag.vals, ag.ld_vals, ag.out, ag.ld_out = pp.h, pp.ld_h, pp.a, Hp
+                    ag.edge_mat0, ag.edge_vec0 = pp.edge_mat, pp.edge_vec
+                    engine.check(lib.dagnn_variant_aggregate(C.byref(plan.desc), C.byref(ag), d, 0, N, stream), "dagnn_variant_aggregate")
+                    if is_max:
+                        w = torch.zeros(max(E, 1), _lib.PULL_ROW, **f32)
+                        pp.weights = w.data_ptr()
+                        engine.check(lib.dagnn_plain_max_weights(C.byref(plan.desc), C.byref(pp), d, H, 0, N, stream),
+                                     "dagnn_plain_max_weights")
+                    else:
+                        if ones is None:
+                            ones = torch.ones(max(E, 1), **f32)
+                        w = ones
+                    plain[(d, i)] = (a, w)
+            res = engine.bwd_dataflow_sweep(plan, dirs, L, Hp, cells, hb, ctx.gi, g_ext, r.groups,
+                                            arena=mod._arena_for(x, "backward"), preact=ctx.preact, plain=plain)
+            # ---- epilogue: the edge encoder (one fixed order: per row over its in-edges, then `colsums` over the rows) ...
+            es_jobs, es_at = [], {}
+            for d in dirs:
+                for i in range(L):
+                    if "we" not in cellp[(d, i)] or (shared_flow and d == 1) or R == 0:
+                        continue
+                    pp = pulls[(d, i)]
+                    esum = torch.zeros(N, (R + 1) * H, **f32)
+                    pp.da_granules, pp.gld, pp.esum = res[(d, i)]["da_granules"].data_ptr(), Hp, esum.data_ptr()
+                    engine.check(lib.dagnn_plain_edge_grads(C.byref(plan.desc), C.byref(pp), d, H, 0, N, stream), "dagnn_plain_edge_grads")
+                    es_at[(d, i)] = len(es_jobs)
+                    es_jobs.append((esum, None))
+            es = engine.colsums(es_jobs, N) if es_jobs else []
+            # ... and the GRU weights and biases, every cell in one batch (csrc/wgrad.hip)
+            jobs = []
+            for d in dirs:
+                for i in range(L):
+                    o = res[(d, i)]
+                    jobs += [(o["dgi"], x if i == 0 else hb[d][i - 1][:, :H], True), (o["dgh"], plain[(d, i)][0][:, :H], True)]
+            wg = engine.wgrad(jobs, N, Hp, H)
+            grads, kq = {}, 0
+            dx = torch.zeros_like(x) if ctx.needs_input_grad[3] else None
+            for d in dirs:
+                for i in range(L):
+                    cp = cellp[(d, i)]
+                    (grads[(d, i, "w_ih")], grads[(d, i, "b_ih")]), (grads[(d, i, "w_hh")], grads[(d, i, "b_hh")]) = wg[kq], wg[kq + 1]
+                    kq += 2
+                    if i == 0 and dx is not None:
+                        dgi = res[(d, i)]["dgi"]
+                        dx.addmm_(dgi if Hp == H else dgi.view(N, 3, Hp)[:, :, :H].reshape(N, 3 * H), cp["w_ih"])
+                    if "we" in cp:
+                        if (d, i) in es_at:
+                            cs = es[es_at[(d, i)]].view(R + 1, H)
+                            grads[(d, i, "we")], grads[(d, i, "be")] = cs[:R].t().contiguous(), cs[R].clone()
+                        else:
+                            grads[(d, i, "we")], grads[(d, i, "be")] = torch.zeros_like(cp["we"]), torch.zeros_like(cp["be"])
+            del res
         return (None, None, None, dx) + tuple(grads[n] for n in names)

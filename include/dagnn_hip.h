@@ -591,6 +591,10 @@ typedef struct dagnn_bwd_dataflow_args {
     int stat_rows_written;    /* nonzero: the forward launch of this step wrote rows 1..7 of every `stat` record
                                * (dagnn_dataflow_args.stat_rows); prepare only scatters g_ext into row 0 and gi / gh / a / b_hh / h
                                * of the cells are not read */
+    int pull_rows;            /* nonzero (agg = max of the constructor-string variants; H <= 256, not the wide entry): every cell's
+                               * `alpha` is [E, DAGNN_PULL_ROW] - per original edge id a row of per-unit pull weights in the loaders'
+                               * lane order (dagnn_plain_max_weights; all zeros for a cell that pulls nothing) - instead of one
+                               * scalar per edge; `w_key` must be zeros, and sigma / edge_feat_grad come out as zeros */
 } dagnn_bwd_dataflow_args;
 
 size_t dagnn_bwd_dataflow_record_bytes(int64_t N);
@@ -600,6 +604,33 @@ int dagnn_bwd_dataflow_prepare(const dagnn_plan* plan /* host */, const dagnn_bw
 int dagnn_bwd_dataflow_run(const dagnn_plan* plan /* host */, const dagnn_bwd_dataflow_args* args /* host */, void* stream);
 /* H = 320: the same sweep with five column blocks per lane (csrc/bwd_dataflow_w.hip; 12 waves like H <= 256); dagnn_bwd_dataflow_run forwards H > 256 here */
 int dagnn_bwd_dataflow_run_wide(const dagnn_plan* plan /* host */, const dagnn_bwd_dataflow_args* args /* host */, void* stream);
+
+/* agg = add / max (AggConv, GRU cells) on the sweep above (csrc/variants_bwd.hip).  `add` is the sweep as it is with
+ * alpha = 1 per edge (0 for a cell whose direction aggregates nothing) and w_key = 0; `max` is `pull_rows`.
+ *   dagnn_plain_max_weights  before the sweep: weights[e, :] of every in-edge e of the rows in [row_begin, row_end) (row slots
+ *      of direction `dir`, as for dagnn_variant_max_prepare): 0 where the message h_j + edge term of e is not the stored maximum
+ *      a_w[k], else 1 / c with c the number of messages of (w, k) that are - the tie rule of dagnn_variant_max_prepare.
+ *      `weights` is [E, DAGNN_PULL_ROW], zero-filled by the caller; column k of a row sits at 4 (k % 64) + k / 64.
+ *   dagnn_plain_edge_grads   behind the sweep: esum[w, r, :] = sum over the in-edges e of w of weight_e (.) da_w f_e[r] (r < R)
+ *      and esum[w, R, :] = sum_e weight_e (.) da_w, in CSR order (`weights` NULL: add, weight 1); da_w from the sweep's
+ *      `da_granules` of this pass.  `esum` is [N, (R + 1) * H], zero-filled by the caller; its column sums are the gradients
+ *      of edge_encoder.weight[:, r] and edge_encoder.bias.  No atomics: the same bits on every run.
+ * Limits: H <= DAGNN_PULL_ROW, at most two edge features, ld_h / ld_a / gld >= H; violations return DAGNN_EINVAL before any launch. */
+#define DAGNN_PULL_ROW 256
+typedef struct dagnn_plain_pull {
+    const float* h;            /* max_weights: [N, ld_h] forward states */
+    const float* a;            /* max_weights: [N, ld_a] aggregates (dagnn_variant_aggregate of the same states) */
+    const float* edge_mat;     /* [H, R] edge_encoder.weight, or NULL (no edge encoder) */
+    const float* edge_vec;     /* [H] edge_encoder.bias, or NULL */
+    float* weights;            /* [E, DAGNN_PULL_ROW]; edge_grads: NULL = add */
+    const void* da_granules;   /* edge_grads: uint64 [N, gld] */
+    float* esum;               /* edge_grads: out [N, (R + 1) * H] */
+    int ld_h, ld_a, gld;
+} dagnn_plain_pull;
+int dagnn_plain_max_weights(const dagnn_plan* plan /* host */, const dagnn_plain_pull* c /* host */, int dir, int H,
+                            int32_t row_begin, int32_t row_end, void* stream);
+int dagnn_plain_edge_grads(const dagnn_plan* plan /* host */, const dagnn_plain_pull* c /* host */, int dir, int H,
+                           int32_t row_begin, int32_t row_end, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Parameter gradients of the GRU cells from the sweep's outputs (csrc/wgrad.hip): for every job
