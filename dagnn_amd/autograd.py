@@ -138,6 +138,52 @@ class PoolNodes(torch.autograd.Function):
         return None, gh, None, None
 
 
+def seed_state_grads(gouts, dirs, L: int, N: int, H: int, Hp: int, device):
+    """g_ext[d][i] [N, Hp], the gradients reaching the states h[d][i] from outside: views of ONE zero fill, the first H columns
+    copied from `gouts` (one per (d, i); None: nobody differentiates that state; no `gouts`: the caller's read-out adds them)."""
+    g_all = torch.zeros(len(dirs) * L, N, Hp, dtype=torch.float32, device=device)
+    g_ext = [[g_all[dirs.index(d) * L + i] if d in dirs else None for i in range(L)] for d in range(2)]
+    for q, go in enumerate(gouts or ()):
+        if go is not None:
+            g_ext[dirs[q // L]][q % L][:, :H] = go
+    return g_ext
+
+
+def unflatten_params(mod, params):
+    """Flat parameters in `variants._cell_params` order -> (names [(d, i, name)], cellp {(d, i): {name: tensor}})."""
+    from .variants import _cell_params
+    it, names, cellp = iter(params), [], {}
+    for d in mod.dirs:
+        for i in range(mod.num_layers):
+            cellp[(d, i)] = {n: next(it) for n, _ in _cell_params(mod, d, i)}
+            names += [(d, i, n) for n in cellp[(d, i)]]
+    return names, cellp
+
+
+def wgrad_jobs(res, inp, dirs, L: int, H: int):
+    """Jobs of `engine.wgrad` for the GRU cells in (d, i) order: (dgi, the cell's input `inp(d, i)`), then (dgh, the aggregate)."""
+    jobs = []
+    for d in dirs:
+        for i in range(L):
+            r = res[(d, i)]
+            jobs += [(r["dgi"], inp(d, i), True), (r["dgh"], r["a"][:, :H], True)]
+    return jobs
+
+
+def gru_grads(jobs, like, N: int, Hp: int, H: int):
+    """(g_wih, g_bih, g_whh, g_bhh) per cell of `wgrad_jobs`; an empty batch: zeros like `like`, (w_ih, b_ih, w_hh, b_hh) per cell."""
+    if N == 0 or not jobs:
+        return [tuple(torch.zeros_like(t) for t in cell) for cell in like]
+    wg = engine.wgrad(jobs, N, Hp, H)
+    return [wg[k] + wg[k + 1] for k in range(0, len(wg), 2)]
+
+
+def add_input_grad(dx, dgi, w_ih, H: int, Hp: int) -> None:
+    """dx += dgi ([N, 3Hp] in gate blocks of Hp -> [N, 3H]) @ w_ih, in place (dx is the caller's own buffer: no add kernel)."""
+    N = dgi.shape[0]
+    dx.addmm_(dgi if Hp == H else dgi.view(N, 3, Hp)[:, :, :H].reshape(N, 3 * H), w_ih)
+
+
 class Recurrence(torch.autograd.Function):
     """Plan + node inputs -> graph read-out, differentiable (dagnn.py:144-193; dvae/dagnn.py:99-175).
 
@@ -157,11 +203,11 @@ class Recurrence(torch.autograd.Function):
         L, H, dirs = mod.num_layers, mod.hidden_dim, mod.dirs
         ctx.set_materialize_grads(False)   # (outputs nobody differentiates arrive as None in backward, not as [N, H] zero fills)
         cells = mod._cells(fresh=True)   # a differentiable pass: the optimizer changes the parameters every step
-        keep = {}
+        rec = engine.PassRecord()
         sscore = mod._static_scores(x, cells)   # keys from the inputs (`*_x` aggregators): one score per node and cell
-        h = run_stack_lockstep(plan, x, cells, dirs, L, H, vid_nodes=mod._vid_nodes, arena=mod._arena_for(x), keep=keep,
+        h = run_stack_lockstep(plan, x, cells, dirs, L, H, vid_nodes=mod._vid_nodes, arena=mod._arena_for(x), record=rec,
                                static_score=sscore, route=plan.route)
-        ctx.mod, ctx.plan, ctx.cells, ctx.keep, ctx.h, ctx.fused = mod, plan, cells, keep, h, bool(fused)
+        ctx.mod, ctx.plan, ctx.cells, ctx.rec, ctx.h, ctx.fused = mod, plan, cells, rec, h, bool(fused)
         ctx.sscore = sscore
         ctx.save_for_backward(x, *[p for p in params if p is not None])
         ctx.present = [p is not None for p in params]
@@ -174,87 +220,60 @@ class Recurrence(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, *gouts):
-        mod, plan, cells, keep, h = ctx.mod, ctx.plan, ctx.cells, ctx.keep, ctx.h
+        mod, plan, cells, rec, h = ctx.mod, ctx.plan, ctx.cells, ctx.rec, ctx.h
         saved = list(ctx.saved_tensors)
         x, it = saved[0], iter(saved[1:])
         params = [next(it) if present else None for present in ctx.present]
-        L, H, dirs, Hp = mod.num_layers, mod.hidden_dim, mod.dirs, keep["Hp"]
-        N, dev = x.shape[0], x.device
-        g_all = torch.zeros(len(dirs) * L, N, Hp, dtype=torch.float32, device=dev)   # (one fill instead of one per cell)
-        g_ext = [[g_all[dirs.index(d) * L + i] if d in dirs else None for i in range(L)] for d in range(2)]
+        L, H, dirs, Hp = mod.num_layers, mod.hidden_dim, mod.dirs, rec.Hp
+        N = x.shape[0]
+        # (not fused: the gradients of the states themselves, from whatever autograd ops followed)
+        g_ext = seed_state_grads(None if ctx.fused else gouts, dirs, L, N, H, Hp, x.device)
         dx = torch.zeros_like(x)
-        if ctx.fused:
-            if gouts[0] is not None:
-                mod._readout_backward(plan, x, h, gouts[0].contiguous().float(), g_ext, dx)
-        else:   # gradients of the states themselves, from whatever autograd ops followed
-            for q, d in enumerate(dirs):
-                for i in range(L):
-                    if gouts[q * L + i] is not None:
-                        g_ext[d][i][:, :H] = gouts[q * L + i]
-        if keep["route"].reverse == "dataflow":   # (decided with the forward's path: it runs on the forward's schedule)
-            res = engine.bwd_dataflow_sweep(plan, dirs, L, Hp, cells, keep["h_buf"], keep["gi0"], g_ext, keep["route"].groups,
-                                            arena=mod._arena_for(x, "backward"), vid_mod=mod._vid_nodes,
-                                            static_score=ctx.sscore, preact=keep.get("preact"))
+        if ctx.fused and gouts[0] is not None:
+            mod._readout_backward(plan, x, h, gouts[0].contiguous().float(), g_ext, dx)
+        kw = dict(arena=mod._arena_for(x, "backward"), vid_mod=mod._vid_nodes, static_score=ctx.sscore)
+        # (decided with the forward's path: it runs on the forward's schedule; `held`: what its launch reads, alive until this returns)
+        if rec.route.reverse == "dataflow":
+            res, held = engine.bwd_dataflow_sweep(plan, dirs, L, Hp, cells, rec.h_buf, rec.gi0, g_ext, rec.route.groups, record=rec, **kw)
         else:
-            res = engine.backward_sweep(plan, dirs, L, Hp, cells, keep["h_buf"], keep["gi0"], g_ext,
-                                        arena=mod._arena_for(x, "backward"), vid_mod=mod._vid_nodes,
-                                        static_score=ctx.sscore)
-
-        ep = engine._span("backward_epilogue", x)
-        ep.__enter__()
-
-        def gates(t):  # [N, 3Hp] in gate blocks of Hp -> [N, 3H]
-            return t if Hp == H else t.view(N, 3, Hp)[:, :, :H].reshape(N, 3 * H)
-
-        # weight / bias gradients of every cell: ONE batch of split transposed products in HIP (csrc/wgrad.hip)
-        jobs = []
-        for d in dirs:
-            for i in range(L):
+            res = engine.backward_sweep(plan, dirs, L, Hp, cells, rec.h_buf, rec.gi0, g_ext, **kw)
+        with engine._span("backward_epilogue", x):
+            # weight / bias gradients of every cell: ONE batch of split transposed products in HIP (csrc/wgrad.hip)
+            P, order = Recurrence.PER_CELL, [(d, i) for d in dirs for i in range(L)]
+            wg = gru_grads(wgrad_jobs(res, lambda d, i: x if i == 0 else h[d][i - 1], dirs, L, H),
+                           [[params[k + q] for q in (0, 2, 1, 3)] for k in range(0, len(params), P)], N, Hp, H)
+            # the small reductions of the attention / edge-encoder gradients, all cells in one batch (csrc/wgrad.hip):
+            # sum_v sigma_v keys_v, sum_v (edge-feature sums)_v, sum_v sigma_v
+            cs_jobs, cs_at = [], {}
+            for d, i in (order if N > 0 else ()):
                 r = res[(d, i)]
-                jobs.append((r["dgi"], x if i == 0 else h[d][i - 1], True))
-                jobs.append((r["dgh"], r["a"][:, :H], True))
-        wg = engine.wgrad(jobs, N, Hp, H) if N > 0 else None
-        # the small reductions of the attention / edge-encoder gradients, all cells in one batch (csrc/wgrad.hip):
-        # sum_v sigma_v keys_v, sum_v (edge-feature sums)_v, sum_v sigma_v
-        cs_jobs, cs_at = [], {}
-        if N > 0:
-            for d in dirs:
-                for i in range(L):
-                    r = res[(d, i)]
-                    keys = x if ctx.sscore is not None else h[d][i]
-                    cs_at[(d, i)] = len(cs_jobs)
-                    cs_jobs.append((keys, r["sigma"]))
-                    if r["edge_feat_grad"] is not None:
-                        cs_jobs += [(r["edge_feat_grad"], None), (r["sigma"], None)]
-        cs = engine.colsums(cs_jobs, N) if cs_jobs else None
-        # gradients of attn_lin.weight and of the edge encoder, every cell in ONE launch (csrc/wgrad.hip).  The attention logit is
-        # s_e = w_key . (h_p + W_e feat_e + b_e) [+ w_vid[p mod n]] (+ query and bias terms that cancel in the segment
-        # softmax: their gradients are exact zeros)
-        ag = None
-        if cs is not None:
-            ag_jobs = []
-            for k, (d, i) in enumerate([(d, i) for d in dirs for i in range(L)]):
-                w_ih, w_hh, b_ih, b_hh, attn_w, attn_b, edge_w, edge_b = params[k * Recurrence.PER_CELL:(k + 1) * Recurrence.PER_CELL]
-                at = cs_at[(d, i)]
-                has_e = edge_w is not None and res[(d, i)]["edge_feat_grad"] is not None
-                ag_jobs.append({"key_sum": cs[at], "feat_sum": cs[at + 1] if has_e else None,
-                                "sigma_sum": cs[at + 2] if has_e else None, "edge_w": edge_w if has_e else None, "edge_b": edge_b,
-                                "attn_w": attn_w, "dq": mod._key_offset(i)})
-            ag = engine.attn_grads(ag_jobs)
-        grads = []
-        k = 0
-        for d in dirs:
-            for i in range(L):
-                w_ih, w_hh, b_ih, b_hh, attn_w, attn_b, edge_w, edge_b = params[k:k + Recurrence.PER_CELL]
+                keys = x if ctx.sscore is not None else h[d][i]
+                cs_at[(d, i)] = len(cs_jobs)
+                cs_jobs.append((keys, r["sigma"]))
+                if r["edge_feat_grad"] is not None:
+                    cs_jobs += [(r["edge_feat_grad"], None), (r["sigma"], None)]
+            cs = engine.colsums(cs_jobs, N) if cs_jobs else None
+            # gradients of attn_lin.weight and of the edge encoder, every cell in ONE launch (csrc/wgrad.hip).  The attention logit is
+            # s_e = w_key . (h_p + W_e feat_e + b_e) [+ w_vid[p mod n]] (+ query and bias terms that cancel in the segment
+            # softmax: their gradients are exact zeros)
+            ag = None
+            if cs is not None:
+                ag_jobs = []
+                for k, (d, i) in enumerate(order):
+                    w_ih, w_hh, b_ih, b_hh, attn_w, attn_b, edge_w, edge_b = params[k * P:(k + 1) * P]
+                    at = cs_at[(d, i)]
+                    has_e = edge_w is not None and res[(d, i)]["edge_feat_grad"] is not None
+                    ag_jobs.append({"key_sum": cs[at], "feat_sum": cs[at + 1] if has_e else None,
+                                    "sigma_sum": cs[at + 2] if has_e else None, "edge_w": edge_w if has_e else None, "edge_b": edge_b,
+                                    "attn_w": attn_w, "dq": mod._key_offset(i)})
+                ag = engine.attn_grads(ag_jobs)
+            grads = []
+            for ci, (d, i) in enumerate(order):
+                w_ih, w_hh, b_ih, b_hh, attn_w, attn_b, edge_w, edge_b = params[ci * P:(ci + 1) * P]
                 r = res[(d, i)]
-                ci = k // Recurrence.PER_CELL
-                if wg is not None:
-                    (g_wih, g_bih), (g_whh, g_bhh) = wg[2 * ci], wg[2 * ci + 1]
-                else:
-                    g_wih, g_bih, g_whh, g_bhh = (torch.zeros_like(t) for t in (w_ih, b_ih, w_hh, b_hh))
-                k += Recurrence.PER_CELL
+                g_wih, g_bih, g_whh, g_bhh = wg[ci]
                 if i == 0 and x.requires_grad:
-                    dx.addmm_(gates(r["dgi"]), w_ih)   # (dx is this call's own buffer: accumulate in place, no add kernel)
+                    add_input_grad(dx, r["dgi"], w_ih, H, Hp)
                 dq = mod._key_offset(i)
                 sigma = r["sigma"]
                 kd = attn_w.shape[1] - dq - mod._vid_nodes     # key width: H, or the input width for the `*_x` aggregators
@@ -272,5 +291,4 @@ class Recurrence(torch.autograd.Function):
                     g_attn[0, dq + kd:dq + kd + mod._vid_nodes] = sigma.view(-1, mod._vid_nodes).sum(0)
                 grads += [g_wih, g_whh, g_bih, g_bhh, g_attn, None if attn_b is None else torch.zeros_like(attn_b),
                           g_edge_w, g_edge_b]
-        ep.__exit__(None, None, None)
         return (None, None, None, None, dx if x.requires_grad else None) + tuple(grads)

@@ -399,12 +399,12 @@ def _warn_off_dataflow(dev, ndirs: int, L: int, r: routing.Route) -> None:
 def run_stack_lockstep(plan: engine.PlanHandle, x: torch.Tensor, cells: Dict[Tuple[int, int], CellParams],
                        dirs: Sequence[int], L: int, H: int, vid_nodes: int = 0,
                        arena: Optional[engine.GranuleArena] = None, static_score=None,
-                       keep: Optional[dict] = None, gi0: Optional[Sequence[torch.Tensor]] = None,
+                       record: Optional[engine.PassRecord] = None, gi0: Optional[Sequence[torch.Tensor]] = None,
                        route: Optional[routing.Route] = None) -> List[List[torch.Tensor]]:
     """Lock-step schedule (default): one batched input GEMM for stacked layer 0 of every direction, then the recurrence
     on the path `routing.with_plan` names: the persistent dataflow kernel, the tile kernel, or T + L - 1 frontier launches
-    covering all cells (csrc/frontier.hip), with or without the tile kernel on the thin tail.  `keep` (training) receives
-    what the backward pass needs: the raw state buffers (`h_buf`), `gi0` and the route.  `gi0` (one [N, 3Hp] per
+    covering all cells (csrc/frontier.hip), with or without the tile kernel on the thin tail.  `record` (training) receives
+    what the backward pass needs (`engine.PassRecord`).  `gi0` (one [N, 3Hp] per
     direction): the input-side pre-activations of stacked layer 0 when the caller already has them (model._folded_gi0).
     `route`: what `routing.before_plan` told the caller that built the plan; it counts if it is for these cells' width."""
     c0 = cells[(dirs[0], 0)]
@@ -419,7 +419,7 @@ def run_stack_lockstep(plan: engine.PlanHandle, x: torch.Tensor, cells: Dict[Tup
     h = [[torch.empty(N, ld, dtype=torch.float32, device=dev) if d in dirs else None for _ in range(L)]
          for d in range(2)]
     plan.wait_ready()   # a plan built on the side stream (model._plan_of) meets the caller's stream here
-    active, train = arena is not None and N > 0, keep is not None
+    active, train = arena is not None and N > 0, record is not None
     if route is None or route.Hp != Hp:
         route = routing.before_plan(dev, H, L, len(dirs), plan.R, plan.B, keys_hidden, vid_nodes, c0.edge_gain is not None, train,
                                     Hp=Hp, active=active)
@@ -435,19 +435,15 @@ def run_stack_lockstep(plan: engine.PlanHandle, x: torch.Tensor, cells: Dict[Tup
         engine.tiles_run(plan, dirs, L, Hp, cells, gi, h, arena, first_layer=route.split, vid_mod=vid_nodes)
     elif route.kind == "dataflow":
         pack_dataflow(cells.values(), transposed_too=train and bool(engine.BWD_DATAFLOW))
-        preact = {} if (train and engine.BWD_DATAFLOW) else None
-        if route.stat_rows:
-            preact["stat_rows"] = True
         engine.dataflow_run(plan, dirs, L, Hp, cells, gi, h, route.groups, vid_mod=vid_nodes, arena=arena,
-                            static_score=static_score, score_parts=train, preact=preact, training=train)
-        if train:
-            keep["preact"] = preact
+                            static_score=static_score, score_parts=train, record=record if engine.BWD_DATAFLOW else None,
+                            training=train, stat_rows=route.stat_rows)
     else:
         _warn_off_dataflow(dev, len(dirs), L, route)
         pack_lockstep(cells.values(), force=True)
         engine.frontier_run(plan, dirs, L, Hp, cells, gi, h, vid_mod=vid_nodes, arena=arena, static_score=static_score, chains=arena)
     if train:
-        keep["h_buf"], keep["gi0"], keep["Hp"], keep["route"] = h, gi, Hp, route
+        record.h_buf, record.gi0, record.Hp, record.route = h, gi, Hp, route
     return [[h[d][i][:, :H] if h[d][i] is not None else None for i in range(L)] for d in range(2)]
 
 

@@ -637,17 +637,31 @@ def dataflow_groups(device, num_dirs: int, num_stacked: int, H: int, B: int, tra
     return min(g, DF_GROUPS) if DF_GROUPS > 0 else g
 
 
+class PassRecord(object):
+    """What a training pass's forward hands its reverse sweep: the raw state buffers `h_buf[d][i]`, `gi0[d]`, the width `Hp`, the
+    `route` and, per cell (d, i), what the dataflow launch left: the sweep's static rows `stat`, or `gh` (`gi` above layer 0).
+    `handover()`: "stat" - it wrote static rows; "preact" - it kept gh / gi; None - neither, the reverse sweep recomputes them."""
+    __slots__ = ("h_buf", "gi0", "Hp", "route", "gh", "gi", "stat")
+
+    def __init__(self, route=None):
+        self.h_buf = self.gi0 = self.Hp = None
+        self.route, self.gh, self.gi, self.stat = route, {}, {}, {}
+
+    def handover(self) -> Optional[str]:
+        return "stat" if self.stat else "preact" if self.gh else None
+
+
 def dataflow_run(plan: PlanHandle, dirs: Sequence[int], L: int, H: int, cells, gi0, h, groups: int, vid_mod: int = 0,
                  arena: Optional["GranuleArena"] = None, static_score=None, score_parts: bool = False,
-                 preact: Optional[dict] = None, training: bool = False) -> None:
+                 record: Optional[PassRecord] = None, training: bool = False, stat_rows: bool = False) -> None:
     """The whole recurrence as one persistent launch (csrc/dataflow.hip).  Same operands as `frontier_run`;
-    `score_parts` adds the partial attention scores behind the state rows (what the backward pass reads); `preact`
-    (a dict, training passes) receives the pre-activations the kernel computed anyway - `("gh", d, i)` [N,3H] for every
-    cell and `("gi", d, i)` for the stacked layers above the first - so the reverse sweep need not recompute them."""
+    `score_parts` adds the partial attention scores behind the state rows (what the backward pass reads); `record`
+    (training passes) receives the pre-activations the kernel computed anyway - `gh` [N,3H] of every cell, `gi` of the stacked
+    layers above the first - or, with `stat_rows` (`Route.stat_rows`), the static rows of the reverse sweep it wrote itself."""
     if arena is None:
         raise DagnnHipError("the dataflow kernel needs a GranuleArena (persistent, zero-initialised granule buffers)")
     lib = _lib.load()
-    args = dataflow_args(plan, dirs, L, H, cells, gi0, h, groups, vid_mod, arena, static_score, preact, training)
+    args = dataflow_args(plan, dirs, L, H, cells, gi0, h, groups, vid_mod, arena, static_score, record, training, None, stat_rows)
     with persistent_launch(plan.ws), _span("dataflow_run", plan.ws):
         check(lib.dagnn_dataflow_run(C.byref(plan.desc), C.byref(args), _stream(plan.ws)), "dagnn_dataflow_run")
     if score_parts and static_score is None:
@@ -668,8 +682,8 @@ STAT_FWD = _env_int("DAGNN_AMD_STAT_FWD", 1)   # 1: a training pass's forward la
 
 
 def dataflow_args(plan: PlanHandle, dirs: Sequence[int], L: int, H: int, cells, gi0, h, groups: int, vid_mod: int = 0,
-                  arena: Optional["GranuleArena"] = None, static_score=None, preact: Optional[dict] = None,
-                  training: bool = False, args=None):
+                  arena: Optional["GranuleArena"] = None, static_score=None, record: Optional[PassRecord] = None,
+                  training: bool = False, args=None, stat_rows: bool = False):
     """The argument struct of `dagnn_dataflow_run` for this pass (a fresh epoch of `arena`'s granule buffers, the plan's
     schedule for `groups`); `args`: fill this struct instead of a new one (the `df` member of `EncodeArgs`)."""
     if args is None:
@@ -700,19 +714,19 @@ def dataflow_args(plan: PlanHandle, dirs: Sequence[int], L: int, H: int, cells, 
             fc.h_out = h[d][i].data_ptr()
             fc.granules = gran[(d, i)].data_ptr()
             fc.proj_granules = gran[("p", d, i)].data_ptr() if i > 0 else None
-            if preact is not None and preact.get("stat_rows"):
+            if record is not None and stat_rows:
                 # the reverse sweep's static record of every node, rows 1..7 written by this launch (bwd_dataflow_sweep adds
                 # row 0); widths other than 256 / 320 leave the columns >= H to the fill
                 nfl = lib_static_floats(plan.N, H)
-                preact[("stat", d, i)] = (torch.empty if H in (256, 320) else torch.zeros)(nfl, dtype=torch.float32, device=plan.ws.device)
-                fc.gh_out = preact[("stat", d, i)].data_ptr()
+                record.stat[(d, i)] = (torch.empty if H in (256, 320) else torch.zeros)(nfl, dtype=torch.float32, device=plan.ws.device)
+                fc.gh_out = record.stat[(d, i)].data_ptr()
                 args.stat_rows = 1
-            elif preact is not None:
-                preact[("gh", d, i)] = torch.empty(plan.N, 3 * H, dtype=torch.float32, device=plan.ws.device)
-                fc.gh_out = preact[("gh", d, i)].data_ptr()
+            elif record is not None:
+                record.gh[(d, i)] = torch.empty(plan.N, 3 * H, dtype=torch.float32, device=plan.ws.device)
+                fc.gh_out = record.gh[(d, i)].data_ptr()
                 if i > 0:
-                    preact[("gi", d, i)] = torch.empty(plan.N, 3 * H, dtype=torch.float32, device=plan.ws.device)
-                    fc.gi_out = preact[("gi", d, i)].data_ptr()
+                    record.gi[(d, i)] = torch.empty(plan.N, 3 * H, dtype=torch.float32, device=plan.ws.device)
+                    fc.gi_out = record.gi[(d, i)].data_ptr()
     args.num_stacked, args.dir_mask, args.H, args.ld_h, args.gld = L, mask, H, h[dirs[0]][0].shape[1], gld
     args.pld = H   # (row pitch of the projection granules, in 16-byte granules)
     args.vid_mod, args.groups, args.epoch = int(vid_mod), int(groups), epoch
@@ -1053,11 +1067,7 @@ def frontier_run(plan: PlanHandle, dirs: Sequence[int], L: int, H: int, cells, g
     args.tail_replicas, args.tail_max_blocks = (TAIL_REPLICAS if use_tail else 0), TAIL_MAX_BLOCKS
     args.tail_slice_units = TAIL_SLICE
     args.epoch, args.tail_err = epoch, _ptr(err)
-    ptrs = (C.POINTER(C.c_int32) * 2)()
-    nl = (C.c_int32 * 2)()
-    for d in (0, 1):
-        ptrs[d] = sched[d].ctypes.data_as(C.POINTER(C.c_int32))
-        nl[d] = len(sched[d]) - 1
+    ptrs, nl = _schedule_ptrs(sched)
     if chains is not None and not use_tail and len(dirs) == 2 and DUAL_CHAINS and DEBUG_TIMING is None:
         args.side_stream = chains.side_stream(plan.ws.device).cuda_stream
         args.fork_event, args.join_event = chains.fork_join_events(plan.ws.device)
@@ -1187,6 +1197,39 @@ def attn_grads(jobs):
     return out
 
 
+def _schedule_ptrs(sched):
+    """(ptrs, nl) of a lock-step launch: per direction the schedule's layer offsets (arrays the caller keeps) and layer count."""
+    ptrs = (C.POINTER(C.c_int32) * 2)(*[sched[d].ctypes.data_as(C.POINTER(C.c_int32)) for d in (0, 1)])
+    return ptrs, (C.c_int32 * 2)(*[len(sched[d]) - 1 for d in (0, 1)])
+
+
+def _key_side(bc, c, o, h, score, H: int, R: int, vid_mod: int, keep: list) -> torch.Tensor:
+    """Key-side fields of one `BackwardCell`; returns the key in use (`score`: keys from the inputs - a zero key, held by `keep`)."""
+    key = c.w_key
+    if score is not None:
+        key = torch.zeros(H, dtype=torch.float32, device=h.device)
+        keep.append(key)
+        bc.static_score = _dev(score, "static score", torch.float32).data_ptr()
+    bc.w_key = key.data_ptr()
+    bc.edge_gain = _ptr(c.edge_gain) if R > 0 else None
+    bc.vid_bias = _ptr(c.vid_bias) if vid_mod > 0 else None
+    bc.h, bc.a, bc.alpha = h.data_ptr(), o["a"].data_ptr(), o["alpha"].data_ptr()
+    return key
+
+
+def _recompute_preact(keys, cells, out, h, H: int, gi: dict) -> dict:
+    """gh of every cell (returned) and gi above layer 0 (into `gi`), recomputed by batched MFMA GEMMs: every h is known."""
+    gh = {}
+    for k0 in range(0, len(keys), 4):
+        grp = keys[k0:k0 + 4]
+        gh.update(zip(grp, gemm_nt_bias([out[k]["a"] for k in grp], [cells[k].w_hh_raw for k in grp], [cells[k].b_hh for k in grp])))
+    up = [k for k in keys if k[1] > 0]
+    for k0 in range(0, len(up), 4):
+        grp = up[k0:k0 + 4]
+        gi.update(zip(grp, gemm_nt_bias([h[d][i - 1][:, :H] for d, i in grp], [cells[k].w_ih for k in grp], [cells[k].b_ih for k in grp])))
+    return gh
+
+
 def backward_sweep(plan: PlanHandle, dirs: Sequence[int], L: int, H: int, cells, h, gi0, g_ext,
                    arena: Optional[GranuleArena] = None, vid_mod: int = 0, static_score=None):
     """Reverse pass of the lock-step recurrence (csrc/backward.hip).  `h[d][i]` [N, frontier_ld(H)] are the
@@ -1203,7 +1246,6 @@ def backward_sweep(plan: PlanHandle, dirs: Sequence[int], L: int, H: int, cells,
     gkeys = [("da", d, i) for d in dirs for i in range(L)] + [("du", d, i) for d in dirs for i in range(L - 1)]
     gran, epoch, err = arena.get(gkeys, N, H, dev) if use_tail else ({}, 0, None)
     keep = []
-    keep_alive = keep
     if arena is not None:
         arena.poll()
     for d in dirs:
@@ -1221,15 +1263,7 @@ def backward_sweep(plan: PlanHandle, dirs: Sequence[int], L: int, H: int, cells,
                      edge_feat_grad=torch.empty(N, R, **f32) if R > 0 else None)
             out[(d, i)] = o
             bc.w_hh, bc.w_ih = c.w_hh_raw.data_ptr(), (c.w_ih.data_ptr() if i > 0 else None)
-            if static_score is not None:   # keys from the inputs: scores are given, the states' gradient gets no key term
-                zero_key = torch.zeros(H, **f32)
-                keep_alive.append(zero_key)
-                bc.w_key, bc.static_score = zero_key.data_ptr(), _dev(static_score[(d, i)], "static score", torch.float32).data_ptr()
-            else:
-                bc.w_key = c.w_key.data_ptr()
-            bc.edge_gain = _ptr(c.edge_gain) if R > 0 else None
-            bc.vid_bias = _ptr(c.vid_bias) if vid_mod > 0 else None
-            bc.h, bc.a, bc.alpha = h[d][i].data_ptr(), o["a"].data_ptr(), o["alpha"].data_ptr()
+            _key_side(bc, c, o, h[d][i], None if static_score is None else static_score[(d, i)], H, R, vid_mod, keep)
             bc.g_ext, bc.da, bc.dgi, bc.dgh = g_ext[d][i].data_ptr(), o["da"].data_ptr(), o["dgi"].data_ptr(), o["dgh"].data_ptr()
             bc.sigma, bc.edge_feat_grad = o["sigma"].data_ptr(), _ptr(o["edge_feat_grad"])
     args.num_stacked, args.dir_mask, args.H, args.ld_h = L, mask, H, h[dirs[0]][0].shape[1]
@@ -1241,29 +1275,14 @@ def backward_sweep(plan: PlanHandle, dirs: Sequence[int], L: int, H: int, cells,
     lib = _lib.load()
     with _span("backward_prepare", plan.ws):
         check(lib.dagnn_backward_prepare(C.byref(plan.desc), C.byref(args), _stream(plan.ws)), "dagnn_backward_prepare")
-    # pre-activations of every cell, recomputed by batched MFMA GEMMs (all rows at once: every h is known)
     keys = [(d, i) for d in dirs for i in range(L)]
-    gh = {}
-    for k0 in range(0, len(keys), 4):
-        grp = keys[k0:k0 + 4]
-        res = gemm_nt_bias([out[k]["a"] for k in grp], [cells[k].w_hh_raw for k in grp], [cells[k].b_hh for k in grp])
-        gh.update(dict(zip(grp, res)))
     gi = {(d, 0): gi0[d] for d in dirs}
-    up = [(d, i) for d in dirs for i in range(1, L)]
-    for k0 in range(0, len(up), 4):
-        grp = up[k0:k0 + 4]
-        res = gemm_nt_bias([h[d][i - 1][:, :H] for d, i in grp], [cells[k].w_ih for k in grp],
-                           [cells[k].b_ih for k in grp])
-        gi.update(dict(zip(grp, res)))
+    gh = _recompute_preact(keys, cells, out, h, H, gi)
     for k in keys:
         args.cell[k[0]][k[1]].gi, args.cell[k[0]][k[1]].gh = gi[k].data_ptr(), gh[k].data_ptr()
         out[k]["gi"], out[k]["gh"] = gi[k], gh[k]
     sched = plan.read_schedule()
-    ptrs = (C.POINTER(C.c_int32) * 2)()
-    nl = (C.c_int32 * 2)()
-    for d in (0, 1):
-        ptrs[d] = sched[d].ctypes.data_as(C.POINTER(C.c_int32))
-        nl[d] = len(sched[d]) - 1
+    ptrs, nl = _schedule_ptrs(sched)
     if use_tail and SPLIT_DEEP:
         splits = plan.read_splits()
         args.side_stream = arena.side_stream(dev).cuda_stream
@@ -1322,10 +1341,11 @@ def bwd_dataflow_fits(device, N: int, cells: int) -> bool:
 
 
 def bwd_dataflow_sweep(plan: PlanHandle, dirs: Sequence[int], L: int, H: int, cells, h, gi0, g_ext, groups: int,
-                       arena: "GranuleArena", vid_mod: int = 0, static_score=None, preact: Optional[dict] = None,
+                       arena: "GranuleArena", vid_mod: int = 0, static_score=None, record: Optional[PassRecord] = None,
                        plain: Optional[dict] = None):
-    """Reverse pass of the recurrence as ONE persistent dataflow launch (csrc/bwd_dataflow.hip).  Same operands and
-    the same result dictionary as `backward_sweep`; `groups` must be the group count of the forward pass's schedule.
+    """Reverse pass of the recurrence as ONE persistent dataflow launch (csrc/bwd_dataflow.hip).  Same operands as
+    `backward_sweep`, returns (its result dictionary, the buffers the launch reads); `groups` must be the group count of the
+    forward pass's schedule, `record` says what the forward launch handed over (`PassRecord.handover`).
     `plain` (agg = add / max, `variants.PlainRecurrence`): {(d, i): (a [N, H] contiguous, pull)} - the aggregates and the
     pull weights the caller prepared instead of `dagnn_backward_prepare`'s: `pull` is [E] (add: ones, or zeros for a cell
     that aggregates nothing), or with `plain["pull_rows"]` (max) [E, _lib.PULL_ROW] per-unit weight rows; the keys are
@@ -1335,58 +1355,37 @@ def bwd_dataflow_sweep(plan: PlanHandle, dirs: Sequence[int], L: int, H: int, ce
     lib = _lib.load()
     f32 = dict(dtype=torch.float32, device=dev)
     arena.poll()
-    out, keep = {}, []
+    out, keep, wkey = {}, [], {}
     pargs = BackwardArgs()
     mask = 0
     for d in dirs:
         mask |= 1 << d
         for i in range(L):
-            c, bc = cells[(d, i)], pargs.cell[d][i]
             o = dict(a=plain[(d, i)][0] if plain else torch.empty(N, H, **f32),
                      alpha=plain[(d, i)][1] if plain else torch.empty(max(E, 1), **f32),
                      dgi=torch.empty(N, 3 * H, **f32), dgh=torch.empty(N, 3 * H, **f32), sigma=torch.empty(N, **f32),
                      edge_feat_grad=torch.empty(N, R, **f32) if R > 0 else None)
             out[(d, i)] = o
             if plain:
-                o["_wkey"] = torch.zeros(H, **f32)
-                keep.append(o["_wkey"])
-                continue
-            if static_score is not None:
-                zero_key = torch.zeros(H, **f32)
-                keep.append(zero_key)
-                bc.w_key, bc.static_score = zero_key.data_ptr(), _dev(static_score[(d, i)], "static score", torch.float32).data_ptr()
-                o["_wkey"] = zero_key
+                wkey[(d, i)] = torch.zeros(H, **f32)
+                keep.append(wkey[(d, i)])
             else:
-                bc.w_key = c.w_key.data_ptr()
-                o["_wkey"] = c.w_key
-            bc.edge_gain = _ptr(c.edge_gain) if R > 0 else None
-            bc.vid_bias = _ptr(c.vid_bias) if vid_mod > 0 else None
-            bc.h, bc.a, bc.alpha = h[d][i].data_ptr(), o["a"].data_ptr(), o["alpha"].data_ptr()
+                wkey[(d, i)] = _key_side(pargs.cell[d][i], cells[(d, i)], o, h[d][i],
+                                         None if static_score is None else static_score[(d, i)], H, R, vid_mod, keep)
     pargs.num_stacked, pargs.dir_mask, pargs.H, pargs.ld_h = L, mask, H, h[dirs[0]][0].shape[1]
     pargs.vid_mod = int(vid_mod)
     with _span("backward_prepare", plan.ws):
         if not plain:
             check(lib.dagnn_backward_prepare(C.byref(plan.desc), C.byref(pargs), _stream(plan.ws)), "dagnn_backward_prepare")
         keys = [(d, i) for d in dirs for i in range(L)]
-        gh = {}
-        gi = {(d, 0): gi0[d] for d in dirs}
-        up = [(d, i) for d in dirs for i in range(1, L)]
-        stat_fwd = bool(preact) and all(("stat",) + k in preact for k in keys)   # the forward launch wrote rows 1..7 (`stat_rows`)
-        if stat_fwd:
-            gi = {}
-        elif preact and all(("gh",) + k in preact for k in keys):   # the forward kernel kept the pre-activations of this pass
-            gh = {k: preact[("gh",) + k] for k in keys}
-            gi.update({k: preact[("gi",) + k] for k in up})
-        else:
-            for k0 in range(0, len(keys), 4):
-                grp = keys[k0:k0 + 4]
-                res = gemm_nt_bias([out[k]["a"] for k in grp], [cells[k].w_hh_raw for k in grp], [cells[k].b_hh for k in grp])
-                gh.update(dict(zip(grp, res)))
-            for k0 in range(0, len(up), 4):
-                grp = up[k0:k0 + 4]
-                res = gemm_nt_bias([h[d][i - 1][:, :H] for d, i in grp], [cells[k].w_ih for k in grp],
-                                   [cells[k].b_ih for k in grp])
-                gi.update(dict(zip(grp, res)))
+        kept = record.handover() if record is not None else None
+        stat_fwd = kept == "stat"   # the forward launch wrote rows 1..7 (`Route.stat_rows`)
+        gh, gi = {}, ({} if stat_fwd else {(d, 0): gi0[d] for d in dirs})
+        if kept == "preact":   # the forward kernel kept the pre-activations of this pass
+            gh = record.gh
+            gi.update(record.gi)
+        elif not stat_fwd:
+            gh = _recompute_preact(keys, cells, out, h, H, gi)
         gkeys = [("da", d, i) for d in dirs for i in range(L)] + [("q", d, i) for d in dirs for i in range(L)] + \
                 [("dgi", d, i) for d in dirs for i in range(1, L)] + [("du", d, i) for d in dirs for i in range(L - 1)]
         widths = {k: (1 if k[0] == "q" else 3 * H) for k in gkeys if k[0] in ("q", "dgi")}
@@ -1400,10 +1399,10 @@ def bwd_dataflow_sweep(plan: PlanHandle, dirs: Sequence[int], L: int, H: int, ce
             if getattr(c, "w_hh_bt", None) is None:
                 c.w_hh_bt = pack_dataflow_transposed(c.w_hh_raw, H)
                 c.w_ih_bt = pack_dataflow_transposed(c.w_ih, H) if i > 0 else None
-            stat = preact[("stat",) + k] if stat_fwd else torch.empty(stat_bytes // 4, **f32)
+            stat = record.stat[k] if stat_fwd else torch.empty(stat_bytes // 4, **f32)
             keep.append(stat)
             bc.w_hh_t, bc.w_ih_t = c.w_hh_bt.data_ptr(), _ptr(c.w_ih_bt)
-            bc.w_key, bc.alpha = o["_wkey"].data_ptr(), o["alpha"].data_ptr()
+            bc.w_key, bc.alpha = wkey[k].data_ptr(), o["alpha"].data_ptr()
             bc.gi, bc.gh, bc.a, bc.b_hh = _ptr(gi.get(k)), _ptr(gh.get(k)), o["a"].data_ptr(), c.b_hh.data_ptr()
             bc.h, bc.g_ext, bc.stat = h[d][i].data_ptr(), g_ext[d][i].data_ptr(), stat.data_ptr()
             bc.da_granules, bc.q_granules = gran[("da", d, i)].data_ptr(), gran[("q", d, i)].data_ptr()
@@ -1429,12 +1428,10 @@ def bwd_dataflow_sweep(plan: PlanHandle, dirs: Sequence[int], L: int, H: int, ce
     with persistent_launch(plan.ws), _span("backward_run", plan.ws):
         check(lib.dagnn_bwd_dataflow_run(C.byref(plan.desc), C.byref(args), _stream(plan.ws)), "dagnn_bwd_dataflow_run")
     arena.watch(plan, folded=True)
-    for k, o in out.items():
-        o.pop("_wkey", None)
-        if plain:
+    if plain:
+        for k, o in out.items():
             o["da_granules"] = gran[("da",) + k]
-    out["_keep"] = keep   # buffers the launch reads: alive until the caller drops the result
-    return out
+    return out, keep   # (`keep`: buffers the launch reads - the caller holds them until its backward returns)
 
 
 _WGRAD_WS = {}   # per (kind, device, stream): the partial-tile workspaces of `wgrad` / `colsums` (grown on demand, reused by

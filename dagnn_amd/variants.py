@@ -34,7 +34,7 @@ from typing import List, Optional
 
 import torch
 
-from . import _lib, engine, route as routing
+from . import _lib, autograd as rev, engine, route as routing
 
 
 def _segment_softmax(logit: torch.Tensor, seg: torch.Tensor, num_seg: int) -> torch.Tensor:
@@ -280,8 +280,8 @@ def _plain_cells(mod, R: int, dev):
     return mod._cache("plain_df").get(srcs, make, fresh=mod.training)
 
 
-def _plain_forward(mod, x: torch.Tensor, plan, r, cells, preact: Optional[dict] = None):
-    """One launch of the dataflow kernel over the plain cells on route `r`: (raw state buffers h[d][i] [N, ld], gi0 per direction)."""
+def _plain_forward(mod, x: torch.Tensor, plan, r, cells, record: Optional[engine.PassRecord] = None):
+    """One launch of the dataflow kernel over the plain cells on route `r`: the raw state buffers h[d][i] [N, ld] (and `record`)."""
     L, dirs = mod.num_layers, list(mod.dirs)
     N, dev = x.shape[0], x.device
     arena = mod._arena_for(x)
@@ -293,8 +293,11 @@ def _plain_forward(mod, x: torch.Tensor, plan, r, cells, preact: Optional[dict] 
     ld = engine.frontier_ld(r.Hp)
     h = [[torch.empty(N, ld, dtype=torch.float32, device=dev) if d in dirs else None for _ in range(L)] for d in range(2)]
     plan.wait_ready()
-    engine.dataflow_run(plan, dirs, L, r.Hp, cells, gi, h, r.groups, arena=arena, preact=preact, training=preact is not None)
-    return h, gi
+    engine.dataflow_run(plan, dirs, L, r.Hp, cells, gi, h, r.groups, arena=arena, record=record, training=record is not None,
+                        stat_rows=r.stat_rows)
+    if record is not None:
+        record.h_buf, record.gi0, record.Hp = h, gi, r.Hp
+    return h
 
 
 def run_plain_dataflow(mod, x: torch.Tensor, plan) -> Optional[List[List[Optional[torch.Tensor]]]]:
@@ -310,7 +313,7 @@ def run_plain_dataflow(mod, x: torch.Tensor, plan) -> Optional[List[List[Optiona
     cells = _plain_cells(mod, plan.R, x.device)
     if cells is None:
         return None
-    h, _ = _plain_forward(mod, x, plan, r, cells)
+    h = _plain_forward(mod, x, plan, r, cells)
     return [[h[d][i][:, :H] if h[d][i] is not None else None for i in range(L)] for d in range(2)]
 
 
@@ -704,6 +707,140 @@ def _aggregator_grads(mod, mode, o, cp, vals, query, R, W, i, dx_d):
     return g
 
 
+_GRU = ("w_ih", "b_ih", "w_hh", "b_hh")   # (the order of `autograd.gru_grads`)
+
+
+def _variant_setup(mod, plan, x, hb, gouts, cellp, sched):
+    """`VariantRecurrence.backward`, set-up: (sweep arguments, state gradients g[(d, i)] [N, Hp] seeded from `gouts`, buffers
+    res[(d, i)] of every cell, the `agg_x` aggregator aggx[d] of a direction, input gradient dxd[d] per direction)."""
+    N, H, L, E = x.shape[0], mod.hidden_dim, mod.num_layers, mod.emb_dim
+    Hp = row_pitch(H)   # row pitch of every state-like buffer below; columns H..Hp-1 are zero and no kernel writes them
+    f32 = dict(dtype=torch.float32, device=x.device)
+    mode = _BWD_MODES[mod.agg]
+    stream = engine._stream(x)
+    prm = _derive(mod)
+    shared_flow = mod.agg in ("add", "max") and getattr(mod, "shared_agg_flow", True)
+    recurr, agg_x = bool(mod.recurr), bool(mod.agg_x)
+    args = _lib.VariantBwdArgs()
+    args.num_stacked, args.H, args.ld, args.dir_mask = L, H, Hp, sum(1 << d for d in mod.dirs)
+    g, res, aggx = {}, {}, {}
+    q = 0
+    for d in mod.dirs:
+        for i in range(L):
+            go = gouts[q]
+            q += 1
+            if Hp == H:
+                g[(d, i)] = go.detach().float().contiguous().clone() if go is not None else torch.zeros(N, H, **f32)
+            else:
+                g[(d, i)] = torch.zeros(N, Hp, **f32)
+                if go is not None:
+                    g[(d, i)][:, :H] = go.detach()
+    dxd = {d: torch.zeros(N, E, **f32) for d in mod.dirs}
+    for d in mod.dirs:
+        lands = 0 if (shared_flow and d == 1) else 1
+        T = len(sched[d]) - 1
+        rows = (int(sched[d][1]), int(sched[d][T])) if T > 1 else (0, 0)
+        given = None
+        if agg_x:
+            # the aggregator reads x only (dagnn.py:159-169): its output a_x [N, E] (zero-padded to H) is the
+            # aggregate of EVERY stacked cell of the direction
+            ao = dict(a=torch.zeros(N, E, **f32))
+            bca = _lib.VariantBwdCell()
+            bca.in_dim = E
+            _setup_aggregator(mod, plan, bca, ao, prm[(d, 0)], cellp[(d, 0)], mode, lands, d, 0, x, x, E, ao["a"], rows, stream, x)
+            given = torch.zeros(N, Hp, **f32)
+            given[:, :E] = ao["a"]
+            aggx[d] = (bca, ao)
+        for i in range(L):
+            p, cp, bc = prm[(d, i)], cellp[(d, i)], args.cell[d][i]
+            hi = hb[(d, i)]                             # [N, Hp]
+            u = x if i == 0 else hb[(d, i - 1)]
+            in_dim = E if i == 0 else H
+            o = dict(u=u, dgi=torch.zeros(N, 3 * Hp, **f32), dgh=torch.zeros(N, 3 * Hp, **f32), da=torch.zeros(N, Hp, **f32))
+            bc.in_dim, bc.recurrent, bc.ld_in = in_dim, int(recurr), (0 if i == 0 else Hp)
+            if agg_x:
+                o["a"] = given
+                bc.mode, bc.lands = _lib.AGG_GIVEN, 1
+                bc.h, bc.a = hi.data_ptr(), given.data_ptr()
+            else:
+                o["a"] = torch.zeros(N, Hp, **f32)
+                _setup_aggregator(mod, plan, bc, o, p, cp, mode, lands, d, i, hi, u, H, o["a"], rows, stream, x)
+            a = o["a"]
+            if recurr and Hp == H:
+                o["gi"] = engine.gemm_nt_bias([u], [cp["w_ih"]], [cp["b_ih"]])[0]
+                o["gh"] = engine.gemm_nt_bias([a], [cp["w_hh"]], [cp["b_hh"]])[0]
+            elif recurr:   # gate blocks at a pitch of Hp: zero rows (and bias) between them leave the padding of gi / gh zero
+                o["gi"] = engine.gemm_nt_bias([u], [_pad_gates(cp["w_ih"], H, Hp, u.shape[1])], [_pad_gates(cp["b_ih"], H, Hp)])[0]
+                o["gh"] = engine.gemm_nt_bias([a], [_pad_gates(cp["w_hh"], H, Hp, Hp)], [_pad_gates(cp["b_hh"], H, Hp)])[0]
+            if recurr:
+                bc.gi, bc.gh = o["gi"].data_ptr(), o["gh"].data_ptr()
+                bc.w_hh, bc.w_ih = cp["w_hh"].data_ptr(), cp["w_ih"].data_ptr()
+            else:   # Linear cell: W = [W_in | W_agg]
+                o["w_in"] = cp["w_lin"][:, :in_dim].contiguous()
+                o["w_agg"] = cp["w_lin"][:, in_dim:].contiguous()
+                bc.w_ih, bc.w_hh = o["w_in"].data_ptr(), o["w_agg"].data_ptr()
+            o["in_dim"] = in_dim
+            bc.g = g[(d, i)].data_ptr()
+            bc.g_in = (g[(d, i - 1)] if i > 0 else dxd[d]).data_ptr()
+            bc.da, bc.dgi, bc.dgh = o["da"].data_ptr(), o["dgi"].data_ptr(), o["dgh"].data_ptr()
+            res[(d, i)] = o
+    return args, g, res, aggx, dxd
+
+
+def _variant_sweep(mod, plan, x, args, res, aggx, dxd, sched):
+    """The reverse sweep of csrc/variants_bwd.hip, then - `agg_x` - the aggregator's own: one shot over all rows, into dxd."""
+    import numpy as np
+    lib, stream = _lib.load(), engine._stream(x)
+    N, L, E = x.shape[0], mod.num_layers, mod.emb_dim
+    if mod.agg_x:   # nothing couples the layers - one pseudo-layer of all rows
+        sched = [np.array([0, N], dtype=np.int32)] * 2
+    ptrs, nl = engine._schedule_ptrs(sched)
+    with engine._span("variant_backward_run", x):
+        engine.check(lib.dagnn_variant_backward_run(C.byref(plan.desc), C.byref(args), ptrs, nl, stream),
+                     "dagnn_variant_backward_run")
+        for d in (mod.dirs if mod.agg_x else ()):
+            bca, ao = aggx[d]
+            if not bca.lands:
+                continue
+            dps = res[(d, 0)]["da"]
+            for i in range(1, L):
+                dps = dps + res[(d, i)]["da"]
+            ao["da"] = dps[:, :E].contiguous()
+            bca.da, bca.g, bca.g_in = ao["da"].data_ptr(), dxd[d].data_ptr(), dxd[d].data_ptr()
+            engine.check(lib.dagnn_variant_aggregator_backward(C.byref(plan.desc), C.byref(bca), d, E, 0, N, stream),
+                         "dagnn_variant_aggregator_backward")
+
+
+def _variant_param_grads(mod, plan, x, h, g, res, aggx, dxd, cellp):
+    """The epilogue: {(d, i, name): gradient} of every parameter (transposed products over all nodes)."""
+    N, H, L, E, R = x.shape[0], mod.hidden_dim, mod.num_layers, mod.emb_dim, plan.R
+    mode, recurr = _BWD_MODES[mod.agg], bool(mod.recurr)
+    grads = {}
+    if recurr:
+        wg = iter(rev.gru_grads(rev.wgrad_jobs(res, lambda d, i: res[(d, i)]["u"][:, :res[(d, i)]["in_dim"]], mod.dirs, L, H),
+                                [[cp[n] for n in _GRU] for cp in cellp.values()], N, row_pitch(H), H))
+    for d in mod.dirs:
+        for i in range(L):
+            o, cp = res[(d, i)], cellp[(d, i)]
+            if not recurr:   # Linear cell: dW = g^T [u ; a], db = sum g (g holds the total gradient of every row now)
+                gt = g[(d, i)][:, :H]
+                grads[(d, i, "w_lin")] = torch.cat([gt.t() @ o["u"][:, :o["in_dim"]], gt.t() @ o["a"][:, :H]], 1)
+                grads[(d, i, "b_lin")] = gt.sum(0)
+            else:
+                grads.update(zip([(d, i, n) for n in _GRU], next(wg)))
+            if mod.agg_x:
+                if i == 0:
+                    _, ao = aggx[d]
+                    ag = _aggregator_grads(mod, mode, ao, cp, x, x, R, E, 0, dxd[d]) if "da" in ao else {}
+                    for n in cp:
+                        if n not in _GRU + ("w_lin", "b_lin"):
+                            grads[(d, i, n)] = ag.get(n, torch.zeros_like(cp[n]))
+            else:
+                for n, v in _aggregator_grads(mod, mode, o, cp, h[d][i], o["u"][:, :o["in_dim"]], R, H, i, dxd[d]).items():
+                    grads[(d, i, n)] = v
+    return grads
+
+
 class VariantRecurrence(torch.autograd.Function):
     """States h[d][i] of a constructor-string variant, differentiable: forward = `run_hip` (the generic lock-step kernels
     of csrc/variants.hip), backward = the reverse sweep of csrc/variants_bwd.hip + a parallel epilogue (weight gradients as
@@ -724,152 +861,16 @@ class VariantRecurrence(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, *gouts):
-        mod, plan, h, hb = ctx.mod, ctx.plan, ctx.h, ctx.hbuf
+        mod, plan = ctx.mod, ctx.plan
         saved = list(ctx.saved_tensors)
         x, params = saved[0].detach(), [p.detach() for p in saved[1:]]
-        N, H, L, E = x.shape[0], mod.hidden_dim, mod.num_layers, mod.emb_dim
-        Hp = row_pitch(H)   # row pitch of every state-like buffer below; columns H..Hp-1 are zero and no kernel writes them
-        f32 = dict(dtype=torch.float32, device=x.device)
-        lib = _lib.load()
-        mode = _BWD_MODES[mod.agg]
-        R = plan.R
         sched = plan.read_schedule()
-        stream = engine._stream(x)
-        prm = _derive(mod)
-        shared_flow = mod.agg in ("add", "max") and getattr(mod, "shared_agg_flow", True)
-        recurr, agg_x = bool(mod.recurr), bool(mod.agg_x)
-        names, cellp, k = [], {}, 0
-        for d in mod.dirs:
-            for i in range(L):
-                spec = _cell_params(mod, d, i)
-                cellp[(d, i)] = {n: params[k + q] for q, (n, _) in enumerate(spec)}
-                names += [(d, i, n) for n, _ in spec]
-                k += len(spec)
-        args = _lib.VariantBwdArgs()
-        args.num_stacked, args.H, args.ld, args.dir_mask = L, H, Hp, sum(1 << d for d in mod.dirs)
-        g, res, aggx = {}, {}, {}
-        q = 0
-        for d in mod.dirs:
-            for i in range(L):
-                go = gouts[q]
-                q += 1
-                if Hp == H:
-                    g[(d, i)] = go.detach().float().contiguous().clone() if go is not None else torch.zeros(N, H, **f32)
-                else:
-                    g[(d, i)] = torch.zeros(N, Hp, **f32)
-                    if go is not None:
-                        g[(d, i)][:, :H] = go.detach()
-        dxd = {d: torch.zeros(N, E, **f32) for d in mod.dirs}
+        names, cellp = rev.unflatten_params(mod, params)
         with torch.no_grad():
-            for d in mod.dirs:
-                lands = 0 if (shared_flow and d == 1) else 1
-                T = len(sched[d]) - 1
-                rows = (int(sched[d][1]), int(sched[d][T])) if T > 1 else (0, 0)
-                given = None
-                if agg_x:
-                    # the aggregator reads x only (dagnn.py:159-169): its output a_x [N, E] (zero-padded to H) is the
-                    # aggregate of EVERY stacked cell of the direction
-                    ao = dict(a=torch.zeros(N, E, **f32))
-                    bca = _lib.VariantBwdCell()
-                    bca.in_dim = E
-                    _setup_aggregator(mod, plan, bca, ao, prm[(d, 0)], cellp[(d, 0)], mode, lands, d, 0, x, x, E, ao["a"], rows, stream, x)
-                    given = torch.zeros(N, Hp, **f32)
-                    given[:, :E] = ao["a"]
-                    aggx[d] = (bca, ao)
-                for i in range(L):
-                    p, cp, bc = prm[(d, i)], cellp[(d, i)], args.cell[d][i]
-                    hi = hb[(d, i)]                             # [N, Hp]
-                    u = x if i == 0 else hb[(d, i - 1)]
-                    in_dim = E if i == 0 else H
-                    o = dict(u=u, dgi=torch.zeros(N, 3 * Hp, **f32), dgh=torch.zeros(N, 3 * Hp, **f32), da=torch.zeros(N, Hp, **f32))
-                    bc.in_dim, bc.recurrent, bc.ld_in = in_dim, int(recurr), (0 if i == 0 else Hp)
-                    if agg_x:
-                        o["a"] = given
-                        bc.mode, bc.lands = _lib.AGG_GIVEN, 1
-                        bc.h, bc.a = hi.data_ptr(), given.data_ptr()
-                    else:
-                        o["a"] = torch.zeros(N, Hp, **f32)
-                        _setup_aggregator(mod, plan, bc, o, p, cp, mode, lands, d, i, hi, u, H, o["a"], rows, stream, x)
-                    a = o["a"]
-                    if recurr and Hp == H:
-                        o["gi"] = engine.gemm_nt_bias([u], [cp["w_ih"]], [cp["b_ih"]])[0]
-                        o["gh"] = engine.gemm_nt_bias([a], [cp["w_hh"]], [cp["b_hh"]])[0]
-                    elif recurr:   # gate blocks at a pitch of Hp: zero rows (and bias) between them leave the padding of gi / gh zero
-                        o["gi"] = engine.gemm_nt_bias([u], [_pad_gates(cp["w_ih"], H, Hp, u.shape[1])], [_pad_gates(cp["b_ih"], H, Hp)])[0]
-                        o["gh"] = engine.gemm_nt_bias([a], [_pad_gates(cp["w_hh"], H, Hp, Hp)], [_pad_gates(cp["b_hh"], H, Hp)])[0]
-                    if recurr:
-                        bc.gi, bc.gh = o["gi"].data_ptr(), o["gh"].data_ptr()
-                        bc.w_hh, bc.w_ih = cp["w_hh"].data_ptr(), cp["w_ih"].data_ptr()
-                    else:   # Linear cell: W = [W_in | W_agg]
-                        o["w_in"] = cp["w_lin"][:, :in_dim].contiguous()
-                        o["w_agg"] = cp["w_lin"][:, in_dim:].contiguous()
-                        bc.w_ih, bc.w_hh = o["w_in"].data_ptr(), o["w_agg"].data_ptr()
-                    o["in_dim"] = in_dim
-                    bc.g = g[(d, i)].data_ptr()
-                    bc.g_in = (g[(d, i - 1)] if i > 0 else dxd[d]).data_ptr()
-                    bc.da, bc.dgi, bc.dgh = o["da"].data_ptr(), o["dgi"].data_ptr(), o["dgh"].data_ptr()
-                    res[(d, i)] = o
-            import numpy as np
-            ptrs = (C.POINTER(C.c_int32) * 2)()
-            nl = (C.c_int32 * 2)()
-            one = np.array([0, N], dtype=np.int32)   # agg_x: nothing couples the layers - one pseudo-layer of all rows
-            for d in (0, 1):
-                sd = one if agg_x else sched[d]
-                ptrs[d] = sd.ctypes.data_as(C.POINTER(C.c_int32))
-                nl[d] = len(sd) - 1
-            with engine._span("variant_backward_run", x):
-                engine.check(lib.dagnn_variant_backward_run(C.byref(plan.desc), C.byref(args), ptrs, nl, stream),
-                             "dagnn_variant_backward_run")
-                if agg_x:   # the aggregator's own reverse pass: one shot over all rows, into the gradient of x
-                    for d in mod.dirs:
-                        bca, ao = aggx[d]
-                        if not bca.lands:
-                            continue
-                        dps = res[(d, 0)]["da"]
-                        for i in range(1, L):
-                            dps = dps + res[(d, i)]["da"]
-                        ao["da"] = dps[:, :E].contiguous()
-                        bca.da, bca.g, bca.g_in = ao["da"].data_ptr(), dxd[d].data_ptr(), dxd[d].data_ptr()
-                        engine.check(lib.dagnn_variant_aggregator_backward(C.byref(plan.desc), C.byref(bca), d, E, 0, N, stream),
-                                     "dagnn_variant_aggregator_backward")
-            # ---- epilogue: parameter gradients (transposed products over all nodes) ----
-            grads = {}
-            jobs = []
-            if recurr:
-                for d in mod.dirs:
-                    for i in range(L):
-                        o = res[(d, i)]
-                        jobs += [(o["dgi"], o["u"][:, :o["in_dim"]], True), (o["dgh"], o["a"][:, :H], True)]
-            wg = engine.wgrad(jobs, N, Hp, H) if (N > 0 and jobs) else None
-            kq = 0
-            for d in mod.dirs:
-                for i in range(L):
-                    o, cp = res[(d, i)], cellp[(d, i)]
-                    if not recurr:   # Linear cell: dW = g^T [u ; a], db = sum g (g holds the total gradient of every row now)
-                        gt = g[(d, i)][:, :H]
-                        grads[(d, i, "w_lin")] = torch.cat([gt.t() @ o["u"][:, :o["in_dim"]], gt.t() @ o["a"][:, :H]], 1)
-                        grads[(d, i, "b_lin")] = gt.sum(0)
-                    else:
-                        if wg is not None:
-                            (gw_ih, gb_ih), (gw_hh, gb_hh) = wg[kq], wg[kq + 1]
-                        else:
-                            gw_ih, gb_ih, gw_hh, gb_hh = (torch.zeros_like(cp[n]) for n in ("w_ih", "b_ih", "w_hh", "b_hh"))
-                        kq += 2
-                        grads[(d, i, "w_ih")], grads[(d, i, "b_ih")] = gw_ih, gb_ih
-                        grads[(d, i, "w_hh")], grads[(d, i, "b_hh")] = gw_hh, gb_hh
-                    if agg_x:
-                        if i == 0:
-                            _, ao = aggx[d]
-                            ag = _aggregator_grads(mod, mode, ao, cp, x, x, R, E, 0, dxd[d]) if "da" in ao else {}
-                            for n in cp:
-                                if n not in ("w_ih", "w_hh", "b_ih", "b_hh", "w_lin", "b_lin"):
-                                    grads[(d, i, n)] = ag.get(n, torch.zeros_like(cp[n]))
-                    else:
-                        for n, v in _aggregator_grads(mod, mode, o, cp, h[d][i], o["u"][:, :o["in_dim"]], R, H, i, dxd[d]).items():
-                            grads[(d, i, n)] = v
-            dx = None
-            if ctx.needs_input_grad[3]:
-                dx = sum(dxd[d] for d in mod.dirs)
+            args, g, res, aggx, dxd = _variant_setup(mod, plan, x, ctx.hbuf, gouts, cellp, sched)
+            _variant_sweep(mod, plan, x, args, res, aggx, dxd, sched)
+            grads = _variant_param_grads(mod, plan, x, ctx.h, g, res, aggx, dxd, cellp)
+            dx = sum(dxd[d] for d in mod.dirs) if ctx.needs_input_grad[3] else None
         return (None, None, None, dx) + tuple(grads[n] for n in names)
 
 
@@ -926,17 +927,18 @@ class PlainRecurrence(torch.autograd.Function):
         cells = _plain_cells(mod, plan.R, xd.device)
         if cells is None or cells[(mod.dirs[0], 0)].Hp != r.Hp:
             raise engine.DagnnHipError("plain dataflow pass: the cells' width does not match the route's (%d)" % r.Hp)
-        preact = {"stat_rows": True} if r.stat_rows else {}
-        hbuf, gi = _plain_forward(mod, xd, plan, r, cells, preact=preact)
+        rec = engine.PassRecord(r)
+        hbuf = _plain_forward(mod, xd, plan, r, cells, record=rec)
         H, L = mod.hidden_dim, mod.num_layers
-        ctx.mod, ctx.plan, ctx.route, ctx.cells, ctx.hbuf, ctx.gi, ctx.preact = mod, plan, r, cells, hbuf, gi, preact
+        ctx.mod, ctx.plan, ctx.cells, ctx.rec = mod, plan, cells, rec
         ctx.save_for_backward(x, *params)
         ctx.set_materialize_grads(False)
         return tuple(hbuf[d][i][:, :H] for d in mod.dirs for i in range(L))
 
     @staticmethod
     def backward(ctx, *gouts):
-        mod, plan, r, cells, hb = ctx.mod, ctx.plan, ctx.route, ctx.cells, ctx.hbuf
+        mod, plan, rec, cells = ctx.mod, ctx.plan, ctx.rec, ctx.cells
+        r, hb = rec.route, rec.h_buf
         saved = list(ctx.saved_tensors)
         x, params = saved[0].detach(), [p.detach() for p in saved[1:]]
         N, H, L, Hp, R, E = x.shape[0], mod.hidden_dim, mod.num_layers, r.Hp, plan.R, plan.E
@@ -946,20 +948,9 @@ class PlainRecurrence(torch.autograd.Function):
         stream = engine._stream(x)
         is_max = mod.agg == "max"
         shared_flow = getattr(mod, "shared_agg_flow", True)
-        names, cellp, k = [], {}, 0
-        for d in dirs:
-            for i in range(L):
-                spec = _cell_params(mod, d, i)
-                cellp[(d, i)] = {n: params[k + q] for q, (n, _) in enumerate(spec)}
-                names += [(d, i, n) for n, _ in spec]
-                k += len(spec)
+        names, cellp = rev.unflatten_params(mod, params)
         with torch.no_grad():
-            g_all = torch.zeros(len(dirs) * L, N, Hp, **f32)
-            g_ext = [[g_all[dirs.index(d) * L + i] if d in dirs else None for i in range(L)] for d in range(2)]
-            for q, d in enumerate(dirs):
-                for i in range(L):
-                    if gouts[q * L + i] is not None:
-                        g_ext[d][i][:, :H] = gouts[q * L + i]
+            g_ext = rev.seed_state_grads(gouts, dirs, L, N, H, Hp, x.device)
             # per cell: the aggregate a (the W_hh gradient's operand; for max also what a message is compared with) and the pull
             plain, pulls, nothing = {"pull_rows": is_max}, {}, None
             ones = None
@@ -994,8 +985,8 @@ class PlainRecurrence(torch.autograd.Function):
                             ones = torch.ones(max(E, 1), **f32)
                         w = ones
                     plain[(d, i)] = (a, w)
-            res = engine.bwd_dataflow_sweep(plan, dirs, L, Hp, cells, hb, ctx.gi, g_ext, r.groups,
-                                            arena=mod._arena_for(x, "backward"), preact=ctx.preact, plain=plain)
+            res, held = engine.bwd_dataflow_sweep(plan, dirs, L, Hp, cells, hb, rec.gi0, g_ext, r.groups,
+                                                  arena=mod._arena_for(x, "backward"), record=rec, plain=plain)
             # ---- epilogue: the edge encoder (one fixed order: per row over its in-edges, then `colsums` over the rows) ...
             es_jobs, es_at = [], {}
             for d in dirs:
@@ -1010,27 +1001,21 @@ class PlainRecurrence(torch.autograd.Function):
                     es_jobs.append((esum, None))
             es = engine.colsums(es_jobs, N) if es_jobs else []
             # ... and the GRU weights and biases, every cell in one batch (csrc/wgrad.hip)
-            jobs = []
-            for d in dirs:
-                for i in range(L):
-                    o = res[(d, i)]
-                    jobs += [(o["dgi"], x if i == 0 else hb[d][i - 1][:, :H], True), (o["dgh"], plain[(d, i)][0][:, :H], True)]
-            wg = engine.wgrad(jobs, N, Hp, H)
-            grads, kq = {}, 0
+            wg = iter(rev.gru_grads(rev.wgrad_jobs(res, lambda d, i: x if i == 0 else hb[d][i - 1][:, :H], dirs, L, H),
+                                    [[cp[n] for n in _GRU] for cp in cellp.values()], N, Hp, H))
+            grads = {}
             dx = torch.zeros_like(x) if ctx.needs_input_grad[3] else None
             for d in dirs:
                 for i in range(L):
                     cp = cellp[(d, i)]
-                    (grads[(d, i, "w_ih")], grads[(d, i, "b_ih")]), (grads[(d, i, "w_hh")], grads[(d, i, "b_hh")]) = wg[kq], wg[kq + 1]
-                    kq += 2
+                    grads.update(zip([(d, i, n) for n in _GRU], next(wg)))
                     if i == 0 and dx is not None:
-                        dgi = res[(d, i)]["dgi"]
-                        dx.addmm_(dgi if Hp == H else dgi.view(N, 3, Hp)[:, :, :H].reshape(N, 3 * H), cp["w_ih"])
+                        rev.add_input_grad(dx, res[(d, i)]["dgi"], cp["w_ih"], H, Hp)
                     if "we" in cp:
                         if (d, i) in es_at:
                             cs = es[es_at[(d, i)]].view(R + 1, H)
                             grads[(d, i, "we")], grads[(d, i, "be")] = cs[:R].t().contiguous(), cs[R].clone()
                         else:
                             grads[(d, i, "we")], grads[(d, i, "be")] = torch.zeros_like(cp["we"]), torch.zeros_like(cp["be"])
-            del res
+            del res, held
         return (None, None, None, dx) + tuple(grads[n] for n in names)

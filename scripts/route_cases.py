@@ -74,8 +74,8 @@ def _before(name, a):
 
 def _after(name, a, rec, out):
     if name in ("dataflow_run", "bwd_dataflow_sweep"):
-        p = a.get("preact")
-        rec["preact"] = None if p is None else int(bool(p.get("stat_rows")))   # (None: no pre-activations kept; 1: static rows)
+        p = a.get("record")   # (`engine.PassRecord`, read after the call: the forward launch has filled it)
+        rec["preact"] = None if p is None else int(p.handover() == "stat")   # (None: no pre-activations kept; 1: static rows)
     if name in ("dataflow_schedule", "launch_prepare"):
         rec["built"] = int(a["groups"] > 0 and rec["built"] and _df_key(a["groups"]) in a["self"].__dict__.get("_df", {}))
     if name == "tiles_launches":
