@@ -224,6 +224,12 @@ class DvaeDecodeArgs(C.Structure):
                 ("agg", C.c_int), ("gate_w", C.c_void_p), ("gate_b", C.c_void_p), ("mapper_w", C.c_void_p)]
 
 
+class DvaeDecodeArgsTyped(DvaeDecodeArgs):
+    """dagnn_dvae_decode_args as the header has it today: the layout above (agg = 0 / 1, which the library still takes - fields
+    are only ever appended, and one is read only under the `agg` value that introduced it) plus the type-keyed table (agg = 2)."""
+    _fields_ = [("key_type", C.c_void_p)]
+
+
 class DvaeDecodeGrads(C.Structure):
     _fields_ = [("g_res", C.c_void_p), ("work", C.c_void_p), ("work_bytes", C.c_size_t), ("d_h0", C.c_void_p),
                 ("d_w_ih", C.c_void_p * MAX_STACKED), ("d_w_hh", C.c_void_p * MAX_STACKED),
@@ -232,6 +238,10 @@ class DvaeDecodeGrads(C.Structure):
                 ("d_av_w1", C.c_void_p), ("d_av_b1", C.c_void_p), ("d_av_w2", C.c_void_p), ("d_av_b2", C.c_void_p),
                 ("d_ae_w1", C.c_void_p), ("d_ae_b1", C.c_void_p), ("d_ae_w2", C.c_void_p), ("d_ae_b2", C.c_void_p),
                 ("d_gate_w", C.c_void_p), ("d_gate_b", C.c_void_p), ("d_mapper_w", C.c_void_p)]
+
+
+class DvaeDecodeGradsTyped(DvaeDecodeGrads):
+    _fields_ = [("d_key_type", C.c_void_p)]   # agg = 2
 
 
 class DvaeSampleArgs(C.Structure):
@@ -245,6 +255,10 @@ class DvaeSampleArgs(C.Structure):
                 ("u_type", C.c_void_p), ("u_edge", C.c_void_p), ("types", C.c_void_p), ("preds", C.c_void_p),
                 ("nv", C.c_void_p), ("states", C.c_void_p), ("work", C.c_void_p), ("work_bytes", C.c_size_t),
                 ("agg", C.c_int), ("gate_w", C.c_void_p), ("gate_b", C.c_void_p), ("mapper_w", C.c_void_p)]
+
+
+class DvaeSampleArgsTyped(DvaeSampleArgs):
+    _fields_ = [("key_type", C.c_void_p)]   # agg = 2; see DvaeDecodeArgsTyped
 
 
 DVAE_ENAS, DVAE_BN = 0, 1                        # DAGNN_DVAE_ENAS / DAGNN_DVAE_BN
@@ -439,6 +453,8 @@ SYMBOLS = {
     "dagnn_vid_colsums": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
     "dagnn_iprop_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.c_void_p, C.c_int, C.POINTER(IpropLayer), C.c_int, C.c_void_p, C.c_void_p]),
+    "dagnn_iprop_step_typed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                         C.c_void_p, C.c_int, C.POINTER(IpropLayer), C.c_int, C.c_void_p, C.c_void_p]),
     "dagnn_encode_forward": (C.c_int, [C.POINTER(EncodeArgs), C.c_void_p]),
     "dagnn_dvae_decode_saved_bytes": (C.c_size_t, [C.POINTER(DvaeDecodeArgs)]),
     "dagnn_dvae_decode_work_bytes": (C.c_size_t, [C.POINTER(DvaeDecodeArgs)]),

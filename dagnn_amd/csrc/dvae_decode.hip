@@ -23,6 +23,11 @@
 // bias).  In reverse, dm_u pulls d hagg from every update that read it, and one product turns it into u's layer-0
 // state gradient before u's own cells run backwards.
 //   message rows  q = u * B + b                 for u = 0..n-2 (vertex n-1 has no successors)
+//
+// agg = attn_x (BN): the keys are the predecessors' one-hot types (dvae/dagnn_bn.py:203-225), so the score of a real slot is
+// one entry of the table key_type [nvt] and the values stay the layer-0 states: the same launches and saved records as
+// attn_h with the score product replaced by a lookup.  In reverse the keys carry no state gradient, and d key_type[t]
+// pulls the score gradients of every slot whose predecessor has type t (one workgroup per type, fixed order).
 #include "common.h"
 
 namespace {
@@ -151,11 +156,12 @@ inline int64_t dd_take(int64_t& at, int64_t count) {
 bool dd_layout(const dagnn_dvae_decode_args* a, DDLayout& o) {
     if (!a || a->B <= 0 || a->n < 2 || a->n > DAGNN_DVAE_MAX_N || a->hs <= 0 || a->L < 1 || a->L > DAGNN_MAX_STACKED ||
         a->nvt <= 0 || a->nvt > DAGNN_DVAE_MAX_TYPES || a->start_type < 0 || a->start_type >= a->nvt || a->edge_hidden <= 0 ||
-        a->vertex_hidden <= 0 || (a->bn != 0 && a->bn != 1) || (a->agg != 0 && a->agg != 1))
+        a->vertex_hidden <= 0 || (a->bn != 0 && a->bn != 1) || a->agg < 0 || a->agg > 2)
         return false;
     if (a->agg == 1 && (a->bn || !a->gate_w || !a->gate_b || !a->mapper_w)) return false;
+    if (a->agg == 2 && (!a->bn || !a->key_type)) return false;
     o.B = a->B; o.n = a->n; o.H = a->hs; o.L = a->L; o.nvt = a->nvt;
-    o.gated = a->agg;
+    o.gated = a->agg == 1;
     o.ein = (a->bn ? 3 : 2) * a->hs; o.E1 = a->edge_hidden; o.V1 = a->vertex_hidden;
     o.NU = dd_U(o.n);
     o.RU = o.NU * o.B; o.RE = dd_E(o.n) * o.B; o.RV = (int64_t)(o.n - 1) * o.B;
@@ -204,12 +210,20 @@ bool dd_layout(const dagnn_dvae_decode_args* a, DDLayout& o) {
     return true;
 }
 
-// ---- forward: the aggregate of every update of vertex v (grid [v+1, B]); v = 0: H0
+__device__ inline int dd_type_of(const int32_t* __restrict__ types, int64_t b, int n, int u, int nvt, int start_type) {
+    const int t = u == 0 ? start_type : types[b * n + u];
+    return t < 0 ? 0 : (t >= nvt ? nvt - 1 : t);   // (the host validates the types; never read outside the table)
+}
+
+// ---- forward: the aggregate of every update of vertex v (grid [v+1, B]); v = 0: H0.  TYPE_KEY: a real slot scores
+// key_type[type of its predecessor] (attn_x) instead of w_key . state + vid_bias
+template <bool TYPE_KEY>
 __global__ void __launch_bounds__(DD_T) dd_agg_kernel(int v, int n, int64_t B, int H, const uint32_t* __restrict__ preds,
                                                       const float* __restrict__ h0state, const float* __restrict__ w_key,
                                                       const float* __restrict__ vid_bias, const float* __restrict__ H0,
                                                       float* __restrict__ hagg, float* __restrict__ alpha, int32_t* __restrict__ pid,
-                                                      int32_t* __restrict__ pcount) {
+                                                      int32_t* __restrict__ pcount, const float* __restrict__ key_type,
+                                                      const int32_t* __restrict__ types, int nvt, int start_type) {
     __shared__ float red[DD_T / 64];
     __shared__ float sc[DAGNN_DVAE_MAX_N];
     __shared__ int ids[DAGNN_DVAE_MAX_N];
@@ -235,12 +249,16 @@ __global__ void __launch_bounds__(DD_T) dd_agg_kernel(int v, int n, int64_t B, i
     }
     __syncthreads();
     const int P = sP, cnt = sCnt;
-    for (int j = 0; j < cnt; ++j) {
-        const float* hv = h0state + (dd_U(ids[j]) * B + b) * H;
-        float s = 0.f;
-        for (int c = threadIdx.x; c < H; c += DD_T) s = fmaf(w_key[c], hv[c], s);
-        s = dd_block_sum(s, red);
-        if (threadIdx.x == 0) sc[j] = s + (vid_bias ? vid_bias[ids[j]] : 0.f);
+    if (TYPE_KEY) {
+        if ((int)threadIdx.x < cnt) sc[threadIdx.x] = key_type[dd_type_of(types, b, n, ids[threadIdx.x], nvt, start_type)];
+    } else {
+        for (int j = 0; j < cnt; ++j) {
+            const float* hv = h0state + (dd_U(ids[j]) * B + b) * H;
+            float s = 0.f;
+            for (int c = threadIdx.x; c < H; c += DD_T) s = fmaf(w_key[c], hv[c], s);
+            s = dd_block_sum(s, red);
+            if (threadIdx.x == 0) sc[j] = s + (vid_bias ? vid_bias[ids[j]] : 0.f);
+        }
     }
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -493,7 +511,8 @@ __global__ void __launch_bounds__(DD_T) dd_agg_bwd_kernel(int v, int n, int64_t 
                 const int u = pid[row * n + j];
                 if (u < 0) break;
                 float* d = dH0 + (dd_U(u) * B + b) * H + c;
-                *d += alpha[row * n + j] * dhagg[row * H + c] + sds[k][j] * w_key[c];
+                if (w_key) *d += alpha[row * n + j] * dhagg[row * H + c] + sds[k][j] * w_key[c];
+                else *d += alpha[row * n + j] * dhagg[row * H + c];   // (attn_x: the keys are types, not states)
             }
         }
     }
@@ -529,6 +548,26 @@ __global__ void __launch_bounds__(DD_T) dd_key_grad_kernel(int64_t B, int n, int
             }
         dvid[u] = s;
     }
+}
+
+// attn_x: d key_type[t] = sum of ds over every (update row, real slot) whose predecessor has type t.  One workgroup per
+// type: thread i sums the rows i, i + DD_T, .. in ascending order, then the block adds the partials in a fixed order
+__global__ void __launch_bounds__(DD_T) dd_type_key_grad_kernel(int64_t B, int n, int nvt, int start_type, int64_t NU,
+                                                                const int32_t* __restrict__ types, const int32_t* __restrict__ pid,
+                                                                const float* __restrict__ ds, float* __restrict__ dkey) {
+    __shared__ float red[DD_T / 64];
+    const int t = blockIdx.x;
+    float s = 0.f;
+    for (int64_t row = B + threadIdx.x; row < NU * B; row += DD_T) {   // (update 0 has no predecessors)
+        const int64_t b = row % B;
+        for (int j = 0; j < n; ++j) {
+            const int u = pid[row * n + j];
+            if (u < 0) break;
+            if (dd_type_of(types, b, n, u, nvt, start_type) == t) s += ds[row * n + j];
+        }
+    }
+    s = dd_block_sum(s, red);
+    if (threadIdx.x == 0) dkey[t] = s;
 }
 
 // d H0: vertex 0's aggregate IS H0, plus (BN) the H0 part of every edge row
@@ -664,7 +703,7 @@ int dd_colsum(hipStream_t st, const float* A, int64_t lda, int64_t R, int N, con
     } while (0)
 
 bool dd_weights_ok(const dagnn_dvae_decode_args* a) {
-    if (!a->types || !a->preds || !a->h0 || (a->agg == 0 && !a->w_key) || !a->ll || !a->saved || !a->av_w1 || !a->av_b1 || !a->av_w2 ||
+    if (!a->types || !a->preds || !a->h0 || (a->agg == 0 && !a->w_key) || (a->agg == 2 && !a->key_type) || !a->ll || !a->saved || !a->av_w1 || !a->av_b1 || !a->av_w2 ||
         !a->av_b2 || !a->ae_w1 || !a->ae_b1 || !a->ae_w2 || !a->ae_b2)
         return false;
     for (int l = 0; l < a->L; ++l)
@@ -706,9 +745,14 @@ extern "C" int dagnn_dvae_decode_forward(const dagnn_dvae_decode_args* a, void* 
         if (o.gated) {
             hipLaunchKernelGGL(dd_gated_agg_kernel, dim3(hb, (unsigned)M), dim3(DD_T), 0, st, v, n, B, (int)H, a->preds, S + o.msg,
                                a->h0, S + o.hagg);
+        } else if (a->agg == 2) {
+            hipLaunchKernelGGL(dd_agg_kernel<true>, dim3((unsigned)(v == 0 ? 1 : v + 1), (unsigned)B), dim3(DD_T), 0, st, v, n, B, (int)H,
+                               a->preds, S + o.h[0], nullptr, nullptr, a->h0, S + o.hagg, S + o.alpha, pid, pcount, a->key_type,
+                               a->types, o.nvt, a->start_type);
         } else {
-            hipLaunchKernelGGL(dd_agg_kernel, dim3((unsigned)(v == 0 ? 1 : v + 1), (unsigned)B), dim3(DD_T), 0, st, v, n, B, (int)H,
-                               a->preds, S + o.h[0], a->w_key, a->vid_bias, a->h0, S + o.hagg, S + o.alpha, pid, pcount);
+            hipLaunchKernelGGL(dd_agg_kernel<false>, dim3((unsigned)(v == 0 ? 1 : v + 1), (unsigned)B), dim3(DD_T), 0, st, v, n, B, (int)H,
+                               a->preds, S + o.h[0], a->w_key, a->vid_bias, a->h0, S + o.hagg, S + o.alpha, pid, pcount, nullptr,
+                               nullptr, o.nvt, a->start_type);
         }
         DAGNN_CHECK_LAUNCH();
         for (int l = 0; l < L; ++l) {
@@ -751,7 +795,7 @@ extern "C" int dagnn_dvae_decode_forward(const dagnn_dvae_decode_args* a, void* 
 
 extern "C" int dagnn_dvae_decode_backward(const dagnn_dvae_decode_args* a, const dagnn_dvae_decode_grads* g, void* stream) {
     DDLayout o;
-    if (!dd_layout(a, o) || !dd_weights_ok(a) || !g || !g->g_res || !g->work || !g->d_h0 || (a->agg == 0 && !g->d_w_key) || !g->d_av_w1 ||
+    if (!dd_layout(a, o) || !dd_weights_ok(a) || !g || !g->g_res || !g->work || !g->d_h0 || (a->agg == 0 && !g->d_w_key) || (a->agg == 2 && !g->d_key_type) || !g->d_av_w1 ||
         !g->d_av_b1 || !g->d_av_w2 || !g->d_av_b2 || !g->d_ae_w1 || !g->d_ae_b1 || !g->d_ae_w2 || !g->d_ae_b2 ||
         (a->agg == 0 && a->vid_bias && !g->d_vid_bias) || (a->agg == 1 && (!g->d_gate_w || !g->d_gate_b || !g->d_mapper_w)))
         return DAGNN_EINVAL;
@@ -800,7 +844,8 @@ extern "C" int dagnn_dvae_decode_backward(const dagnn_dvae_decode_args* a, const
                                W + o.dH[l - 1] + r0 * H, H, 1, 0));
         }
         if (v > 0 && !o.gated) {
-            hipLaunchKernelGGL(dd_agg_bwd_kernel, dim3((unsigned)B), dim3(DD_T), 0, st, v, n, B, (int)H, S + o.h[0], a->w_key,
+            hipLaunchKernelGGL(dd_agg_bwd_kernel, dim3((unsigned)B), dim3(DD_T), 0, st, v, n, B, (int)H, S + o.h[0],
+                               a->agg == 2 ? nullptr : a->w_key,
                                S + o.alpha, pid, pcount, W + o.dhagg, W + o.ds, W + o.dH[0]);
             DAGNN_CHECK_LAUNCH();
         }
@@ -826,6 +871,10 @@ extern "C" int dagnn_dvae_decode_backward(const dagnn_dvae_decode_args* a, const
                            (int)H, W + o.dmpre, g->d_gate_w, g->d_mapper_w);
         DAGNN_CHECK_LAUNCH();
         DD_TRY(dd_colsum(st, W + o.dmpre, 2 * H, o.RM, (int)H, nullptr, g->d_gate_b));
+    } else if (a->agg == 2) {
+        hipLaunchKernelGGL(dd_type_key_grad_kernel, dim3((unsigned)o.nvt), dim3(DD_T), 0, st, B, n, o.nvt, a->start_type, o.NU,
+                           a->types, pid, W + o.ds, g->d_key_type);
+        DAGNN_CHECK_LAUNCH();
     } else {
         hipLaunchKernelGGL(dd_key_grad_kernel, dim3(hb + 1), dim3(DD_T), 0, st, B, n, (int)H, o.NU, S + o.h[0], pid, W + o.ds,
                            g->d_w_key, a->vid_bias ? g->d_vid_bias : nullptr);

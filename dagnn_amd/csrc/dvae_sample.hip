@@ -23,6 +23,9 @@
 // product against the stacked state columns of the gate and the mapper, then the vertex-id columns, bg and the
 // sigmoid-times), and the aggregate launch becomes a masked sum of message rows in ascending order, with no soft-max.
 // The padding width P is still reduced but not read: the reference's zero padding rows contribute exactly 0.
+//
+// agg = attn_x (BN): the key of a vertex is one entry of the table key_type [nvt], looked up by its type when the vertex is
+// final; the padded soft-max launch then serves unchanged.
 #include "common.h"
 
 namespace {
@@ -53,9 +56,10 @@ bool ds_layout(const dagnn_dvae_sample_args* a, DSLayout& o) {
     if (!a || a->G <= 0 || a->B <= 0 || a->n < 2 || a->n > DAGNN_DVAE_MAX_N || a->hs <= 0 || a->L < 1 ||
         a->L > DAGNN_MAX_STACKED || a->nvt <= 0 || a->nvt > DAGNN_DVAE_MAX_TYPES || a->start_type < 0 ||
         a->start_type >= a->nvt || a->end_type < 0 || a->end_type >= a->nvt || (a->bn != 0 && a->bn != 1) ||
-        (a->stochastic != 0 && a->stochastic != 1) || a->edge_hidden <= 0 || a->vertex_hidden <= 0 || (a->agg != 0 && a->agg != 1))
+        (a->stochastic != 0 && a->stochastic != 1) || a->edge_hidden <= 0 || a->vertex_hidden <= 0 || a->agg < 0 || a->agg > 2)
         return false;
     if (a->agg == 1 && (a->bn || !a->gate_w || !a->gate_b || !a->mapper_w)) return false;
+    if (a->agg == 2 && (!a->bn || !a->key_type)) return false;
     if (a->G > ((int64_t)1 << 31) || a->B > ((int64_t)1 << 31) || a->G * a->B > ((int64_t)1 << 30) || a->hs > (1 << 20) ||
         a->edge_hidden > (1 << 22) || a->vertex_hidden > (1 << 22))
         return false;
@@ -88,7 +92,7 @@ bool ds_layout(const dagnn_dvae_sample_args* a, DSLayout& o) {
     o.fin = ds_take(at, R);
     o.succ = ds_take(at, R);
     o.pbuf = ds_take(at, o.NE * o.G);
-    o.gated = a->agg;
+    o.gated = a->agg == 1;
     if (o.gated) {
         o.wgm = ds_take(at, 2 * (int64_t)o.hs * HP);
         o.mpre = ds_take(at, R * 2 * o.hs);
@@ -178,6 +182,15 @@ __global__ void __launch_bounds__(DS_T) ds_key_kernel(int64_t R, int n, int hs, 
     for (int c = lane; c < hs; c += 64) s = fmaf(w_key[c], x[c], s);
     s = wave_sum(s);
     if (lane == 0) key[r * n + v] = s + (vid_bias ? vid_bias[v] : 0.f);
+}
+
+// attn_x: the key of vertex v is the table entry of its type (0 for a row that has no vertex v: never read)
+__global__ void __launch_bounds__(DS_T) ds_type_key_kernel(int64_t R, int n, int nvt, int v, const int32_t* __restrict__ types,
+                                                           const float* __restrict__ key_type, float* __restrict__ key) {
+    for (int64_t r = (int64_t)blockIdx.x * DS_T + threadIdx.x; r < R; r += (int64_t)gridDim.x * DS_T) {
+        const int t = types[r * n + v];
+        key[r * n + v] = t < 0 ? 0.f : key_type[t < nvt ? t : nvt - 1];
+    }
 }
 
 // graph state of every row (stride HP, zero pad): NA the top state of its last vertex, BN the sum of its top states
@@ -466,6 +479,9 @@ extern "C" int dagnn_dvae_sample(const dagnn_dvae_sample_args* a, void* stream) 
             DS_TRY(ds_gemm(st, R, 2 * hs, HP, W + o.h[0] + (int64_t)idx * HP, ldh, W + o.wgm, nullptr, W + o.mpre, 2 * hs));
             hipLaunchKernelGGL(ds_gated_msg_kernel, dim3(ds_blocks(R * hs)), dim3(DS_T), 0, st, R, n, hs, idx, W + o.mpre, a->gate_w,
                                a->gate_b, a->mapper_w, W + o.msg);
+        } else if (a->agg == 2) {
+            hipLaunchKernelGGL(ds_type_key_kernel, dim3(ds_blocks(R)), dim3(DS_T), 0, st, R, n, o.nvt, idx, a->types, a->key_type,
+                               W + o.key);
         } else {
             hipLaunchKernelGGL(ds_key_kernel, dim3(row_waves), dim3(DS_T), 0, st, R, n, hs, HP, idx, W + o.h[0], a->w_key, a->vid_bias,
                                W + o.key);

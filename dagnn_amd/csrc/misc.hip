@@ -96,7 +96,7 @@ __global__ void __launch_bounds__(256) iprop_step_kernel(const float* __restrict
                                                           int P, int hs, const float* __restrict__ w_key,
                                                           const float* __restrict__ vid_bias, const float* __restrict__ H_given,
                                                           const float* __restrict__ x, int in0, IpropLayers W, int L,
-                                                          float* __restrict__ states, int64_t B) {
+                                                          float* __restrict__ states, int64_t B, int nkey) {
     extern __shared__ float lds[];
     const int g = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -111,12 +111,15 @@ __global__ void __launch_bounds__(256) iprop_step_kernel(const float* __restrict
     } else {
         const float* vg = values + (int64_t)g * P * hs;
         for (int p = wave; p < P; p += 4) {
-            const int id = pred_vid[(int64_t)g * P + p];
+            int id = pred_vid[(int64_t)g * P + p];
             float s = 0.f;
-            if (id >= 0) {
+            if (id >= 0 && w_key) {
                 for (int k = lane; k < hs; k += 64) s = fmaf(w_key[k], vg[(int64_t)p * hs + k], s);
                 s = wave_sum(s);
                 if (vid_bias) s += vid_bias[id];
+            } else if (id >= 0) {   // type-keyed (nkey > 0): the slot's id is its predecessor's type, its score one table entry
+                id = id < nkey ? id : nkey - 1;
+                s = vid_bias[id];
             }
             if (lane == 0) sc[p] = s;
         }
@@ -281,12 +284,15 @@ extern "C" int dagnn_gather_rows_batch(const dagnn_gather_job* jobs, int n, int6
     return DAGNN_OK;
 }
 
-extern "C" int dagnn_iprop_step(const float* values, const int32_t* pred_vid, int64_t B, int P, int hs, const float* w_key,
-                                const float* vid_bias, const float* H_given, const float* x, int in0,
-                                const dagnn_iprop_layer* layers, int L, float* states, void* stream) {
+namespace {
+// both forms of the step: state keys (w_key [+ table = vid_bias over vertex ids], nkey = 0) or type keys (w_key = NULL, table =
+// key_type over nkey vertex types)
+int iprop_launch(const float* values, const int32_t* pred_id, int64_t B, int P, int hs, const float* w_key, const float* table,
+                 int nkey, const float* H_given, const float* x, int in0, const dagnn_iprop_layer* layers, int L, float* states,
+                 void* stream) {
     if (B < 0 || P < 0 || hs <= 0 || in0 <= 0 || L <= 0 || L > DAGNN_MAX_STACKED || !layers || !x || !states)
         return DAGNN_EINVAL;
-    if (!H_given && P > 0 && (!values || !pred_vid || !w_key)) return DAGNN_EINVAL;
+    if (!H_given && P > 0 && (!values || !pred_id || (nkey > 0 ? !table : !w_key))) return DAGNN_EINVAL;
     if (B == 0) return DAGNN_OK;
     IpropLayers W;
     for (int l = 0; l < L; ++l) {
@@ -300,8 +306,22 @@ extern "C" int dagnn_iprop_step(const float* values, const int32_t* pred_vid, in
     const void* fn = reinterpret_cast<const void*>(iprop_step_kernel);
     if (lds > 48 * 1024 && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
         return DAGNN_EHIP(hipGetLastError());
-    hipLaunchKernelGGL(iprop_step_kernel, dim3((unsigned)B), dim3(256), lds, (hipStream_t)stream, values, pred_vid, P, hs,
-                       w_key, vid_bias, H_given, x, in0, W, L, states, B);
+    hipLaunchKernelGGL(iprop_step_kernel, dim3((unsigned)B), dim3(256), lds, (hipStream_t)stream, values, pred_id, P, hs,
+                       w_key, table, H_given, x, in0, W, L, states, B, nkey);
     DAGNN_CHECK_LAUNCH();
     return DAGNN_OK;
+}
+}  // namespace
+
+extern "C" int dagnn_iprop_step(const float* values, const int32_t* pred_vid, int64_t B, int P, int hs, const float* w_key,
+                                const float* vid_bias, const float* H_given, const float* x, int in0,
+                                const dagnn_iprop_layer* layers, int L, float* states, void* stream) {
+    return iprop_launch(values, pred_vid, B, P, hs, w_key, vid_bias, 0, H_given, x, in0, layers, L, states, stream);
+}
+
+extern "C" int dagnn_iprop_step_typed(const float* values, const int32_t* pred_type, int64_t B, int P, int hs,
+                                      const float* key_type, int nvt, const float* H_given, const float* x, int in0,
+                                      const dagnn_iprop_layer* layers, int L, float* states, void* stream) {
+    if (nvt <= 0) return DAGNN_EINVAL;
+    return iprop_launch(values, pred_type, B, P, hs, nullptr, key_type, nvt, H_given, x, in0, layers, L, states, stream);
 }

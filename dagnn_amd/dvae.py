@@ -91,13 +91,15 @@ def _iprop_dense(values, pred_vid, w_key, vid_bias, H, X, cells):
     """The decoder-side step as dense device-side torch ops, the form its reverse pass differentiates (`dvae/dagnn.py:187-239`):
     padded slots score 0 (their key is a zero row, and the query term `w_q.q + b` is common to every slot of a soft-max
     row, so it cancels - the query half of `attn_lin` and its bias get exact zero gradients), the aggregate of the
-    layer-0 states feeds every stacked layer."""
+    layer-0 states feeds every stacked layer.  `w_key` None: the type-keyed form (`attn_x` on the BN model,
+    dvae/dagnn_bn.py:203-225) - `pred_vid` holds the predecessors' vertex TYPES, `vid_bias` the table key_type [nvt], and a
+    real slot scores its table entry alone."""
     B = X.shape[0]
     if H is None:
         if values is None or values.shape[1] == 0:
             H = X.new_zeros(B, cells[0].weight_hh.shape[1])
         else:
-            scores = values @ w_key
+            scores = values @ w_key if w_key is not None else values.new_zeros(values.shape[:2])
             if vid_bias is not None:
                 real = pred_vid >= 0
                 scores = scores + torch.where(real, vid_bias[pred_vid.clamp(min=0).long()], torch.zeros_like(scores))
@@ -126,6 +128,8 @@ class _IpropStep(torch.autograd.Function):
         ctx.save_for_backward(*[t for t in (values, pred_vid, w_key, vid_bias, H, X) if t is not None], *flat)
         ctx.have = [t is not None for t in (values, pred_vid, w_key, vid_bias, H, X)]
         ctx.L = L
+        if w_key is None and vid_bias is not None:   # type-keyed: `pred_vid` are types, `vid_bias` is key_type
+            return engine.iprop_step(values, pred_vid, None, None, H, X, cells, key_type=vid_bias)
         return engine.iprop_step(values, pred_vid, w_key, vid_bias, H, X, cells)
 
     @staticmethod
@@ -557,7 +561,7 @@ def select_decoded(decoded, data_type, nvt, start_type, end_type, n_nodes=None, 
 class _DecodeLoss(torch.autograd.Function):
     """`res` of `DVAE_PYG.loss()` (the negative log-likelihood of the true graphs under teacher forcing) as ONE call of
     `dagnn_dvae_decode_forward`; its gradients as ONE call of `dagnn_dvae_decode_backward`.  Inputs after the fixed
-    ones: the aggregator's tensors (attn_h: attn_lin.weight; gated_sum: gate_forward.0.0.{weight,bias},
+    ones: the aggregator's tensors (attn_h / attn_x: attn_lin.weight; gated_sum: gate_forward.0.0.{weight,bias},
     mapper_forward.0.0.weight), then 4 tensors per grud cell, add_vertex.{0,2}.{weight,bias}, add_edge.{0,2}.{weight,bias}."""
 
     @staticmethod
@@ -575,7 +579,7 @@ class _DecodeLoss(torch.autograd.Function):
         if spec["agg"] == K.NA_GATED_SUM:
             d_h0, d_cells, d_av, d_ae, d_agg = dec.backward(g_res, None, 0, None)
         else:
-            d_attn = torch.zeros_like(saved[1])
+            d_attn = torch.zeros_like(saved[1])   # (the query half stays zero: it cancels in the soft-max)
             d_h0, d_cells, d_av, d_ae = dec.backward(g_res, d_attn, spec["dq"], spec["dq"] + spec["hs"] if spec["vid"] else None)
             d_agg = [d_attn]
         ctx.dec = None
@@ -594,7 +598,10 @@ def _make_decode(spec, types, preds, h0, params):
         t["gate"] = [x.detach() for x in agg]
     else:
         w = agg[0].detach()[0]
-        t.update(w_key=w[dq:dq + hs], vid_bias=w[dq + hs:dq + hs + spec["n"]] if spec["vid"] else None)
+        if spec["agg"] == K.NA_ATTN_X:   # the keys are one-hot types: the key half is a table over the types (a view, no copy)
+            t.update(key_type=w[dq:dq + spec["nvt"]])
+        else:
+            t.update(w_key=w[dq:dq + hs], vid_bias=w[dq + hs:dq + hs + spec["n"]] if spec["vid"] else None)
     return engine.DvaeDecode(spec["n"], spec["nvt"], spec["start_type"], spec["bn"], t)
 
 
@@ -670,16 +677,21 @@ class _DvaeDagnn(_DvaeBase):
         self.hidden_dim = hidden_dim
         self.out_hidden_dim = emb_dim + hidden_dim * num_layers if out_wx else hidden_dim * num_layers
         self._agg_plain = agg in (K.NA_GATED_SUM, K.NA_SUM, K.NA_MAX)
-        if not self._agg_plain and agg not in (K.NA_ATTN_H, K.NA_SELF_ATTN_H):
+        if self.agg_attn and self.agg_attn_x and self._use_vids:
+            raise NotImplementedError("DAGNN_NA with agg=%r: the reference forbids input-keyed attention on this model "
+                                      "(`assert not (\"_x\" in agg and \"attn\" in agg)`, dvae/dagnn.py:28); DAGNN_BN takes it" % (agg,))
+        if not self._agg_plain and agg not in (K.NA_ATTN_H, K.NA_SELF_ATTN_H, K.NA_ATTN_X, K.NA_SELF_ATTN_X):
             raise NotImplementedError("D-VAE encoders: agg=%r (attn_h - the reference's default, dvae/train.py:86 -, self_attn_h, "
-                                      "gated_sum, add, max)" % (agg,))
+                                      "gated_sum, add, max; DAGNN_BN also attn_x, self_attn_x)" % (agg,))
         if agg == K.NA_GATED_SUM and not self._use_vids:
             raise NotImplementedError("DAGNN_BN with agg='gated_sum': the reference itself cannot run it - DVAE_BN_PYG re-creates the "
                                       "first layer's mapper / gate with nvt inputs (dvae/models_pyg.py:539-560) and GatedSumConv feeds "
                                       "them hs-wide states (dvae/dagnn_bn.py:289): a shape error in its first message")
         extra = num_nodes if self._use_vids else 0
         pred_dim = hidden_dim + extra
-        attn_dim = hidden_dim + extra
+        # (`_x`, BN only: keys and queries are the node inputs G.x, dvae/dagnn_bn.py:48,129-131 - AttnConv's Linear(2 emb_dim, 1)
+        # for every stacked layer, SelfAttnConv's Linear(emb_dim, 1))
+        attn_dim = emb_dim if self.agg_attn_x else hidden_dim + extra
         if self._agg_plain:
             # GatedSumConv / AggConv own no parameters of their own here: gated_sum uses the base class's mapper / gate
             # (dvae/dagnn.py:60-65), add / max have none (num_rels = 1: no edge encoder)
@@ -690,7 +702,7 @@ class _DvaeDagnn(_DvaeBase):
                 return m
             self.node_aggr_0 = nn.ModuleList([conv(self.mapper_forward[l], self.gate_forward[l]) for l in range(num_layers)])
             self.node_aggr_1 = nn.ModuleList([conv(self.mapper_backward[l], self.gate_backward[l]) for l in range(num_layers)])
-        elif agg == K.NA_SELF_ATTN_H:   # keys scored alone: `attn_lin` has no query half (dvae/dagnn.py:49-54, 301-312)
+        elif agg in (K.NA_SELF_ATTN_H, K.NA_SELF_ATTN_X):   # keys scored alone: `attn_lin` has no query half (dvae/dagnn.py:49-54, 301-312)
             self.node_aggr_0 = nn.ModuleList([_SelfAttnParams(attn_dim, num_relations=1) for _ in range(num_layers)])
             self.node_aggr_1 = nn.ModuleList([_SelfAttnParams(attn_dim, num_relations=1, reverse=True)
                                               for _ in range(num_layers)])
@@ -735,7 +747,8 @@ class _DvaeDagnn(_DvaeBase):
                     dq = self._key_offset(i)
                     out[(d, i)] = derive_cell(c.weight_ih, c.weight_hh, c.bias_ih, c.bias_hh, a.attn_lin.weight,
                                               self.hidden_dim, dq, i > 0, None, extra, schedule=self.schedule,
-                                              pack=False, stacked=self.num_layers)
+                                              key_dim=self.emb_dim if self.agg_attn_x else None, pack=False,
+                                              stacked=self.num_layers)
             if self.schedule == "lockstep":
                 pack_lockstep(out.values())
             return out
@@ -748,13 +761,18 @@ class _DvaeDagnn(_DvaeBase):
         return self.num_nodes if self._use_vids else 0
 
     def _key_offset(self, i: int) -> int:
-        """Where the key half of `attn_lin.weight` starts: behind the query half - which `self_attn_h` does not have."""
-        if self.agg == K.NA_SELF_ATTN_H:
+        """Where the key half of `attn_lin.weight` starts: behind the query half - which `self_attn_{h,x}` do not have.  The
+        `_x` aggregators (BN) query with the inputs in every stacked layer: emb_dim for every i."""
+        if self.agg in (K.NA_SELF_ATTN_H, K.NA_SELF_ATTN_X):
             return 0
-        return self.emb_dim if i == 0 else self.hidden_dim + self._vid_nodes
+        return self.emb_dim if i == 0 or self.agg_attn_x else self.hidden_dim + self._vid_nodes
 
     def _static_scores(self, x, cells):
-        return None
+        """`*_x` aggregators: the keys are the node inputs, one score per node and cell (dvae/dagnn_bn.py:129-131) - the
+        query part and the bias are common to all in-edges of a node and cancel in the segment soft-max."""
+        if not self.agg_attn_x:
+            return None
+        return {k: torch.mv(x.detach(), c.key_raw) for k, c in cells.items()}
 
     def _readout(self, plan, B, x, h):
         """End vertex of every graph for d = 0, start vertex for d = 1 (dvae/dagnn.py:147-161, dagnn_bn.py:138-152)."""
@@ -804,8 +822,8 @@ class _DvaeDagnn(_DvaeBase):
             raise ValueError("every graph must have exactly num_nodes=%d nodes (dvae/dagnn.py:150-158)" % nn_)
         B = N // nn_
         bl = G.bi_layer_index
-        if not train and not self._agg_plain and not self.output_all and ENCODE_FUSED and self.schedule == "lockstep" \
-                and engine.TIMER is None:
+        if not train and not self._agg_plain and not self.agg_attn_x and not self.output_all and ENCODE_FUSED \
+                and self.schedule == "lockstep" and engine.TIMER is None:
             out = self._encode_fused(G, x, B)
             if out is not None:
                 return out
@@ -817,16 +835,18 @@ class _DvaeDagnn(_DvaeBase):
                 from .autograd import Recurrence
                 flat = Recurrence.apply(self, plan, B, False, x, *self._train_params())
             else:
-                hh = run_stack(plan, x, self._cells(), self.dirs, L, H, vid_nodes=self._vid_nodes,
-                               schedule=self.schedule, arena=self._arena_for(x))
+                cells = self._cells()
+                hh = run_stack(plan, x, cells, self.dirs, L, H, vid_nodes=self._vid_nodes, schedule=self.schedule,
+                               arena=self._arena_for(x), static_score=self._static_scores(x, cells))
                 flat = [hh[d][i] for d in self.dirs for i in range(L)]
             return self._pool_all(G, plan, x, flat, B)
         if train:
             from .autograd import Recurrence
             hcat = Recurrence.apply(self, plan, B, True, x, *self._train_params())[0]
         else:
-            h = run_stack(plan, x, self._cells(), self.dirs, L, H, vid_nodes=self._vid_nodes,
-                          schedule=self.schedule, arena=self._arena_for(x))
+            cells = self._cells()
+            h = run_stack(plan, x, cells, self.dirs, L, H, vid_nodes=self._vid_nodes, schedule=self.schedule,
+                          arena=self._arena_for(x), static_score=self._static_scores(x, cells))
             hcat = self._readout(plan, B, x, h)
         G.h = hcat
         G.batch = G.batch[0::nn_] if self.bidirectional else G.batch[nn_ - 1::nn_]
@@ -963,7 +983,8 @@ class _DvaeDagnn(_DvaeBase):
         """The evaluation pass up to (and including, when it is small) the final Linear as ONE call into the library
         (`dagnn_encode_forward`, csrc/encode.hip): the same launches as the step-by-step path below, without the Python
         between them - these batches (64 x 8 / 128 x 10 nodes) are host-bound.  None: the shape is not one the dataflow
-        kernel serves (the caller takes the general path)."""
+        kernel serves (the caller takes the general path).  Not for the `_x` aggregators: `dagnn_encode_forward` has no
+        static-score input, so `_forward` never calls this for them (they take the step-by-step path)."""
         import ctypes as C
         from . import _lib
         from .core import pack_dataflow
@@ -1060,8 +1081,9 @@ class _DvaeDagnn(_DvaeBase):
         the true graphs under the teacher-forced decoder plus the KL term.  The decoder and its reverse pass are HIP
         (csrc/dvae_decode.hip: one library call each); the schedule (types, predecessor masks) is built once on the host
         and copied once.  Gradients reach mu / logvar, fc3, grud, attn_lin (key / vertex-id part), add_vertex and
-        add_edge.  Graphs must have exactly max_n vertices; agg must be attn_h or (DAGNN_NA) gated_sum, whose gradients
-        reach gate_forward.0.0 / mapper_forward.0.0 (the encoder's layer-0 gate and mapper: both add up in .grad)."""
+        add_edge.  Graphs must have exactly max_n vertices; agg must be attn_h, (DAGNN_BN) attn_x - the gradient reaches the
+        key half of attn_lin through the type table - or (DAGNN_NA) gated_sum, whose gradients reach gate_forward.0.0 /
+        mapper_forward.0.0 (the encoder's layer-0 gate and mapper: both add up in .grad)."""
         self._check_decoder_agg("loss(): the teacher-forced decoder")
         if type(G_true) != list:
             G_true = [G_true]
@@ -1112,13 +1134,22 @@ class _DvaeDagnn(_DvaeBase):
         return spec, params
 
     def _check_decoder_agg(self, what):
-        """The decoders serve attn_h and (NA) gated_sum.  Both read the predecessors' hs-wide states (NA: with a
-        one-hot(u, max_n) vertex id) through the encoder's layer-0 module: gated_sum's gate / mapper, attn_h's key half of
-        attn_lin, which is hidden_dim (+ num_nodes) wide.  So the reference itself needs hidden_dim == hs and (NA)
-        num_nodes == max_n - a shape error otherwise - and the kernels would read the wrong columns."""
-        if self.agg not in (K.NA_ATTN_H, K.NA_GATED_SUM):
-            raise NotImplementedError("%s is built for agg='attn_h' (the reference's D-VAE default, dvae/train.py:86) and "
-                                      "agg='gated_sum', not %r" % (what, self.agg))
+        """The decoders serve attn_h, (NA) gated_sum and (BN) attn_x.  The first two read the predecessors' hs-wide states
+        (NA: with a one-hot(u, max_n) vertex id) through the encoder's layer-0 module: gated_sum's gate / mapper, attn_h's
+        key half of attn_lin, which is hidden_dim (+ num_nodes) wide.  So the reference itself needs hidden_dim == hs and
+        (NA) num_nodes == max_n - a shape error otherwise - and the kernels would read the wrong columns.  attn_x keys
+        with the predecessors' one-hot types (dvae/dagnn_bn.py:203-225: `_one_hot(type, nvt)` against an emb_dim-wide key
+        half), so it needs emb_dim == nvt; the aggregated values are still the hs-wide states."""
+        if self.agg == K.NA_SELF_ATTN_X:
+            raise NotImplementedError("%s with agg='self_attn_x': the reference's own SelfAttnConv calls an undefined `attn_linear` "
+                                      "on this path (dvae/dagnn_bn.py:311-315); the decoders serve attn_h, gated_sum and (DAGNN_BN) "
+                                      "attn_x" % (what,))
+        if self.agg not in (K.NA_ATTN_H, K.NA_GATED_SUM, K.NA_ATTN_X):
+            raise NotImplementedError("%s is built for agg='attn_h' (the reference's D-VAE default, dvae/train.py:86), "
+                                      "agg='gated_sum' and (DAGNN_BN) agg='attn_x', not %r" % (what, self.agg))
+        if self.agg == K.NA_ATTN_X and self.emb_dim != self.nvt:
+            raise ValueError("%s with agg='attn_x' needs emb_dim == nvt: the keys are the one-hot vertex types "
+                             "(got emb_dim=%d, nvt=%d)" % (what, self.emb_dim, self.nvt))
         if self.hidden_dim != self.hs or (self._use_vids and self.num_nodes != self.max_n):
             raise ValueError("%s with agg=%r needs hidden_dim == hs%s (got hidden_dim=%d, hs=%d, num_nodes=%d, max_n=%d)"
                              % (what, self.agg, " and num_nodes == max_n" if self._use_vids else "", self.hidden_dim,
@@ -1142,7 +1173,10 @@ class _DvaeDagnn(_DvaeBase):
             return t
         w = self.node_aggr_0[0].attn_lin.weight.detach()[0]
         dq = self._key_offset(0)
-        t.update(w_key=w[dq:dq + self.hs], vid_bias=w[dq + self.hs:dq + self.hs + self.max_n] if self._use_vids else None)
+        if self.agg == K.NA_ATTN_X:
+            t.update(key_type=w[dq:dq + self.nvt])
+        else:
+            t.update(w_key=w[dq:dq + self.hs], vid_bias=w[dq + self.hs:dq + self.hs + self.max_n] if self._use_vids else None)
         return t
 
     def decode_dense(self, z, stochastic=True, attempts=1, draws=None, states=False):
@@ -1225,9 +1259,14 @@ class _DvaeDagnn(_DvaeBase):
         layer above (`H` is no longer None in the later iterations of the reference's loop).  The host side only
         gathers the igraph-style inputs into dense tensors and writes the new states back into the vertices."""
         assert not reverse
-        if self.agg == K.NA_SELF_ATTN_H:
-            raise NotImplementedError("the decoder-side step with agg='self_attn_h': the reference's own SelfAttnConv calls an "
-                                      "undefined `attn_linear` on this path (dvae/dagnn.py:317-321)")
+        if self.agg in (K.NA_SELF_ATTN_H, K.NA_SELF_ATTN_X):
+            raise NotImplementedError("the decoder-side step with agg=%r: the reference's own SelfAttnConv calls an "
+                                      "undefined `attn_linear` on this path (dvae/dagnn.py:317-321, dvae/dagnn_bn.py:311-315)"
+                                      % (self.agg,))
+        typed = self.agg == K.NA_ATTN_X   # keys = the predecessors' one-hot types: a slot scores key_type[type] (dagnn_bn.py:203-225)
+        if typed and self.emb_dim != self.nvt:
+            raise ValueError("the decoder-side step with agg='attn_x' needs emb_dim == nvt (got emb_dim=%d, nvt=%d)"
+                             % (self.emb_dim, self.nvt))
         G = [g for g in G if g.vcount() > v]
         if len(G) == 0:
             return None
@@ -1247,18 +1286,25 @@ class _DvaeDagnn(_DvaeBase):
                 zero = self._get_zeros(1, self.hs)
                 for g, p in zip(G, preds):
                     rows += [g.vs[x]["H_forward0"].to(dev) for x in p] + [zero] * (P - len(p))
-                    ids += list(p) + [-1] * (P - len(p))
+                    ids += ([int(g.vs[x]["type"]) for x in p] if typed else list(p)) + [-1] * (P - len(p))
+                if typed and not all(-1 <= t < self.nvt for t in ids):
+                    raise ValueError("_ipropagate_to: a predecessor's type is not in [0, nvt=%d)" % self.nvt)
                 values = torch.cat(rows, 0).view(len(G), P, self.hs)
                 pred_vid = torch.tensor(ids, dtype=torch.int32).view(len(G), P).to(dev)
         cells = list(propagator)[:self.num_layers]
-        w_key = w[dq:dq + self.hs]
-        vid_bias = w[dq + self.hs:dq + self.hs + self.max_n] if self._use_vids else None
+        if typed:   # (`_iprop_dense`: w_key None, the table in vid_bias' place)
+            w_key, vid_bias = None, w[dq:dq + self.nvt]
+        else:
+            w_key = w[dq:dq + self.hs]
+            vid_bias = w[dq + self.hs:dq + self.hs + self.max_n] if self._use_vids else None
         flat = [t for c in cells for t in (c.weight_ih, c.weight_hh, c.bias_ih, c.bias_hh)]
         diff = [t for t in [values, H, w_key, vid_bias] + flat if t is not None]
         if torch.is_grad_enabled() and any(t.requires_grad for t in diff):
             # training (`models_pyg.py:398-442`: the reconstruction loss reaches `grud`, `attn_lin` and `H0 = tanh(fc3(z))`
             # through these states): the same HIP launch forward, its reverse pass behind an autograd.Function
             states = _IpropStep.apply(values, pred_vid, w_key, vid_bias, H, X, len(cells), *flat)
+        elif typed:
+            states = engine.iprop_step(values, pred_vid, None, None, H, X, cells, key_type=vid_bias)
         else:
             states = engine.iprop_step(values, pred_vid, w_key, vid_bias, H, X, cells)
         for l in range(self.num_layers):

@@ -1562,11 +1562,13 @@ def gather_rows(h: torch.Tensor, num_graphs: int, stride: int, node_off: int, ou
                                         out.data_ptr(), out.shape[1], col_off, _stream(h)), "dagnn_gather_rows")
 
 
-def iprop_step(values: Optional[torch.Tensor], pred_vid: Optional[torch.Tensor], w_key: torch.Tensor,
-               vid_bias: Optional[torch.Tensor], H_given: Optional[torch.Tensor], x: torch.Tensor, cells) -> torch.Tensor:
+def iprop_step(values: Optional[torch.Tensor], pred_vid: Optional[torch.Tensor], w_key: Optional[torch.Tensor],
+               vid_bias: Optional[torch.Tensor], H_given: Optional[torch.Tensor], x: torch.Tensor, cells,
+               key_type: Optional[torch.Tensor] = None) -> torch.Tensor:
     """`_ipropagate_to` for all graphs of a decoder step in one launch (`dagnn_iprop_step`).  values [B,P,hs] /
     pred_vid [B,P] int32 (or None with `H_given` [B,hs]); x [B,in0]; cells: the propagator's GRUCells.  Returns the
-    new states [L,B,hs]."""
+    new states [L,B,hs].  `key_type` [nvt] (attn_x, `dagnn_iprop_step_typed`): `pred_vid` then holds the predecessors'
+    vertex TYPES and w_key / vid_bias are not read."""
     x = _dev(x, "x", torch.float32)
     B, in0 = x.shape
     hs = cells[0].weight_hh.shape[1]
@@ -1587,6 +1589,12 @@ def iprop_step(values: Optional[torch.Tensor], pred_vid: Optional[torch.Tensor],
     states = torch.empty(L, B, hs, dtype=torch.float32, device=x.device)
     if H_given is None and P == 0:   # no graph has a predecessor: the aggregate is zero (`_get_zero_hidden`)
         H_given = torch.zeros(B, hs, dtype=torch.float32, device=x.device)
+    if key_type is not None:
+        kt = _dev(key_type.detach(), "key_type", torch.float32)
+        check(_lib.load().dagnn_iprop_step_typed(_ptr(values), _ptr(pred_vid), B, P, hs, kt.data_ptr(), kt.shape[0], _ptr(H_given),
+                                                 x.data_ptr(), in0, layers, L, states.data_ptr(), _stream(x)),
+              "dagnn_iprop_step_typed")
+        return states
     wk = _dev(w_key.detach(), "w_key", torch.float32)
     vb = None if vid_bias is None else _dev(vid_bias.detach(), "vid_bias", torch.float32)
     check(_lib.load().dagnn_iprop_step(_ptr(values), _ptr(pred_vid), B, P, hs, wk.data_ptr(), _ptr(vb), _ptr(H_given),
@@ -1626,14 +1634,15 @@ class DvaeDecode(object):
     """One teacher-forced decode (`dagnn_dvae_decode_forward` / `_backward`): the argument struct, the tensors its pointers
     borrow, and the saved activations of the forward call.  `tensors`: dict with h0 [B,hs], types / preds [B,n] int32,
     w_key [hs], vid_bias [n] or None, cells (list of (w_ih, w_hh, b_ih, b_hh)), av / ae (lists of (w1, b1, w2, b2));
-    agg = gated_sum: gate = (gate_w [hs,hs+n], gate_b [hs], mapper_w [hs,hs+n]) in place of w_key / vid_bias."""
+    agg = gated_sum: gate = (gate_w [hs,hs+n], gate_b [hs], mapper_w [hs,hs+n]) in place of w_key / vid_bias; agg = attn_x
+    (BN): key_type [nvt] in place of them."""
 
     def __init__(self, n: int, nvt: int, start_type: int, bn: bool, tensors: dict):
         h0 = _dev(tensors["h0"], "H0", torch.float32)
         dev = h0.device
         self.keep = {"h0": h0}
         f = lambda t, what: _dev(t.detach(), what, torch.float32)  # noqa: E731
-        a = _lib.DvaeDecodeArgs()
+        a = _lib.DvaeDecodeArgsTyped()
         B, hs = h0.shape
         cells = tensors["cells"]
         a.B, a.n, a.hs, a.L, a.nvt, a.start_type, a.bn = B, n, hs, len(cells), nvt, start_type, int(bool(bn))
@@ -1649,12 +1658,16 @@ class DvaeDecode(object):
             a.w_ih[l], a.w_hh[l], a.b_ih[l], a.b_hh[l] = (t.data_ptr() for t in ts)
         gate = tensors.get("gate")
         gate = None if gate is None else [f(t, "gate / mapper parameter") for t in gate]
-        wk = None if gate is not None else f(tensors["w_key"], "w_key")
-        vb = None if gate is not None or tensors.get("vid_bias") is None else f(tensors["vid_bias"], "vid_bias")
+        kt = None if tensors.get("key_type") is None else f(tensors["key_type"], "key_type")
+        wk = None if gate is not None or kt is not None else f(tensors["w_key"], "w_key")
+        vb = None if wk is None or tensors.get("vid_bias") is None else f(tensors["vid_bias"], "vid_bias")
         a.w_key, a.vid_bias = _ptr(wk), _ptr(vb)
         if gate is not None:
             a.agg = 1
             a.gate_w, a.gate_b, a.mapper_w = (t.data_ptr() for t in gate)
+        elif kt is not None:
+            a.agg = 2
+            a.key_type = kt.data_ptr()
         av = [f(t, "add_vertex parameter") for t in tensors["av"]]
         ae = [f(t, "add_edge parameter") for t in tensors["ae"]]
         a.av_w1, a.av_b1, a.av_w2, a.av_b2 = (t.data_ptr() for t in av)
@@ -1666,6 +1679,8 @@ class DvaeDecode(object):
                 (ae[0], (E1, ein)), (ae[1], (E1,)), (ae[2], (1, E1)), (ae[3], (1,))]
         if gate is not None:
             want += [(gate[0], (hs, hs + n)), (gate[1], (hs,)), (gate[2], (hs, hs + n))]
+        elif kt is not None:
+            want.append((kt, (nvt,)))
         else:
             want.append((wk, (hs,)))
         if vb is not None:
@@ -1676,7 +1691,7 @@ class DvaeDecode(object):
         for t, shape in want:
             if tuple(t.shape) != shape:
                 raise ValueError("dagnn_dvae_decode: a tensor of shape %s where %s is needed" % (tuple(t.shape), shape))
-        keep += [wk, vb] + av + ae + (gate or [])
+        keep += [wk, vb, kt] + av + ae + (gate or [])
         self.ll = torch.empty(2 * B + 1, dtype=torch.float32, device=dev)
         a.ll = self.ll.data_ptr()
         lib = _lib.load()
@@ -1687,6 +1702,7 @@ class DvaeDecode(object):
         a.saved, a.saved_bytes = self.saved.data_ptr(), nbytes
         self.args, self.tensors, self.B, self.hs, self.L = a, keep, B, hs, len(cells)
         self.av, self.ae, self.cells, self.h0, self.gate = av, ae, keep[2:2 + 4 * len(cells)], h0, gate
+        self.type_keyed = kt is not None
 
     def forward(self) -> torch.Tensor:
         """Runs the decode; returns ll [2B+1]: per-graph vertex and edge log-likelihoods, then res."""
@@ -1696,13 +1712,13 @@ class DvaeDecode(object):
     def backward(self, g_res: torch.Tensor, d_attn: Optional[torch.Tensor], key_off: int, vid_off: Optional[int]):
         """Gradients of res (scaled by the device scalar g_res) for h0, the cells, the add_vertex / add_edge tensors;
         the key / vertex-id parts are written into the zeroed `d_attn` (a [1, D] attn_lin.weight gradient) at the given
-        column offsets.  Returns (d_h0, [per cell (d_w_ih, d_w_hh, d_b_ih, d_b_hh)], d_av, d_ae); gated_sum (d_attn =
-        None): (d_h0, d_cells, d_av, d_ae, [d_gate_w, d_gate_b, d_mapper_w])."""
+        column offsets (attn_x: the [nvt] table gradient at `key_off`).  Returns (d_h0, [per cell (d_w_ih, d_w_hh, d_b_ih,
+        d_b_hh)], d_av, d_ae); gated_sum (d_attn = None): (d_h0, d_cells, d_av, d_ae, [d_gate_w, d_gate_b, d_mapper_w])."""
         lib = _lib.load()
         g_res = _dev(g_res.reshape(1), "grad", torch.float32)
         nbytes = lib.dagnn_dvae_decode_work_bytes(C.byref(self.args))
         work = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=self.h0.device)
-        g = _lib.DvaeDecodeGrads()
+        g = _lib.DvaeDecodeGradsTyped()
         g.g_res, g.work, g.work_bytes = g_res.data_ptr(), work.data_ptr(), nbytes
         d_h0 = torch.empty_like(self.h0)
         g.d_h0 = d_h0.data_ptr()
@@ -1722,7 +1738,10 @@ class DvaeDecode(object):
             return d_h0, d_cells, d_av, d_ae, d_gate
         if not d_attn.is_contiguous():
             raise DagnnHipError("dagnn_dvae_decode_backward: the attn_lin gradient must be contiguous")
-        g.d_w_key = d_attn.data_ptr() + 4 * key_off
+        if self.type_keyed:
+            g.d_key_type = d_attn.data_ptr() + 4 * key_off
+        else:
+            g.d_w_key = d_attn.data_ptr() + 4 * key_off
         g.d_vid_bias = None if vid_off is None else d_attn.data_ptr() + 4 * vid_off
         check(lib.dagnn_dvae_decode_backward(C.byref(self.args), C.byref(g), _stream(self.h0)), "dagnn_dvae_decode_backward")
         return d_h0, d_cells, d_av, d_ae
@@ -1733,7 +1752,8 @@ def dvae_sample(h0: torch.Tensor, groups: int, n: int, nvt: int, start_type: int
                 u_type: Optional[torch.Tensor] = None, u_edge: Optional[torch.Tensor] = None, states: bool = False):
     """One call of `dagnn_dvae_sample` over `groups` groups of h0.shape[0] // groups rows.  `tensors`: cells (list of
     (w_ih, w_hh, b_ih, b_hh)), w_key [hs], vid_bias [n] or None, av / ae (lists of (w1, b1, w2, b2)); agg = gated_sum:
-    gate = (gate_w [hs,hs+n], gate_b [hs], mapper_w [hs,hs+n]) in place of w_key / vid_bias.  u_type [G,n,B] and
+    gate = (gate_w [hs,hs+n], gate_b [hs], mapper_w [hs,hs+n]) in place of w_key / vid_bias; agg = attn_x (BN): key_type
+    [nvt] in place of them.  u_type [G,n,B] and
     u_edge [G,n(n-1)/2,B] (both or neither): the draws of a sampled decode; None: argmax.  Returns (types [R,n] int32,
     preds [R,n] int32 bitmasks, nv [R] int32, states [R,n,hs] or None) on h0's device, without synchronising."""
     h0 = _dev(h0, "H0", torch.float32)
@@ -1748,8 +1768,9 @@ def dvae_sample(h0: torch.Tensor, groups: int, n: int, nvt: int, start_type: int
         raise DagnnHipError("dagnn_dvae_sample: 1 to %d stacked cells" % _lib.MAX_STACKED)
     gate = tensors.get("gate")
     gate = None if gate is None else [f(t, "gate / mapper parameter") for t in gate]
-    wk = None if gate is not None else f(tensors["w_key"], "w_key")
-    vb = None if gate is not None or tensors.get("vid_bias") is None else f(tensors["vid_bias"], "vid_bias")
+    kt = None if tensors.get("key_type") is None else f(tensors["key_type"], "key_type")
+    wk = None if gate is not None or kt is not None else f(tensors["w_key"], "w_key")
+    vb = None if wk is None or tensors.get("vid_bias") is None else f(tensors["vid_bias"], "vid_bias")
     av = [f(t, "add_vertex parameter") for t in tensors["av"]]
     ae = [f(t, "add_edge parameter") for t in tensors["ae"]]
     V1, E1, ein = av[0].shape[0], ae[0].shape[0], (3 if bn else 2) * hs
@@ -1758,6 +1779,8 @@ def dvae_sample(h0: torch.Tensor, groups: int, n: int, nvt: int, start_type: int
             (ae[0], (E1, ein)), (ae[1], (E1,)), (ae[2], (1, E1)), (ae[3], (1,))]
     if gate is not None:
         want += [(gate[0], (hs, hs + n)), (gate[1], (hs,)), (gate[2], (hs, hs + n))]
+    elif kt is not None:
+        want.append((kt, (nvt,)))
     else:
         want.append((wk, (hs,)))
     if vb is not None:
@@ -1774,7 +1797,7 @@ def dvae_sample(h0: torch.Tensor, groups: int, n: int, nvt: int, start_type: int
     for t, shape in want:
         if tuple(t.shape) != shape:
             raise ValueError("dagnn_dvae_sample: a tensor of shape %s where %s is needed" % (tuple(t.shape), shape))
-    a = _lib.DvaeSampleArgs()
+    a = _lib.DvaeSampleArgsTyped()
     a.G, a.B, a.n, a.hs, a.L, a.nvt = groups, B, n, hs, len(cells), nvt
     a.start_type, a.end_type, a.bn, a.stochastic = int(start_type), int(end_type), int(bool(bn)), int(stochastic)
     a.edge_hidden, a.vertex_hidden = E1, V1
@@ -1785,6 +1808,9 @@ def dvae_sample(h0: torch.Tensor, groups: int, n: int, nvt: int, start_type: int
     if gate is not None:
         a.agg = 1
         a.gate_w, a.gate_b, a.mapper_w = (t.data_ptr() for t in gate)
+    elif kt is not None:
+        a.agg = 2
+        a.key_type = kt.data_ptr()
     a.av_w1, a.av_b1, a.av_w2, a.av_b2 = (t.data_ptr() for t in av)
     a.ae_w1, a.ae_b1, a.ae_w2, a.ae_b2 = (t.data_ptr() for t in ae)
     a.u_type, a.u_edge = _ptr(u_type), _ptr(u_edge)

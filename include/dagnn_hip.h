@@ -958,6 +958,12 @@ typedef struct dagnn_iprop_layer {
 int dagnn_iprop_step(const float* values, const int32_t* pred_vid, int64_t B, int P, int hs, const float* w_key,
                      const float* vid_bias /* [max_n] or NULL */, const float* H_given /* or NULL */, const float* x, int in0,
                      const dagnn_iprop_layer* layers /* host [L] */, int L, float* states, void* stream);
+/* ... with type-keyed attention (`attn_x` on the BN model, dvae/dagnn_bn.py:203-225): pred_type [B,P] holds the vertex
+ * TYPE of each predecessor (-1 for padding; clamped to nvt-1), a real slot scores key_type[type] (key_type [nvt]: the key
+ * half of attn_lin.weight), a padded one 0; the values are the predecessors' layer-0 states as above. */
+int dagnn_iprop_step_typed(const float* values, const int32_t* pred_type, int64_t B, int P, int hs, const float* key_type,
+                           int nvt, const float* H_given /* or NULL */, const float* x, int in0,
+                           const dagnn_iprop_layer* layers /* host [L] */, int L, float* states, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Teacher-forced D-VAE decoder: `DVAE_PYG.loss()` (dvae/models_pyg.py:398-456) without the latent part - H0 =
@@ -986,6 +992,14 @@ int dagnn_iprop_step(const float* values, const int32_t* pred_vid, int64_t B, in
  * mapper_forward.0.0, [hs, hs+n] row-major); w_key / vid_bias are not read.  Their gradients go to d_gate_w / d_gate_b
  * / d_mapper_w, and d_w_key / d_vid_bias are not written.  agg = 1 with bn = 1 or a missing gate / mapper pointer is
  * refused (the size queries return 0).  The fields are appended: a zero-filled struct is agg = 0 (attn_h).
+ * agg = 2 (`attn_x`, BN only: dvae/dagnn_bn.py:203-225): the attention keys are the predecessors' one-hot TYPES, so a
+ * real slot scores key_type[type of u] - key_type [nvt] is the key half of node_aggr_0[0].attn_lin.weight ([1, 2 nvt]:
+ * columns nvt..2nvt-1) -, a padded slot 0, and the values stay the layer-0 states; w_key / vid_bias are not read.  In
+ * reverse d_key_type[t] (written, not accumulated) is the sum of the score gradients of every (update, real slot) whose
+ * predecessor has type t, in one fixed order; the keys do not depend on the states, so a predecessor's state gradient
+ * is alpha * d hagg alone; d_w_key / d_vid_bias are not written.  agg = 2 with bn = 0 or without key_type is refused.
+ * key_type / d_key_type are appended behind the agg = 1 fields and read only when agg = 2 passed the checks above, so a
+ * caller built against the earlier structs (agg = 0 / 1) is served as before.
  * ---------------------------------------------------------------------------------------- */
 #define DAGNN_DVAE_MAX_N 32
 #define DAGNN_DVAE_MAX_TYPES 64
@@ -1012,10 +1026,11 @@ typedef struct dagnn_dvae_decode_args {
     float* ll;
     float* saved;
     size_t saved_bytes;
-    int agg;                 /* 0: attn_h (w_key / vid_bias), 1: gated_sum (gate_w / gate_b / mapper_w) */
+    int agg;                 /* 0: attn_h (w_key / vid_bias), 1: gated_sum (gate_w / gate_b / mapper_w), 2: attn_x (key_type) */
     const float* gate_w;     /* [hs, hs+n] */
     const float* gate_b;     /* [hs] */
     const float* mapper_w;   /* [hs, hs+n] */
+    const float* key_type;   /* agg = 2: [nvt] */
 } dagnn_dvae_decode_args;
 typedef struct dagnn_dvae_decode_grads {
     const float* g_res;      /* device scalar: d loss / d res */
@@ -1031,6 +1046,7 @@ typedef struct dagnn_dvae_decode_grads {
     float *d_av_w1, *d_av_b1, *d_av_w2, *d_av_b2;
     float *d_ae_w1, *d_ae_b1, *d_ae_w2, *d_ae_b2;
     float *d_gate_w, *d_gate_b, *d_mapper_w;   /* agg = 1 */
+    float* d_key_type;       /* agg = 2: [nvt] */
 } dagnn_dvae_decode_grads;
 size_t dagnn_dvae_decode_saved_bytes(const dagnn_dvae_decode_args* args /* host */);
 size_t dagnn_dvae_decode_work_bytes(const dagnn_dvae_decode_args* args /* host */);
@@ -1054,6 +1070,8 @@ int dagnn_dvae_decode_backward(const dagnn_dvae_decode_args* args /* host */, co
  *   work >= dagnn_dvae_sample_work_bytes(args) bytes.  No allocation, no synchronisation, bitwise repeatable (no float
  *   atomics).  The size query returns 0 for arguments the entry point refuses with DAGNN_EINVAL.
  *   agg = 1: the gated_sum aggregate, with the gate / mapper tensors and rules of dagnn_dvae_decode_args.
+ *   agg = 2: type-keyed attention (BN only), key_type [nvt] as in dagnn_dvae_decode_args: a vertex's key score is
+ *   key_type[its type], written when the vertex is final; w_key / vid_bias are not read.
  * ---------------------------------------------------------------------------------------- */
 typedef struct dagnn_dvae_sample_args {
     int64_t G;               /* groups (independent decode calls) */
@@ -1083,10 +1101,11 @@ typedef struct dagnn_dvae_sample_args {
     float* states;           /* or NULL */
     float* work;
     size_t work_bytes;
-    int agg;                 /* as in dagnn_dvae_decode_args: 0 attn_h, 1 gated_sum */
+    int agg;                 /* as in dagnn_dvae_decode_args: 0 attn_h, 1 gated_sum, 2 attn_x */
     const float* gate_w;
     const float* gate_b;
     const float* mapper_w;
+    const float* key_type;   /* agg = 2: [nvt] */
 } dagnn_dvae_sample_args;
 size_t dagnn_dvae_sample_work_bytes(const dagnn_dvae_sample_args* args /* host */);
 int dagnn_dvae_sample(const dagnn_dvae_sample_args* args /* host */, void* stream);
