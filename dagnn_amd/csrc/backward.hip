@@ -78,7 +78,6 @@ struct BArgs {
     int ncell, H, ld_h, R, vid_mod;
 };
 
-__device__ __forceinline__ float bsigm(float x) { return 1.0f / (1.0f + expf(-x)); }
 
 __device__ __forceinline__ float bscore(const float* __restrict__ tail, int nparts) {
     float s = 0.f;
@@ -453,8 +452,8 @@ __device__ __forceinline__ void bwd_block(const int32_t* __restrict__ plan, cons
         const int r = idx / H, u = idx - r * H;
         float dr = 0.f, dz = 0.f, dn = 0.f, dnr = 0.f, zg = 0.f;
         if (r < nrows) {
-            const float rr = bsigm(gir + ghr);
-            const float zz = bsigm(giz + ghz);
+            const float rr = sigm_div(gir + ghr);
+            const float zz = sigm_div(giz + ghz);
             const float nn = tanhf(gin + rr * ghn);
             const float Gv = g_s[idx];
             dn = Gv * (1.0f - zz) * (1.0f - nn * nn);         // d pre-activation of n
@@ -659,7 +658,7 @@ __global__ void __launch_bounds__(256) bwd_rows_kernel(const int32_t* __restrict
         float4 dr, dz, dn, dnr, zg;
 #define DAGNN_GATE_BWD(f)                                                                    \
         {                                                                                    \
-            const float rr = bsigm(ir.f + hr.f), zz = bsigm(iz.f + hz.f);                    \
+            const float rr = sigm_div(ir.f + hr.f), zz = sigm_div(iz.f + hz.f);              \
             const float nn = tanhf(in.f + rr * hn.f);                                        \
             dn.f = G.f * (1.0f - zz) * (1.0f - nn * nn);                                     \
             dz.f = G.f * (av.f - nn) * zz * (1.0f - zz);                                     \

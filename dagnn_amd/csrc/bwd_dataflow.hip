@@ -46,11 +46,7 @@ constexpr int BD_WPS = 4;            // loader waves per stream: one row of a bl
 constexpr int BD_RPW = DF_RB / BD_WPS;   // rows of a block per loader wave, one after the other
 constexpr int BD_NLW = DF_NLS * BD_WPS;
 constexpr int BD_THREADS = 64 * (DF_NCW + BD_NLW);
-constexpr int BD_SP = DF_STAT_SP;    // pitch of a static row (floats): lane l holds columns {l, 64 + l, 128 + l, 192 + l} at [4l, 4l + 4)
-// H = 320 (round 4): a fifth column block {256 + l}.  The record of a (cell, node) is then part A = the eight 256-float rows as
-// before, part B = eight 64-float rows behind them (row r, lane l at 8 * 256 + 64 r + l): 10 KB instead of 8
-__host__ __device__ constexpr int bd_stat_floats(int H) { return df_stat_floats(H); }
-constexpr int BD_NSTAT = DF_NSTAT;   // static rows per (cell, node): Gext, h, c_r, c_z, c_nr, c_n, z, c_q (df_common.h)
+// (a (cell, node)'s static record - DF_NSTAT rows of pitch DF_STAT_SP, part B behind them at H = 320: df_common.h)
 constexpr int BD_RD = 6;             // a loader wave requests a record this many of its blocks ahead (ring: 8 entries)
 // a successor record (bd_records_kernel): 64 words = one DMA of a full wave
 //   [0..3] v, first / last CSR slot of v's row in direction 1 - d, 0     [4..7] first four successors   [8..11] their edge ids
@@ -63,12 +59,11 @@ constexpr int BD_RECW = 64;
 static_assert(BD_WPS == 4, "the workgroup shape: 4 compute + 2 x 4 loader waves (the 8-wave shape of round 4 is in scripts/experiments/)");
 constexpr int BD_SCAL_SL = 1;        // slice whose compute waves store sigma_v and the edge-feature sums (slice 0 stores q_v)
 enum { BD_DA = 0, BD_DU = 1 };
-enum { ST_GEXT = DF_ST_GEXT, ST_H = DF_ST_H, ST_CR = DF_ST_CR, ST_CZ = DF_ST_CZ, ST_CNR = DF_ST_CNR, ST_CN = DF_ST_CN, ST_Z = DF_ST_Z, ST_CQ = DF_ST_CQ };
 
 struct BdCell {            // (104 bytes: 30 kernel cells - 8 stacked layers, both directions - fit the kernel-argument segment)
     const float4* w;       // packed slices (dagnn_pack_dataflow of the gate-wise transposed matrix)
     const float* wkey;     // da: [H] key weights (zeros when the scores are static)
-    const float* alpha;    // da: [E] attention weights by original edge id (PULLW: [E, BD_SP] per-unit weight rows)
+    const float* alpha;    // da: [E] attention weights by original edge id (PULLW: [E, DF_STAT_SP] per-unit weight rows)
     const float* stat;     // da: [N, 8 * 256] static rows
     const gran_t* du_in;   // da: [N, gld] du arriving from stacked layer i + 1, or null (top layer)
     gran_t* out_g;         // da: [N, gld] granules of da (also read by this cell's own loaders); du: [N, gld] granules of du
@@ -84,12 +79,8 @@ struct BdCell {            // (104 bytes: 30 kernel cells - 8 stacked layers, bo
     int partner, layer;    // da: index of the input-gradient cell that reads this cell's dgi granules, or -1; the stacked layer
 };
 
-#define BD_MAX_KCELLS 24
-#define BD_MAX_WGS 320
-#define BD_IDLE_ROLE 0xffffu
-
 struct BdArgs {
-    BdCell cell[BD_MAX_KCELLS];
+    BdCell cell[DF_MAX_KCELLS];
     const int32_t* sched;   // schedule workspace (dagnn_dataflow_schedule)
     const int32_t* brecs;   // successor records in schedule order (dagnn_bwd_dataflow_prepare)
     int64_t gtab[2], brec[2];   // word offsets into sched / brecs
@@ -98,11 +89,12 @@ struct BdArgs {
     unsigned epoch, spin_limit;
     const int32_t* status;
     int* err;
-    // XCD-aware placement, verified at run time (see DfArgs::role in dataflow.hip): unit = a state-gradient cell's slices +
-    // the slices of its input-gradient cell; da / q / dgi granules stay in the XCD's L2 when all of them run there
+    // XCD-aware placement, verified at run time (df_place_roles in df_common.h, DfArgs::role in dataflow.hip): unit = a
+    // state-gradient cell's slices + the slices of its input-gradient cell; da / q / dgi granules stay in the XCD's L2 when all
+    // of them run there
     gran_t* xcc_tab;
     int nroles;
-    unsigned short role[BD_MAX_WGS];
+    unsigned short role[DF_MAX_WGS];
 #ifdef BD_STAMPS
     unsigned long long* dbg;   // [grid][2] start / end of every workgroup, then [blocks][NLS][16] stamps of the workgroup with role dbg_role
     unsigned dbg_role;
@@ -118,10 +110,8 @@ struct BdArgs {
 #endif
 static_assert(sizeof(BdArgs) + 8 <= 4096, "the cell and role tables must fit the kernel-argument segment");
 
-template <int KPT> struct BdPad { static constexpr int kp8 = 2 * KPT; static constexpr int seg = kp8 + 4; static constexpr int row = 8 * seg + 8; };
-
 template <int KPT> struct BdSlot {
-    static constexpr int AP = BdPad<KPT>::row;
+    static constexpr int AP = DfPad<KPT>::row;
     static constexpr int op_off = 0;                          // [3][RB][AP] operand rows: gate block g of row r at (g * RB + r) * AP
     static constexpr int zg_off = 3 * DF_RB * AP;             // [RB][32]    z (.) G of the slice's units
     static constexpr int dn_off = zg_off + DF_RB * DF_JS;     // [RB][32]    c_n (.) G of the slice's units (the n block of dgi)
@@ -139,57 +129,11 @@ struct BdLds {
     int* local;    // [1] every reader of this cell's granules runs on this workgroup's XCD
 };
 
-__device__ __forceinline__ int bd_flag_ld(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
-__device__ __forceinline__ void bd_flag_st(int* p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
-
-__device__ __forceinline__ bool bd_wait4(const int* f, int target, int* err, unsigned limit) {
-    unsigned spins = 0;
-    for (;;) {
-        const int a = bd_flag_ld(f), b = bd_flag_ld(f + 1), c = bd_flag_ld(f + 2), d = bd_flag_ld(f + 3);
-        if (min(min(a, b), min(c, d)) >= target) return true;
-        __builtin_amdgcn_s_sleep(1);
-        if (++spins > 4 * limit) { __hip_atomic_fetch_or(err, 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); return false; }
-        if ((spins & 1023) == 0 && __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) return false;
-    }
-}
-
-__device__ __forceinline__ bool bd_retry(unsigned& spins, int* err, unsigned limit) {
-    __builtin_amdgcn_s_sleep(1);
-    if (++spins > limit) { __hip_atomic_fetch_or(err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); return false; }
-    if ((spins & 255) == 0 && __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) return false;
-    return true;
-}
-
 // a pointer / value the "s" operand of an asm statement can take (the compiler does not always see that it is wave-uniform)
 __device__ __forceinline__ const void* bd_sptr(const void* p) {
     const unsigned long long u = (unsigned long long)(uintptr_t)p;
     const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)u), hi = __builtin_amdgcn_readfirstlane((unsigned)(u >> 32));
     return reinterpret_cast<const void*>((uintptr_t)(((unsigned long long)hi << 32) | lo));
-}
-__device__ __forceinline__ float bd_dpp_row_sum16(float v) {
-#define BD_DPP_ADD(ctrl) \
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), ctrl, 0xf, 0xf, true))
-    BD_DPP_ADD(0x111); BD_DPP_ADD(0x112); BD_DPP_ADD(0x114); BD_DPP_ADD(0x118);
-#undef BD_DPP_ADD
-    return v;
-}
-// sum over the 64 lanes, broadcast as a wave-uniform value (row scans, then row_bcast15 / row_bcast31)
-__device__ __forceinline__ float bd_wave_sum(float v) {
-    v = bd_dpp_row_sum16(v);
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x142, 0xa, 0xf, false));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x143, 0xc, 0xf, false));
-    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
-}
-template <int CTRL> __device__ __forceinline__ float bd_dpp(float v) {   // 0 where the source lane is outside the DPP row
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, true));
-}
-__device__ __forceinline__ float bd_row_pair_sum(float x) {   // (see df_row_pair_sum in dataflow.hip: the swap must be inline asm)
-    float a = x, b = x;
-    asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(a), "+v"(b));
-    return a + b;
-}
-__device__ __host__ __forceinline__ int bd_stream_group(int pair, int set, int groups) {
-    return df_group_of_stream(pair, set, groups);
 }
 
 // ---------------------------------------------------------------- preparation kernels
@@ -256,8 +200,6 @@ struct BdStatCell {
 };
 struct BdStatArgs { BdStatCell cell[DAGNN_MAX_DIRS * DAGNN_MAX_STACKED]; int ncell, H, ld_h, ld_g; };
 
-__device__ __forceinline__ float bd_sigm(float x) { return 1.0f / (1.0f + expf(-x)); }
-
 // one wave per (cell, node): the eight static rows in the lane order the sweep's loader waves read them in
 __global__ void __launch_bounds__(256) bd_stat_kernel(BdStatArgs A, int64_t N) {
     const int lane = threadIdx.x & 63;
@@ -265,36 +207,36 @@ __global__ void __launch_bounds__(256) bd_stat_kernel(BdStatArgs A, int64_t N) {
     if (v >= N) return;
     const BdStatCell& C = A.cell[blockIdx.y];
     const int H = A.H, H3 = 3 * H;
-    float o[BD_NSTAT][5];
+    float o[DF_NSTAT][5];
 #pragma unroll
     for (int q = 0; q < 5; ++q) {
         const int c = 64 * q + lane;
 #pragma unroll
-        for (int r = 0; r < BD_NSTAT; ++r) o[r][q] = 0.f;
+        for (int r = 0; r < DF_NSTAT; ++r) o[r][q] = 0.f;
         if (c < H) {
             const float* gi = C.gi + v * H3;
             const float* gh = C.gh + v * H3;
             const float ghr = gh[c], ghz = gh[H + c], ghn = gh[2 * H + c];
-            const float rr = bd_sigm(gi[c] + ghr), zz = bd_sigm(gi[H + c] + ghz);
+            const float rr = sigm_div(gi[c] + ghr), zz = sigm_div(gi[H + c] + ghz);
             const float nn = tanhf(gi[2 * H + c] + rr * ghn);
             const float av = C.a[v * H + c];
             const float cn = (1.0f - zz) * (1.0f - nn * nn);
             const float cz = (av - nn) * zz * (1.0f - zz);
             const float cr = cn * ghn * rr * (1.0f - rr);
             const float cnr = cn * rr;
-            o[ST_GEXT][q] = C.gext[v * A.ld_g + c];
-            o[ST_H][q] = C.h[v * A.ld_h + c];
-            o[ST_CR][q] = cr; o[ST_CZ][q] = cz; o[ST_CNR][q] = cnr; o[ST_CN][q] = cn; o[ST_Z][q] = zz;
-            o[ST_CQ][q] = zz * av + cr * (ghr - C.b_hh[c]) + cz * (ghz - C.b_hh[H + c]) + cnr * (ghn - C.b_hh[2 * H + c]);
+            o[DF_ST_GEXT][q] = C.gext[v * A.ld_g + c];
+            o[DF_ST_H][q] = C.h[v * A.ld_h + c];
+            o[DF_ST_CR][q] = cr; o[DF_ST_CZ][q] = cz; o[DF_ST_CNR][q] = cnr; o[DF_ST_CN][q] = cn; o[DF_ST_Z][q] = zz;
+            o[DF_ST_CQ][q] = zz * av + cr * (ghr - C.b_hh[c]) + cz * (ghz - C.b_hh[H + c]) + cnr * (ghn - C.b_hh[2 * H + c]);
         }
     }
-    float* rec = C.stat + v * bd_stat_floats(H);
+    float* rec = C.stat + v * df_stat_floats(H);
     float4* dst = reinterpret_cast<float4*>(rec) + lane;
 #pragma unroll
-    for (int r = 0; r < BD_NSTAT; ++r) dst[r * (BD_SP / 4)] = make_float4(o[r][0], o[r][1], o[r][2], o[r][3]);
+    for (int r = 0; r < DF_NSTAT; ++r) dst[r * (DF_STAT_SP / 4)] = make_float4(o[r][0], o[r][1], o[r][2], o[r][3]);
     if (H > 256) {
 #pragma unroll
-        for (int r = 0; r < BD_NSTAT; ++r) rec[BD_NSTAT * BD_SP + 64 * r + lane] = o[r][4];
+        for (int r = 0; r < DF_NSTAT; ++r) rec[DF_NSTAT * DF_STAT_SP + 64 * r + lane] = o[r][4];
     }
 }
 
@@ -309,9 +251,9 @@ __global__ void __launch_bounds__(256) bd_gext_kernel(BdStatArgs A, int64_t N) {
     float o[5];
 #pragma unroll
     for (int q = 0; q < 5; ++q) o[q] = 64 * q + lane < H ? g[64 * q + lane] : 0.f;
-    float* rec = C.stat + v * bd_stat_floats(H);
-    reinterpret_cast<float4*>(rec)[ST_GEXT * (BD_SP / 4) + lane] = make_float4(o[0], o[1], o[2], o[3]);
-    if (H > 256) rec[BD_NSTAT * BD_SP + 64 * ST_GEXT + lane] = o[4];
+    float* rec = C.stat + v * df_stat_floats(H);
+    reinterpret_cast<float4*>(rec)[DF_ST_GEXT * (DF_STAT_SP / 4) + lane] = make_float4(o[0], o[1], o[2], o[3]);
+    if (H > 256) rec[DF_NSTAT * DF_STAT_SP + 64 * DF_ST_GEXT + lane] = o[4];
 }
 
 // ---------------------------------------------------------------- loader waves
@@ -436,14 +378,14 @@ struct BdSweep {
 #define BD_CASES(n_) BD_CASE(n_, 0) BD_CASE(n_, 1)
 
 // PULLW (agg = max of the constructor-string variants, dagnn_bwd_dataflow_args.pull_rows): the pull of row v weighs successor
-// w's da row per unit - C.alpha is [E, BD_SP], a row of static weights per original edge id in this loader's lane order
+// w's da row per unit - C.alpha is [E, DF_STAT_SP], a row of static weights per original edge id in this loader's lane order
 // (dagnn_plain_max_weights), read with one plain 16-byte load per successor in front of the chunk's first trip.  Same polls,
 // granules, hand-offs and flags; no scores, so sigma_v and the edge-feature sums are zeros.
 template <int KPT, bool HAS_DU, bool PULLW = false>
 __device__ __forceinline__ void bd_loader_da(const int32_t* __restrict__ plan, const BdArgs& S, const BdCell& C, int sl,
                                              int group, const BdLds& lds, int w, int set) {
     constexpr int H = 16 * KPT;
-    constexpr int SEG = BdPad<KPT>::seg, KP8 = BdPad<KPT>::kp8;
+    constexpr int SEG = DfPad<KPT>::seg, KP8 = DfPad<KPT>::kp8;
     constexpr int NQ4 = H / 64;
     typedef BdSlot<KPT> Slot;
     const int lane = threadIdx.x & 63;
@@ -468,7 +410,7 @@ __device__ __forceinline__ void bd_loader_da(const int32_t* __restrict__ plan, c
     const float* const alpha = C.alpha;
     int* const dn = lds.dn + set * DF_NCW;
     constexpr int NC = NQ4 > 4 ? NQ4 : 4;   // column blocks a lane carries
-    constexpr int SREC = bd_stat_floats(H);
+    constexpr int SREC = df_stat_floats(H);
     float wk[NC];
     int cpos[NC];   // (64 % KP8 == 0: cpos[q] = cpos[0] + a constant - one address register, immediate offsets)
 #pragma unroll
@@ -565,15 +507,15 @@ __device__ __forceinline__ void bd_loader_da(const int32_t* __restrict__ plan, c
         if (v >= 0) {
             const int deg = ee - eb;
             const float* sa = stat + (int64_t)v * SREC;
-            const float* sb = sa + 4 * BD_SP;
-            const float* sc = sa + BD_NSTAT * BD_SP;   // part B of the record (H = 320)
-            float ST5[BD_NSTAT];                       // ... the lane's fifth column of the eight static rows
+            const float* sb = sa + 4 * DF_STAT_SP;
+            const float* sc = sa + DF_NSTAT * DF_STAT_SP;   // part B of the record (H = 320)
+            float ST5[DF_NSTAT];                       // ... the lane's fifth column of the eight static rows
             const gran_t* ub = HAS_DU ? du_in + (unsigned)v * (unsigned)gld : da_g;
             float acc[NC];
 #pragma unroll
             for (int q = 0; q < NC; ++q) acc[q] = 0.f;
             float sig = 0.f, m0 = 0.f, m1 = 0.f;
-            bf4 ST[BD_NSTAT];   // the node's static rows: outputs of the FIRST trip only, so they stay put across re-polls
+            bf4 ST[DF_NSTAT];   // the node's static rows: outputs of the FIRST trip only, so they stay put across re-polls
             float du[NC];
 #pragma unroll
             for (int q = 0; q < NC; ++q) du[q] = 0.f;
@@ -596,7 +538,7 @@ __device__ __forceinline__ void bd_loader_da(const int32_t* __restrict__ plan, c
                         static_assert(!PULLW || NC == 4, "a weight row is one float4 per lane");
                         pj[e] = FIRST ? s4[e] : col[eb + c0 + e];
                         const int eid = FIRST ? e4[e] : eidx[eb + c0 + e];
-                        mw[e] = *reinterpret_cast<const bf4*>(alpha + ((int64_t)eid * BD_SP + 4 * lane));
+                        mw[e] = *reinterpret_cast<const bf4*>(alpha + ((int64_t)eid * DF_STAT_SP + 4 * lane));
                     } else if (FIRST) { pj[e] = s4[e]; al[e] = ral[e]; f0[e] = rf0[e]; f1[e] = rf1[e]; }
                     else {
                         pj[e] = col[eb + c0 + e];
@@ -641,7 +583,7 @@ __device__ __forceinline__ void bd_loader_da(const int32_t* __restrict__ plan, c
                     // trip stay live across the statement and the register allocator copies the whole sweep every turn)
                     bool more;
                     do {
-                        more = bd_retry(spins, err, spin_limit);
+                        more = df_retry(spins, err, spin_limit);
 #ifdef BD_STAMPS
                         t_issue = wall_clock64(); ++npoll;
 #endif
@@ -664,12 +606,12 @@ __device__ __forceinline__ void bd_loader_da(const int32_t* __restrict__ plan, c
                         for (int q = 0; q < NC; ++q) acc[q] = fmaf(mw[e][q & 3], BD_X(q), acc[q]);
                         continue;
                     }
-                    float dot = BD_X(0) * ST[ST_H].x;
-                    if (NQ4 > 1) dot = fmaf(BD_X(1), ST[ST_H].y, dot);
-                    if (NQ4 > 2) dot = fmaf(BD_X(2), ST[ST_H].z, dot);
-                    if (NQ4 > 3) dot = fmaf(BD_X(3), ST[ST_H].w, dot);
-                    if (NQ4 > 4) dot = fmaf(BD_X(4), ST5[ST_H], dot);
-                    const float ds = al[e] * (bd_wave_sum(dot) - __uint_as_float((unsigned)A.q[e]));
+                    float dot = BD_X(0) * ST[DF_ST_H].x;
+                    if (NQ4 > 1) dot = fmaf(BD_X(1), ST[DF_ST_H].y, dot);
+                    if (NQ4 > 2) dot = fmaf(BD_X(2), ST[DF_ST_H].z, dot);
+                    if (NQ4 > 3) dot = fmaf(BD_X(3), ST[DF_ST_H].w, dot);
+                    if (NQ4 > 4) dot = fmaf(BD_X(4), ST5[DF_ST_H], dot);
+                    const float ds = al[e] * (dpp_wave_sum(dot) - __uint_as_float((unsigned)A.q[e]));
                     sig += ds;
                     m0 = fmaf(ds, f0[e], m0);
                     m1 = fmaf(ds, f1[e], m1);
@@ -680,7 +622,7 @@ __device__ __forceinline__ void bd_loader_da(const int32_t* __restrict__ plan, c
             };
             typedef std::integral_constant<bool, true> first_t;
             typedef std::integral_constant<bool, false> later_t;
-            if (b >= BD_NSLOT) bd_wait4(dn, b - BD_NSLOT + 1, err, spin_limit);   // the ring slot is free again (before the poll: off the dependent chain)
+            if (b >= BD_NSLOT) df_wait4(dn, b - BD_NSLOT + 1, err, spin_limit);   // the ring slot is free again (before the poll: off the dependent chain)
             BD_STAMP(prof, b, set, 1);   // slot free
             if (deg <= 0) chunk(std::integral_constant<int, 0>(), first_t(), 0);
             else if (deg == 1) chunk(std::integral_constant<int, 1>(), first_t(), 0);
@@ -704,12 +646,12 @@ __device__ __forceinline__ void bd_loader_da(const int32_t* __restrict__ plan, c
             auto stv = [&](int r, int q) -> float { return q < 4 ? ST[r][q] : ST5[r]; };   // (q is a constant after unrolling)
             float G[NC];
 #pragma unroll
-            for (int q = 0; q < NC; ++q) G[q] = stv(ST_GEXT, q) + du[q] + acc[q] + sig * wk[q];
+            for (int q = 0; q < NC; ++q) G[q] = stv(DF_ST_GEXT, q) + du[q] + acc[q] + sig * wk[q];
             float dr[NC], dz[NC], dnr[NC], dnn[NC], zg[NC];
 #pragma unroll
             for (int q = 0; q < NC; ++q) {
-                dr[q] = G[q] * stv(ST_CR, q); dz[q] = G[q] * stv(ST_CZ, q); dnr[q] = G[q] * stv(ST_CNR, q);
-                dnn[q] = G[q] * stv(ST_CN, q); zg[q] = G[q] * stv(ST_Z, q);
+                dr[q] = G[q] * stv(DF_ST_CR, q); dz[q] = G[q] * stv(DF_ST_CZ, q); dnr[q] = G[q] * stv(DF_ST_CNR, q);
+                dnn[q] = G[q] * stv(DF_ST_CN, q); zg[q] = G[q] * stv(DF_ST_Z, q);
             }
             float* op = sbase + Slot::op_off + lw * Slot::AP;
 #pragma unroll
@@ -726,11 +668,11 @@ __device__ __forceinline__ void bd_loader_da(const int32_t* __restrict__ plan, c
             // The row's outputs to memory (q, sigma, the edge-feature sums, the slice's columns of dgi / dgh) are the COMPUTE
             // waves' job (round 4: a row costs its loader wave ~3 us of single-wave instruction issue, the compute waves idle
             // two thirds of the sweep): compute wave r stores row r, from the operand rows it reads anyway + what follows
-            float qd = G[0] * ST[ST_CQ].x;   // q_v = G_v . c_q,v: the per-lane parts
-            if (NQ4 > 1) qd = fmaf(G[1], ST[ST_CQ].y, qd);
-            if (NQ4 > 2) qd = fmaf(G[2], ST[ST_CQ].z, qd);
-            if (NQ4 > 3) qd = fmaf(G[3], ST[ST_CQ].w, qd);
-            if (NQ4 > 4) qd = fmaf(G[4], ST5[ST_CQ], qd);
+            float qd = G[0] * ST[DF_ST_CQ].x;   // q_v = G_v . c_q,v: the per-lane parts
+            if (NQ4 > 1) qd = fmaf(G[1], ST[DF_ST_CQ].y, qd);
+            if (NQ4 > 2) qd = fmaf(G[2], ST[DF_ST_CQ].z, qd);
+            if (NQ4 > 3) qd = fmaf(G[3], ST[DF_ST_CQ].w, qd);
+            if (NQ4 > 4) qd = fmaf(G[4], ST5[DF_ST_CQ], qd);
             const float mr = pick(dr), mz = pick(dz), mn = pick(dnn), mnr = pick(dnr);
             if (sl == BD_SCAL_SL) {   // (every lane: same words, same values)
                 float* sc = sbase + Slot::sc_off + lw * 4;
@@ -738,11 +680,11 @@ __device__ __forceinline__ void bd_loader_da(const int32_t* __restrict__ plan, c
             }
             if (rr == BD_RPW - 1) {
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                bd_flag_st(lds.rdy + set * BD_WPS + w, b + 1);
+                df_flag_st(lds.rdy + set * BD_WPS + w, b + 1);
             }
             BD_STAMP(prof, b, set, 5);   // flag raised
             if (sl == 0) {   // (next to the compute waves' products: off the dependent chain)
-                qd = bd_wave_sum(qd);
+                qd = dpp_wave_sum(qd);
                 if (lane == 0) {
                     if (local_st) C.q_g[v] = gran_pack(epoch, qd);
                     else __hip_atomic_store(C.q_g + v, gran_pack(epoch, qd), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -791,11 +733,11 @@ __device__ __forceinline__ void bd_loader_da(const int32_t* __restrict__ plan, c
             BD_STAMP(prof, b, set, 6);   // row outputs issued
         } else {
             glds4(ra, rl);   // an idle row keeps the record ring moving
-            if (b >= BD_NSLOT) bd_wait4(dn, b - BD_NSLOT + 1, err, spin_limit);
+            if (b >= BD_NSLOT) df_wait4(dn, b - BD_NSLOT + 1, err, spin_limit);
             v_s[lw] = v;
             if (rr == BD_RPW - 1) {
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                bd_flag_st(lds.rdy + set * BD_WPS + w, b + 1);
+                df_flag_st(lds.rdy + set * BD_WPS + w, b + 1);
             }
         }
       }
@@ -843,7 +785,7 @@ __device__ __forceinline__ void bd_loader_da(const int32_t* __restrict__ plan, c
 template <int KPT>
 __device__ __forceinline__ void bd_loader_du(const BdArgs& S, const BdCell& C, int group, const BdLds& lds, int w, int set) {
     constexpr int H = 16 * KPT;
-    constexpr int SEG = BdPad<KPT>::seg, KP8 = BdPad<KPT>::kp8;
+    constexpr int SEG = DfPad<KPT>::seg, KP8 = DfPad<KPT>::kp8;
     constexpr int NQ4 = H / 64;
     typedef BdSlot<KPT> Slot;
     const int lane = threadIdx.x & 63;
@@ -919,9 +861,9 @@ __device__ __forceinline__ void bd_loader_du(const BdArgs& S, const BdCell& C, i
                 for (int g = 0; g < 3; ++g)
 #pragma unroll
                     for (int q = 0; q < NC; ++q) ok = ok && (unsigned)(Y[g][q] >> 32) == epoch;
-                if (__all(ok) || !bd_retry(spins, err, spin_limit)) break;
+                if (__all(ok) || !df_retry(spins, err, spin_limit)) break;
             }
-            if (b >= BD_NSLOT) bd_wait4(dn, b - BD_NSLOT + 1, err, spin_limit);
+            if (b >= BD_NSLOT) df_wait4(dn, b - BD_NSLOT + 1, err, spin_limit);
             float* op = sbase + Slot::op_off + lw * Slot::AP;
 #pragma unroll
             for (int g = 0; g < 3; ++g)
@@ -929,12 +871,12 @@ __device__ __forceinline__ void bd_loader_du(const BdArgs& S, const BdCell& C, i
                 for (int q = 0; q < NQ4; ++q) op[g * DF_RB * Slot::AP + cpos[q]] = __uint_as_float((unsigned)Y[g][q]);
         } else {
             glds4(ra, rl);
-            if (b >= BD_NSLOT) bd_wait4(dn, b - BD_NSLOT + 1, err, spin_limit);
+            if (b >= BD_NSLOT) df_wait4(dn, b - BD_NSLOT + 1, err, spin_limit);
         }
         if (lane == 0) v_s[lw] = v;
       }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        if (lane == 0) bd_flag_st(lds.rdy + set * BD_WPS + w, b + 1);
+        if (lane == 0) df_flag_st(lds.rdy + set * BD_WPS + w, b + 1);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
@@ -946,7 +888,7 @@ __device__ __forceinline__ void bd_loader_du(const BdArgs& S, const BdCell& C, i
 template <int KPT>
 __device__ __forceinline__ void bd_compute(const BdArgs& S, const BdCell& C, int sl, int pair, const BdLds& lds, int cw) {
     constexpr int H = 16 * KPT;
-    constexpr int SEG = BdPad<KPT>::seg, KP8 = BdPad<KPT>::kp8, NK4 = KP8 / 4;
+    constexpr int SEG = DfPad<KPT>::seg, KP8 = DfPad<KPT>::kp8, NK4 = KP8 / 4;
     typedef BdSlot<KPT> Slot;
     const int tc = threadIdx.x & 255;
     const int lane = tc & 63;
@@ -957,7 +899,7 @@ __device__ __forceinline__ void bd_compute(const BdArgs& S, const BdCell& C, int
     int nb[DF_NLS];
 #pragma unroll
     for (int q = 0; q < DF_NLS; ++q) {
-        const int grp = bd_stream_group(pair, q, S.groups);
+        const int grp = df_group_of_stream(pair, q, S.groups);
         nb[q] = grp >= 0 ? S.sched[S.gtab[d] + 2 * grp + 1] : 0;
     }
     float wr[KP8], wz[KP8], wn[KP8];
@@ -1071,15 +1013,15 @@ __device__ __forceinline__ void bd_compute(const BdArgs& S, const BdCell& C, int
 #ifdef BD_STAMPS
                 { asm volatile("" :: "v"(t[0]), "v"(t[3])); BD_STAMP(prof, b, st, 10); }   // products done
 #endif
-                const float u0 = t[0] + bd_dpp<0x104>(t[0]), u1 = t[1] + bd_dpp<0x104>(t[1]);
-                const float u2 = t[2] + bd_dpp<0x114>(t[2]), u3 = t[3] + bd_dpp<0x114>(t[3]);
+                const float u0 = t[0] + dpp<0x104>(t[0]), u1 = t[1] + dpp<0x104>(t[1]);
+                const float u2 = t[2] + dpp<0x114>(t[2]), u3 = t[3] + dpp<0x114>(t[3]);
                 const float e0 = s0 ? u2 : u0, e1 = s0 ? u3 : u1;
-                const float f0 = e0 + bd_dpp<0x108>(e0), f1 = e1 + bd_dpp<0x118>(e1);
-                gsum = bd_row_pair_sum(s1 ? f1 : f0);
+                const float f0 = e0 + dpp<0x108>(e0), f1 = e1 + dpp<0x118>(e1);
+                gsum = row_pair_sum(s1 ? f1 : f0);
                 flags_min(r0, r1);
             }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            bd_flag_st(dn_or_dump + st * dn_step, b + 1);   // this wave is done with the slot
+            df_flag_st(dn_or_dump + st * dn_step, b + 1);   // this wave is done with the slot
             // (the bound on the node id also covers padding rows, id -1, and whatever a slot holds once a wait has expired)
             if (lane_st && (unsigned)gv < (unsigned)num_nodes) {
                 gran_t* po = out_g + (__umul24((unsigned)gv, (unsigned)gld) + (unsigned)unit);   // (N * gld < 2^31, N < 2^24: host check)
@@ -1110,6 +1052,7 @@ __global__ void __launch_bounds__(BD_THREADS, BD_THREADS / 256) bwd_dataflow_ker
     typedef BdSlot<KPT> Slot;
     constexpr int NS = 16 * KPT / DF_JS;
     const int tid = threadIdx.x;
+    // (this prologue - status and schedule check, role decode, XCD publication - is dataflow_kernel's too: kept in step by hand)
     if (S.status && S.status[0] != 0) {
         if (tid == 0) __hip_atomic_fetch_or(S.err, 4 | ((S.status[0] & 0xff) << 8), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         return;
@@ -1122,8 +1065,8 @@ __global__ void __launch_bounds__(BD_THREADS, BD_THREADS / 256) bwd_dataflow_ker
     int pair, c, sl;
     if (S.nroles > 0) {
         const unsigned role = S.role[blockIdx.x];
-        if (role == BD_IDLE_ROLE) return;
-        pair = (int)(role >> 10); c = (int)((role >> 5) & 31u); sl = (int)(role & 31u);
+        if (role == DF_IDLE_ROLE) return;
+        pair = (int)(role >> DF_ROLE_SET_SHIFT); c = (int)((role >> DF_ROLE_CELL_SHIFT) & DF_ROLE_FIELD); sl = (int)(role & DF_ROLE_FIELD);
     } else {
         const int per_pair = S.ncell * NS;
         pair = blockIdx.x / per_pair;
@@ -1156,9 +1099,9 @@ __global__ void __launch_bounds__(BD_THREADS, BD_THREADS / 256) bwd_dataflow_ker
             bool same = true;
             for (int b0 = 0; b0 < S.nroles; b0 += 64) {
                 const int b = b0 + (tid & 63);
-                const unsigned r = b < S.nroles ? S.role[b] : BD_IDLE_ROLE;
-                const int rc = (int)((r >> 5) & 31u);
-                const bool member = r != BD_IDLE_ROLE && (int)(r >> 10) == pair && (rc == c || rc == C.partner);
+                const unsigned r = b < S.nroles ? S.role[b] : DF_IDLE_ROLE;
+                const int rc = (int)((r >> DF_ROLE_CELL_SHIFT) & DF_ROLE_FIELD);
+                const bool member = r != DF_IDLE_ROLE && (int)(r >> DF_ROLE_SET_SHIFT) == pair && (rc == c || rc == C.partner);
                 unsigned spins = 0;
                 bool have = !member;
                 unsigned theirs = xcc;
@@ -1167,7 +1110,7 @@ __global__ void __launch_bounds__(BD_THREADS, BD_THREADS / 256) bwd_dataflow_ker
                         const gran_t g = gran_ld(S.xcc_tab + b);
                         if ((unsigned)(g >> 32) == S.epoch) { theirs = (unsigned)g; have = true; }
                     }
-                    if (__all(have) || !bd_retry(spins, S.err, S.spin_limit)) break;
+                    if (__all(have) || !df_retry(spins, S.err, S.spin_limit)) break;
                 }
                 same = same && have && theirs == xcc;
             }
@@ -1182,7 +1125,7 @@ __global__ void __launch_bounds__(BD_THREADS, BD_THREADS / 256) bwd_dataflow_ker
 #endif
     } else {
         const int set = (wave - DF_NCW) / BD_WPS, w = (wave - DF_NCW) % BD_WPS;
-        const int grp = bd_stream_group(pair, set, S.groups);
+        const int grp = df_group_of_stream(pair, set, S.groups);
         if (grp >= 0) {
             if (C.kind == BD_DU) bd_loader_du<KPT>(S, C, grp, lds, w, set);
             else if (C.du_in) bd_loader_da<KPT, true, PULLW>(plan, S, C, sl, grp, lds, w, set);
@@ -1214,12 +1157,12 @@ extern "C" size_t dagnn_bwd_dataflow_record_bytes(int64_t N) {
 
 extern "C" size_t dagnn_bwd_dataflow_static_bytes(int64_t N) {
     if (N < 0) return 0;
-    return (size_t)N * BD_NSTAT * BD_SP * sizeof(float);
+    return (size_t)N * DF_NSTAT * DF_STAT_SP * sizeof(float);
 }
 
 extern "C" size_t dagnn_bwd_dataflow_static_bytes_h(int64_t N, int H) {   // H = 320: 10 KB per (cell, node)
     if (N < 0 || H <= 0) return 0;
-    return (size_t)N * bd_stat_floats(H) * sizeof(float);
+    return (size_t)N * df_stat_floats(H) * sizeof(float);
 }
 
 extern "C" int dagnn_bwd_dataflow_prepare(const dagnn_plan* pl, const dagnn_bwd_dataflow_args* a, void* stream) {
@@ -1292,7 +1235,7 @@ extern "C" int dagnn_bwd_dataflow_run(const dagnn_plan* pl, const dagnn_bwd_data
                 (pl->num_edge_feats > 0 && !c.edge_feat_grad) || (i > 0 && (!c.w_ih_t || !c.dgi_granules)) ||
                 (i + 1 < Ls && !c.du_granules))
                 return DAGNN_EINVAL;
-            if (nc + (i > 0 ? 2 : 1) > BD_MAX_KCELLS) return DAGNN_EINVAL;
+            if (nc + (i > 0 ? 2 : 1) > DF_MAX_KCELLS) return DAGNN_EINVAL;
             BdCell K = {};
             K.w = (const float4*)c.w_hh_t; K.wkey = c.w_key; K.alpha = c.alpha; K.stat = c.stat;
             K.du_in = i + 1 < Ls ? (const gran_t*)c.du_granules : nullptr;
@@ -1311,9 +1254,7 @@ extern "C" int dagnn_bwd_dataflow_run(const dagnn_plan* pl, const dagnn_bwd_data
             }
         }
     }
-    hipStream_t st = (hipStream_t)stream;
-    const int NS = H / DF_JS;
-    const int sets = (G + DF_NLS - 1) / DF_NLS;
+    const int NS = H / DF_JS, sets = df_sets_for(G);
     S.sched = (const int32_t*)a->schedule;
     S.brecs = (const int32_t*)a->records;
     const DfLayout SL = df_layout_words(pl->N, pl->B, G);
@@ -1324,68 +1265,21 @@ extern "C" int dagnn_bwd_dataflow_run(const dagnn_plan* pl, const dagnn_bwd_data
         S.col[d] = L.col[d]; S.eidx[d] = L.eidx[d]; S.eattr[d] = L.eattr[d];
     }
     S.ncell = nc; S.H = H; S.gld = a->gld; S.R = pl->num_edge_feats; S.groups = G; S.N = (int)pl->N;
-    S.epoch = a->epoch; S.spin_limit = a->spin_limit ? a->spin_limit : (1u << 22);
+    S.epoch = a->epoch; S.spin_limit = a->spin_limit ? a->spin_limit : DF_SPIN_LIMIT;
     S.status = (const int32_t*)a->plan_status;
     S.err = (int*)a->err;
-    unsigned grid = (unsigned)(sets * nc * NS);
-    S.nroles = 0; S.xcc_tab = (gran_t*)a->xcc_table;
-    if (a->num_cus >= 8 && a->num_cus <= BD_MAX_WGS && a->xcc_table && sets < 64 && nc <= 31) {   // (dataflow.hip: same packing)
-        const int cap = a->num_cus / 8;
-        int fill[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        const int xrot = (a->xcd_first % 8 + 8) % 8;   // bin x of the packing = XCD (x + xcd_first) mod 8
-        for (int b = 0; b < BD_MAX_WGS; ++b) S.role[b] = BD_IDLE_ROLE;
-        bool ok = true;
-        int top = 0;
-        for (int pass = 0; pass < 2 && ok; ++pass)
-            for (int set = 0; set < sets && ok; ++set)
-                for (int c = 0; c < nc && ok; ++c) {
-                    if (S.cell[c].kind != BD_DA || (S.cell[c].partner >= 0) != (pass == 0)) continue;
-                    const int members[2] = {c, S.cell[c].partner};
-                    const int size = NS * (members[1] >= 0 ? 2 : 1);
-                    int x = 0;
-                    while (x < 8 && fill[x] + size > cap) ++x;
-                    if (x == 8) { ok = false; break; }
-                    for (int m = 0; m < 2; ++m) {
-                        if (members[m] < 0) continue;
-                        for (int sl = 0; sl < NS; ++sl) {
-                            const int b = fill[x]++ * 8 + (x + xrot) % 8;
-                            S.role[b] = (unsigned short)((set << 10) | (members[m] << 5) | sl);
-                            if (b + 1 > top) top = b + 1;
-                        }
-                    }
-                }
-        if (ok) { S.nroles = top; grid = (unsigned)top; }
-    }
+    S.xcc_tab = (gran_t*)a->xcc_table;
+    S.nroles = df_place_roles(S.role, S.cell, nc, BD_DA, NS, sets, a->num_cus, a->xcd_first, a->xcc_table != nullptr);
+    const unsigned grid = S.nroles > 0 ? (unsigned)S.nroles : (unsigned)(sets * nc * NS);
 #ifdef BD_STAMPS
     S.dbg = g_bd_dbg; S.dbg_role = g_bd_dbg_role;
 #endif
     const int32_t* plan = (const int32_t*)pl->data;
-#define BD_LAUNCH(KPT, PW)                                                                                               \
-    do {                                                                                                                 \
-        const void* fn = reinterpret_cast<const void*>(bwd_dataflow_kernel<KPT, PW>);                                    \
-        const hipError_t ea = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bd_lds_bytes<KPT>()); \
-        if (ea != hipSuccess) return DAGNN_EHIP(ea);                                                                     \
-        hipLaunchKernelGGL((bwd_dataflow_kernel<KPT, PW>), dim3(grid), dim3(BD_THREADS), bd_lds_bytes<KPT>(), st, plan, S); \
-    } while (0)
-#ifdef BD_WIDE_TU
-    BD_LAUNCH(20, false);
-#else
-    if (a->pull_rows)
-        switch (H / 16) {
-            case 4: BD_LAUNCH(4, true); break;
-            case 8: BD_LAUNCH(8, true); break;
-            case 12: BD_LAUNCH(12, true); break;
-            default: BD_LAUNCH(16, true); break;
-        }
-    else
-        switch (H / 16) {
-            case 4: BD_LAUNCH(4, false); break;
-            case 8: BD_LAUNCH(8, false); break;
-            case 12: BD_LAUNCH(12, false); break;
-            default: BD_LAUNCH(16, false); break;
-        }
-#endif
-#undef BD_LAUNCH
-    DAGNN_CHECK_LAUNCH();
-    return DAGNN_OK;
+    static_assert(BD_THREADS == DF_THREADS, "df_launch: one workgroup shape");
+    return df_for_width<BD_TU_MAX_H>(H, [&](auto kpt) {
+        constexpr int KPT = decltype(kpt)::value;
+        if constexpr (KPT <= 16)   // (per-unit pull weights exist for H <= 256 only)
+            if (a->pull_rows) return df_launch(bwd_dataflow_kernel<KPT, true>, bd_lds_bytes<KPT>(), grid, (hipStream_t)stream, plan, S);
+        return df_launch(bwd_dataflow_kernel<KPT, false>, bd_lds_bytes<KPT>(), grid, (hipStream_t)stream, plan, S);
+    });
 }

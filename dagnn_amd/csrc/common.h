@@ -158,6 +158,47 @@ __device__ __forceinline__ int wave_max_i(int v) {
     return v;
 }
 
+// ---- the same on DPP (no trip through the LDS crossbar)
+// inclusive scan over the 16 lanes of a DPP row (row_shr 1,2,4,8; out-of-row lanes read 0):
+// lane 15 of every row ends with the row total, always in the same order -> deterministic
+__device__ __forceinline__ float dpp_row_sum16(float v) {
+#define DAGNN_DPP_ADD(ctrl) \
+    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), ctrl, 0xf, 0xf, true))
+    DAGNN_DPP_ADD(0x111); DAGNN_DPP_ADD(0x112); DAGNN_DPP_ADD(0x114); DAGNN_DPP_ADD(0x118);
+#undef DAGNN_DPP_ADD
+    return v;
+}
+// sum over the 64 lanes, broadcast as a wave-uniform value (row scans, then row_bcast15 / row_bcast31).  NOT wave_sum: the
+// additions come in another order, the two differ in the last bits
+__device__ __forceinline__ float dpp_wave_sum(float v) {
+    v = dpp_row_sum16(v);
+    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x142, 0xa, 0xf, false));
+    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x143, 0xc, 0xf, false));
+    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
+}
+template <int CTRL> __device__ __forceinline__ float dpp(float v) {   // 0 where the source lane is outside the DPP row
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, true));
+}
+// x + (x of the lane 16 away, i.e. the neighbouring DPP row of the pair): v_permlane16_swap on two copies of x leaves
+// rows (0, 0, 2, 2) in one and (1, 1, 3, 3) in the other
+__device__ __forceinline__ float row_pair_sum(float x) {
+    // (inline asm: with both operands holding the same value hipcc 7.2 folds the builtin's two results into one and
+    // emits v1 + v1 behind the swap; volatile also keeps it out of the divergent branch that uses the sum)
+    float a = x, b = x;
+    asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(a), "+v"(b));
+    return a + b;
+}
+
+// ---- gate non-linearities, three forms that differ in the last bits: a call site keeps the one its results were checked with
+// on the hardware exp / rcp (both ~1 ulp): sigma(x) = 1 / (1 + e^-x), tanh(x) = 1 - 2 / (1 + e^2x)
+// (saturates correctly: e^2x = inf -> 1, e^2x = 0 -> -1)
+__device__ __forceinline__ float sigm_rcp(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
+__device__ __forceinline__ float tanh_rcp(float x) { return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __expf(2.0f * x)); }
+// IEEE division and the library's expf
+__device__ __forceinline__ float sigm_div(float x) { return 1.0f / (1.0f + expf(-x)); }
+// IEEE division and the hardware exp
+__device__ __forceinline__ float sigm_div_fexp(float x) { return 1.f / (1.f + __expf(-x)); }
+
 // ---- granules: the hand-off format inside the persistent tail kernel ---------------------------
 // Every state float (and partial score) also exists as an 8-byte {tag = epoch of this forward pass,
 // value} granule written by ONE aligned 8-byte store.  A consumer re-reads the granules it needs

@@ -138,10 +138,6 @@ struct DfCell {
     int agg;              // DAGNN_DF_AGG_*: 0 attention (the soft-max fold), 1 add, 2 max, 3 none (the aggregate is zero)
 };
 
-#define DF_MAX_KCELLS 24   // (24 x 136 bytes of cell table + the role table + the rest stay inside the 4 KB kernel-argument segment)
-#define DF_MAX_WGS 320     // workgroups the XCD-aware placement table covers (one per CU)
-#define DF_IDLE_ROLE 0xffffu
-
 struct DfArgs {
     DfCell cell[DF_MAX_KCELLS];
     const int32_t* sched;   // schedule workspace (dagnn_dataflow_schedule)
@@ -153,9 +149,8 @@ struct DfArgs {
     const int32_t* status;      // plan status word (dagnn_plan_build), or null
     int* err;
     unsigned long long* dbg;    // optional: [grid][2] start / end stamps, then [blocks][8] stamps of workgroup dbg_wg (100 MHz)
-    // XCD-aware placement (nroles > 0): role[b] = set << 10 | cell << 5 | slice of workgroup b (DF_IDLE_ROLE: none), chosen so
-    // that - with the observed dispatch rule "workgroup b runs on XCD b % 8" - a recurrent cell's 8 slices and the
-    // projection cell reading its rows share one XCD, i.e. one L2.  Nothing is ASSUMED about the placement: every
+    // XCD-aware placement (nroles > 0): role[b] of workgroup b (df_place_roles, df_common.h), chosen so that a recurrent cell's
+    // slices and the projection cell reading its rows share one XCD, i.e. one L2.  Nothing is ASSUMED about the placement: every
     // workgroup publishes the XCD it actually runs on (xcc_tab, tagged granules) and a recurrent cell keeps its state rows
     // in that L2 (plain stores instead of write-through ones) only when it SEES all their readers there.
     gran_t* xcc_tab;
@@ -166,27 +161,6 @@ struct DfArgs {
 
 static_assert(sizeof(DfArgs) + 8 <= 4096, "the cell and role tables must fit the kernel-argument segment");
 
-__device__ __forceinline__ float df_dpp_row_sum16(float v) {
-#define DF_DPP_ADD(ctrl) \
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), ctrl, 0xf, 0xf, true))
-    DF_DPP_ADD(0x111); DF_DPP_ADD(0x112); DF_DPP_ADD(0x114); DF_DPP_ADD(0x118);
-#undef DF_DPP_ADD
-    return v;
-}
-
-// sum over the 64 lanes, broadcast as a wave-uniform value (row scans, then row_bcast15 / row_bcast31)
-__device__ __forceinline__ float df_wave_sum(float v) {
-    v = df_dpp_row_sum16(v);
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x142, 0xa, 0xf, false));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x143, 0xc, 0xf, false));
-    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
-}
-
-// gate non-linearities on the hardware exp / rcp (both ~1 ulp): sigma(x) = 1 / (1 + e^-x), tanh(x) = 1 - 2 / (1 + e^2x)
-// (saturates correctly: e^2x = inf -> 1, e^2x = 0 -> -1)
-__device__ __forceinline__ float df_sigm(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
-__device__ __forceinline__ float df_tanh(float x) { return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __expf(2.0f * x)); }
-
 // The forward kernel's compute shape: one compute wave per SIMD, 8 hidden units each (3 H/8 resident weights per lane), K split over
 // 8 lanes.  (Round 6 measured the other shape the register file allows - two compute waves per SIMD with 4 units each, K over 16
 // lanes, 16 waves per workgroup at <= 128 VGPRs: 1.50 against 1.33 ms on the headline batch; the complete kernel
@@ -195,21 +169,12 @@ __device__ __forceinline__ float df_tanh(float x) { return 1.0f - 2.0f * __built
 // is the reverse sweep's too: df_common.h.  (The 64-unit shape - 8 compute waves, two per SIMD, and ONE stream of 4 loader waves:
 // the same time, bitwise the same results - is a patch under scripts/experiments/, see its README.)
 static_assert(DF_NCW * 8 == DF_JS && DF_NLW % DF_NLS == 0 && DF_WPS == DF_RB, "workgroup shape: a loader wave per row of a block");
-// operand rows in LDS: the K dimension is split over 8 lanes (KP8 = H / 8 values each); K-lane segment s starts at
-// s * (KP8 + 4): the 8 segments a half DPP row reads concurrently (ds_read_b128) fall on disjoint banks
-template <int KPT> struct DfPad { static constexpr int kp8 = 2 * KPT; static constexpr int seg = kp8 + 4; static constexpr int row = 8 * seg + 8; };
 
 constexpr int DF_CSLEEP_N = 1;   // s_sleep argument (x 64 cycles) of the compute waves' look at the ready flags
-constexpr int DF_WSLEEP_N = 1;   // ... of a loader's wait for its ring slot (4 / 16 x longer: measured flat)
 constexpr int DF_RD = 6;       // a loader wave requests a row record this many of ITS blocks ahead (record ring: 8 entries)
 constexpr int DF_GD = 2;       // a gi0 slice this many (its node id must have landed: DF_RD >= DF_GD + 2)
 constexpr int DF_GI_LANES = 3 * DF_JS / 4;          // lanes of a gi0 slice's DMA: 16 bytes each, gate-major
 constexpr int DF_GIRING = DF_NSLOT + DF_GD + 2;   // blocks in a stream's gi0 ring: slots in use + prefetch distance + slack
-
-// workgroup sets of a pass: stream `set` of set `pair` serves group df_group_of_stream(pair, set, groups) (df_common.h).
-// (Measured and dropped: the first set serving the deepest graph's group alone, 9 groups on 5 sets - 2.15 ms against 1.93:
-// what binds the pass is the sets' throughput, not that one chain.)
-__host__ inline int df_sets_for(int groups) { return (groups + DF_NLS - 1) / DF_NLS; }
 
 struct DfLds {
     float* ring;     // [NLS][NSLOT] slots: a ring per stream
@@ -229,29 +194,6 @@ template <int KPT> struct DfSlot {
     static constexpr int v_off = gi_off + DF_RB * 3 * DF_JS;   // [RB] ints (16 B)
     static constexpr int words = v_off + 4;
 };
-
-__device__ __forceinline__ int df_flag_ld(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
-__device__ __forceinline__ void df_flag_st(int* p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
-
-__device__ __forceinline__ bool df_wait4(const int* f, int target, int* err, unsigned limit) {
-    unsigned spins = 0;
-    for (;;) {
-        int m = min(min(df_flag_ld(f), df_flag_ld(f + 1)), min(df_flag_ld(f + 2), df_flag_ld(f + 3)));   // (every compute wave's flag)
-        if (m >= target) return true;
-        __builtin_amdgcn_s_sleep(DF_WSLEEP_N);
-        if (++spins > 4 * limit) { __hip_atomic_fetch_or(err, 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); return false; }
-        // once any wait of the launch has failed, nobody waits long again (the pass is lost; it must still end)
-        if ((spins & 1023) == 0 && __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) return false;
-    }
-}
-
-// bounded global poll: false (and error bit 0) once the budget is spent
-__device__ __forceinline__ bool df_retry(unsigned& spins, int* err, unsigned limit) {
-    __builtin_amdgcn_s_sleep(1);
-    if (++spins > limit) { __hip_atomic_fetch_or(err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); return false; }
-    if ((spins & 255) == 0 && __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) return false;
-    return true;
-}
 
 // ---- loader wave: row `lw` of every block of this group
 // PLAIN: the cell's aggregator is not an attention soft-max but `add` / `max` over the messages h_j + e_j, e_j =
@@ -545,7 +487,7 @@ __device__ __forceinline__ void df_loader(const int32_t* __restrict__ plan, cons
                 for (int e = 0; e < NN; ++e) s[e] = DF_ROW(e, 0) * wk[0] + DF_ROW(e, 1) * wk[1] + DF_ROW(e, 2) * wk[2] + DF_ROW(e, 3) * wk[3];
                 if (!sscore) {
 #pragma unroll
-                    for (int e = 0; e < NN; ++e) s[e] = df_wave_sum(s[e]);
+                    for (int e = 0; e < NN; ++e) s[e] = dpp_wave_sum(s[e]);
                 }
                 float mc = m;
 #pragma unroll
@@ -883,7 +825,7 @@ __device__ __forceinline__ void df_loader_fast(const int32_t* __restrict__ plan,
 #pragma unroll
                 for (int e = 0; e < NN; ++e) { s[e] = DF_ROWF(e, 0) * wk[0] + DF_ROWF(e, 1) * wk[1] + DF_ROWF(e, 2) * wk[2] + DF_ROWF(e, 3) * wk[3]; if (NC > 4) s[e] = fmaf(DF_ROWF(e, 4), wk[NC - 1], s[e]); }
 #pragma unroll
-                for (int e = 0; e < NN; ++e) s[e] = df_wave_sum(s[e]);
+                for (int e = 0; e < NN; ++e) s[e] = dpp_wave_sum(s[e]);
                 float mc = -INFINITY;
 #pragma unroll
                 for (int e = 0; e < NN; ++e) { s[e] += fe[e]; mc = fmaxf(mc, s[e]); }
@@ -944,7 +886,7 @@ __device__ __forceinline__ void df_loader_fast(const int32_t* __restrict__ plan,
                     float mc = m;
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
-                        s[e] = df_wave_sum(s[e]) + fe[e];
+                        s[e] = dpp_wave_sum(s[e]) + fe[e];
                         if (e < nn) mc = fmaxf(mc, s[e]);
                     }
                     const float sc = __expf(m - mc);   // 0 on the first chunk (m = -inf)
@@ -995,19 +937,6 @@ __device__ __forceinline__ void df_loader_fast(const int32_t* __restrict__ plan,
 #undef DF_IFCS
 
 typedef float f4v __attribute__((ext_vector_type(4)));
-template <int CTRL> __device__ __forceinline__ float df_dpp(float v) {   // 0 where the source lane is outside the DPP row
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, true));
-}
-// x + (x of the lane 16 away, i.e. the neighbouring DPP row of the pair): v_permlane16_swap on two copies of x leaves
-// rows (0, 0, 2, 2) in one and (1, 1, 3, 3) in the other
-__device__ __forceinline__ float df_row_pair_sum(float x) {
-    // (inline asm: with both operands holding the same value hipcc 7.2 folds the builtin's two results into one and
-    // emits v1 + v1 behind the swap; volatile also keeps it out of the divergent branch that uses the sum)
-    float a = x, b = x;
-    asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(a), "+v"(b));
-    return a + b;
-}
-
 // element index of (row v, column c) in a buffer of `ld` elements per row: ONE full-rate v_mad_u32_u24 instead of the 64-bit
 // multiply (quarter rate, on the compute wave's serial chain) - v < 2^24 and v * ld + c < 2^31 (the host checks N * ld < 2^31)
 __device__ __forceinline__ unsigned df_idx(int v, int ld, int c) { return __umul24((unsigned)v, (unsigned)ld) + (unsigned)c; }
@@ -1181,7 +1110,7 @@ __device__ __forceinline__ void df_compute(const DfArgs& S, const DfCell& C, int
                         "v_add_f32_dpp %2, %0, %0 row_shl:8 row_mask:0xf bank_mask:0x3\n\t"
                         "v_add_f32_dpp %2, %1, %1 row_shr:8 row_mask:0xf bank_mask:0xc"
                         : "=&v"(e0), "=&v"(e1), "=&v"(f) : "v"(A[0]), "v"(A[1]), "v"(A[2]), "v"(A[3]));
-                    return df_row_pair_sum(f);
+                    return row_pair_sum(f);
                 };
 #pragma unroll
                 for (int q = 0; q < NK4; ++q) {
@@ -1205,9 +1134,9 @@ __device__ __forceinline__ void df_compute(const DfArgs& S, const DfCell& C, int
             const float p_r = g3[0] + b_r, p_z = g3[1] + b_z, p_n = g3[2] + b_n;   // W a + b: the cell's pre-activations
             float hv = 0.f, ng = 0.f;
             if (!proj) {   // (every lane: no branch around the gates)
-                rg = df_sigm(p_r + gi_r);
-                zg = df_sigm(p_z + gi_z);
-                ng = df_tanh(fmaf(rg, p_n, gi_n));
+                rg = sigm_rcp(p_r + gi_r);
+                zg = sigm_rcp(p_z + gi_z);
+                ng = tanh_rcp(fmaf(rg, p_n, gi_n));
                 hv = fmaf(zg, aval - ng, ng);   // n + z * (a - n)
             }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -1275,6 +1204,7 @@ __global__ void __launch_bounds__(DF_THREADS, DF_THREADS / 256) dataflow_kernel(
         if (tid == 0) __hip_atomic_fetch_or(S.err, 4 | ((S.status[0] & 0xff) << 8), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         return;
     }
+    // (this prologue - status and schedule check, role decode, XCD publication - is bwd_dataflow_kernel's too: kept in step by hand)
     if (S.sched[0] != S.groups || S.sched[1] != DF_MAGIC || S.sched[2] != DF_RB) {   // a schedule built for another group count
         if (tid == 0) __hip_atomic_fetch_or(S.err, 8, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // (or not built at all) would
         return;                                                                                      // index gtab / grec out of bounds
@@ -1285,7 +1215,7 @@ __global__ void __launch_bounds__(DF_THREADS, DF_THREADS / 256) dataflow_kernel(
     if (S.nroles > 0) {
         const unsigned role = S.role[blockIdx.x];
         if (role == DF_IDLE_ROLE) return;
-        pair = (int)(role >> 10); c = (int)((role >> 5) & 31u); sl = (int)(role & 31u);
+        pair = (int)(role >> DF_ROLE_SET_SHIFT); c = (int)((role >> DF_ROLE_CELL_SHIFT) & DF_ROLE_FIELD); sl = (int)(role & DF_ROLE_FIELD);
     } else {
         const int per_pair = S.ncell * NS;
         pair = blockIdx.x / per_pair;
@@ -1318,8 +1248,8 @@ __global__ void __launch_bounds__(DF_THREADS, DF_THREADS / 256) dataflow_kernel(
             for (int b0 = 0; b0 < S.nroles; b0 += 64) {
                 const int b = b0 + (tid & 63);
                 const unsigned r = b < S.nroles ? S.role[b] : DF_IDLE_ROLE;
-                const int rc = (int)((r >> 5) & 31u);
-                const bool member = r != DF_IDLE_ROLE && (int)(r >> 10) == pair && (rc == c || rc == C.partner);
+                const int rc = (int)((r >> DF_ROLE_CELL_SHIFT) & DF_ROLE_FIELD);
+                const bool member = r != DF_IDLE_ROLE && (int)(r >> DF_ROLE_SET_SHIFT) == pair && (rc == c || rc == C.partner);
                 unsigned spins = 0;
                 bool have = !member;
                 unsigned theirs = xcc;
@@ -1659,7 +1589,7 @@ extern "C" int dagnn_dataflow_run(const dagnn_plan* pl, const dagnn_dataflow_arg
     S.sched = (const int32_t*)a->schedule;
     PlanLayout L = dagnn_plan_layout_words(pl->N, pl->E, pl->B, pl->num_edge_feats);
     for (int d = 0; d < 2; ++d) { S.gtab[d] = SL.gtab[d]; S.grec[d] = SL.grec[d]; S.col[d] = L.col[d]; S.eattr[d] = L.eattr[d]; }
-    S.spin_limit = a->spin_limit ? a->spin_limit : (1u << 22);
+    S.spin_limit = a->spin_limit ? a->spin_limit : DF_SPIN_LIMIT;
     S.N = (int)pl->N;
     S.aux_stat = a->stat_rows ? 1 : 0;
     S.ncell = nc; S.H = H; S.ld_h = a->ld_h; S.gld = a->gld; S.pld = a->pld; S.R = pl->num_edge_feats;
@@ -1669,58 +1599,14 @@ extern "C" int dagnn_dataflow_run(const dagnn_plan* pl, const dagnn_dataflow_arg
     S.dbg_wg = a->debug_wg;
     S.status = (const int32_t*)a->plan_status;
     const int32_t* plan = (const int32_t*)pl->data;
-    unsigned grid = (unsigned)(df_sets_for(G) * nc * (H / DF_JS));
-    // XCD-aware placement (optional: the caller names the CU count and lends a tagged table): units = a recurrent cell's
-    // slices + the slices of the projection cell reading its rows; bins = the 8 XCDs (num_cus / 8 CUs each, one workgroup
-    // per CU); largest units first, first fit; workgroup (slot k of XCD x) = k * 8 + x under the observed dispatch rule.
-    // If the units do not fit, the linear mapping stays (and every hand-off store is write-through, as before).
-    S.nroles = 0; S.xcc_tab = (gran_t*)a->xcc_table;
-    if (a->num_cus >= 8 && a->num_cus <= DF_MAX_WGS && a->xcc_table && df_sets_for(G) < 64 && nc <= 31) {
-        const int NS = H / DF_JS, sets = df_sets_for(G), cap = a->num_cus / 8;
-        int fill[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        const int xrot = (a->xcd_first % 8 + 8) % 8;   // bin x of the packing = XCD (x + xcd_first) mod 8
-        for (int b = 0; b < DF_MAX_WGS; ++b) S.role[b] = DF_IDLE_ROLE;
-        bool ok = true;
-        int top = 0;
-        for (int pass = 0; pass < 2 && ok; ++pass)       // pass 0: units with a partner (2 NS workgroups), pass 1: without
-            for (int set = 0; set < sets && ok; ++set)
-                for (int c = 0; c < nc && ok; ++c) {
-                    if (S.cell[c].kind != DF_RECURRENT || (S.cell[c].partner >= 0) != (pass == 0)) continue;
-                    const int members[2] = {c, S.cell[c].partner};
-                    const int size = NS * (members[1] >= 0 ? 2 : 1);
-                    int x = 0;
-                    while (x < 8 && fill[x] + size > cap) ++x;
-                    if (x == 8) { ok = false; break; }
-                    for (int m = 0; m < 2; ++m) {
-                        if (members[m] < 0) continue;
-                        for (int sl = 0; sl < NS; ++sl) {
-                            const int b = fill[x]++ * 8 + (x + xrot) % 8;
-                            S.role[b] = (unsigned short)((set << 10) | (members[m] << 5) | sl);
-                            if (b + 1 > top) top = b + 1;
-                        }
-                    }
-                }
-        if (ok) { S.nroles = top; grid = (unsigned)top; }
-    }
-    hipStream_t st = (hipStream_t)stream;
-#define DF_LAUNCH(KPT)                                                                                                   \
-    do {                                                                                                                 \
-        const void* fn = reinterpret_cast<const void*>(dataflow_kernel<KPT>);                                            \
-        const hipError_t ea = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)df_lds_bytes<KPT>()); \
-        if (ea != hipSuccess) return DAGNN_EHIP(ea);                                                                     \
-        hipLaunchKernelGGL((dataflow_kernel<KPT>), dim3(grid), dim3(DF_THREADS), df_lds_bytes<KPT>(), st, plan, S);      \
-    } while (0)
-#if defined(DF_WIDE_TU)
-    DF_LAUNCH(20);
-#else
-    switch (H / 16) {
-        case 4: DF_LAUNCH(4); break;
-        case 8: DF_LAUNCH(8); break;
-        case 12: DF_LAUNCH(12); break;
-        default: DF_LAUNCH(16); break;
-    }
-#endif
-#undef DF_LAUNCH
-    DAGNN_CHECK_LAUNCH();
-    return DAGNN_OK;
+    // XCD-aware placement when the caller names the CU count and lends a tagged table (df_place_roles); else workgroup ids
+    // pair-major, then cell, then slice
+    const int NS = H / DF_JS, sets = df_sets_for(G);
+    S.xcc_tab = (gran_t*)a->xcc_table;
+    S.nroles = df_place_roles(S.role, S.cell, nc, DF_RECURRENT, NS, sets, a->num_cus, a->xcd_first, a->xcc_table != nullptr);
+    const unsigned grid = S.nroles > 0 ? (unsigned)S.nroles : (unsigned)(sets * nc * NS);
+    return df_for_width<DF_TU_MAX_H>(H, [&](auto kpt) {
+        constexpr int KPT = decltype(kpt)::value;
+        return df_launch(dataflow_kernel<KPT>, df_lds_bytes<KPT>(), grid, (hipStream_t)stream, plan, S);
+    });
 }

@@ -1,8 +1,11 @@
 // Definitions shared by the two persistent dataflow kernels: dataflow.hip (forward recurrence) and bwd_dataflow.hip (its
 // reverse-mode sweep).  Both walk the same schedule workspace (dagnn_dataflow_schedule) and use the same workgroup
-// shape: 4 compute waves + 2 loader sets x 4 loader waves, 32 hidden units per slice, blocks of 4 rows.
+// shape: 4 compute waves + 2 loader sets x 4 loader waves, 32 hidden units per slice, blocks of 4 rows.  Hence one copy of the
+// schedule layout and its LPT assignment, the static record, the hand-off primitives inside a workgroup (ready flags, bounded
+// polls, operand-row padding), the workgroups' role word with its XCD-aware placement, and the launch.
 #pragma once
 #include "common.h"
+#include <type_traits>
 
 namespace {
 
@@ -22,6 +25,10 @@ __device__ __host__ __forceinline__ int df_group_of_stream(int pair, int set, in
     const int g = DF_NLS * pair + set;
     return g < groups ? g : -1;
 }
+// workgroup sets of a pass: stream `set` of set `pair` serves group df_group_of_stream(pair, set, groups).
+// (Measured and dropped: the first set serving the deepest graph's group alone, 9 groups on 5 sets - 2.15 ms against 1.93:
+// what binds the pass is the sets' throughput, not that one chain.)
+__host__ inline int df_sets_for(int groups) { return (groups + DF_NLS - 1) / DF_NLS; }
 constexpr int DF_THREADS = 64 * (DF_NCW + DF_NLW);
 constexpr int DF_MAX_GROUPS = 64;
 constexpr int DF_MAGIC = 0x44463031;   // "DF01"
@@ -198,5 +205,107 @@ constexpr int DF_NSTAT = 8;
 constexpr int DF_STAT_SP = 256;
 __host__ __device__ constexpr int df_stat_floats(int H) { return DF_NSTAT * (H > 256 ? 320 : 256); }
 enum { DF_ST_GEXT = 0, DF_ST_H = 1, DF_ST_CR = 2, DF_ST_CZ = 3, DF_ST_CNR = 4, DF_ST_CN = 5, DF_ST_Z = 6, DF_ST_CQ = 7 };
+
+// ---------------------------------------------------------------- hand-off inside a workgroup, bounded polls
+// operand rows in LDS: the K dimension is split over 8 lanes (KP8 = H / 8 values each); K-lane segment s starts at
+// s * (KP8 + 4): the 8 segments a half DPP row reads concurrently (ds_read_b128) fall on disjoint banks
+template <int KPT> struct DfPad { static constexpr int kp8 = 2 * KPT; static constexpr int seg = kp8 + 4; static constexpr int row = 8 * seg + 8; };
+
+constexpr int DF_WSLEEP_N = 1;   // s_sleep argument (x 64 cycles) of a loader's wait for its ring slot (4 / 16 x longer: measured flat)
+constexpr unsigned DF_SPIN_LIMIT = 1u << 22;   // polls of one wait before the pass gives up, unless the caller names a budget
+
+// ready flags in LDS (relaxed workgroup-scope atomics: plain ds_ accesses; a volatile access compiles to a FLAT load + vmcnt(0))
+__device__ __forceinline__ int df_flag_ld(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
+__device__ __forceinline__ void df_flag_st(int* p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
+
+// all four flags at f have reached `target`; false (and error bit 1) once the budget is spent
+__device__ __forceinline__ bool df_wait4(const int* f, int target, int* err, unsigned limit) {
+    unsigned spins = 0;
+    for (;;) {
+        int m = min(min(df_flag_ld(f), df_flag_ld(f + 1)), min(df_flag_ld(f + 2), df_flag_ld(f + 3)));   // (every compute wave's flag)
+        if (m >= target) return true;
+        __builtin_amdgcn_s_sleep(DF_WSLEEP_N);
+        if (++spins > 4 * limit) { __hip_atomic_fetch_or(err, 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); return false; }
+        // once any wait of the launch has failed, nobody waits long again (the pass is lost; it must still end)
+        if ((spins & 1023) == 0 && __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) return false;
+    }
+}
+
+// bounded global poll: false (and error bit 0) once the budget is spent
+__device__ __forceinline__ bool df_retry(unsigned& spins, int* err, unsigned limit) {
+    __builtin_amdgcn_s_sleep(1);
+    if (++spins > limit) { __hip_atomic_fetch_or(err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); return false; }
+    if ((spins & 255) == 0 && __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) return false;
+    return true;
+}
+
+// ---------------------------------------------------------------- workgroup roles and their placement (host)
+// role[b] = set << 10 | cell << 5 | slice of workgroup b (DF_IDLE_ROLE: none); a kernel's argument struct carries the table
+constexpr int DF_MAX_KCELLS = 24;   // (24 x 136 bytes of forward cell table + the role table + the rest stay inside the 4 KB kernel-argument segment)
+constexpr int DF_MAX_WGS = 320;     // workgroups the XCD-aware placement table covers (one per CU)
+constexpr int DF_ROLE_SET_SHIFT = 10, DF_ROLE_CELL_SHIFT = 5;
+constexpr unsigned DF_ROLE_FIELD = 31u;   // mask of the cell and slice fields
+constexpr unsigned DF_IDLE_ROLE = 0xffffu;
+constexpr unsigned short df_role(int set, int cell, int slice) {
+    return (unsigned short)((set << DF_ROLE_SET_SHIFT) | (cell << DF_ROLE_CELL_SHIFT) | slice);
+}
+
+// XCD-aware placement (optional: the caller names the CU count and lends a tagged table, `lent`): units = a leading cell's
+// (kind == lead_kind: recurrent / state-gradient) slices + the slices of the partner cell reading its rows; bins = the 8 XCDs
+// (num_cus / 8 CUs each, one workgroup per CU); largest units first, first fit; workgroup (slot k of XCD x) = k * 8 + x under
+// the observed dispatch rule "workgroup b runs on XCD b % 8".  Fills role[] and returns the workgroups of the table; 0: the
+// units do not fit (or no placement was asked for) and the linear mapping stays (every hand-off store is write-through).
+// A set index of 63 or a cell index of 31 could spell DF_IDLE_ROLE: neither is admitted.
+template <class Cell>
+inline int df_place_roles(unsigned short (&role)[DF_MAX_WGS], const Cell* cell, int ncell, int lead_kind, int slices, int sets,
+                          int num_cus, int xcd_first, bool lent) {
+    if (num_cus < 8 || num_cus > DF_MAX_WGS || !lent || sets >= 64 || ncell > 31) return 0;
+    const int cap = num_cus / 8;
+    int fill[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    const int xrot = (xcd_first % 8 + 8) % 8;   // bin x of the packing = XCD (x + xcd_first) mod 8
+    for (int b = 0; b < DF_MAX_WGS; ++b) role[b] = DF_IDLE_ROLE;
+    int top = 0;
+    for (int pass = 0; pass < 2; ++pass)       // pass 0: units with a partner (2 x slices workgroups), pass 1: without
+        for (int set = 0; set < sets; ++set)
+            for (int c = 0; c < ncell; ++c) {
+                if (cell[c].kind != lead_kind || (cell[c].partner >= 0) != (pass == 0)) continue;
+                const int members[2] = {c, cell[c].partner};
+                const int size = slices * (members[1] >= 0 ? 2 : 1);
+                int x = 0;
+                while (x < 8 && fill[x] + size > cap) ++x;
+                if (x == 8) return 0;
+                for (int m = 0; m < 2; ++m) {
+                    if (members[m] < 0) continue;
+                    for (int sl = 0; sl < slices; ++sl) {
+                        const int b = fill[x]++ * 8 + (x + xrot) % 8;
+                        role[b] = df_role(set, members[m], sl);
+                        if (b + 1 > top) top = b + 1;
+                    }
+                }
+            }
+    return top;
+}
+
+// ---------------------------------------------------------------- launch (host)
+// f(std::integral_constant<int, KPT>) for the kernel instance of width H = 16 KPT that this translation unit ships: the wide
+// units (MAX_H = 320: dataflow_w.hip, bwd_dataflow_w.hip) hold KPT = 20 alone, the others 4 / 8 / 12 / 16
+template <int MAX_H, class F> inline int df_for_width(int H, F&& f) {
+    if constexpr (MAX_H > 256) return f(std::integral_constant<int, 20>());
+    else switch (H / 16) {
+        case 4: return f(std::integral_constant<int, 4>());
+        case 8: return f(std::integral_constant<int, 8>());
+        case 12: return f(std::integral_constant<int, 12>());
+        default: return f(std::integral_constant<int, 16>());
+    }
+}
+// one persistent launch of DF_THREADS threads per workgroup with `lds` bytes of dynamic LDS
+template <class Args>
+inline int df_launch(void (*kernel)(const int32_t*, Args), size_t lds, unsigned grid, hipStream_t st, const int32_t* plan, const Args& S) {
+    const hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (ea != hipSuccess) return DAGNN_EHIP(ea);
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(DF_THREADS), lds, st, plan, S);
+    DAGNN_CHECK_LAUNCH();
+    return DAGNN_OK;
+}
 
 }  // namespace

@@ -48,7 +48,6 @@ __device__ inline int dd_vertex_of_pair(int64_t p) {      // E(v) <= p < E(v+1),
     return v;
 }
 
-__device__ inline float dd_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
 
 // block-wide sum of one value per thread (DD_T threads), in a fixed order; every thread gets the result
 __device__ inline float dd_block_sum(float v, float* red) {
@@ -300,7 +299,7 @@ __global__ void __launch_bounds__(DD_T) dd_gru_kernel(int64_t r0, int v, int64_t
         ir = gi[i * 3 * H + c]; iz = gi[i * 3 * H + H + c]; in_ = gi[i * 3 * H + 2 * H + c];
     }
     const float hr = gh[i * 3 * H + c], hz = gh[i * 3 * H + H + c], hn = gh[i * 3 * H + 2 * H + c];
-    const float r = dd_sigmoid(ir + hr), z = dd_sigmoid(iz + hz);
+    const float r = sigm_div(ir + hr), z = sigm_div(iz + hz);
     const float nn = tanhf(in_ + r * hn);
     const float hp = hagg[row * H + c];
     h[row * H + c] = nn + z * (hp - nn);   // torch's GRUCell: (h - n) * z + n
@@ -336,7 +335,7 @@ __global__ void __launch_bounds__(DD_T) dd_edge_head_kernel(int E1, const float*
     for (int c = threadIdx.x; c < E1; c += DD_T) s = fmaf(hid[e * E1 + c], w2[c], s);
     s = dd_block_sum(s, red) + b2[0];
     if (threadIdx.x == 0) {
-        const float p = dd_sigmoid(s);
+        const float p = sigm_div(s);
         s_out[e] = p;
         ll[e] = y[e] > 0.5f ? fmaxf(logf(p), -100.f) : fmaxf(logf(1.0f - p), -100.f);
     }
@@ -620,7 +619,7 @@ __global__ void __launch_bounds__(DD_T) dd_gated_msg_kernel(int u, int n, int64_
     const int c = blockIdx.x * DD_T + threadIdx.x;
     if (c >= H) return;
     const int64_t b = blockIdx.y, q = (int64_t)u * B + b;
-    const float g = dd_sigmoid(pre[q * 2 * H + c] + gate_w[(int64_t)c * (H + n) + H + u] + gate_b[c]);
+    const float g = sigm_div(pre[q * 2 * H + c] + gate_w[(int64_t)c * (H + n) + H + u] + gate_b[c]);
     const float m = pre[q * 2 * H + H + c] + mapper_w[(int64_t)c * (H + n) + H + u];
     xmsg[q * H + c] = h0state[(dd_U(u) * B + b) * H + c];
     mgate[q * H + c] = g;

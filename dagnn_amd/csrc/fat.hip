@@ -72,8 +72,6 @@ __device__ __forceinline__ float4 ldg4(uint64_t a) {
 __device__ __forceinline__ float ldg1(uint64_t a) { return *reinterpret_cast<const __attribute__((address_space(1))) float*>(a); }
 
 // gate non-linearities on the hardware exp / rcp (as dataflow.hip): sigma(x) = 1 / (1 + e^-x), tanh(x) = 1 - 2 / (1 + e^2x)
-__device__ __forceinline__ float fat_sigm(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
-__device__ __forceinline__ float fat_tanh(float x) { return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __expf(2.0f * x)); }
 
 // LDS float index of 16-byte chunk c (0..15) of row r inside an A slot
 __device__ __forceinline__ int a_idx(int r, int c) { return r * 64 + ((c ^ (r & 15)) << 2); }
@@ -464,9 +462,9 @@ __device__ __forceinline__ void fat_main(const FatArgs& S, const FatTile& T, con
                 else { pr = o0[jj] + o1[jj]; pz = o0[32 + jj] + o1[32 + jj]; pn = o0[64 + jj] + o1[64 + jj]; }
                 hr += pr; hz += pz; hn += pn;
             }
-            const float rg = fat_sigm(gr + hr);
-            const float zg = fat_sigm(gz + hz);
-            const float ng = fat_tanh(fmaf(rg, hn, gn));
+            const float rg = sigm_rcp(gr + hr);
+            const float zg = sigm_rcp(gz + hz);
+            const float ng = tanh_rcp(fmaf(rg, hn, gn));
             hv = fmaf(zg, av[p] - ng, ng);
             spart = wk * hv;
         }

@@ -227,8 +227,8 @@ __device__ __forceinline__ void process_block(const int32_t* __restrict__ plan, 
             const float hz = gh_s[gr_ * SW + JS + gj_] + bh_z;
             const float hn = gh_s[gr_ * SW + 2 * JS + gj_] + bh_n;
             const float a = a_s[gr_ * op_ld + apad(j, kpt)];
-            const float rg = sigm(gr + hr);
-            const float zg = sigm(gz + hz);
+            const float rg = sigm_div(gr + hr);
+            const float zg = sigm_div(gz + hz);
             const float ng = tanhf(fmaf(rg, hn, gn));
             hv = fmaf(zg, a - ng, ng);  // n + z * (a - n)
             sp = wk * hv;

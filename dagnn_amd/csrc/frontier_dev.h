@@ -50,16 +50,6 @@ struct StepArgs {
 // segments a DPP row reads concurrently (ds_read_b128) fall on disjoint banks.
 __device__ __forceinline__ int apad(int k, int kpt) { return k + 4 * (k / kpt); }
 
-__device__ __forceinline__ float dpp_row_sum16(float v) {
-    // inclusive scan over the 16 lanes of a DPP row (row_shr 1,2,4,8; out-of-row lanes read 0):
-    // lane 15 of every row ends with the row total, always in the same order -> deterministic
-#define DAGNN_DPP_ADD(ctrl) \
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), ctrl, 0xf, 0xf, true))
-    DAGNN_DPP_ADD(0x111); DAGNN_DPP_ADD(0x112); DAGNN_DPP_ADD(0x114); DAGNN_DPP_ADD(0x118);
-#undef DAGNN_DPP_ADD
-    return v;
-}
-
 __device__ __forceinline__ void fma4(float4& acc, float al, const float4& v) {
     acc.x = fmaf(al, v.x, acc.x); acc.y = fmaf(al, v.y, acc.y); acc.z = fmaf(al, v.z, acc.z); acc.w = fmaf(al, v.w, acc.w);
 }
@@ -319,7 +309,6 @@ __device__ __forceinline__ void aggregate(const Cell& C, const int32_t* __restri
     }
 }
 
-__device__ __forceinline__ float sigm(float x) { return 1.0f / (1.0f + expf(-x)); }
 
 }  // namespace
 

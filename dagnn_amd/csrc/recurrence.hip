@@ -39,7 +39,6 @@ struct RecArgs {
     unsigned long long* dbg;  // optional [8] phase timing of work item 0 (wall_clock64 ticks, 100 MHz)
 };
 
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
 
 // padded index of element k of an aggregate row in LDS: 4 floats of pad between K slices so the
 // KSL slices a wave reads concurrently (ds_read_b128) fall on different banks.
@@ -179,8 +178,8 @@ __device__ __forceinline__ void gates_row(int v, const float* __restrict__ gi, c
             hr += gh_row[j]; hz += gh_row[H + j]; hn += gh_row[2 * H + j];
             a = a_row[a_idx(j, kper)];
         }
-        const float r = sigmoidf_(g[j] + hr);
-        const float z = sigmoidf_(g[H + j] + hz);
+        const float r = sigm_div(g[j] + hr);
+        const float z = sigm_div(g[H + j] + hz);
         const float n = tanhf(fmaf(r, hn, g[2 * H + j]));
         const float hv = fmaf(z, a - n, n);
         hbuf[(int64_t)v * ld_h + j] = hv;

@@ -180,8 +180,6 @@ __device__ __forceinline__ float t_wave_total(float v) {
 }
 
 // gate non-linearities on the hardware exp / rcp (as dataflow.hip): sigma(x) = 1 / (1 + e^-x), tanh(x) = 1 - 2 / (1 + e^2x)
-__device__ __forceinline__ float t_sigm(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
-__device__ __forceinline__ float t_tanh(float x) { return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __expf(2.0f * x)); }
 
 // passes of 4 rows a tile of nr live rows takes on the 4x4x1 products (0: the 16-column products)
 __device__ __forceinline__ int t_thin_passes(int nr) { return nr <= T_THIN_ROWS ? (nr + 3) >> 2 : 0; }
@@ -688,12 +686,12 @@ __device__ __forceinline__ void tile_body(const int32_t* __restrict__ plan, cons
         sums(0, gi, gh);
         {
             const float4 c = *reinterpret_cast<const float4*>(cst + 4 * q);
-            rg = make_float4(t_sigm((gi.x + gh.x) + c.x), t_sigm((gi.y + gh.y) + c.y), t_sigm((gi.z + gh.z) + c.z), t_sigm((gi.w + gh.w) + c.w));
+            rg = make_float4(sigm_rcp((gi.x + gh.x) + c.x), sigm_rcp((gi.y + gh.y) + c.y), sigm_rcp((gi.z + gh.z) + c.z), sigm_rcp((gi.w + gh.w) + c.w));
         }
         sums(1, gi, gh);
         {
             const float4 c = *reinterpret_cast<const float4*>(cst + TU + 4 * q);
-            zg = make_float4(t_sigm((gi.x + gh.x) + c.x), t_sigm((gi.y + gh.y) + c.y), t_sigm((gi.z + gh.z) + c.z), t_sigm((gi.w + gh.w) + c.w));
+            zg = make_float4(sigm_rcp((gi.x + gh.x) + c.x), sigm_rcp((gi.y + gh.y) + c.y), sigm_rcp((gi.z + gh.z) + c.z), sigm_rcp((gi.w + gh.w) + c.w));
         }
         sums(2, gi, gh);
         asm volatile("" : "+v"(gi.x), "+v"(gi.y), "+v"(gi.z), "+v"(gi.w), "+v"(gh.x), "+v"(gh.y), "+v"(gh.z), "+v"(gh.w));   // (the sums above are complete)
@@ -703,8 +701,8 @@ __device__ __forceinline__ void tile_body(const int32_t* __restrict__ plan, cons
             const float4 ci = *reinterpret_cast<const float4*>(cst + 2 * TU + 4 * q), ch = *reinterpret_cast<const float4*>(cst + 3 * TU + 4 * q);
             const float4 a4 = *reinterpret_cast<const float4*>(asv + (slot3 * TR + n) * TU + 4 * q);
             const float4 wk = *reinterpret_cast<const float4*>(cst + 4 * TU + 4 * q);
-            const float n0 = t_tanh(fmaf(rg.x, gh.x + ch.x, gi.x + ci.x)), n1 = t_tanh(fmaf(rg.y, gh.y + ch.y, gi.y + ci.y)),
-                        n2 = t_tanh(fmaf(rg.z, gh.z + ch.z, gi.z + ci.z)), n3 = t_tanh(fmaf(rg.w, gh.w + ch.w, gi.w + ci.w));
+            const float n0 = tanh_rcp(fmaf(rg.x, gh.x + ch.x, gi.x + ci.x)), n1 = tanh_rcp(fmaf(rg.y, gh.y + ch.y, gi.y + ci.y)),
+                        n2 = tanh_rcp(fmaf(rg.z, gh.z + ch.z, gi.z + ci.z)), n3 = tanh_rcp(fmaf(rg.w, gh.w + ch.w, gi.w + ci.w));
             hv = make_float4(fmaf(zg.x, a4.x - n0, n0), fmaf(zg.y, a4.y - n1, n1), fmaf(zg.z, a4.z - n2, n2), fmaf(zg.w, a4.w - n3, n3));
             part = fmaf(wk.w, hv.w, fmaf(wk.z, hv.z, fmaf(wk.y, hv.y, wk.x * hv.x)));
         }

@@ -179,7 +179,6 @@ struct VJobArgs {
     int r0[VMAXC], r1[VMAXC];
 };
 
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + __expf(-x)); }
 
 // Workgroup = (4 * RPT rows, 64 output units); thread = (unit, row group of RPT rows).  G = 3: GRU gates r,z,n;
 // G = 1: plain linear map.  LDS: the rows' inputs and aggregates, zero-padded to a multiple of 4 floats.
@@ -259,8 +258,8 @@ __global__ void __launch_bounds__(256) variant_cell_kernel(const int32_t* __rest
             const int H = J.out_dim;
             const float bi_r = J.b_in[unit], bi_z = J.b_in[H + unit], bi_n = J.b_in[2 * H + unit];
             const float bh_r = J.b_agg[unit], bh_z = J.b_agg[H + unit], bh_n = J.b_agg[2 * H + unit];
-            const float rr = sigmoidf_(ai[r][0] + bi_r + ah[r][0] + bh_r);
-            const float zz = sigmoidf_(ai[r][1] + bi_z + ah[r][1] + bh_z);
+            const float rr = sigm_div_fexp(ai[r][0] + bi_r + ah[r][0] + bh_r);
+            const float zz = sigm_div_fexp(ai[r][1] + bi_z + ah[r][1] + bh_z);
             const float nn = tanhf(ai[r][2] + bi_n + rr * (ah[r][2] + bh_n));
             const float hp = (dag && unit < J.agg_dim) ? s_ag[row * dag + unit] : 0.f;
             res = (1.f - zz) * nn + zz * hp;
@@ -357,8 +356,8 @@ __global__ void __launch_bounds__(256) variant_cell_thin_kernel(const int32_t* _
     float res;
     if constexpr (G == 3) {
         const int H = J.out_dim;
-        const float rr = sigmoidf_(p[0] + J.b_in[unit] + p[3] + J.b_agg[unit]);
-        const float zz = sigmoidf_(p[1] + J.b_in[H + unit] + p[4] + J.b_agg[H + unit]);
+        const float rr = sigm_div_fexp(p[0] + J.b_in[unit] + p[3] + J.b_agg[unit]);
+        const float zz = sigm_div_fexp(p[1] + J.b_in[H + unit] + p[4] + J.b_agg[H + unit]);
         const float nn = tanhf(p[2] + J.b_in[2 * H + unit] + rr * (p[5] + J.b_agg[2 * H + unit]));
         const float hp = (dag && unit < J.agg_dim) ? s_ag[row * dag + unit] : 0.f;
         res = (1.f - zz) * nn + zz * hp;

@@ -41,7 +41,6 @@ namespace {
 
 constexpr int VBC = 8;   // cells per launch (the step table travels as a kernel argument: 8 x ~270 bytes)
 
-__device__ __forceinline__ float vb_sigm(float x) { return 1.0f / (1.0f + expf(-x)); }
 
 __device__ __forceinline__ float vb_edge_term(const float* __restrict__ m, const float* __restrict__ v, int k, int R,
                                               const float* __restrict__ attr) {
@@ -82,7 +81,7 @@ __global__ void __launch_bounds__(256) vb_pull_kernel(const int32_t* __restrict_
             float aP = 0.f, aM = 0.f, eg[2] = {0.f, 0.f}, em[2] = {0.f, 0.f};
             for (int e = eb; e < ee; ++e) {
                 const float* attr = ea + (int64_t)e * R;
-                const float gt = vb_sigm(P + vb_edge_term(C.edge_mat0, C.edge_vec0, k, R, attr));
+                const float gt = sigm_div(P + vb_edge_term(C.edge_mat0, C.edge_vec0, k, R, attr));
                 const float mp = M + vb_edge_term(C.edge_mat1, C.edge_vec1, k, R, attr);
                 const float dw = C.da[(int64_t)col[e] * ld + k];
                 const float dg = dw * mp * gt * (1.0f - gt), dm = dw * gt;
@@ -198,7 +197,7 @@ __global__ void __launch_bounds__(256) vb_gru_kernel(const int32_t* __restrict__
         const float* gi = C.gi + (int64_t)v * H3;
         const float* gh = C.gh + (int64_t)v * H3;
         const float ghn = gh[2 * ld + k];
-        const float rr = vb_sigm(gi[k] + gh[k]), zz = vb_sigm(gi[ld + k] + gh[ld + k]);
+        const float rr = sigm_div(gi[k] + gh[k]), zz = sigm_div(gi[ld + k] + gh[ld + k]);
         const float nn = tanhf(gi[2 * ld + k] + rr * ghn);
         const float G = C.g[(int64_t)v * ld + k], av = C.a[(int64_t)v * ld + k];
         const float dn = G * (1.0f - zz) * (1.0f - nn * nn);
