@@ -210,23 +210,26 @@ class IpropLayer(C.Structure):
 
 MAX_STACKED = 8   # DAGNN_MAX_STACKED
 DVAE_MAX_N = 32   # DAGNN_DVAE_MAX_N
+DVAE_AGG_ATTN_H, DVAE_AGG_GATED_SUM, DVAE_AGG_ATTN_X = 0, 1, 2   # DAGNN_DVAE_AGG_*
+
+# what dagnn_dvae_decode_args and dagnn_dvae_sample_args declare alike: the decoder's weights, and the block appended for gated_sum
+_DVAE_WEIGHTS = [("w_ih", C.c_void_p * MAX_STACKED), ("w_hh", C.c_void_p * MAX_STACKED), ("b_ih", C.c_void_p * MAX_STACKED),
+                 ("b_hh", C.c_void_p * MAX_STACKED), ("w_key", C.c_void_p), ("vid_bias", C.c_void_p),
+                 ("av_w1", C.c_void_p), ("av_b1", C.c_void_p), ("av_w2", C.c_void_p), ("av_b2", C.c_void_p),
+                 ("ae_w1", C.c_void_p), ("ae_b1", C.c_void_p), ("ae_w2", C.c_void_p), ("ae_b2", C.c_void_p)]
+_DVAE_AGG = [("agg", C.c_int), ("gate_w", C.c_void_p), ("gate_b", C.c_void_p), ("mapper_w", C.c_void_p)]
 
 
 class DvaeDecodeArgs(C.Structure):
     _fields_ = [("B", C.c_int64), ("n", C.c_int), ("hs", C.c_int), ("L", C.c_int), ("nvt", C.c_int), ("start_type", C.c_int),
                 ("bn", C.c_int), ("edge_hidden", C.c_int), ("vertex_hidden", C.c_int),
-                ("types", C.c_void_p), ("preds", C.c_void_p), ("h0", C.c_void_p),
-                ("w_ih", C.c_void_p * MAX_STACKED), ("w_hh", C.c_void_p * MAX_STACKED), ("b_ih", C.c_void_p * MAX_STACKED),
-                ("b_hh", C.c_void_p * MAX_STACKED), ("w_key", C.c_void_p), ("vid_bias", C.c_void_p),
-                ("av_w1", C.c_void_p), ("av_b1", C.c_void_p), ("av_w2", C.c_void_p), ("av_b2", C.c_void_p),
-                ("ae_w1", C.c_void_p), ("ae_b1", C.c_void_p), ("ae_w2", C.c_void_p), ("ae_b2", C.c_void_p),
-                ("ll", C.c_void_p), ("saved", C.c_void_p), ("saved_bytes", C.c_size_t),
-                ("agg", C.c_int), ("gate_w", C.c_void_p), ("gate_b", C.c_void_p), ("mapper_w", C.c_void_p)]
+                ("types", C.c_void_p), ("preds", C.c_void_p), ("h0", C.c_void_p)] + _DVAE_WEIGHTS + \
+               [("ll", C.c_void_p), ("saved", C.c_void_p), ("saved_bytes", C.c_size_t)] + _DVAE_AGG
 
 
 class DvaeDecodeArgsTyped(DvaeDecodeArgs):
-    """dagnn_dvae_decode_args as the header has it today: the layout above (agg = 0 / 1, which the library still takes - fields
-    are only ever appended, and one is read only under the `agg` value that introduced it) plus the type-keyed table (agg = 2)."""
+    """dagnn_dvae_decode_args as the header has it today: the layout above (attn_h / gated_sum, which the library still takes - fields
+    are only ever appended, and one is read only under the `agg` value that introduced it) plus the type-keyed table (DVAE_AGG_ATTN_X)."""
     _fields_ = [("key_type", C.c_void_p)]
 
 
@@ -241,24 +244,19 @@ class DvaeDecodeGrads(C.Structure):
 
 
 class DvaeDecodeGradsTyped(DvaeDecodeGrads):
-    _fields_ = [("d_key_type", C.c_void_p)]   # agg = 2
+    _fields_ = [("d_key_type", C.c_void_p)]   # DVAE_AGG_ATTN_X
 
 
 class DvaeSampleArgs(C.Structure):
     _fields_ = [("G", C.c_int64), ("B", C.c_int64), ("n", C.c_int), ("hs", C.c_int), ("L", C.c_int), ("nvt", C.c_int),
                 ("start_type", C.c_int), ("end_type", C.c_int), ("bn", C.c_int), ("stochastic", C.c_int),
-                ("edge_hidden", C.c_int), ("vertex_hidden", C.c_int), ("h0", C.c_void_p),
-                ("w_ih", C.c_void_p * MAX_STACKED), ("w_hh", C.c_void_p * MAX_STACKED), ("b_ih", C.c_void_p * MAX_STACKED),
-                ("b_hh", C.c_void_p * MAX_STACKED), ("w_key", C.c_void_p), ("vid_bias", C.c_void_p),
-                ("av_w1", C.c_void_p), ("av_b1", C.c_void_p), ("av_w2", C.c_void_p), ("av_b2", C.c_void_p),
-                ("ae_w1", C.c_void_p), ("ae_b1", C.c_void_p), ("ae_w2", C.c_void_p), ("ae_b2", C.c_void_p),
-                ("u_type", C.c_void_p), ("u_edge", C.c_void_p), ("types", C.c_void_p), ("preds", C.c_void_p),
-                ("nv", C.c_void_p), ("states", C.c_void_p), ("work", C.c_void_p), ("work_bytes", C.c_size_t),
-                ("agg", C.c_int), ("gate_w", C.c_void_p), ("gate_b", C.c_void_p), ("mapper_w", C.c_void_p)]
+                ("edge_hidden", C.c_int), ("vertex_hidden", C.c_int), ("h0", C.c_void_p)] + _DVAE_WEIGHTS + \
+               [("u_type", C.c_void_p), ("u_edge", C.c_void_p), ("types", C.c_void_p), ("preds", C.c_void_p),
+                ("nv", C.c_void_p), ("states", C.c_void_p), ("work", C.c_void_p), ("work_bytes", C.c_size_t)] + _DVAE_AGG
 
 
 class DvaeSampleArgsTyped(DvaeSampleArgs):
-    _fields_ = [("key_type", C.c_void_p)]   # agg = 2; see DvaeDecodeArgsTyped
+    _fields_ = [("key_type", C.c_void_p)]   # DVAE_AGG_ATTN_X; see DvaeDecodeArgsTyped
 
 
 DVAE_ENAS, DVAE_BN = 0, 1                        # DAGNN_DVAE_ENAS / DAGNN_DVAE_BN

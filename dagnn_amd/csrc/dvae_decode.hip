@@ -28,7 +28,7 @@
 // one entry of the table key_type [nvt] and the values stay the layer-0 states: the same launches and saved records as
 // attn_h with the score product replaced by a lookup.  In reverse the keys carry no state gradient, and d key_type[t]
 // pulls the score gradients of every slot whose predecessor has type t (one workgroup per type, fixed order).
-#include "common.h"
+#include "dvae_common.h"
 
 namespace {
 
@@ -146,65 +146,54 @@ struct DDLayout {
     int64_t RM, wgm, xmsg, mpre, mgate, mmap, msg, dmpre;
 };
 
-inline int64_t dd_take(int64_t& at, int64_t count) {
-    const int64_t off = at;
-    at += (count + 63) / 64 * 64;
-    return off;
-}
-
 bool dd_layout(const dagnn_dvae_decode_args* a, DDLayout& o) {
-    if (!a || a->B <= 0 || a->n < 2 || a->n > DAGNN_DVAE_MAX_N || a->hs <= 0 || a->L < 1 || a->L > DAGNN_MAX_STACKED ||
-        a->nvt <= 0 || a->nvt > DAGNN_DVAE_MAX_TYPES || a->start_type < 0 || a->start_type >= a->nvt || a->edge_hidden <= 0 ||
-        a->vertex_hidden <= 0 || (a->bn != 0 && a->bn != 1) || a->agg < 0 || a->agg > 2)
-        return false;
-    if (a->agg == 1 && (a->bn || !a->gate_w || !a->gate_b || !a->mapper_w)) return false;
-    if (a->agg == 2 && (!a->bn || !a->key_type)) return false;
+    if (!a || a->B <= 0 || !dvae_decoder_ok(a)) return false;
     o.B = a->B; o.n = a->n; o.H = a->hs; o.L = a->L; o.nvt = a->nvt;
-    o.gated = a->agg == 1;
+    o.gated = a->agg == DAGNN_DVAE_AGG_GATED_SUM;
     o.ein = (a->bn ? 3 : 2) * a->hs; o.E1 = a->edge_hidden; o.V1 = a->vertex_hidden;
     o.NU = dd_U(o.n);
     o.RU = o.NU * o.B; o.RE = dd_E(o.n) * o.B; o.RV = (int64_t)(o.n - 1) * o.B;
     const int64_t H = o.H, maxM = (int64_t)o.n * o.B;
     if (o.RU * 4 * H >= ((int64_t)1 << 40) || o.RE * (o.E1 > o.ein ? o.E1 : o.ein) >= ((int64_t)1 << 40)) return false;
     int64_t at = 0;
-    o.hagg = dd_take(at, o.RU * H);
-    for (int l = 0; l < o.L; ++l) { o.h[l] = dd_take(at, o.RU * H); o.gates[l] = dd_take(at, o.RU * 4 * H); }
-    o.alpha = dd_take(at, o.RU * o.n);
-    o.pid = dd_take(at, o.RU * o.n);
-    o.pcount = dd_take(at, o.NU);
-    o.gi = dd_take(at, maxM * 3 * H);
-    o.gh = dd_take(at, maxM * 3 * H);
-    o.xe = dd_take(at, o.RE * o.ein);
-    o.y_e = dd_take(at, o.RE);
-    o.hid_e = dd_take(at, o.RE * o.E1);
-    o.s_e = dd_take(at, o.RE);
-    o.ll_e = dd_take(at, o.RE);
-    o.hg = dd_take(at, o.RV * H);
-    o.hid_v = dd_take(at, o.RV * o.V1);
-    o.logit_v = dd_take(at, o.RV * o.nvt);
-    o.ll_v = dd_take(at, o.RV);
+    o.hagg = dvae_take(at, o.RU * H);
+    for (int l = 0; l < o.L; ++l) { o.h[l] = dvae_take(at, o.RU * H); o.gates[l] = dvae_take(at, o.RU * 4 * H); }
+    o.alpha = dvae_take(at, o.RU * o.n);
+    o.pid = dvae_take(at, o.RU * o.n);
+    o.pcount = dvae_take(at, o.NU);
+    o.gi = dvae_take(at, maxM * 3 * H);
+    o.gh = dvae_take(at, maxM * 3 * H);
+    o.xe = dvae_take(at, o.RE * o.ein);
+    o.y_e = dvae_take(at, o.RE);
+    o.hid_e = dvae_take(at, o.RE * o.E1);
+    o.s_e = dvae_take(at, o.RE);
+    o.ll_e = dvae_take(at, o.RE);
+    o.hg = dvae_take(at, o.RV * H);
+    o.hid_v = dvae_take(at, o.RV * o.V1);
+    o.logit_v = dvae_take(at, o.RV * o.nvt);
+    o.ll_v = dvae_take(at, o.RV);
     o.RM = (int64_t)(o.n - 1) * o.B;
     if (o.gated) {
-        o.wgm = dd_take(at, 2 * H * H);
-        o.xmsg = dd_take(at, o.RM * H);
-        o.mpre = dd_take(at, o.RM * 2 * H);
-        o.mgate = dd_take(at, o.RM * H);
-        o.mmap = dd_take(at, o.RM * H);
-        o.msg = dd_take(at, o.RM * H);
+        o.wgm = dvae_take(at, 2 * H * H);
+        o.xmsg = dvae_take(at, o.RM * H);
+        o.mpre = dvae_take(at, o.RM * 2 * H);
+        o.mgate = dvae_take(at, o.RM * H);
+        o.mmap = dvae_take(at, o.RM * H);
+        o.msg = dvae_take(at, o.RM * H);
     }
     o.saved_end = at;
     at = 0;
-    o.dlog_e = dd_take(at, o.RE);
-    o.dpre = dd_take(at, o.RE * o.E1);
-    o.dxe = dd_take(at, o.RE * o.ein);
-    o.dlog_v = dd_take(at, o.RV * o.nvt);
-    o.dhid_v = dd_take(at, o.RV * o.V1);
-    o.dhg = dd_take(at, o.RV * H);
-    for (int l = 0; l < o.L; ++l) o.dH[l] = dd_take(at, o.RU * H);
-    o.dhagg = dd_take(at, o.RU * H);
-    for (int l = 0; l < o.L; ++l) { o.dGi[l] = dd_take(at, o.RU * 3 * H); o.dGh[l] = dd_take(at, o.RU * 3 * H); }
-    o.ds = dd_take(at, o.RU * o.n);
-    if (o.gated) o.dmpre = dd_take(at, o.RM * 2 * H);
+    o.dlog_e = dvae_take(at, o.RE);
+    o.dpre = dvae_take(at, o.RE * o.E1);
+    o.dxe = dvae_take(at, o.RE * o.ein);
+    o.dlog_v = dvae_take(at, o.RV * o.nvt);
+    o.dhid_v = dvae_take(at, o.RV * o.V1);
+    o.dhg = dvae_take(at, o.RV * H);
+    for (int l = 0; l < o.L; ++l) o.dH[l] = dvae_take(at, o.RU * H);
+    o.dhagg = dvae_take(at, o.RU * H);
+    for (int l = 0; l < o.L; ++l) { o.dGi[l] = dvae_take(at, o.RU * 3 * H); o.dGh[l] = dvae_take(at, o.RU * 3 * H); }
+    o.ds = dvae_take(at, o.RU * o.n);
+    if (o.gated) o.dmpre = dvae_take(at, o.RM * 2 * H);
     o.work_end = at;
     return true;
 }
@@ -701,13 +690,9 @@ int dd_colsum(hipStream_t st, const float* A, int64_t lda, int64_t R, int N, con
         if (rc_ != DAGNN_OK) return rc_; \
     } while (0)
 
-bool dd_weights_ok(const dagnn_dvae_decode_args* a) {
-    if (!a->types || !a->preds || !a->h0 || (a->agg == 0 && !a->w_key) || (a->agg == 2 && !a->key_type) || !a->ll || !a->saved || !a->av_w1 || !a->av_b1 || !a->av_w2 ||
-        !a->av_b2 || !a->ae_w1 || !a->ae_b1 || !a->ae_w2 || !a->ae_b2)
-        return false;
-    for (int l = 0; l < a->L; ++l)
-        if (!a->w_ih[l] || !a->w_hh[l] || !a->b_ih[l] || !a->b_hh[l]) return false;
-    return true;
+// (after dd_layout, which has established key_type for attn_x)
+bool dd_pointers_ok(const dagnn_dvae_decode_args* a) {
+    return dvae_weights_ok(a) && a->types && a->preds && a->ll && a->saved;
 }
 
 }  // namespace
@@ -724,7 +709,7 @@ extern "C" size_t dagnn_dvae_decode_work_bytes(const dagnn_dvae_decode_args* a) 
 
 extern "C" int dagnn_dvae_decode_forward(const dagnn_dvae_decode_args* a, void* stream) {
     DDLayout o;
-    if (!dd_layout(a, o) || !dd_weights_ok(a)) return DAGNN_EINVAL;
+    if (!dd_layout(a, o) || !dd_pointers_ok(a)) return DAGNN_EINVAL;
     if (a->saved_bytes < (size_t)o.saved_end * sizeof(float)) return DAGNN_ENOSPC;
     hipStream_t st = (hipStream_t)stream;
     float* S = a->saved;
@@ -744,7 +729,7 @@ extern "C" int dagnn_dvae_decode_forward(const dagnn_dvae_decode_args* a, void* 
         if (o.gated) {
             hipLaunchKernelGGL(dd_gated_agg_kernel, dim3(hb, (unsigned)M), dim3(DD_T), 0, st, v, n, B, (int)H, a->preds, S + o.msg,
                                a->h0, S + o.hagg);
-        } else if (a->agg == 2) {
+        } else if (a->agg == DAGNN_DVAE_AGG_ATTN_X) {
             hipLaunchKernelGGL(dd_agg_kernel<true>, dim3((unsigned)(v == 0 ? 1 : v + 1), (unsigned)B), dim3(DD_T), 0, st, v, n, B, (int)H,
                                a->preds, S + o.h[0], nullptr, nullptr, a->h0, S + o.hagg, S + o.alpha, pid, pcount, a->key_type,
                                a->types, o.nvt, a->start_type);
@@ -794,9 +779,9 @@ extern "C" int dagnn_dvae_decode_forward(const dagnn_dvae_decode_args* a, void* 
 
 extern "C" int dagnn_dvae_decode_backward(const dagnn_dvae_decode_args* a, const dagnn_dvae_decode_grads* g, void* stream) {
     DDLayout o;
-    if (!dd_layout(a, o) || !dd_weights_ok(a) || !g || !g->g_res || !g->work || !g->d_h0 || (a->agg == 0 && !g->d_w_key) || (a->agg == 2 && !g->d_key_type) || !g->d_av_w1 ||
+    if (!dd_layout(a, o) || !dd_pointers_ok(a) || !g || !g->g_res || !g->work || !g->d_h0 || (a->agg == DAGNN_DVAE_AGG_ATTN_H && !g->d_w_key) || (a->agg == DAGNN_DVAE_AGG_ATTN_X && !g->d_key_type) || !g->d_av_w1 ||
         !g->d_av_b1 || !g->d_av_w2 || !g->d_av_b2 || !g->d_ae_w1 || !g->d_ae_b1 || !g->d_ae_w2 || !g->d_ae_b2 ||
-        (a->agg == 0 && a->vid_bias && !g->d_vid_bias) || (a->agg == 1 && (!g->d_gate_w || !g->d_gate_b || !g->d_mapper_w)))
+        (a->agg == DAGNN_DVAE_AGG_ATTN_H && a->vid_bias && !g->d_vid_bias) || (a->agg == DAGNN_DVAE_AGG_GATED_SUM && (!g->d_gate_w || !g->d_gate_b || !g->d_mapper_w)))
         return DAGNN_EINVAL;
     for (int l = 0; l < a->L; ++l)
         if (!g->d_w_ih[l] || !g->d_w_hh[l] || !g->d_b_ih[l] || !g->d_b_hh[l]) return DAGNN_EINVAL;
@@ -844,7 +829,7 @@ extern "C" int dagnn_dvae_decode_backward(const dagnn_dvae_decode_args* a, const
         }
         if (v > 0 && !o.gated) {
             hipLaunchKernelGGL(dd_agg_bwd_kernel, dim3((unsigned)B), dim3(DD_T), 0, st, v, n, B, (int)H, S + o.h[0],
-                               a->agg == 2 ? nullptr : a->w_key,
+                               a->agg == DAGNN_DVAE_AGG_ATTN_X ? nullptr : a->w_key,
                                S + o.alpha, pid, pcount, W + o.dhagg, W + o.ds, W + o.dH[0]);
             DAGNN_CHECK_LAUNCH();
         }
@@ -870,7 +855,7 @@ extern "C" int dagnn_dvae_decode_backward(const dagnn_dvae_decode_args* a, const
                            (int)H, W + o.dmpre, g->d_gate_w, g->d_mapper_w);
         DAGNN_CHECK_LAUNCH();
         DD_TRY(dd_colsum(st, W + o.dmpre, 2 * H, o.RM, (int)H, nullptr, g->d_gate_b));
-    } else if (a->agg == 2) {
+    } else if (a->agg == DAGNN_DVAE_AGG_ATTN_X) {
         hipLaunchKernelGGL(dd_type_key_grad_kernel, dim3((unsigned)o.nvt), dim3(DD_T), 0, st, B, n, o.nvt, a->start_type, o.NU,
                            a->types, pid, W + o.ds, g->d_key_type);
         DAGNN_CHECK_LAUNCH();

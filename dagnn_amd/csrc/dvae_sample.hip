@@ -26,7 +26,7 @@
 //
 // agg = attn_x (BN): the key of a vertex is one entry of the table key_type [nvt], looked up by its type when the vertex is
 // final; the padded soft-max launch then serves unchanged.
-#include "common.h"
+#include "dvae_common.h"
 
 namespace {
 
@@ -46,20 +46,10 @@ struct DSLayout {
     int64_t wgm, mpre, msg;
 };
 
-inline int64_t ds_take(int64_t& at, int64_t count) {
-    const int64_t off = at;
-    at += (count + 63) / 64 * 64;
-    return off;
-}
-
 bool ds_layout(const dagnn_dvae_sample_args* a, DSLayout& o) {
-    if (!a || a->G <= 0 || a->B <= 0 || a->n < 2 || a->n > DAGNN_DVAE_MAX_N || a->hs <= 0 || a->L < 1 ||
-        a->L > DAGNN_MAX_STACKED || a->nvt <= 0 || a->nvt > DAGNN_DVAE_MAX_TYPES || a->start_type < 0 ||
-        a->start_type >= a->nvt || a->end_type < 0 || a->end_type >= a->nvt || (a->bn != 0 && a->bn != 1) ||
-        (a->stochastic != 0 && a->stochastic != 1) || a->edge_hidden <= 0 || a->vertex_hidden <= 0 || a->agg < 0 || a->agg > 2)
+    if (!a || a->G <= 0 || a->B <= 0 || !dvae_decoder_ok(a) || a->end_type < 0 || a->end_type >= a->nvt ||
+        (a->stochastic != 0 && a->stochastic != 1))
         return false;
-    if (a->agg == 1 && (a->bn || !a->gate_w || !a->gate_b || !a->mapper_w)) return false;
-    if (a->agg == 2 && (!a->bn || !a->key_type)) return false;
     if (a->G > ((int64_t)1 << 31) || a->B > ((int64_t)1 << 31) || a->G * a->B > ((int64_t)1 << 30) || a->hs > (1 << 20) ||
         a->edge_hidden > (1 << 22) || a->vertex_hidden > (1 << 22))
         return false;
@@ -71,32 +61,32 @@ bool ds_layout(const dagnn_dvae_sample_args* a, DSLayout& o) {
         (int64_t)n * HP > INT32_MAX || (int64_t)(n - 1) * o.E1 > INT32_MAX || H3 * o.L > INT32_MAX)
         return false;
     int64_t at = 0;
-    o.w_hh_all = ds_take(at, o.L * H3 * HP);
-    o.b_hh_all = ds_take(at, o.L * H3);
-    for (int l = 0; l < o.L; ++l) o.w_ih[l] = l == 0 ? 0 : ds_take(at, H3 * HP);
-    o.w_left = ds_take(at, (int64_t)o.E1 * HP);
-    o.w_mid = ds_take(at, (int64_t)o.E1 * HP);
-    o.w_h0 = a->bn ? ds_take(at, (int64_t)o.E1 * HP) : 0;
-    o.w_v1 = ds_take(at, (int64_t)o.V1 * HP);
-    o.h0p = ds_take(at, R * HP);
-    for (int l = 0; l < o.L; ++l) o.h[l] = ds_take(at, R * n * HP);
-    o.hagg = ds_take(at, R * HP);
-    o.gh = ds_take(at, R * H3 * o.L);
-    o.gi = ds_take(at, R * H3);
-    o.etmp = ds_take(at, R * o.E1);
-    o.aedge = ds_take(at, R * (n - 1) * o.E1);
-    o.c0 = a->bn ? ds_take(at, R * o.E1) : 0;
-    o.key = ds_take(at, R * n);
-    o.hg = ds_take(at, R * HP);
-    o.hidv = ds_take(at, R * o.V1);
-    o.fin = ds_take(at, R);
-    o.succ = ds_take(at, R);
-    o.pbuf = ds_take(at, o.NE * o.G);
-    o.gated = a->agg == 1;
+    o.w_hh_all = dvae_take(at, o.L * H3 * HP);
+    o.b_hh_all = dvae_take(at, o.L * H3);
+    for (int l = 0; l < o.L; ++l) o.w_ih[l] = l == 0 ? 0 : dvae_take(at, H3 * HP);
+    o.w_left = dvae_take(at, (int64_t)o.E1 * HP);
+    o.w_mid = dvae_take(at, (int64_t)o.E1 * HP);
+    o.w_h0 = a->bn ? dvae_take(at, (int64_t)o.E1 * HP) : 0;
+    o.w_v1 = dvae_take(at, (int64_t)o.V1 * HP);
+    o.h0p = dvae_take(at, R * HP);
+    for (int l = 0; l < o.L; ++l) o.h[l] = dvae_take(at, R * n * HP);
+    o.hagg = dvae_take(at, R * HP);
+    o.gh = dvae_take(at, R * H3 * o.L);
+    o.gi = dvae_take(at, R * H3);
+    o.etmp = dvae_take(at, R * o.E1);
+    o.aedge = dvae_take(at, R * (n - 1) * o.E1);
+    o.c0 = a->bn ? dvae_take(at, R * o.E1) : 0;
+    o.key = dvae_take(at, R * n);
+    o.hg = dvae_take(at, R * HP);
+    o.hidv = dvae_take(at, R * o.V1);
+    o.fin = dvae_take(at, R);
+    o.succ = dvae_take(at, R);
+    o.pbuf = dvae_take(at, o.NE * o.G);
+    o.gated = a->agg == DAGNN_DVAE_AGG_GATED_SUM;
     if (o.gated) {
-        o.wgm = ds_take(at, 2 * (int64_t)o.hs * HP);
-        o.mpre = ds_take(at, R * 2 * o.hs);
-        o.msg = ds_take(at, R * n * o.hs);
+        o.wgm = dvae_take(at, 2 * (int64_t)o.hs * HP);
+        o.mpre = dvae_take(at, R * 2 * o.hs);
+        o.msg = dvae_take(at, R * n * o.hs);
     }
     o.end = at;
     return true;
@@ -406,12 +396,7 @@ int ds_pad(hipStream_t st, int64_t rows, int cols, const float* src, int64_t lds
 }
 
 bool ds_pointers_ok(const dagnn_dvae_sample_args* a) {
-    if (!a->h0 || (a->agg == 0 && !a->w_key) || !a->av_w1 || !a->av_b1 || !a->av_w2 || !a->av_b2 || !a->ae_w1 || !a->ae_b1 || !a->ae_w2 ||
-        !a->ae_b2 || !a->types || !a->preds || !a->nv || !a->work || (a->stochastic && (!a->u_type || !a->u_edge)))
-        return false;
-    for (int l = 0; l < a->L; ++l)
-        if (!a->w_ih[l] || !a->w_hh[l] || !a->b_ih[l] || !a->b_hh[l]) return false;
-    return true;
+    return dvae_weights_ok(a) && a->types && a->preds && a->nv && a->work && (!a->stochastic || (a->u_type && a->u_edge));
 }
 
 }  // namespace
@@ -479,7 +464,7 @@ extern "C" int dagnn_dvae_sample(const dagnn_dvae_sample_args* a, void* stream) 
             DS_TRY(ds_gemm(st, R, 2 * hs, HP, W + o.h[0] + (int64_t)idx * HP, ldh, W + o.wgm, nullptr, W + o.mpre, 2 * hs));
             hipLaunchKernelGGL(ds_gated_msg_kernel, dim3(ds_blocks(R * hs)), dim3(DS_T), 0, st, R, n, hs, idx, W + o.mpre, a->gate_w,
                                a->gate_b, a->mapper_w, W + o.msg);
-        } else if (a->agg == 2) {
+        } else if (a->agg == DAGNN_DVAE_AGG_ATTN_X) {
             hipLaunchKernelGGL(ds_type_key_kernel, dim3(ds_blocks(R)), dim3(DS_T), 0, st, R, n, o.nvt, idx, a->types, a->key_type,
                                W + o.key);
         } else {

@@ -15,7 +15,7 @@ from __future__ import annotations
 import collections
 import copy
 from collections import namedtuple
-from typing import List
+from typing import List, NamedTuple, Optional
 
 import numpy as np
 
@@ -558,51 +558,68 @@ def select_decoded(decoded, data_type, nvt, start_type, end_type, n_nodes=None, 
     return SelectedDense(t(valid), t(pick), t(n_valid), t(n_same), torch.from_numpy(keys))
 
 
+class _Decoder(NamedTuple):
+    """What the D-VAE decoder reads, stated once per call by `_DvaeDagnn._decoder` for its HIP consumers: the teacher-forced
+    loss (`engine.DvaeDecode`), the sampling decode (`engine.dvae_sample`) and the single-vertex step
+    (`engine.iprop_step`).  `engine._marshal_decoder` checks every shape against the dimensions here."""
+    n: int                # max_n
+    nvt: int
+    hs: int
+    L: int                # stacked grud cells
+    start_type: int
+    end_type: int
+    bn: bool
+    agg: int              # _lib.DVAE_AGG_*
+    # the differentiable parameters, in the order `_DecodeLoss` takes them and returns their gradients: the aggregator's
+    # (attn_h / attn_x: attn_lin.weight; gated_sum: gate_forward.0.0.{weight,bias}, mapper_forward.0.0.weight), 4 per
+    # grud cell, add_vertex.{0,2}.{weight,bias}, add_edge.{0,2}.{weight,bias}
+    params: list
+    cells: list           # per layer (w_ih, w_hh, b_ih, b_hh)
+    av: list              # add_vertex (w1, b1, w2, b2)
+    ae: list              # add_edge (w1, b1, w2, b2)
+    # what the library reads of the aggregator - views, no copies: attn_h w_key [hs] and (NA) vid_bias [n]; attn_x key_type
+    # [nvt]; gated_sum gate = (gate_w, gate_b, mapper_w); the others None
+    w_key: Optional[torch.Tensor]
+    vid_bias: Optional[torch.Tensor]
+    key_type: Optional[torch.Tensor]
+    gate: Optional[list]
+    # columns of the attn_lin.weight gradient where the key (attn_x: the type table) and the vertex-id gradients land
+    key_off: int
+    vid_off: Optional[int]
+
+
 class _DecodeLoss(torch.autograd.Function):
     """`res` of `DVAE_PYG.loss()` (the negative log-likelihood of the true graphs under teacher forcing) as ONE call of
     `dagnn_dvae_decode_forward`; its gradients as ONE call of `dagnn_dvae_decode_backward`.  Inputs after the fixed
-    ones: the aggregator's tensors (attn_h / attn_x: attn_lin.weight; gated_sum: gate_forward.0.0.{weight,bias},
-    mapper_forward.0.0.weight), then 4 tensors per grud cell, add_vertex.{0,2}.{weight,bias}, add_edge.{0,2}.{weight,bias}."""
+    ones: `dec.params`."""
 
     @staticmethod
-    def forward(ctx, spec, types, preds, h0, *params):
-        dec = _make_decode(spec, types, preds, h0, params)
-        ll = dec.forward()
-        ctx.dec, ctx.spec = dec, spec
+    def forward(ctx, dec, types, preds, h0, *params):
+        run = _make_decode(dec, types, preds, h0, params)
+        ll = run.forward()
+        ctx.run, ctx.dec = run, dec
         ctx.save_for_backward(h0, *params)   # (version checks: backward reads these through the saved pointers)
         return ll[2 * h0.shape[0]].clone()
 
     @staticmethod
     def backward(ctx, g_res):
         saved = ctx.saved_tensors   # raises if a parameter was modified in place since the forward call
-        spec, dec = ctx.spec, ctx.dec
-        if spec["agg"] == K.NA_GATED_SUM:
-            d_h0, d_cells, d_av, d_ae, d_agg = dec.backward(g_res, None, 0, None)
+        dec, run = ctx.dec, ctx.run
+        if dec.agg == _lib.DVAE_AGG_GATED_SUM:
+            d_h0, d_cells, d_av, d_ae, d_agg = run.backward(g_res, None, 0, None)
         else:
             d_attn = torch.zeros_like(saved[1])   # (the query half stays zero: it cancels in the soft-max)
-            d_h0, d_cells, d_av, d_ae = dec.backward(g_res, d_attn, spec["dq"], spec["dq"] + spec["hs"] if spec["vid"] else None)
+            d_h0, d_cells, d_av, d_ae = run.backward(g_res, d_attn, dec.key_off, dec.vid_off)
             d_agg = [d_attn]
-        ctx.dec = None
+        ctx.run = None
         flat = [t for c in d_cells for t in c] + d_av + d_ae
         return (None, None, None, d_h0) + tuple(d_agg) + tuple(flat)
 
 
-def _make_decode(spec, types, preds, h0, params):
-    L, hs, dq = spec["L"], spec["hs"], spec["dq"]
-    na = 3 if spec["agg"] == K.NA_GATED_SUM else 1
-    agg, params = params[:na], params[na:]
-    cells = [tuple(params[4 * l:4 * l + 4]) for l in range(L)]
-    av, ae = list(params[4 * L:4 * L + 4]), list(params[4 * L + 4:4 * L + 8])
-    t = dict(h0=h0.detach(), types=types, preds=preds, cells=cells, av=av, ae=ae)
-    if na == 3:
-        t["gate"] = [x.detach() for x in agg]
-    else:
-        w = agg[0].detach()[0]
-        if spec["agg"] == K.NA_ATTN_X:   # the keys are one-hot types: the key half is a table over the types (a view, no copy)
-            t.update(key_type=w[dq:dq + spec["nvt"]])
-        else:
-            t.update(w_key=w[dq:dq + hs], vid_bias=w[dq + hs:dq + hs + spec["n"]] if spec["vid"] else None)
-    return engine.DvaeDecode(spec["n"], spec["nvt"], spec["start_type"], spec["bn"], t)
+def _make_decode(dec, types, preds, h0, params=None):
+    """The teacher-forced decode of the description `dec` on (types, preds, h0).  `params` are `dec.params`, as
+    `_decode_loss_inputs` returns them beside it; the description already holds what is read of them."""
+    return engine.DvaeDecode(dec, types, preds, h0.detach())
 
 
 _LOSS_NEEDS_GPU = ("loss(): the model must live on a ROCm GPU - the teacher-forced decoder is HIP "
@@ -1113,25 +1130,48 @@ class _DvaeDagnn(_DvaeBase):
         if types.device != H0.device or preds.device != H0.device:
             raise ValueError("loss_dense(): types and preds must be on the model's device %s" % H0.device)
         types, preds = types.contiguous(), preds.contiguous()
-        spec, params = self._decode_loss_inputs()
+        dec, params = self._decode_loss_inputs()
         if torch.is_grad_enabled() and any(t.requires_grad for t in [H0] + params):
-            res = _DecodeLoss.apply(spec, types, preds, H0, *params)
+            res = _DecodeLoss.apply(dec, types, preds, H0, *params)
         else:   # (no autograd record: the saved activations die with this call)
-            res = _make_decode(spec, types, preds, H0, params).forward()[2 * H0.shape[0]].clone()
+            res = _make_decode(dec, types, preds, H0, params).forward()[2 * H0.shape[0]].clone()
         kld = -0.5 * torch.sum(1 + logvar - mu.pow(2) - logvar.exp())
         return res + beta * kld, res, kld
 
     def _decode_loss_inputs(self):
-        """(spec, tensors) of `_DecodeLoss` / `_make_decode`: the aggregator's tensors, 4 per grud cell, then add_vertex
-        and add_edge."""
-        cells = list(self.grud)[:self.num_layers]
-        params = self._decoder_agg_tensors()
-        params += [t for c in cells for t in (c.weight_ih, c.weight_hh, c.bias_ih, c.bias_hh)]
-        params += [self.add_vertex[0].weight, self.add_vertex[0].bias, self.add_vertex[2].weight, self.add_vertex[2].bias,
-                   self.add_edge[0].weight, self.add_edge[0].bias, self.add_edge[2].weight, self.add_edge[2].bias]
-        spec = dict(n=self.max_n, nvt=self.nvt, start_type=int(self.START_TYPE), bn=not self._use_vids, vid=self._use_vids,
-                    L=len(cells), hs=self.hs, dq=self._key_offset(0), agg=self.agg)
-        return spec, params
+        """(description, its differentiable parameters) of `_DecodeLoss` / `_make_decode`."""
+        dec = self._decoder()
+        return dec, dec.params
+
+    def _decoder(self, attached=False):
+        """The `_Decoder` of this model (behind `_check_decoder_agg`).  The one place that cuts attn_lin.weight up: its row
+        holds the query half up to `_key_offset(0)`, then the key half - hs state columns and (NA) max_n vertex-id columns,
+        or with attn_x, whose keys are the one-hot types, a table over the nvt types.  `attached`: the views stay in the
+        autograd graph (`_ipropagate_to` under autograd backpropagates through them); otherwise they are detached, as the
+        loss - whose gradients come from the library - and the sampling decode want them."""
+        cells = [(c.weight_ih, c.weight_hh, c.bias_ih, c.bias_hh) for c in list(self.grud)[:self.num_layers]]
+        av = [self.add_vertex[0].weight, self.add_vertex[0].bias, self.add_vertex[2].weight, self.add_vertex[2].bias]
+        ae = [self.add_edge[0].weight, self.add_edge[0].bias, self.add_edge[2].weight, self.add_edge[2].bias]
+        w_key = vid_bias = key_type = gate = vid_off = None
+        dq = self._key_offset(0)
+        if self.agg == K.NA_GATED_SUM:   # the layer-0 gate and mapper that node_aggr_0[0] shares with the encoder
+            agg = _lib.DVAE_AGG_GATED_SUM
+            own = [self.gate_forward[0][0].weight, self.gate_forward[0][0].bias, self.mapper_forward[0][0].weight]
+            gate = own if attached else [t.detach() for t in own]
+        else:
+            own = [self.node_aggr_0[0].attn_lin.weight]   # AttnConv.forward with edge_index=None (`dagnn.py:391-399`), stacked layer 0
+            w = (own[0] if attached else own[0].detach())[0]
+            if self.agg == K.NA_ATTN_X:
+                agg, key_type = _lib.DVAE_AGG_ATTN_X, w[dq:dq + self.nvt]
+            else:
+                agg, w_key = _lib.DVAE_AGG_ATTN_H, w[dq:dq + self.hs]
+                if self._use_vids:
+                    vid_off = dq + self.hs
+                    vid_bias = w[vid_off:vid_off + self.max_n]
+        return _Decoder(n=self.max_n, nvt=self.nvt, hs=self.hs, L=len(cells), start_type=int(self.START_TYPE),
+                        end_type=int(self.END_TYPE), bn=not self._use_vids, agg=agg,
+                        params=own + [t for c in cells for t in c] + av + ae, cells=cells, av=av, ae=ae, w_key=w_key,
+                        vid_bias=vid_bias, key_type=key_type, gate=gate, key_off=dq, vid_off=vid_off)
 
     def _check_decoder_agg(self, what):
         """The decoders serve attn_h, (NA) gated_sum and (BN) attn_x.  The first two read the predecessors' hs-wide states
@@ -1155,30 +1195,7 @@ class _DvaeDagnn(_DvaeBase):
                              % (what, self.agg, " and num_nodes == max_n" if self._use_vids else "", self.hidden_dim,
                                 self.hs, self.num_nodes, self.max_n))
 
-    def _decoder_agg_tensors(self):
-        """The decoder's aggregator tensors: attn_h the attn_lin weight, gated_sum the layer-0 gate (weight, bias) and
-        mapper weight that node_aggr_0[0] shares with the encoder."""
-        if self.agg == K.NA_GATED_SUM:
-            return [self.gate_forward[0][0].weight, self.gate_forward[0][0].bias, self.mapper_forward[0][0].weight]
-        return [self.node_aggr_0[0].attn_lin.weight]
-
     # ------------------------------------------------------------------ sampling decoder (dvae/models_pyg.py:338-396)
-    def _decode_tensors(self):
-        cells = list(self.grud)[:self.num_layers]
-        t = dict(cells=[(c.weight_ih, c.weight_hh, c.bias_ih, c.bias_hh) for c in cells],
-                 av=[self.add_vertex[0].weight, self.add_vertex[0].bias, self.add_vertex[2].weight, self.add_vertex[2].bias],
-                 ae=[self.add_edge[0].weight, self.add_edge[0].bias, self.add_edge[2].weight, self.add_edge[2].bias])
-        if self.agg == K.NA_GATED_SUM:
-            t["gate"] = [x.detach() for x in self._decoder_agg_tensors()]
-            return t
-        w = self.node_aggr_0[0].attn_lin.weight.detach()[0]
-        dq = self._key_offset(0)
-        if self.agg == K.NA_ATTN_X:
-            t.update(key_type=w[dq:dq + self.nvt])
-        else:
-            t.update(w_key=w[dq:dq + self.hs], vid_bias=w[dq + self.hs:dq + self.hs + self.max_n] if self._use_vids else None)
-        return t
-
     def decode_dense(self, z, stochastic=True, attempts=1, draws=None, states=False):
         """`decode(z, stochastic)` for `attempts` independent attempts on the same B latent rows, as dense device tensors,
         without synchronising: DecodedDense(types [attempts, B, max_n] int32 (-1 past the end), preds [attempts, B, max_n]
@@ -1212,8 +1229,7 @@ class _DvaeDagnn(_DvaeBase):
                     u_type, u_edge = draws
                     if tuple(u_type.shape) != st or tuple(u_edge.shape) != se:
                         raise ValueError("decode(): draws must be shaped %s and %s" % (st, se))
-            types, preds, nv, hs = engine.dvae_sample(h0, attempts, n, self.nvt, self.START_TYPE, self.END_TYPE,
-                                                      not self._use_vids, self._decode_tensors(), u_type, u_edge, states)
+            types, preds, nv, hs = engine.dvae_sample(h0, attempts, self._decoder(), u_type, u_edge, states)
         return DecodedDense(types.view(attempts, B, n), preds.view(attempts, B, n), nv.view(attempts, B),
                             None if hs is None else hs.view(attempts, B, n, self.hs))
 
@@ -1275,9 +1291,7 @@ class _DvaeDagnn(_DvaeBase):
             H = H[list(range(len(G)))].to(dev)   # the reference indexes with the positions of the already filtered list
         X = self._one_hot([g.vs[v]["type"] for g in G], self.nvt)
         values = pred_vid = None
-        lin = self.node_aggr_0[0].attn_lin   # AttnConv.forward with edge_index=None (`dagnn.py:391-399`), stacked layer 0
-        dq = self._key_offset(0)
-        w = lin.weight[0]   # (not detached: the training caller `loss()` -> `_update_iv` backpropagates through this step)
+        dec = self._decoder(attached=True)   # (the training caller `loss()` -> `_update_iv` backpropagates through this step)
         if H is None:
             preds = [g.predecessors(v) for g in G]
             P = max(len(p) for p in preds)
@@ -1292,11 +1306,8 @@ class _DvaeDagnn(_DvaeBase):
                 values = torch.cat(rows, 0).view(len(G), P, self.hs)
                 pred_vid = torch.tensor(ids, dtype=torch.int32).view(len(G), P).to(dev)
         cells = list(propagator)[:self.num_layers]
-        if typed:   # (`_iprop_dense`: w_key None, the table in vid_bias' place)
-            w_key, vid_bias = None, w[dq:dq + self.nvt]
-        else:
-            w_key = w[dq:dq + self.hs]
-            vid_bias = w[dq + self.hs:dq + self.hs + self.max_n] if self._use_vids else None
+        # (`_iprop_dense`, typed: w_key None, the table in vid_bias' place)
+        w_key, vid_bias = (None, dec.key_type) if typed else (dec.w_key, dec.vid_bias)
         flat = [t for c in cells for t in (c.weight_ih, c.weight_hh, c.bias_ih, c.bias_hh)]
         diff = [t for t in [values, H, w_key, vid_bias] + flat if t is not None]
         if torch.is_grad_enabled() and any(t.requires_grad for t in diff):

@@ -1629,80 +1629,82 @@ def topo_layers(edge_index: torch.Tensor, batch: torch.Tensor, num_graphs: int):
     return lf, lb, status
 
 
-# ------------------------------------------------------------------ teacher-forced D-VAE decoder (csrc/dvae_decode.hip)
+# ------------------------------------------------------------------ the D-VAE decoders (csrc/dvae_decode.hip, csrc/dvae_sample.hip)
+def decoder_shapes(d) -> list:
+    """[(tensor, shape it must have)] for every weight of a decoder description `d` (`dvae._Decoder`: n, nvt, hs, bn, agg,
+    cells, av, ae and the aggregator's views).  The library reads all of them through bare pointers."""
+    n, nvt, hs = d.n, d.nvt, d.hs
+    av, ae = d.av, d.ae
+    V1, E1, ein = av[0].shape[0], ae[0].shape[0], (3 if d.bn else 2) * hs
+    want = [(av[0], (V1, hs)), (av[1], (V1,)), (av[2], (nvt, V1)), (av[3], (nvt,)),
+            (ae[0], (E1, ein)), (ae[1], (E1,)), (ae[2], (1, E1)), (ae[3], (1,))]
+    if d.agg == _lib.DVAE_AGG_GATED_SUM:
+        want += [(d.gate[0], (hs, hs + n)), (d.gate[1], (hs,)), (d.gate[2], (hs, hs + n))]
+    elif d.agg == _lib.DVAE_AGG_ATTN_X:
+        want.append((d.key_type, (nvt,)))
+    else:
+        want.append((d.w_key, (hs,)))
+        if d.vid_bias is not None:
+            want.append((d.vid_bias, (n,)))
+    for l, (w_ih, w_hh, b_ih, b_hh) in enumerate(d.cells):
+        want += [(w_ih, (3 * hs, nvt if l == 0 else hs)), (w_hh, (3 * hs, hs)), (b_ih, (3 * hs,)), (b_hh, (3 * hs,))]
+    return want
+
+
+def check_shapes(entry: str, want) -> None:
+    for t, shape in want:
+        if tuple(t.shape) != shape:
+            raise ValueError("%s: a tensor of shape %s where %s is needed" % (entry, tuple(t.shape), shape))
+
+
+def _marshal_decoder(a, d, entry: str, also=()):
+    """The decoder fields of `a` - dagnn_dvae_decode_args or dagnn_dvae_sample_args, which name them alike - from the
+    description `d`: every weight on the device as float32, every shape checked (`also`: the entry point's own
+    (tensor, shape) pairs), then dimensions, `agg` and pointers.  Returns `d` with the tensors the pointers borrow."""
+    if not 1 <= d.L <= _lib.MAX_STACKED:
+        raise DagnnHipError("%s: 1 to %d stacked cells" % (entry, _lib.MAX_STACKED))
+    f = lambda t, what: None if t is None else _dev(t.detach(), what, torch.float32)  # noqa: E731
+    d = d._replace(cells=[[f(t, "grud parameter") for t in c] for c in d.cells],
+                   gate=None if d.gate is None else [f(t, "gate / mapper parameter") for t in d.gate],
+                   key_type=f(d.key_type, "key_type"), w_key=f(d.w_key, "w_key"), vid_bias=f(d.vid_bias, "vid_bias"),
+                   av=[f(t, "add_vertex parameter") for t in d.av], ae=[f(t, "add_edge parameter") for t in d.ae])
+    check_shapes(entry, list(also) + decoder_shapes(d))
+    a.n, a.hs, a.L, a.nvt, a.start_type, a.bn, a.agg = d.n, d.hs, d.L, d.nvt, int(d.start_type), int(bool(d.bn)), d.agg
+    a.vertex_hidden, a.edge_hidden = d.av[0].shape[0], d.ae[0].shape[0]
+    for l, c in enumerate(d.cells):
+        a.w_ih[l], a.w_hh[l], a.b_ih[l], a.b_hh[l] = (t.data_ptr() for t in c)
+    a.w_key, a.vid_bias, a.key_type = _ptr(d.w_key), _ptr(d.vid_bias), _ptr(d.key_type)
+    if d.gate is not None:
+        a.gate_w, a.gate_b, a.mapper_w = (t.data_ptr() for t in d.gate)
+    a.av_w1, a.av_b1, a.av_w2, a.av_b2 = (t.data_ptr() for t in d.av)
+    a.ae_w1, a.ae_b1, a.ae_w2, a.ae_b2 = (t.data_ptr() for t in d.ae)
+    return d
+
+
 class DvaeDecode(object):
     """One teacher-forced decode (`dagnn_dvae_decode_forward` / `_backward`): the argument struct, the tensors its pointers
-    borrow, and the saved activations of the forward call.  `tensors`: dict with h0 [B,hs], types / preds [B,n] int32,
-    w_key [hs], vid_bias [n] or None, cells (list of (w_ih, w_hh, b_ih, b_hh)), av / ae (lists of (w1, b1, w2, b2));
-    agg = gated_sum: gate = (gate_w [hs,hs+n], gate_b [hs], mapper_w [hs,hs+n]) in place of w_key / vid_bias; agg = attn_x
-    (BN): key_type [nvt] in place of them."""
+    borrow, and the saved activations of the forward call.  `d`: the decoder description (`dvae._Decoder`); h0 [B,hs],
+    types / preds [B,n] int32."""
 
-    def __init__(self, n: int, nvt: int, start_type: int, bn: bool, tensors: dict):
-        h0 = _dev(tensors["h0"], "H0", torch.float32)
+    def __init__(self, d, types: torch.Tensor, preds: torch.Tensor, h0: torch.Tensor):
+        h0 = _dev(h0, "H0", torch.float32)
         dev = h0.device
-        self.keep = {"h0": h0}
-        f = lambda t, what: _dev(t.detach(), what, torch.float32)  # noqa: E731
+        B = h0.shape[0]
+        types = _dev(types, "types", torch.int32)
+        preds = _dev(preds, "predecessor masks", torch.int32)
         a = _lib.DvaeDecodeArgsTyped()
-        B, hs = h0.shape
-        cells = tensors["cells"]
-        a.B, a.n, a.hs, a.L, a.nvt, a.start_type, a.bn = B, n, hs, len(cells), nvt, start_type, int(bool(bn))
-        types = _dev(tensors["types"], "types", torch.int32)
-        preds = _dev(tensors["preds"], "predecessor masks", torch.int32)
+        d = _marshal_decoder(a, d, "dagnn_dvae_decode", [(h0, (B, d.hs)), (types, (B, d.n)), (preds, (B, d.n))])
+        a.B = B
         a.types, a.preds, a.h0 = types.data_ptr(), preds.data_ptr(), h0.data_ptr()
-        keep = [types, preds]
-        if len(cells) > _lib.MAX_STACKED:
-            raise DagnnHipError("dagnn_dvae_decode: at most %d stacked cells" % _lib.MAX_STACKED)
-        for l, c in enumerate(cells):
-            ts = [f(t, "grud parameter") for t in c]
-            keep += ts
-            a.w_ih[l], a.w_hh[l], a.b_ih[l], a.b_hh[l] = (t.data_ptr() for t in ts)
-        gate = tensors.get("gate")
-        gate = None if gate is None else [f(t, "gate / mapper parameter") for t in gate]
-        kt = None if tensors.get("key_type") is None else f(tensors["key_type"], "key_type")
-        wk = None if gate is not None or kt is not None else f(tensors["w_key"], "w_key")
-        vb = None if wk is None or tensors.get("vid_bias") is None else f(tensors["vid_bias"], "vid_bias")
-        a.w_key, a.vid_bias = _ptr(wk), _ptr(vb)
-        if gate is not None:
-            a.agg = 1
-            a.gate_w, a.gate_b, a.mapper_w = (t.data_ptr() for t in gate)
-        elif kt is not None:
-            a.agg = 2
-            a.key_type = kt.data_ptr()
-        av = [f(t, "add_vertex parameter") for t in tensors["av"]]
-        ae = [f(t, "add_edge parameter") for t in tensors["ae"]]
-        a.av_w1, a.av_b1, a.av_w2, a.av_b2 = (t.data_ptr() for t in av)
-        a.ae_w1, a.ae_b1, a.ae_w2, a.ae_b2 = (t.data_ptr() for t in ae)
-        a.vertex_hidden, a.edge_hidden = av[0].shape[0], ae[0].shape[0]
-        # the library reads these through bare pointers: every shape is checked here
-        V1, E1, ein = av[0].shape[0], ae[0].shape[0], (3 if bn else 2) * hs
-        want = [(types, (B, n)), (preds, (B, n)), (av[0], (V1, hs)), (av[1], (V1,)), (av[2], (nvt, V1)), (av[3], (nvt,)),
-                (ae[0], (E1, ein)), (ae[1], (E1,)), (ae[2], (1, E1)), (ae[3], (1,))]
-        if gate is not None:
-            want += [(gate[0], (hs, hs + n)), (gate[1], (hs,)), (gate[2], (hs, hs + n))]
-        elif kt is not None:
-            want.append((kt, (nvt,)))
-        else:
-            want.append((wk, (hs,)))
-        if vb is not None:
-            want.append((vb, (n,)))
-        for l in range(len(cells)):
-            w_ih, w_hh, b_ih, b_hh = keep[2 + 4 * l:6 + 4 * l]
-            want += [(w_ih, (3 * hs, nvt if l == 0 else hs)), (w_hh, (3 * hs, hs)), (b_ih, (3 * hs,)), (b_hh, (3 * hs,))]
-        for t, shape in want:
-            if tuple(t.shape) != shape:
-                raise ValueError("dagnn_dvae_decode: a tensor of shape %s where %s is needed" % (tuple(t.shape), shape))
-        keep += [wk, vb, kt] + av + ae + (gate or [])
         self.ll = torch.empty(2 * B + 1, dtype=torch.float32, device=dev)
         a.ll = self.ll.data_ptr()
         lib = _lib.load()
         nbytes = lib.dagnn_dvae_decode_saved_bytes(C.byref(a))
         if nbytes == 0:
-            raise DagnnHipError("dagnn_dvae_decode: unsupported shape (B=%d, n=%d, hs=%d, L=%d, nvt=%d)" % (B, n, hs, len(cells), nvt))
+            raise DagnnHipError("dagnn_dvae_decode: unsupported shape (B=%d, n=%d, hs=%d, L=%d, nvt=%d)" % (B, d.n, d.hs, d.L, d.nvt))
         self.saved = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=dev)
         a.saved, a.saved_bytes = self.saved.data_ptr(), nbytes
-        self.args, self.tensors, self.B, self.hs, self.L = a, keep, B, hs, len(cells)
-        self.av, self.ae, self.cells, self.h0, self.gate = av, ae, keep[2:2 + 4 * len(cells)], h0, gate
-        self.type_keyed = kt is not None
+        self.args, self.d, self.tensors, self.h0 = a, d, (types, preds), h0
 
     def forward(self) -> torch.Tensor:
         """Runs the decode; returns ll [2B+1]: per-graph vertex and edge log-likelihoods, then res."""
@@ -1722,23 +1724,24 @@ class DvaeDecode(object):
         g.g_res, g.work, g.work_bytes = g_res.data_ptr(), work.data_ptr(), nbytes
         d_h0 = torch.empty_like(self.h0)
         g.d_h0 = d_h0.data_ptr()
+        d = self.d
         d_cells = []
-        for l in range(self.L):
-            ts = [torch.empty_like(t) for t in self.cells[4 * l:4 * l + 4]]
+        for l, c in enumerate(d.cells):
+            ts = [torch.empty_like(t) for t in c]
             d_cells.append(ts)
             g.d_w_ih[l], g.d_w_hh[l], g.d_b_ih[l], g.d_b_hh[l] = (t.data_ptr() for t in ts)
-        d_av = [torch.empty_like(t) for t in self.av]
-        d_ae = [torch.empty_like(t) for t in self.ae]
+        d_av = [torch.empty_like(t) for t in d.av]
+        d_ae = [torch.empty_like(t) for t in d.ae]
         g.d_av_w1, g.d_av_b1, g.d_av_w2, g.d_av_b2 = (t.data_ptr() for t in d_av)
         g.d_ae_w1, g.d_ae_b1, g.d_ae_w2, g.d_ae_b2 = (t.data_ptr() for t in d_ae)
-        if self.gate is not None:
-            d_gate = [torch.empty_like(t) for t in self.gate]
+        if d.agg == _lib.DVAE_AGG_GATED_SUM:
+            d_gate = [torch.empty_like(t) for t in d.gate]
             g.d_gate_w, g.d_gate_b, g.d_mapper_w = (t.data_ptr() for t in d_gate)
             check(lib.dagnn_dvae_decode_backward(C.byref(self.args), C.byref(g), _stream(self.h0)), "dagnn_dvae_decode_backward")
             return d_h0, d_cells, d_av, d_ae, d_gate
         if not d_attn.is_contiguous():
             raise DagnnHipError("dagnn_dvae_decode_backward: the attn_lin gradient must be contiguous")
-        if self.type_keyed:
+        if d.agg == _lib.DVAE_AGG_ATTN_X:
             g.d_key_type = d_attn.data_ptr() + 4 * key_off
         else:
             g.d_w_key = d_attn.data_ptr() + 4 * key_off
@@ -1748,71 +1751,30 @@ class DvaeDecode(object):
 
 
 # ------------------------------------------------------------------ sampling D-VAE decoder (csrc/dvae_sample.hip)
-def dvae_sample(h0: torch.Tensor, groups: int, n: int, nvt: int, start_type: int, end_type: int, bn: bool, tensors: dict,
-                u_type: Optional[torch.Tensor] = None, u_edge: Optional[torch.Tensor] = None, states: bool = False):
-    """One call of `dagnn_dvae_sample` over `groups` groups of h0.shape[0] // groups rows.  `tensors`: cells (list of
-    (w_ih, w_hh, b_ih, b_hh)), w_key [hs], vid_bias [n] or None, av / ae (lists of (w1, b1, w2, b2)); agg = gated_sum:
-    gate = (gate_w [hs,hs+n], gate_b [hs], mapper_w [hs,hs+n]) in place of w_key / vid_bias; agg = attn_x (BN): key_type
-    [nvt] in place of them.  u_type [G,n,B] and
-    u_edge [G,n(n-1)/2,B] (both or neither): the draws of a sampled decode; None: argmax.  Returns (types [R,n] int32,
-    preds [R,n] int32 bitmasks, nv [R] int32, states [R,n,hs] or None) on h0's device, without synchronising."""
+def dvae_sample(h0: torch.Tensor, groups: int, d, u_type: Optional[torch.Tensor] = None, u_edge: Optional[torch.Tensor] = None,
+                states: bool = False):
+    """One call of `dagnn_dvae_sample` over `groups` groups of h0.shape[0] // groups rows.  `d`: the decoder description
+    (`dvae._Decoder`).  u_type [G,n,B] and u_edge [G,n(n-1)/2,B] (both or neither): the draws of a sampled decode; None:
+    argmax.  Returns (types [R,n] int32, preds [R,n] int32 bitmasks, nv [R] int32, states [R,n,hs] or None) on h0's
+    device, without synchronising."""
     h0 = _dev(h0, "H0", torch.float32)
     dev = h0.device
-    R, hs = h0.shape
+    R, n, hs = h0.shape[0], d.n, d.hs
     if groups <= 0 or R % groups:
         raise ValueError("dagnn_dvae_sample: %d rows do not split into %d groups" % (R, groups))
     B = R // groups
-    f = lambda t, what: _dev(t.detach(), what, torch.float32)  # noqa: E731
-    cells = [[f(t, "grud parameter") for t in c] for c in tensors["cells"]]
-    if not 1 <= len(cells) <= _lib.MAX_STACKED:
-        raise DagnnHipError("dagnn_dvae_sample: 1 to %d stacked cells" % _lib.MAX_STACKED)
-    gate = tensors.get("gate")
-    gate = None if gate is None else [f(t, "gate / mapper parameter") for t in gate]
-    kt = None if tensors.get("key_type") is None else f(tensors["key_type"], "key_type")
-    wk = None if gate is not None or kt is not None else f(tensors["w_key"], "w_key")
-    vb = None if wk is None or tensors.get("vid_bias") is None else f(tensors["vid_bias"], "vid_bias")
-    av = [f(t, "add_vertex parameter") for t in tensors["av"]]
-    ae = [f(t, "add_edge parameter") for t in tensors["ae"]]
-    V1, E1, ein = av[0].shape[0], ae[0].shape[0], (3 if bn else 2) * hs
-    # the library reads these through bare pointers: every shape is checked here
-    want = [(av[0], (V1, hs)), (av[1], (V1,)), (av[2], (nvt, V1)), (av[3], (nvt,)),
-            (ae[0], (E1, ein)), (ae[1], (E1,)), (ae[2], (1, E1)), (ae[3], (1,))]
-    if gate is not None:
-        want += [(gate[0], (hs, hs + n)), (gate[1], (hs,)), (gate[2], (hs, hs + n))]
-    elif kt is not None:
-        want.append((kt, (nvt,)))
-    else:
-        want.append((wk, (hs,)))
-    if vb is not None:
-        want.append((vb, (n,)))
-    for l, (w_ih, w_hh, b_ih, b_hh) in enumerate(cells):
-        want += [(w_ih, (3 * hs, nvt if l == 0 else hs)), (w_hh, (3 * hs, hs)), (b_ih, (3 * hs,)), (b_hh, (3 * hs,))]
+    also = [(h0, (R, hs))]
     stochastic = u_type is not None or u_edge is not None
     if stochastic:
         if u_type is None or u_edge is None:
             raise ValueError("dagnn_dvae_sample: give both u_type and u_edge, or neither")
         u_type = _dev(u_type, "u_type", torch.float32)
         u_edge = _dev(u_edge, "u_edge", torch.float32)
-        want += [(u_type, (groups, n, B)), (u_edge, (groups, n * (n - 1) // 2, B))]
-    for t, shape in want:
-        if tuple(t.shape) != shape:
-            raise ValueError("dagnn_dvae_sample: a tensor of shape %s where %s is needed" % (tuple(t.shape), shape))
+        also += [(u_type, (groups, n, B)), (u_edge, (groups, n * (n - 1) // 2, B))]
     a = _lib.DvaeSampleArgsTyped()
-    a.G, a.B, a.n, a.hs, a.L, a.nvt = groups, B, n, hs, len(cells), nvt
-    a.start_type, a.end_type, a.bn, a.stochastic = int(start_type), int(end_type), int(bool(bn)), int(stochastic)
-    a.edge_hidden, a.vertex_hidden = E1, V1
+    d = _marshal_decoder(a, d, "dagnn_dvae_sample", also)
+    a.G, a.B, a.end_type, a.stochastic = groups, B, int(d.end_type), int(stochastic)
     a.h0 = h0.data_ptr()
-    for l, c in enumerate(cells):
-        a.w_ih[l], a.w_hh[l], a.b_ih[l], a.b_hh[l] = (t.data_ptr() for t in c)
-    a.w_key, a.vid_bias = _ptr(wk), _ptr(vb)
-    if gate is not None:
-        a.agg = 1
-        a.gate_w, a.gate_b, a.mapper_w = (t.data_ptr() for t in gate)
-    elif kt is not None:
-        a.agg = 2
-        a.key_type = kt.data_ptr()
-    a.av_w1, a.av_b1, a.av_w2, a.av_b2 = (t.data_ptr() for t in av)
-    a.ae_w1, a.ae_b1, a.ae_w2, a.ae_b2 = (t.data_ptr() for t in ae)
     a.u_type, a.u_edge = _ptr(u_type), _ptr(u_edge)
     types = torch.empty(R, n, dtype=torch.int32, device=dev)
     preds = torch.empty(R, n, dtype=torch.int32, device=dev)
@@ -1823,7 +1785,7 @@ def dvae_sample(h0: torch.Tensor, groups: int, n: int, nvt: int, start_type: int
     nbytes = lib.dagnn_dvae_sample_work_bytes(C.byref(a))
     if nbytes == 0:
         raise DagnnHipError("dagnn_dvae_sample: unsupported shape (G=%d, B=%d, n=%d, hs=%d, L=%d, nvt=%d)"
-                            % (groups, B, n, hs, len(cells), nvt))
+                            % (groups, B, n, hs, d.L, d.nvt))
     work = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=dev)
     a.work, a.work_bytes = work.data_ptr(), nbytes
     check(lib.dagnn_dvae_sample(C.byref(a), _stream(h0)), "dagnn_dvae_sample")

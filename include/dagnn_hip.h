@@ -986,23 +986,34 @@ int dagnn_iprop_step_typed(const float* values, const int32_t* pred_type, int64_
  * dagnn_dvae_decode_backward reads the same args (and the saved activations of the forward call) and writes - not
  * accumulates - d res scaled by the device scalar *g_res for every input above; d_w_key / d_vid_bias may point into one
  * zeroed attn_lin.weight gradient.  `work` >= dagnn_dvae_decode_work_bytes(args) bytes.  Both are bitwise deterministic
- * (no float atomics).  The size queries return 0 for arguments the entry points refuse with DAGNN_EINVAL.
- * agg = 1 (`gated_sum`, NA only): the aggregate of vertex v is sum over its predecessors u of sigmoid(Wg x_u + bg) *
+ * (no float atomics).
+ *
+ * The decoder's description - the fields n, hs, L, nvt, start_type, bn, edge_hidden, vertex_hidden, the grud / av_* /
+ * ae_* weights and `agg` with its tensors - is shared, name by name, with dagnn_dvae_sample_args, and one set of rules
+ * (csrc/dvae_common.h) serves both: the ranges noted on the fields below; edge_hidden, vertex_hidden >= 1; bn 0 or 1;
+ * agg one of DAGNN_DVAE_AGG_*; DAGNN_DVAE_AGG_GATED_SUM only with bn = 0 and all of gate_w / gate_b / mapper_w;
+ * DAGNN_DVAE_AGG_ATTN_X only with bn = 1 and key_type.  The size queries return 0 for arguments that break one of
+ * them (or an entry point's own size limits), and the entry points DAGNN_EINVAL; a missing pointer otherwise - h0, a
+ * weight, DAGNN_DVAE_AGG_ATTN_H's w_key, an output, a workspace - is refused by the entry points alone.
+ * agg = DAGNN_DVAE_AGG_GATED_SUM (`gated_sum`, NA only): the aggregate of vertex v is sum over its predecessors u of sigmoid(Wg x_u + bg) *
  * (Wm x_u), x_u = [layer-0 state of u ; one-hot(u, n)], from gate_w / gate_b / mapper_w (gate_forward.0.0 and
  * mapper_forward.0.0, [hs, hs+n] row-major); w_key / vid_bias are not read.  Their gradients go to d_gate_w / d_gate_b
- * / d_mapper_w, and d_w_key / d_vid_bias are not written.  agg = 1 with bn = 1 or a missing gate / mapper pointer is
- * refused (the size queries return 0).  The fields are appended: a zero-filled struct is agg = 0 (attn_h).
- * agg = 2 (`attn_x`, BN only: dvae/dagnn_bn.py:203-225): the attention keys are the predecessors' one-hot TYPES, so a
+ * / d_mapper_w, and d_w_key / d_vid_bias are not written.  The fields are appended: a zero-filled struct is
+ * DAGNN_DVAE_AGG_ATTN_H.
+ * agg = DAGNN_DVAE_AGG_ATTN_X (`attn_x`, BN only: dvae/dagnn_bn.py:203-225): the attention keys are the predecessors' one-hot TYPES, so a
  * real slot scores key_type[type of u] - key_type [nvt] is the key half of node_aggr_0[0].attn_lin.weight ([1, 2 nvt]:
  * columns nvt..2nvt-1) -, a padded slot 0, and the values stay the layer-0 states; w_key / vid_bias are not read.  In
  * reverse d_key_type[t] (written, not accumulated) is the sum of the score gradients of every (update, real slot) whose
  * predecessor has type t, in one fixed order; the keys do not depend on the states, so a predecessor's state gradient
- * is alpha * d hagg alone; d_w_key / d_vid_bias are not written.  agg = 2 with bn = 0 or without key_type is refused.
- * key_type / d_key_type are appended behind the agg = 1 fields and read only when agg = 2 passed the checks above, so a
- * caller built against the earlier structs (agg = 0 / 1) is served as before.
+ * is alpha * d hagg alone; d_w_key / d_vid_bias are not written.
+ * key_type / d_key_type are appended behind the gated_sum fields and read only once agg = DAGNN_DVAE_AGG_ATTN_X with
+ * bn = 1 is established, so a caller built against the earlier structs (attn_h / gated_sum) is served as before.
  * ---------------------------------------------------------------------------------------- */
 #define DAGNN_DVAE_MAX_N 32
 #define DAGNN_DVAE_MAX_TYPES 64
+#define DAGNN_DVAE_AGG_ATTN_H 0      /* w_key / vid_bias */
+#define DAGNN_DVAE_AGG_GATED_SUM 1   /* gate_w / gate_b / mapper_w; NA only */
+#define DAGNN_DVAE_AGG_ATTN_X 2      /* key_type; BN only */
 typedef struct dagnn_dvae_decode_args {
     int64_t B;               /* graphs */
     int n;                   /* vertices per graph (max_n), 2..DAGNN_DVAE_MAX_N */
@@ -1026,11 +1037,11 @@ typedef struct dagnn_dvae_decode_args {
     float* ll;
     float* saved;
     size_t saved_bytes;
-    int agg;                 /* 0: attn_h (w_key / vid_bias), 1: gated_sum (gate_w / gate_b / mapper_w), 2: attn_x (key_type) */
+    int agg;                 /* DAGNN_DVAE_AGG_* */
     const float* gate_w;     /* [hs, hs+n] */
     const float* gate_b;     /* [hs] */
     const float* mapper_w;   /* [hs, hs+n] */
-    const float* key_type;   /* agg = 2: [nvt] */
+    const float* key_type;   /* DAGNN_DVAE_AGG_ATTN_X: [nvt] */
 } dagnn_dvae_decode_args;
 typedef struct dagnn_dvae_decode_grads {
     const float* g_res;      /* device scalar: d loss / d res */
@@ -1045,8 +1056,8 @@ typedef struct dagnn_dvae_decode_grads {
     float* d_vid_bias;
     float *d_av_w1, *d_av_b1, *d_av_w2, *d_av_b2;
     float *d_ae_w1, *d_ae_b1, *d_ae_w2, *d_ae_b2;
-    float *d_gate_w, *d_gate_b, *d_mapper_w;   /* agg = 1 */
-    float* d_key_type;       /* agg = 2: [nvt] */
+    float *d_gate_w, *d_gate_b, *d_mapper_w;   /* DAGNN_DVAE_AGG_GATED_SUM */
+    float* d_key_type;       /* DAGNN_DVAE_AGG_ATTN_X: [nvt] */
 } dagnn_dvae_decode_grads;
 size_t dagnn_dvae_decode_saved_bytes(const dagnn_dvae_decode_args* args /* host */);
 size_t dagnn_dvae_decode_work_bytes(const dagnn_dvae_decode_args* args /* host */);
@@ -1059,8 +1070,8 @@ int dagnn_dvae_decode_backward(const dagnn_dvae_decode_args* args /* host */, co
  * state = sum of the vertex states, edge head on [H_vi, H_v, H0]) for G independent groups of B rows, R = G*B, in ONE
  * call with no host round trip.  Each group is decoded exactly as one reference call on its B rows: the padding width P
  * of every update and the set of rows still being updated are reduced per group, never across groups.
- *   h0 [R,hs] = tanh(fc3(z)); grud cells, w_key / vid_bias, add_vertex (av_*) and add_edge (ae_*) as in
- *   dagnn_dvae_decode_args; stochastic = 0: argmax types and score > 0.5 edges (the draws are not read);
+ *   h0 [R,hs] = tanh(fc3(z)); the decoder's description - dimensions, grud cells, add_vertex (av_*), add_edge (ae_*),
+ *   agg and its tensors - is that of dagnn_dvae_decode_args, with its rules; end_type in [0, nvt); stochastic = 0: argmax types and score > 0.5 edges (the draws are not read);
  *   stochastic = 1: u_type [G,n,B] (row idx serves the type draw of vertex idx = 1..n-2, as np.random.choice maps
  *   its uniform: searchsorted(cumsum(p)/sum(p), u, 'right') in float64), u_edge [G,n(n-1)/2,B] (pair
  *   idx(idx-1)/2 + (idx-1-vi) serves the edge step (idx, vi) in the reference's call order; edge kept on u < score).
@@ -1068,10 +1079,7 @@ int dagnn_dvae_decode_backward(const dagnn_dvae_decode_args* args /* host */, co
  *   encoding of dagnn_dvae_decode_args), nv [R] int32 vertex counts, states [R,n,hs] (or NULL): the final top-layer
  *   state of every vertex, zero past the end.
  *   work >= dagnn_dvae_sample_work_bytes(args) bytes.  No allocation, no synchronisation, bitwise repeatable (no float
- *   atomics).  The size query returns 0 for arguments the entry point refuses with DAGNN_EINVAL.
- *   agg = 1: the gated_sum aggregate, with the gate / mapper tensors and rules of dagnn_dvae_decode_args.
- *   agg = 2: type-keyed attention (BN only), key_type [nvt] as in dagnn_dvae_decode_args: a vertex's key score is
- *   key_type[its type], written when the vertex is final; w_key / vid_bias are not read.
+ *   atomics).  DAGNN_DVAE_AGG_ATTN_X: a vertex's key score is key_type[its type], written when the vertex is final.
  * ---------------------------------------------------------------------------------------- */
 typedef struct dagnn_dvae_sample_args {
     int64_t G;               /* groups (independent decode calls) */
@@ -1101,11 +1109,11 @@ typedef struct dagnn_dvae_sample_args {
     float* states;           /* or NULL */
     float* work;
     size_t work_bytes;
-    int agg;                 /* as in dagnn_dvae_decode_args: 0 attn_h, 1 gated_sum, 2 attn_x */
+    int agg;                 /* DAGNN_DVAE_AGG_*, as in dagnn_dvae_decode_args */
     const float* gate_w;
     const float* gate_b;
     const float* mapper_w;
-    const float* key_type;   /* agg = 2: [nvt] */
+    const float* key_type;   /* DAGNN_DVAE_AGG_ATTN_X: [nvt] */
 } dagnn_dvae_sample_args;
 size_t dagnn_dvae_sample_work_bytes(const dagnn_dvae_sample_args* args /* host */);
 int dagnn_dvae_sample(const dagnn_dvae_sample_args* args /* host */, void* stream);
