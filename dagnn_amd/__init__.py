@@ -26,6 +26,7 @@ from .model import DAGNN, ASTNodeEncoder, ASTNodeEncoder2  # noqa: F401
 from .train import EpochMeter, GradBucket, seq_ce_step  # noqa: F401
 from . import evaluate  # noqa: F401
 from .evaluate import SeqF1, SeqLoss  # noqa: F401
+from .attention import Attention, attention_host  # noqa: F401   (model.attention(G): per-edge attention weights of a pass)
 from . import lp  # noqa: F401
 from .lp import ClassAccuracy, class_ce_step, class_cross_entropy, evaluate_lp, lp_batches, lp_targets  # noqa: F401
 from .data_parallel import DataParallel  # noqa: F401

@@ -54,6 +54,22 @@ class Plan(C.Structure):
                 ("B", C.c_int64), ("num_edge_feats", C.c_int), ("flags", C.c_int)]
 
 
+ATTN_MAX_CELLS = 16
+
+
+class AttnCell(C.Structure):   # dagnn_attn_cell
+    _fields_ = [("key", C.c_void_p), ("w_key", C.c_void_p), ("query", C.c_void_p), ("w_query", C.c_void_p),
+                ("vid_key", C.c_void_p), ("vid_query", C.c_void_p), ("edge_gain", C.c_void_p), ("edge_vec", C.c_void_p),
+                ("bias", C.c_void_p), ("ld_key", C.c_int), ("key_dim", C.c_int), ("ld_query", C.c_int),
+                ("query_dim", C.c_int), ("dir", C.c_int), ("pad_", C.c_int)]
+
+
+class AttnArgs(C.Structure):   # dagnn_attn_args
+    _fields_ = [("cell", AttnCell * ATTN_MAX_CELLS), ("num_cells", C.c_int), ("mode", C.c_int), ("vid_mod", C.c_int),
+                ("pad_", C.c_int), ("key_score", C.c_void_p), ("query_score", C.c_void_p), ("alpha", C.c_void_p),
+                ("logit", C.c_void_p)]
+
+
 class GemmGroup(C.Structure):
     _fields_ = [("A", C.c_void_p), ("W", C.c_void_p), ("bias", C.c_void_p), ("C", C.c_void_p)]
 
@@ -531,6 +547,7 @@ SYMBOLS = {
     "dagnn_gather_rows_batch": (C.c_int, [C.POINTER(GatherJob), C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "dagnn_gather_rows": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int,
                                     C.c_int, C.c_void_p]),
+    "dagnn_attention_weights": (C.c_int, [C.POINTER(Plan), C.POINTER(AttnArgs), C.c_void_p]),
 }
 
 _lock = threading.Lock()

@@ -825,6 +825,15 @@ class _DvaeDagnn(_DvaeBase):
         self._guard_params(next(self.parameters()))
         return out
 
+    def attention(self, G, logits: bool = False):
+        """The attention weights of an evaluation pass, as `DAGNN.attention`: an `evaluate.Attention` with `out` = what
+        `forward(G)` returns (from the same pass, on the step-by-step route: the fused call returns no states), `alpha`
+        [len(dirs), num_layers, E], `logit` with `logits=True` - NA: the one-hot vertex-id columns of keys and queries
+        included - and `h`, the states the weights weigh (`G.h` keeps the read-out rows only).  `gated_sum`, `add`, `max`
+        raise ValueError."""
+        from .attention import run
+        return run(self, G, logits)
+
     def _forward(self, G):
         if self.output_all and self.out_pool not in (K.P_MAX, K.P_MEAN, K.P_ADD):
             raise NotImplementedError("out_pool=%r over all nodes: the reference's own self-attention pooling of the "
@@ -839,8 +848,9 @@ class _DvaeDagnn(_DvaeBase):
             raise ValueError("every graph must have exactly num_nodes=%d nodes (dvae/dagnn.py:150-158)" % nn_)
         B = N // nn_
         bl = G.bi_layer_index
+        cap = self.__dict__.get("_attn_capture")   # (`attention`: wants the states, which the fused call does not return)
         if not train and not self._agg_plain and not self.agg_attn_x and not self.output_all and ENCODE_FUSED \
-                and self.schedule == "lockstep" and engine.TIMER is None:
+                and self.schedule == "lockstep" and engine.TIMER is None and cap is None:
             out = self._encode_fused(G, x, B)
             if out is not None:
                 return out
@@ -855,6 +865,8 @@ class _DvaeDagnn(_DvaeBase):
                 cells = self._cells()
                 hh = run_stack(plan, x, cells, self.dirs, L, H, vid_nodes=self._vid_nodes, schedule=self.schedule,
                                arena=self._arena_for(x), static_score=self._static_scores(x, cells))
+                if cap is not None:
+                    cap.update(plan=plan, x=x, h=hh, E=G.edge_index.shape[1])
                 flat = [hh[d][i] for d in self.dirs for i in range(L)]
             return self._pool_all(G, plan, x, flat, B)
         if train:
@@ -864,6 +876,8 @@ class _DvaeDagnn(_DvaeBase):
             cells = self._cells()
             h = run_stack(plan, x, cells, self.dirs, L, H, vid_nodes=self._vid_nodes, schedule=self.schedule,
                           arena=self._arena_for(x), static_score=self._static_scores(x, cells))
+            if cap is not None:
+                cap.update(plan=plan, x=x, h=h, E=G.edge_index.shape[1])
             hcat = self._readout(plan, B, x, h)
         G.h = hcat
         G.batch = G.batch[0::nn_] if self.bidirectional else G.batch[nn_ - 1::nn_]

@@ -438,7 +438,9 @@ def build_plan(edge_index: torch.Tensor, layer_fwd: torch.Tensor, layer_bwd: tor
     N, E = layer_fwd.numel(), edge_index.shape[1]
     R = 0
     if edge_attr is not None:
-        edge_attr = _dev(edge_attr, "edge_attr", torch.float32).view(E, -1)
+        edge_attr = _dev(edge_attr, "edge_attr", torch.float32)
+        # (a batch without edges: `view(0, -1)` cannot infer the width)
+        edge_attr = edge_attr.view(E, -1) if E else edge_attr.reshape(0, edge_attr.shape[-1] if edge_attr.dim() > 1 else 1)
         R = edge_attr.shape[1]
     plan = PlanHandle(N, E, num_graphs, R, edge_index.device)
     plan._keep = (edge_index, layer_fwd, layer_bwd, batch, edge_attr)
@@ -1932,6 +1934,70 @@ def dvae_set_query(storage: torch.Tensor, width: int, max_rows: int, types: torc
     a.member, a.count = member.data_ptr(), count.data_ptr()
     check(_lib.load().dagnn_dvae_set_query(C.byref(a), _stream(storage)), "dagnn_dvae_set_query")
     return member, count
+
+
+# ----------------------------------------------------------------------------- attention weights of a finished pass (csrc/attention.hip)
+def attention_weights(plan: PlanHandle, cells: Sequence[dict], E: int, mode: int = 0, vid_mod: int = 0, logits: bool = False):
+    """`dagnn_attention_weights`: (alpha [len(cells), E], logit [len(cells), E] or None) of the cells of a finished pass, one
+    launch pair for all of them (`mode` 1, mattn_h: one launch).  A cell is a dict: `dir`, `key` (fp32 GPU rows, any pitch),
+    `key_dim`, `w_key`, and optionally `query`, `query_dim`, `w_query`, `vid_key`, `vid_query`, `edge_gain` (mode 1: the
+    [key_dim, R] edge matrix), `edge_vec`, `bias` (a one-element device tensor).  Nothing synchronises; E == 0: no launch."""
+    n = len(cells)
+    if not 1 <= n <= _lib.ATTN_MAX_CELLS:
+        raise DagnnHipError("attention_weights: 1..%d cells (directions x stacked layers) per call (got %d)" % (_lib.ATTN_MAX_CELLS, n))
+    if int(E) != plan.E:
+        raise DagnnHipError("attention_weights: the plan holds %d edges, the batch %d" % (plan.E, int(E)))
+    dev = plan.ws.device
+    alpha = torch.empty(n, plan.E, dtype=torch.float32, device=dev)
+    logit = torch.empty(n, plan.E, dtype=torch.float32, device=dev) if logits else None
+    if plan.E == 0 or plan.N == 0:
+        return alpha, logit
+    a = _lib.AttnArgs()
+    a.num_cells, a.mode, a.vid_mod = n, int(mode), int(vid_mod)
+    keep = []
+
+    def vec(t, what, numel=None):
+        if t is None:
+            return None
+        t = _dev(t, what, torch.float32)
+        if numel is not None and t.numel() < numel:
+            raise DagnnHipError("attention_weights: %s holds %d floats, %d needed" % (what, t.numel(), numel))
+        keep.append(t)
+        return t.data_ptr()
+
+    def rows(t, what, dim):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.stride(1) == 1
+                and t.shape[0] == plan.N and t.shape[1] >= dim and t.stride(0) >= dim):
+            raise DagnnHipError("attention_weights: %s must be fp32 GPU rows [%d, >= %d] with unit column stride" % (what, plan.N, dim))
+        keep.append(t)
+        return t.data_ptr(), t.stride(0)
+
+    want_query = False
+    for k, c in enumerate(cells):
+        ac = a.cell[k]
+        ac.dir, ac.key_dim = int(c["dir"]), int(c["key_dim"])
+        ac.key, ac.ld_key = rows(c["key"], "key rows", ac.key_dim)
+        ac.w_key = vec(c.get("w_key"), "w_key", ac.key_dim)
+        if c.get("query") is not None and (logits or mode == 1):
+            ac.query_dim = int(c["query_dim"])
+            ac.query, ac.ld_query = rows(c["query"], "query rows", ac.query_dim)
+            ac.w_query = vec(c.get("w_query"), "w_query", ac.query_dim)
+            want_query = True
+        ac.vid_key, ac.vid_query = vec(c.get("vid_key"), "vid_key", vid_mod), vec(c.get("vid_query"), "vid_query", vid_mod)
+        ac.edge_gain = vec(c.get("edge_gain"), "edge term", plan.R * (ac.key_dim if mode == 1 else 1))
+        ac.edge_vec = vec(c.get("edge_vec"), "edge_vec", ac.key_dim)
+        ac.bias = vec(c.get("bias"), "bias", 1)
+    if mode == 0:
+        ks = torch.empty(n * (2 if (logits and want_query) else 1), plan.N, dtype=torch.float32, device=dev)
+        a.key_score = ks.data_ptr()
+        if logits and want_query:
+            a.query_score = ks.data_ptr() + 4 * n * plan.N
+    a.alpha, a.logit = alpha.data_ptr(), _ptr(logit)
+    plan.wait_ready()
+    with _span("attention_weights", alpha):
+        check(_lib.load().dagnn_attention_weights(C.byref(plan.desc), C.byref(a), _stream(alpha)), "dagnn_attention_weights")
+    del keep
+    return alpha, logit
 
 
 # ----------------------------------------------------------------------------- the TOK task's evaluation path (csrc/predict.hip)

@@ -27,10 +27,11 @@ import numpy as np
 import torch
 
 from . import engine
+from .attention import Attention, attention_host   # (what `model.attention(G)` returns, and its definition in torch ops)
 from .train import heads_base
 
 __all__ = ["rows_argmax", "encode_ref_sets", "tokens_to_seqs", "f1_counts_host", "f1_from_counts", "SeqF1", "evaluate",
-           "heads_score_host", "rows_score", "Score", "SeqLoss"]
+           "heads_score_host", "rows_score", "Score", "SeqLoss", "Attention", "attention_host"]
 
 
 def rows_argmax(pred) -> torch.Tensor:

@@ -605,6 +605,17 @@ class DAGNN(HipModule):
         with torch.no_grad():
             return Score(*self._pass(G, lambda out: self._heads_score(out, y_arr, topk, sums)))
 
+    def attention(self, G, logits: bool = False):
+        """The attention weights of an evaluation pass (PyG's `return_attention_weights`; a hook on `AttnConv.message` in the
+        reference): an `evaluate.Attention` with `out` = what `forward(G)` returns, from the same pass and with its side effects
+        on `G`; `alpha` [len(dirs), num_layers, E] fp32, the weight direction d, stacked layer l gave edge e (column of
+        `G.edge_index`; parallel edges each their own); `logit` (with `logits=True`) the pre-softmax scores, query part and
+        biases included.  Two launches behind the pass for all cells (`dagnn_attention_weights`, csrc/attention.hip; mattn_h:
+        its projection GEMMs and one; more than 16 cells go in chunks of 16), no synchronisation of its own.  Evaluation mode only, under `torch.no_grad()`;
+        `agg_x=True` raises NotImplementedError, an aggregator without attention ValueError."""
+        from .attention import run
+        return run(self, G, logits)
+
     def _heads_score(self, out, y_arr, topk, sums):
         """(tok, logit, lse, nll) of the heads on the pooled graph vectors: the head step of `score`, routed as
         `_heads_argmax` routes `predict`'s."""
@@ -773,6 +784,9 @@ class DAGNN(HipModule):
         pooling is HIP - `autograd.PoolNodes` where a gradient is wanted -, without one (`variant_backend = "torch"`, the
         variants' torch fall-back) torch ops."""
         L, dirs = self.num_layers, self.dirs
+        cap = self.__dict__.get("_attn_capture")
+        if cap is not None:   # (`attention`: the pass's plan, inputs and states, before the read-out narrows `G`)
+            cap.update(plan=plan, x=x, h=h, E=G.edge_index.shape[1])
         G.h = [[h[d][i] for i in range(L)] for d in dirs]  # side effect 4 (dagnn.py:141-142,182)
 
         differentiable = torch.is_grad_enabled() and (x.requires_grad or any(h[d][i].requires_grad

@@ -1742,6 +1742,51 @@ int dagnn_param_fingerprint(const void* const* ptrs /* host array of device poin
  * kernels of a collective that runs next to a training pass.  Touches no memory besides `sink` (one float, may be NULL). */
 int dagnn_debug_occupy(int num_wgs, int threads, int64_t ticks, float* sink, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Attention weights of a finished evaluation pass, per ORIGINAL edge id (`DAGNN.attention`; what a hook on the reference's
+ * conv modules would record: ogbg-code/model/dagnn.py:297-310, 366-373, 399-406, dvae/dagnn.py:109-145, dvae/dagnn_bn.py).
+ * A cell is one (direction, stacked layer).  Every state is written exactly once by the recurrence, so the final states
+ * are the states the aggregation saw.  For every CSR slot s of the plan's direction `dir` (target row t, source u = col[s],
+ * edge id e = eidx[s], R = plan->num_edge_feats):
+ *   additive (mode 0):        score_s = w_key . key[u, :key_dim] + vid_key[u mod vid_mod] + sum_r edge_gain[r] eattr[s, r]
+ *                             logit_e = score_s + w_query . query[t, :query_dim] + vid_query[t mod vid_mod] + *bias
+ *   multiplicative (mode 1):  logit_e = score_s = sum_k query[t, k] (key[u, k] + sum_r edge_mat[k, r] eattr[s, r] + edge_vec[k]),
+ *                             k < key_dim, with `query` / `key` the PROJECTED rows (attn_linl / attn_linr incl. bias: one
+ *                             dagnn_gemm_nt_bias each) - w_key, w_query, bias, vid_* are not read
+ *   alpha_e = exp(score_s - max_seg) / (sum_seg exp(score - max_seg) + 1e-16)                      (PyG's softmax)
+ * (mode 0: the query part and the bias are common to a segment and cancel in alpha; only `logit` needs them.)
+ * Every edge lies in exactly one segment per direction, so alpha[c, e] (and logit[c, e]) is written exactly once for every
+ * e < E: plain stores, no atomics, no [E, H] intermediate.  Launches: mode 0 - one kernel for the node scores of ALL cells
+ * (a wave per row, float4 loads where pointer, pitch and width allow), one for the segment softmax of ALL cells (a wave per
+ * target row, lanes over slots, running max / sum beyond 64 slots); mode 1 - one kernel (a wave per target row).
+ * Limits (violations: DAGNN_EINVAL before any launch): 1 <= num_cells <= DAGNN_ATTN_MAX_CELLS, plan->N and plan->E below
+ * 2^31, 1 <= key_dim <= ld_key, query_dim <= ld_query, NULL alpha / key_score (mode 0) / key / w_key (mode 0) with E > 0,
+ * NULL query_score with `logit` and a query in mode 0, dir outside {0, 1}, vid pointers with vid_mod < 1.  E == 0 or N == 0:
+ * returns 0 without a launch.  No allocation, no synchronisation; borrowed pointers; the caller's stream.
+ * ---------------------------------------------------------------------------------------- */
+#define DAGNN_ATTN_MAX_CELLS 16
+typedef struct dagnn_attn_cell {
+    const float* key;        /* [N, ld_key]: rows the keys are read from (states of this cell, node inputs, or projected keys) */
+    const float* w_key;      /* [key_dim] (mode 0) */
+    const float* query;      /* [N, ld_query] or NULL (self-attention; or no logit wanted) */
+    const float* w_query;    /* [query_dim] (mode 0) */
+    const float* vid_key;    /* [vid_mod] or NULL */
+    const float* vid_query;  /* [vid_mod] or NULL */
+    const float* edge_gain;  /* mode 0: [R] or NULL; mode 1: edge_mat [key_dim, R] row-major or NULL */
+    const float* edge_vec;   /* mode 1: [key_dim] or NULL */
+    const float* bias;       /* mode 0: [1] on the device, the constant of the logit, or NULL */
+    int ld_key, key_dim, ld_query, query_dim, dir, pad_;
+} dagnn_attn_cell;
+typedef struct dagnn_attn_args {
+    dagnn_attn_cell cell[DAGNN_ATTN_MAX_CELLS];
+    int num_cells, mode, vid_mod, pad_;
+    float* key_score;        /* scratch [num_cells, N] (mode 0) */
+    float* query_score;      /* scratch [num_cells, N] (mode 0 with `logit`) */
+    float* alpha;            /* [num_cells, E] */
+    float* logit;            /* [num_cells, E] or NULL */
+} dagnn_attn_args;
+int dagnn_attention_weights(const dagnn_plan* plan /* host */, const dagnn_attn_args* args /* host */, void* stream);
+
 /* Introspection (tests, and the host-side read-back of the lock-step schedule): byte offsets of the
  * plan's arrays from `plan->data`, into a host array of 26 entries: [node_ptr, edge_ptr, depth0,
  * depth1, order0, order1, lstart0, lstart1, rowptr0, rowptr1, col0, col1, eattr0, eattr1, items,
