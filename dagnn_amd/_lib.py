@@ -7,6 +7,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import re
 import threading
 
 from . import build as _build
@@ -17,7 +18,8 @@ MAX_READOUT_JOBS = 24      # DAGNN_MAX_READOUT_JOBS
 ATTN_GRAD_MAX_JOBS = 16    # DAGNN_ATTN_GRAD_MAX_JOBS
 
 DAGNN_OK = 0
-_ERRORS = {-22: "DAGNN_EINVAL (bad argument)", -28: "DAGNN_ENOSPC (workspace too small)"}
+EINVAL, ENOSPC = -22, -28
+_ERRORS = {EINVAL: "DAGNN_EINVAL (bad argument)", ENOSPC: "DAGNN_ENOSPC (workspace too small)"}
 
 
 class DagnnHipError(RuntimeError):
@@ -81,7 +83,7 @@ class LayerArgs(C.Structure):
                 ("vid_mod", C.c_int), ("ld_h", C.c_int), ("static_score", C.c_int), ("debug_timing", C.c_void_p)]
 
 
-MAX_STACKED = 8
+MAX_STACKED = 8   # DAGNN_MAX_STACKED
 
 
 class PackJob(C.Structure):
@@ -178,7 +180,7 @@ class PlainPull(C.Structure):   # dagnn_plain_pull
         [("ld_h", C.c_int), ("ld_a", C.c_int), ("gld", C.c_int)]
 
 
-class GatherJob0(C.Structure):   # (dagnn_gather_job inside dagnn_encode_args; `GatherJob` below has the same layout)
+class GatherJob(C.Structure):   # dagnn_gather_job: dagnn_gather_rows_batch, and the jobs of dagnn_encode_args
     _fields_ = [("h", C.c_void_p), ("ld_h", C.c_int), ("width", C.c_int), ("node_off", C.c_int), ("col_off", C.c_int)]
 
 
@@ -187,7 +189,7 @@ class EncodeArgs(C.Structure):
                 ("batch", C.c_void_p), ("edge_attr", C.c_void_p), ("plan_status", C.c_void_p),
                 ("gemm", GemmGroup * 2), ("num_gemm", C.c_int), ("gemm_cols", C.c_int), ("in_dim", C.c_int), ("ld_x", C.c_int),
                 ("schedule", C.c_void_p), ("schedule_bytes", C.c_size_t), ("cost_layer", C.c_int), ("cost_row", C.c_int),
-                ("df", DataflowArgs), ("jobs", GatherJob0 * 16), ("num_jobs", C.c_int), ("stride", C.c_int),
+                ("df", DataflowArgs), ("jobs", GatherJob * 16), ("num_jobs", C.c_int), ("stride", C.c_int),
                 ("hcat", C.c_void_p), ("ld_hcat", C.c_int), ("w_out", C.c_void_p), ("b_out", C.c_void_p), ("out", C.c_void_p),
                 ("out_dim", C.c_int)]
 
@@ -216,15 +218,10 @@ class VariantCell(C.Structure):
                 ("num_maps", C.c_int32), ("reserved", C.c_int32)]
 
 
-class GatherJob(C.Structure):
-    _fields_ = [("h", C.c_void_p), ("ld_h", C.c_int), ("width", C.c_int), ("node_off", C.c_int), ("col_off", C.c_int)]
-
-
 class IpropLayer(C.Structure):
     _fields_ = [("w_ih", C.c_void_p), ("w_hh", C.c_void_p), ("b_ih", C.c_void_p), ("b_hh", C.c_void_p), ("in_dim", C.c_int)]
 
 
-MAX_STACKED = 8   # DAGNN_MAX_STACKED
 DVAE_MAX_N = 32   # DAGNN_DVAE_MAX_N
 DVAE_AGG_ATTN_H, DVAE_AGG_GATED_SUM, DVAE_AGG_ATTN_X = 0, 1, 2   # DAGNN_DVAE_AGG_*
 
@@ -330,7 +327,6 @@ class VariantArgs(C.Structure):
                 ("H", C.c_int)]
 
 
-# every symbol include/dagnn_hip.h declares: (restype, argtypes)
 class PrepTable(C.Structure):
     _fields_ = [("type_emb", C.c_void_p), ("attr_emb", C.c_void_p), ("depth_emb", C.c_void_p), ("out", C.c_void_p),
                 ("width", C.c_int), ("ld_out", C.c_int)]
@@ -391,6 +387,20 @@ SGP_REFINE_MAX_STARTS, SGP_REFINE_HISTORY = 32, 8    # DAGNN_SGP_REFINE_MAX_STAR
 SGP_REFINE_MEAN, SGP_REFINE_EI = 0, 1                # DAGNN_SGP_REFINE_MEAN / _EI (the objective)
 SGP_REFINE_STATUS = ("running", "converged", "stalled", "budget", "dead")   # DAGNN_SGP_REFINE_RUNNING .. _DEAD
 
+# The C type each mirror above stands for: "dagnn_" + the class's name in snake case, unless stated here.  tests/test_abi_cpu.py has
+# the compiler check every mirror against it - size, each field's offset and type - and every entry of SYMBOLS and every upper-case
+# constant X (against DAGNN_X) likewise: a mirror, an argtypes list or a constant that drifts from the header fails the CPU tests.
+C_TYPES = {PrepTable: "std::remove_extent_t<decltype(dagnn_prepare_rows::table)>",   # the unnamed struct of dagnn_prepare_rows.table[]
+           DvaeDecodeArgsTyped: "dagnn_dvae_decode_args", DvaeDecodeGradsTyped: "dagnn_dvae_decode_grads",
+           DvaeSampleArgsTyped: "dagnn_dvae_sample_args"}
+C_TYPES = {cls: C_TYPES.get(cls, "dagnn_" + re.sub("(?<!^)(?=[A-Z])", "_", cls.__name__).lower())
+           for cls in list(globals().values()) if isinstance(cls, type) and issubclass(cls, C.Structure)}
+C_FIELD_NAMES = {(WgradJob, "inp"): "in"}   # a field the header names with a Python keyword
+# earlier generations of a struct, which the library still serves (fields are only ever appended): each field sits where the
+# header has it and the class is no longer than the header's struct; the *Typed successor is the one checked whole
+C_EARLIER = {DvaeDecodeArgs, DvaeDecodeGrads, DvaeSampleArgs}
+
+# every symbol include/dagnn_hip.h declares: (restype, argtypes)
 SYMBOLS = {
     "dagnn_version": (C.c_char_p, []),
     "dagnn_store_gather": (C.c_int, [C.POINTER(StoreGatherArgs), C.c_void_p]),

@@ -1061,7 +1061,7 @@ class _DvaeDagnn(_DvaeBase):
         if len(jobs) > 16:
             return None
         for k, (t, off, col) in enumerate(jobs):
-            a.jobs[k] = _lib.GatherJob0(t.data_ptr(), t.stride(0), H, int(off), int(col))
+            a.jobs[k] = _lib.GatherJob(t.data_ptr(), t.stride(0), H, int(off), int(col))
         a.num_jobs, a.stride, a.hcat, a.ld_hcat = len(jobs), nn_, hcat.data_ptr(), hcat.shape[1]
         lin = self.hg_unify if self.bidirectional else (self.out_linear if L > 1 else None)
         if isinstance(lin, nn.Sequential) and len(lin) == 1:

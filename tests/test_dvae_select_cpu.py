@@ -133,14 +133,6 @@ def test_decoded_graph_runs_the_reference_utilities_surface():
         g.neighbors(0, "sideways")
 
 
-def test_select_struct_mirrors_the_header():
-    fields = [f[0] for f in _lib.DvaeSelectArgs._fields_]
-    assert fields == ["A", "B", "n", "nvt", "start_type", "end_type", "kind", "n_nodes", "select", "types", "preds", "nv",
-                      "valid", "pick", "n_valid", "n_same", "work", "work_bytes"]
-    assert _lib.DvaeSelectArgs.n.offset == 16 and _lib.DvaeSelectArgs.types.offset == 48
-    assert C.sizeof(_lib.DvaeSelectArgs) == 48 + 8 * 9
-
-
 FAKE = 1 << 20   # a non-null pointer (never dereferenced: nothing here launches)
 
 

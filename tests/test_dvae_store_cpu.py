@@ -1,10 +1,8 @@
 """The D-VAE store on the host (-m "not gpu"): the pack step and the numpy definition of the gather (`dvae_store.gather_host`)
 against the reference-generated fixture (tests/golden/make_golden_dvae_store.py) and against this package's own decoders and
-host collation, the layerings, the error cases, the loader, and the C ABI's argument struct.  Every comparison is exact."""
+host collation, the layerings, the error cases, the loader, and the entry points' argument refusals.  Every comparison is exact."""
 import ctypes as C
 import json
-import os
-import re
 
 import numpy as np
 import pytest
@@ -15,7 +13,6 @@ from dagnn_amd.dvae import decode_schedule
 from dagnn_amd.dvae_store import BATCH_KEYS, gather_host, layers_host, rows_to_dense, transpose_masks
 from tests import helpers as Hh
 
-ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 FIXTURE = "dvae_store_small"
 EINVAL = -22
 SETS = {"enas": ("ENAS", synth.decode_enas_row, 8, 8), "bn": ("BN", synth.decode_bn_row, 10, 10)}   # kind, decoder, n, nvt
@@ -294,24 +291,7 @@ def test_graph_set_holds_the_packed_rows():
     assert gs.contains((t2, p, torch.full((8,), 10, dtype=torch.int32)))[0].tolist() == [1, 1, 1, 0, 1, 1, 1, 1]
 
 
-# ------------------------------------------------------------------ 6. the C ABI
-def test_argument_struct_mirrors_the_header():
-    text = open(os.path.join(ROOT, "include", "dagnn_hip.h")).read()
-    body = re.search(r"typedef struct dagnn_dag_store_gather_args \{(.*?)\} dagnn_dag_store_gather_args;", text, flags=re.S).group(1)
-    fields = re.findall(r"^\s*(const\s+)?(\w+)\s*(\*?)\s*(\w+);\s*$", body, flags=re.M)
-    assert len(fields) == len([l for l in body.splitlines() if l.strip()]) == 20
-    mirror = _lib.DagStoreGatherArgs
-    assert [f[3] for f in fields] == [f[0] for f in mirror._fields_]
-    for i, (_, ctype, star, name) in enumerate(fields):
-        assert star == "*" or ctype == "int64_t", name     # every field is 8 bytes wide, so offsets are 8 i
-        assert getattr(mirror, name).offset == 8 * i and getattr(mirror, name).size == 8, name
-        assert (mirror._fields_[i][1] is C.c_void_p) == (star == "*"), name
-    assert C.sizeof(mirror) == 8 * len(fields)
-    assert re.search(r"int dagnn_dag_store_layers\(const int32_t\* preds, const int32_t\* succs, int64_t M, int n, int32_t\* layer_f, "
-                     r"int32_t\* layer_b,\s*void\* stream\);", text)
-    assert _lib.SYMBOLS["dagnn_dag_store_layers"][1] == [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-
-
+# ------------------------------------------------------------------ 6. the C ABI (its layout: tests/test_abi_cpu.py)
 def test_entry_points_refuse_bad_arguments_without_a_gpu():
     lib = _lib.load()
     assert lib.dagnn_dag_store_gather(None, None) == EINVAL

@@ -1,9 +1,7 @@
 """The graph store on the host (-m "not gpu"): the packed layout, the numpy definition of the gather (`store.gather_host`)
 against the reference-generated fixture (tests/golden/make_golden_code2_store.py) and against this package's own host
-collation, the loader's order and filters, the error cases, and the C ABI's argument struct.  Every comparison is exact."""
+collation, the loader's order and filters, the error cases, and the entry point's argument refusals.  Every comparison is exact."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 import pytest
@@ -14,7 +12,6 @@ from dagnn_amd.evaluate import encode_ref_sets
 from dagnn_amd.store import gather_host
 from tests import helpers as Hh
 
-ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 FIXTURE = "code2_store_small"
 RAW_KEYS = ("x", "node_depth", "edge_index", "node_is_attributed", "y_arr")
 # what a store batch carries (plus the host int `num_graphs`), and nothing else
@@ -242,21 +239,7 @@ def test_loader_order_filters_and_shuffle():
     assert other != one and sorted(i for b in other for i in b) == sorted(pool)
 
 
-# ------------------------------------------------------------------ 7. the C ABI
-def test_argument_struct_mirrors_the_header():
-    text = open(os.path.join(ROOT, "include", "dagnn_hip.h")).read()
-    body = re.search(r"typedef struct dagnn_store_gather_args \{(.*?)\} dagnn_store_gather_args;", text, flags=re.S).group(1)
-    fields = re.findall(r"^\s*(const\s+)?(\w+)\s*(\*?)\s*(\w+);\s*$", body, flags=re.M)
-    assert len(fields) == len([l for l in body.splitlines() if l.strip()]) == 36
-    mirror = _lib.StoreGatherArgs
-    assert [f[3] for f in fields] == [f[0] for f in mirror._fields_]
-    for i, (_, ctype, star, name) in enumerate(fields):
-        assert star == "*" or ctype == "int64_t", name     # every field is 8 bytes wide, so offsets are 8 i
-        assert getattr(mirror, name).offset == 8 * i and getattr(mirror, name).size == 8, name
-        assert (mirror._fields_[i][1] is C.c_void_p) == (star == "*"), name
-    assert C.sizeof(mirror) == 8 * len(fields)
-
-
+# ------------------------------------------------------------------ 7. the C ABI (its layout: tests/test_abi_cpu.py)
 def test_entry_point_refuses_bad_arguments_without_a_gpu():
     lib = _lib.load()
     assert lib.dagnn_store_gather(None, None) == EINVAL

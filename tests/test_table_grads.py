@@ -6,8 +6,6 @@ Bound.  A row of n members in m = ceil(n / 32) chunks: a term passes at most k =
 adds (the adds inside its chunk, then the adds of the later partials; +0.0 + p0 is exact), so
 |out - exact| <= k u / (1 - k u) sum |g| with u = 2^-24."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 import torch
@@ -15,7 +13,6 @@ import torch
 from dagnn_amd import _lib
 from dagnn_amd.autograd import TABLE_GRADS_CHUNK, table_grads_host
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 U = 2.0 ** -24
 FLT_MIN = 2.0 ** -126
 
@@ -49,13 +46,7 @@ def skewed_keys(N, R, seed, share=0.6):
 
 
 def test_chunk_is_one_constant_in_header_binding_and_mirror():
-    text = open(os.path.join(ROOT, "include", "dagnn_hip.h")).read()
-    assert int(re.search(r"#define DAGNN_TABLE_GRADS_CHUNK (\d+)", text).group(1)) == _lib.TABLE_GRADS_CHUNK == TABLE_GRADS_CHUNK == 32
-    assert int(re.search(r"#define DAGNN_TABLE_GRADS_MAX_TABLES (\d+)", text).group(1)) == _lib.TABLE_GRADS_MAX_TABLES
-    assert C.sizeof(_lib.TableGradsTable) == 40 and C.sizeof(_lib.TableGradsArgs) == 8 + 8 + 8 + 4 + 4 + 3 * 40 + 8 + 8 + 4 + 4
-    assert _lib.TableGradsArgs.table.offset == 32 and _lib.TableGradsArgs.workspace.offset == 152
-    assert (_lib.TABLE_GRADS_INDEX, _lib.TABLE_GRADS_SUM) == tuple(
-        int(re.search(r"#define DAGNN_TABLE_GRADS_%s (\d+)" % k, text).group(1)) for k in ("INDEX", "SUM"))
+    assert _lib.TABLE_GRADS_CHUNK == TABLE_GRADS_CHUNK == 32   # (binding against header: tests/test_abi_cpu.py)
 
 
 def raw_call(g, ld_g, N, H, tables, ws, ws_bytes, stages=0, stream=None):
